@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- FBS iterations/sec + achieved HBM GB/s, dense LASSO (soft-threshold prox), MI355X.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One "step" = one FBS iteration of the product solver (fasta_python_amd.FBSolver, driven as fasta() drives it: the library's
@@ -14,9 +14,11 @@ iteration; torch.distributed (gloo) is used only for rendezvous and barriers.  `
 torch.distributed.run environment makes this script start its own N workers (as a child process, before
 anything touches HIP) and relay rank 0's line.
 
-Prints ONE JSON line (rank 0): the driver's contract fields, `roofline` (achieved = the bytes the EXECUTED
-algorithm must move / the dominant kernel's HIP-event time, so frac <= 1), `cpu_baseline`, and `extra`:
-the other BASELINE configs timed by the same code in the same process -- nnls (config 3), tv and
+A plain run does only what the headline needs: it sets up, runs W untimed and exactly K timed steps once, writes the outputs of
+the timed solve if `--dump-outputs DIR` is given, and prints ONE JSON line (rank 0): the driver's contract fields and `roofline`
+(achieved = the bytes the EXECUTED algorithm must move / the dominant kernel's HIP-event time of those same steps, so frac <= 1).
+`--full` adds everything else: the headline as the median of --repeats 5 fresh solves, the read-ceiling probe in `roofline`,
+`cpu_baseline`, and `extra`: the other BASELINE configs timed by the same code in the same process -- nnls (config 3), tv and
 tv_accelerated (config 4; timed over >= 100 iterations after warming up INTO the backtracking regime, whatever --steps says),
 lasso_two_launch (the two-launch structure), lasso_f32_storage (opt-in float32 storage of A), lasso_wide_131072 (the widest
 single-team-of-16 shape), natural_run (configs 2 and 3 to tolerance 1e-5: iterations, loop and whole-call seconds),
@@ -51,17 +53,22 @@ def parse(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--repeats", type=int, default=5, help="the headline's timed region (a fresh solve: setup, W warm-up steps, K timed steps) is run "
-                    "this many times; value = the median run, the spread is reported (SURVEY.md 8(d): median of >= 5 runs)")
-    ap.add_argument("--extra-repeats", type=int, default=3, help="repeats of every sub-result's timed region")
+    ap.add_argument("--full", action="store_true", help="measure everything beyond the headline: --repeats 5 by default, the sub-results (extra), "
+                    "the CPU baseline and the read-ceiling probe of the roofline (a plain run times its K steps once and stops)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="after the timed steps, write what the headline's timed solve returns "
+                    "(solution and histories of its last step) as DIR/<name>.npy, float64, at most 64 MB in all")
+    ap.add_argument("--repeats", type=int, default=None, help="the headline's timed region (a fresh solve: setup, W warm-up steps, K timed steps) is run "
+                    "this many times; value = the median run, the spread is reported (SURVEY.md 8(d): median of >= 5 runs).  "
+                    "Default: 1, with --full 5")
+    ap.add_argument("--extra-repeats", type=int, default=3, help="repeats of every sub-result's timed region (--full)")
     ap.add_argument("--rows", dest="m", type=int, default=65536, help="total rows of A (default: BASELINE config 2)")
     ap.add_argument("--cols", dest="n", type=int, default=65536)
     ap.add_argument("--workload", default="lasso", choices=["lasso", "nnls", "tv"],
                     help="lasso = BASELINE config 2 (default, the headline); nnls = config 3; tv = config 4 (8192^2 image)")
     ap.add_argument("--image", type=int, default=8192, help="TV image side (workload tv and the tv sub-results)")
     ap.add_argument("--accelerate", action="store_true", help="FISTA (workload tv / lasso / nnls)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the nnls / tv / two-launch sub-results")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="--full without the nnls / tv / two-launch sub-results")
     ap.add_argument("--skip-extra", default="", help="comma list of sub-results to skip (e.g. inproc: the two in-process row-block runs, "
                                                      "whose launches of the headline kernel on SMALLER row blocks would otherwise be "
                                                      "averaged into the same rocprofv3 kernel-stats row)")
@@ -90,7 +97,10 @@ def parse(argv=None):
     ap.add_argument("--rdv-timeout", type=float, default=600.0, help="seconds any rendezvous wait may take before the job is abandoned")
     ap.add_argument("--hang-at-rank", type=int, default=-1, help=argparse.SUPPRESS)     # tests: this rank sleeps forever after the first barrier
     ap.add_argument("--die-at-rank", type=int, default=-1, help=argparse.SUPPRESS)      # tests: this rank exits(3) after the first barrier
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    return args
 
 
 # ------------------------------------------------------------------------------------------------------------
@@ -490,7 +500,31 @@ def timed_steps(make_solver, ctx, grp, warmup, steps, repeats=1, trace=False):
     if trace:
         med["spread"]["first_run_step_ms"] = [round(v, 4) for v in runs[0]["step_ms"]]
         med["spread"]["first_run_step_ms_note"] = f"wall time of each step of the first run: {warmup} warm-up steps, then the {steps} timed ones"
+    med["last_solver"] = runs[-1]["solver"]        # the solve whose state the context still holds
     return med
+
+
+DUMP_LIMIT_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(solver, out_dir):
+    """--dump-outputs: what a caller of the timed path receives once its last timed step has run -- the Convergence record of
+    FBSolver.result(): the solution (the best iterate) and the per-iteration histories so far -- as out_dir/<name>.npy, float64.
+    Each array may take an equal share of DUMP_LIMIT_BYTES; a larger one (the TV dual variable at 8192^2 is 1 GiB) is written as a
+    fixed sample: its flattened elements at the sorted, distinct indices drawn by a generator seeded with 0."""
+    import numpy as np
+    c = solver.result()
+    k = c.iteration_count
+    arrays = {"solution": c.solution, "residuals": c.residuals[:k], "norm_residuals": c.norm_residuals[:k], "stepsizes": c.stepsizes[:k]}
+    if c.objectives is not None:
+        arrays["objectives"] = c.objectives[:k + 1]
+    cap = DUMP_LIMIT_BYTES // 8 // len(arrays)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float64)
+        if a.size > cap:
+            a = a.ravel()[np.unique(np.random.default_rng(0).integers(0, a.size, cap))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def kernel_table(per):
@@ -510,9 +544,9 @@ def dense_bytes(m, n, esize=8):
             "fused": m * n * esize + (3 * m + 7 * n) * 8}
 
 
-def run_dense(args, grp, A, m_total, n, workload, fused, steps, warmup, accelerate=False, plain=False, repeats=None, trace=False):
+def run_dense(args, grp, A, m_total, n, workload, fused, steps, warmup, accelerate=False, plain=False, repeats=None, trace=False, dump_dir=""):
     """One dense workload (LASSO or NNLS) on the resident matrix `A` (this rank's row block); the three modes of the reference's
-    test_modes (examples/__init__.py:66-91): adaptive (default), accelerated (FISTA), plain (neither)."""
+    test_modes (examples/__init__.py:66-91): adaptive (default), accelerated (FISTA), plain (neither).  dump_dir: see dump_outputs."""
     import numpy as np
     import fasta_python_amd as fa
     from fasta_python_amd import synthetic
@@ -532,6 +566,8 @@ def run_dense(args, grp, A, m_total, n, workload, fused, steps, warmup, accelera
         return fa.FBSolver(A, loss, reg, np.zeros(n), adaptive=not (accelerate or plain), accelerate=accelerate, verbose=False,
                            max_iters=warmup + steps, tolerance=0.0, backtrack=True, evaluate_objective=False, fused=fused)
     t = timed_steps(make_solver, ctx, grp, warmup, steps, args.extra_repeats if repeats is None else repeats, trace)
+    if dump_dir:
+        dump_outputs(t["last_solver"], dump_dir)
     solver = t["solver"]
     # per LAUNCH: a multi-device context launches once per row block (its timers add up launches and time over the blocks)
     by = dense_bytes(m_local // blocks, n, 4 if getattr(A, "storage", "f64") == "f32" else 8)
@@ -724,8 +760,8 @@ def tv_kernel_name(accelerate, zfree):
     return "fasta_step_accel(k_fused_tv_accel)" if accelerate else "fasta_step(k_fused_tv_step)"
 
 
-def run_tv(args, grp, steps, warmup, fused, accelerate, repeats=3):
-    """BASELINE config 4: TV denoising dual on an image of side --image, 1 GPU."""
+def run_tv(args, grp, steps, warmup, fused, accelerate, repeats=3, dump_dir=""):
+    """BASELINE config 4: TV denoising dual on an image of side --image, 1 GPU.  dump_dir: see dump_outputs."""
     import numpy as np
     import fasta_python_amd as fa
     from fasta_python_amd.examples.tv_denoising import checkerboard
@@ -748,6 +784,8 @@ def run_tv(args, grp, steps, warmup, fused, accelerate, repeats=3):
             return fa.FBSolver(A, loss, reg, np.zeros(M.shape + (2,)), adaptive=not accelerate, accelerate=accelerate,
                                verbose=False, max_iters=warmup + steps, tolerance=0.0, fused=fused)
         t = timed_steps(make_solver, A.ctx, grp, warmup, steps, repeats)
+        if dump_dir:
+            dump_outputs(t["last_solver"], dump_dir)
     finally:
         A.close()
     P = side * side
@@ -898,7 +936,8 @@ def main(argv=None):
     if args.workload == "tv":
         if grp.world != 1:
             raise SystemExit("the TV workload is single-GPU (BASELINE config 4)")
-        print(json.dumps(tv_line(args, run_tv(args, grp, args.steps, args.warmup, fused, args.accelerate, args.repeats), args.accelerate)))
+        r = run_tv(args, grp, args.steps, args.warmup, fused, args.accelerate, args.repeats, dump_dir=args.dump_outputs)
+        print(json.dumps(tv_line(args, r, args.accelerate)))
         return grp.close()
 
     m_total, n = args.m, args.n
@@ -939,7 +978,8 @@ def main(argv=None):
     want_ranks = args.gpus if (args.inproc or grp.world > 1) else 1
     if ranks_seen != want_ranks:
         raise SystemExit(f"row sharding over {want_ranks} GPUs was asked for but the communicator reports {ranks_seen} rank(s)")
-    main_r = run_dense(args, grp, A, m_total, n, args.workload, fused, args.steps, args.warmup, args.accelerate, repeats=args.repeats)
+    main_r = run_dense(args, grp, A, m_total, n, args.workload, fused, args.steps, args.warmup, args.accelerate, repeats=args.repeats,
+                       dump_dir=args.dump_outputs if grp.rank == 0 else "")
     dom = main_r["dominant"]
     d = main_r["per_kernel"][dom]
     ncu = ctx.cu_count()[0]
@@ -947,14 +987,15 @@ def main(argv=None):
                   ("void k_adj_dense<4, 1, 0>(AdjP)" if "adj" in dom else "void k_fwd_dense<8, 1, 1, 0>(FwdP)"))
     traffic, traffic_src = (pmc_traffic(dom_kernel) if (m_total, n, args.gpus, args.storage) == (65536, 65536, 1, "f64") and dom_kernel
                             else (None, "PMC summaries are taken at the default configuration (65536 x 65536 float64, 1 GPU) only"))
-    # read-only ceiling on the same buffer: the probe with one and with two persistent workgroups per CU (the one-pass kernel itself
+    # --full: read-only ceiling on the same buffer: the probe with one and with two persistent workgroups per CU (the one-pass kernel itself
     # can only have one: it uses the whole register file), the better of the two is the ceiling quoted
     ceilings = {}
-    for wg_per_cu in (1, 2):
-        ctx.set_tuning(hip.TUNE_FWD_GRID_CAP, ncu * wg_per_cu)
-        ms, ceil_bytes = ctx.stream_read_ms(3)
-        ceilings[wg_per_cu] = ceil_bytes / ms / 1e6
-    ctx.set_tuning(hip.TUNE_FWD_GRID_CAP, tuning.get(hip.TUNE_FWD_GRID_CAP, 0))
+    if args.full:
+        for wg_per_cu in (1, 2):
+            ctx.set_tuning(hip.TUNE_FWD_GRID_CAP, ncu * wg_per_cu)
+            ms, ceil_bytes = ctx.stream_read_ms(3)
+            ceilings[wg_per_cu] = ceil_bytes / ms / 1e6
+        ctx.set_tuning(hip.TUNE_FWD_GRID_CAP, tuning.get(hip.TUNE_FWD_GRID_CAP, 0))
     fused_kind = ctx.fused_supported()
 
     names = {"lasso": ("LASSO", "soft-threshold"), "nnls": ("NNLS", "non-negativity")}[args.workload]
@@ -967,8 +1008,9 @@ def main(argv=None):
         "warmup": args.warmup,
         "ms_per_step": main_r["ms_per_step"],
         "spread": main_r["spread"],
-        "protocol": (f"value = the MEDIAN of {args.repeats} runs of the timed region; each run is a fresh solve: setup, {args.warmup} untimed steps, exactly "
-                     f"{args.steps} timed steps between barrier + device sync on both sides; spread.ms_per_step gives first / min / median / max"),
+        "protocol": ((f"value = the MEDIAN of {args.repeats} runs of the timed region; each run is" if args.repeats > 1 else "value = one run of the timed region:")
+                     + f" a fresh solve: setup, {args.warmup} untimed steps, exactly {args.steps} timed steps between barrier + device sync on both sides"
+                     + ("; spread.ms_per_step gives first / min / median / max" if args.repeats > 1 else "")),
         "before_start": before_start,
         "higher_is_better": True,
         "scaling": "strong",
@@ -988,12 +1030,12 @@ def main(argv=None):
         "roofline": {"bound": "hbm", "achieved": d["GB/s"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": d["GB/s"] / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
                      "kernel": dom, "kernel_instantiation": dom_kernel, "avg_launch_ms": d["avg_ms"], "algorithmic_bytes_per_launch": d["algorithmic_bytes_per_launch"],
-                     "stream_read_ceiling_GB/s": max(ceilings.values()),
-                     "stream_read_GB/s_by_workgroups_per_cu": ceilings,
-                     "stream_read_probe": "k_stream_probe<16,1> over the same device copy of A: one or two persistent workgroups per CU (best of both), three rotating "
-                                          "register buffers of 16 non-temporal 16-byte loads per lane (32 loads in flight), loads + adds only.  A reference stream, not a bound: "
-                                          "its workgroups run free, the one-pass kernel's teams advance in lockstep over one window of rows (rows dealt cyclically, round 6) "
-                                          "and read the same bytes 1-1.5 % faster than this probe",
+                     **({"stream_read_ceiling_GB/s": max(ceilings.values()),
+                         "stream_read_GB/s_by_workgroups_per_cu": ceilings,
+                         "stream_read_probe": "k_stream_probe<16,1> over the same device copy of A: one or two persistent workgroups per CU (best of both), three rotating "
+                                              "register buffers of 16 non-temporal 16-byte loads per lane (32 loads in flight), loads + adds only.  A reference stream, not a bound: "
+                                              "its workgroups run free, the one-pass kernel's teams advance in lockstep over one window of rows (rows dealt cyclically, round 6) "
+                                              "and read the same bytes 1-1.5 % faster than this probe"} if ceilings else {}),
                      "per_kernel": main_r["per_kernel"],
                      "loop_GB/s_wallclock": main_r["loop_GB/s_wallclock"],
                      "vs_two_pass_model": main_r["vs_two_pass_model"],
@@ -1005,7 +1047,7 @@ def main(argv=None):
     }
 
     extra = {}
-    if not args.no_extra and not args.accelerate and args.workload == "lasso" and args.storage == "f64":
+    if args.full and not args.no_extra and not args.accelerate and args.workload == "lasso" and args.storage == "f64":
         if fused is not False and main_r["fused_steps"]:
             r = run_dense(args, grp, A, m_total, n, "lasso", False, args.steps, args.warmup)
             extra["lasso_two_launch"] = sub_result(r, f"LASSO {m_total}x{n}, two launches per iteration (K-fwd + K-adj, the north-star structure)")
@@ -1116,7 +1158,8 @@ def main(argv=None):
                 A = shard(m_total)                     # (the CPU baseline below pulls the matrix back from HBM)
     if extra:
         result["extra"] = extra
-    if grp.rank == 0 and grp.world == 1 and not args.no_cpu_baseline and args.workload == "lasso" and not args.accelerate and args.storage == "f64":
+    if (args.full and grp.rank == 0 and grp.world == 1 and not args.no_cpu_baseline and args.workload == "lasso" and not args.accelerate
+            and args.storage == "f64"):
         result["cpu_baseline"] = cpu_baseline(A, main_r["b"], main_r["mu"], n, m_total, args.cpu_rows, args.cpu_iters, args.cpu_repeats)
     if grp.rank == 0:
         print(json.dumps(result))

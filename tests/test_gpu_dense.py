@@ -456,3 +456,41 @@ def test_a_large_allocation_reuses_the_kept_block_and_waits_for_the_clearing_of_
     w0, h0 = hip.alloc_settle_waited(), hip.alloc_cache_hits()
     b = fa.DenseMatrixMap.synthetic(4096, 4096, 0, 1e-3); b.close()
     assert hip.alloc_settle_waited() == w0 and hip.alloc_cache_hits() == h0
+
+
+def test_plain_bench_run_dumps_what_its_timed_solve_returns(tmp_path):
+    """`bench.py --steps K --warmup W --dump-outputs DIR` without --full: one line with the headline fields only (no sub-results, no CPU
+    baseline), and DIR holds the Convergence arrays of its solve -- equal to the same recipe solved here: setup, W + K iterations."""
+    import json
+    import os
+    import subprocess
+    import sys
+    from fasta_python_amd import synthetic
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    m, n, steps, warmup = 4096, 8192, 4, 1
+    res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--rows", str(m), "--cols", str(n), "--steps", str(steps),
+                          "--warmup", str(warmup), "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600, cwd=root)
+    assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
+    lines = [ln for ln in res.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1
+    out = json.loads(lines[0])
+    assert out["steps"] == steps and out["ms_per_step"] > 0 and out["spread"]["repeats"] == 1
+    assert "extra" not in out and "cpu_baseline" not in out and "stream_read_ceiling_GB/s" not in out["roofline"]
+    got = {name: np.load(os.path.join(tmp_path, name + ".npy")) for name in ("solution", "residuals", "norm_residuals", "stepsizes")}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert got["solution"].shape == (n,) and got["residuals"].shape == (steps + warmup,)
+    A = fa.DenseMatrixMap.synthetic(m, n, seed=0, scale=synthetic.lasso_scale(m, n))
+    try:
+        x_true = synthetic.sparse_signal(n, seed=1)
+        b = synthetic.lasso_observation(A, x_true, seed_noise=2, sigma=0.01)
+        np.random.seed(3)
+        solver = fa.FBSolver(A, fa.LeastSquares(b), fa.Shrink(0.02), np.zeros(n), verbose=False, max_iters=warmup + steps, tolerance=0.0)
+        solver.setup()
+        solver.advance(warmup)
+        solver.advance(steps)
+        want = solver.result()
+    finally:
+        A.close()
+    assert np.array_equal(got["solution"], want.solution)
+    for name in ("residuals", "norm_residuals", "stepsizes"):
+        assert np.array_equal(got[name], getattr(want, name)[:steps + warmup]), name

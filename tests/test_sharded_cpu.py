@@ -217,6 +217,43 @@ def test_socket_rendezvous_ignores_strangers_and_never_unpickles(tmp_path):
         bench.SocketGroup._recv(b)
 
 
+def test_a_plain_bench_run_times_its_steps_once_and_full_keeps_the_rest():
+    sys.path.insert(0, ROOT)
+    import bench
+    plain = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (plain.full, plain.repeats, plain.steps, plain.warmup, plain.dump_outputs) == (False, 1, 7, 2, "")
+    full = bench.parse(["--full"])
+    assert (full.full, full.repeats, full.extra_repeats) == (True, 5, 3)
+    assert bench.parse(["--full", "--repeats", "2"]).repeats == 2 and bench.parse(["--dump-outputs", "out"]).dump_outputs == "out"
+
+
+def test_dump_outputs_writes_float64_arrays_within_the_cap(tmp_path, monkeypatch):
+    """--dump-outputs: the Convergence arrays of the timed solve as <name>.npy, float64; an array over its share of the cap is a
+    fixed sample (the same indices on every run), never truncated silently to its head."""
+    sys.path.insert(0, ROOT)
+    import bench
+    from fasta_python_amd.solver import Convergence
+    rng = np.random.default_rng(5)
+    sol = rng.standard_normal((40, 25, 2))
+    hist = [rng.standard_normal(9) for _ in range(3)]
+
+    class Solver:
+        def result(self):
+            return Convergence(*hist, 0, np.zeros(10), 6, sol)
+
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4 * 8 * 256)           # 256 float64 per array
+    for d in ("a", "b"):
+        bench.dump_outputs(Solver(), str(tmp_path / d))
+    got = {p.name: np.load(p) for p in (tmp_path / "a").iterdir()}
+    assert sorted(got) == ["norm_residuals.npy", "residuals.npy", "solution.npy", "stepsizes.npy"]
+    assert all(a.dtype == np.float64 for a in got.values()) and sum(a.nbytes for a in got.values()) <= 4 * 8 * 256
+    np.testing.assert_array_equal(got["residuals.npy"], hist[0][:6])
+    np.testing.assert_array_equal(got["stepsizes.npy"], hist[2][:6])
+    s = got["solution.npy"]
+    assert 200 < s.size <= 256 and np.isin(s, sol.ravel()).all()
+    np.testing.assert_array_equal(s, np.load(tmp_path / "b" / "solution.npy"))
+
+
 def test_a_rank_stuck_for_good_is_ended_by_the_job_timeout():
     """A rank that never comes back (as when stuck inside a GPU collective, which no rendezvous timeout covers) must not keep
     `bench.py --gpus N` alive forever: the spawner's wall-clock limit ends every rank and the status is non-zero."""
