@@ -1181,6 +1181,38 @@ extern "C" int fh_run_supported(fh_ctx* c, int* yes) {
   *yes = ((run_entry(c) || chain_ok(c)) && co_resident(c)) ? 1 : 0;
   return 0;
 }
+// ---- what fh_run's two forms (and fh_iterate) share on the host side ----
+// the mapped state block ([0]: what goes up, [1]: what comes back) and the mapped history of max_steps records, grown in steps of 256
+static int ensure_run_buffers(fh_ctx* c, int max_steps) {
+  if (!c->run_st_host) {
+    HIP_TRY(hipHostMalloc(&c->run_st_host, 2 * sizeof(ChainState), hipHostMallocMapped));
+    HIP_TRY(hipHostGetDevicePointer(&c->run_st_host_dev, c->run_st_host, 0));
+  }
+  if ((size_t)max_steps <= c->run_hist_steps) return 0;
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (c->run_hist) { HIP_TRY(hipHostFree(c->run_hist)); c->run_hist = nullptr; c->run_hist_steps = 0; }
+  const size_t steps = round_up((size_t)max_steps, 256);
+  HIP_TRY(hipHostMalloc((void**)&c->run_hist, steps * FR_HIST * sizeof(double), hipHostMallocMapped));
+  HIP_TRY(hipHostGetDevicePointer((void**)&c->run_hist_dev, c->run_hist, 0));
+  c->run_hist_steps = steps;
+  return 0;
+}
+// the caller's state and the context's buffer roles as a device-side loop takes them: scalars, roles, identity `perm`, window
+static void run_state_in(const fh_ctx* c, const fh_run_state* state, RunState* hs) {
+  memset(hs, 0, sizeof(RunState));
+  hs->tau_next = state->tau_next; hs->alpha1 = state->alpha1; hs->max_residual = state->max_residual; hs->best_quality = state->best_quality;
+  hs->iteration = state->iteration; hs->backtracks = state->backtracks; hs->stopped = 0;
+  hs->xi = c->xi; hs->ti = c->ti; hs->bi = c->bi; hs->pc = c->pc; hs->gc = c->gc; hs->zc = c->zc; hs->last_accel = c->last_accel ? 1 : 0;
+  for (int q = 0; q < 5; ++q) hs->perm[q] = q;
+  memcpy(hs->f_window, state->f_window, sizeof(hs->f_window));
+}
+static void run_opts_in(const fh_run_opts* o, RunOpts* r) {
+  r->adaptive = o->adaptive; r->accelerate = o->accelerate; r->backtrack = o->backtrack; r->restart = o->restart;
+  r->evaluate_objective = o->evaluate_objective; r->stop_rule = o->stop_rule; r->window = o->window; r->max_backtracks = o->max_backtracks;
+  r->stepsize_shrink = o->stepsize_shrink; r->tolerance = o->tolerance;
+}
+// g(x) from the prox's reductions (proximal.py: g_from_sums)
+static int g_kind_of(const fh_ctx* c) { return c->prox_kind == FH_PROX_SHRINK ? FC_G_SUM : (c->prox_kind == FH_PROX_LINF ? FC_G_MAX : FC_G_NONE); }
 static int run_adopt(fh_ctx* c, const fh_run_opts* o, const RunState* hs, double* const (&nb)[5], int max_steps, fh_run_state* state, double* history, int* steps_done, const char* what);
 static int run_chain(fh_ctx* c, int max_steps, const fh_run_opts* o, fh_run_state* state, double* history, int* steps_done);
 extern "C" int fh_run(fh_ctx* c, int max_steps, const fh_run_opts* o, fh_run_state* state, double* history, int* steps_done) {
@@ -1194,26 +1226,9 @@ extern "C" int fh_run(fh_ctx* c, int max_steps, const fh_run_opts* o, fh_run_sta
   if (!e || !co_resident(c)) return fail(FH_E_STATE, "fh_run: no device-side loop for this operator / loss / prox (see fh_run_supported)");
   FH_TRY(use_device(c));
   FH_TRY(not_lazy(c, "fh_run"));
-  if (!c->run_st_host) {
-    HIP_TRY(hipHostMalloc(&c->run_st_host, 2 * sizeof(ChainState), hipHostMallocMapped));
-    HIP_TRY(hipHostGetDevicePointer(&c->run_st_host_dev, c->run_st_host, 0));
-  }
-  if ((size_t)max_steps > c->run_hist_steps) {
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (c->run_hist) { HIP_TRY(hipHostFree(c->run_hist)); c->run_hist = nullptr; c->run_hist_steps = 0; }
-    const size_t steps = round_up((size_t)max_steps, 256);
-    HIP_TRY(hipHostMalloc((void**)&c->run_hist, steps * FR_HIST * sizeof(double), hipHostMallocMapped));
-    HIP_TRY(hipHostGetDevicePointer((void**)&c->run_hist_dev, c->run_hist, 0));
-    c->run_hist_steps = steps;
-  }
+  FH_TRY(ensure_run_buffers(c, max_steps));
   RunP p;
-  RunState* hs = &p.init;                               // the state on entry travels as a kernel argument
-  memset(hs, 0, sizeof(RunState));
-  hs->tau_next = state->tau_next; hs->alpha1 = state->alpha1; hs->max_residual = state->max_residual; hs->best_quality = state->best_quality;
-  hs->iteration = state->iteration; hs->backtracks = state->backtracks; hs->stopped = 0;
-  hs->xi = c->xi; hs->ti = c->ti; hs->bi = c->bi; hs->pc = c->pc; hs->gc = c->gc; hs->zc = c->zc; hs->last_accel = c->last_accel ? 1 : 0;
-  for (int q = 0; q < 5; ++q) hs->perm[q] = q;
-  memcpy(hs->f_window, state->f_window, sizeof(hs->f_window));
+  run_state_in(c, state, &p.init);                      // the state on entry travels as a kernel argument
   p.A = c->A; p.n = (uint32_t)c->n; p.m = (uint32_t)c->m; p.mp = (uint32_t)c->mp;
   p.ld2 = (uint32_t)(round_up(c->n, 16) / 2); p.ldp = (uint32_t)(c->ld / 2); p.nv2 = p.ld2;
   p.nteams = (uint32_t)fused_ncu(c);
@@ -1227,10 +1242,8 @@ extern "C" int fh_run(fh_ctx* c, int max_steps, const fh_run_opts* o, fh_run_sta
   p.G[0] = c->G[0]; p.G[1] = c->G[1]; p.Z[0] = c->Z[0]; p.Z[1] = c->Z[1]; p.xhat = c->xhat; p.b = c->b;
   p.loss = c->loss_kind; p.prox_kind = c->prox_kind; p.mu = c->mu; p.lo = c->lo; p.hi = c->hi;
   p.nt = nt_for(c);
-  p.g_kind = c->prox_kind == FH_PROX_SHRINK ? 1 : 0;
-  p.o.adaptive = o->adaptive; p.o.accelerate = o->accelerate; p.o.backtrack = o->backtrack; p.o.restart = o->restart;
-  p.o.evaluate_objective = o->evaluate_objective; p.o.stop_rule = o->stop_rule; p.o.window = o->window; p.o.max_backtracks = o->max_backtracks;
-  p.o.stepsize_shrink = o->stepsize_shrink; p.o.tolerance = o->tolerance;
+  p.g_kind = g_kind_of(c);
+  run_opts_in(o, &p.o);
   p.max_steps = max_steps;
   p.st_out = (RunState*)c->run_st_host_dev; p.hist = c->run_hist_dev;
   memset(c->run_st_host, 0xFF, sizeof(RunState));     // (poisoned: a launch that never wrote its state back cannot pass for one that did)
@@ -1297,27 +1310,11 @@ static int run_adopt(fh_ctx* c, const fh_run_opts* o, const RunState* hs, double
 static int run_chain(fh_ctx* c, int max_steps, const fh_run_opts* o, fh_run_state* state, double* history, int* steps_done) {
   FH_TRY(use_device(c));
   FH_TRY(not_lazy(c, "fh_run"));
-  if (!c->run_st_host) {
-    HIP_TRY(hipHostMalloc(&c->run_st_host, 2 * sizeof(ChainState), hipHostMallocMapped));     // [0]: what goes up, [1]: what comes back
-    HIP_TRY(hipHostGetDevicePointer(&c->run_st_host_dev, c->run_st_host, 0));
-  }
+  FH_TRY(ensure_run_buffers(c, max_steps));
   if (!c->chain_state) HIP_TRY(hipMalloc((void**)&c->chain_state, sizeof(ChainState)));
-  if ((size_t)max_steps > c->run_hist_steps) {
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (c->run_hist) { HIP_TRY(hipHostFree(c->run_hist)); c->run_hist = nullptr; c->run_hist_steps = 0; }
-    const size_t steps = round_up((size_t)max_steps, 256);
-    HIP_TRY(hipHostMalloc((void**)&c->run_hist, steps * FR_HIST * sizeof(double), hipHostMallocMapped));
-    HIP_TRY(hipHostGetDevicePointer((void**)&c->run_hist_dev, c->run_hist, 0));
-    c->run_hist_steps = steps;
-  }
   ChainState* hst = (ChainState*)c->run_st_host;
   memset(hst, 0, sizeof(ChainState));
-  RunState* hs = &hst->rs;
-  hs->tau_next = state->tau_next; hs->alpha1 = state->alpha1; hs->max_residual = state->max_residual; hs->best_quality = state->best_quality;
-  hs->iteration = state->iteration; hs->backtracks = state->backtracks; hs->stopped = 0;
-  hs->xi = c->xi; hs->ti = c->ti; hs->bi = c->bi; hs->pc = c->pc; hs->gc = c->gc; hs->zc = c->zc; hs->last_accel = c->last_accel ? 1 : 0;
-  for (int q = 0; q < 5; ++q) hs->perm[q] = q;
-  memcpy(hs->f_window, state->f_window, sizeof(hs->f_window));
+  run_state_in(c, state, &hst->rs);
   hst->tau_iter = state->tau_next;
   HIP_TRY(hipMemcpyAsync(c->chain_state, hst, sizeof(ChainState), hipMemcpyHostToDevice, c->stream));
   double* nb[5] = {c->X[0], c->X[1], c->X[2], c->P[0], c->P[1]};
@@ -1325,10 +1322,8 @@ static int run_chain(fh_ctx* c, int max_steps, const fh_run_opts* o, fh_run_stat
   for (int q = 0; q < 5; ++q) ch.nbuf[q] = nb[q];
   ch.G[0] = c->G[0]; ch.G[1] = c->G[1]; ch.Z[0] = c->Z[0]; ch.Z[1] = c->Z[1];
   ch.mu = c->mu;
-  ch.o.adaptive = o->adaptive; ch.o.accelerate = o->accelerate; ch.o.backtrack = o->backtrack; ch.o.restart = o->restart;
-  ch.o.evaluate_objective = o->evaluate_objective; ch.o.stop_rule = o->stop_rule; ch.o.window = o->window; ch.o.max_backtracks = o->max_backtracks;
-  ch.o.stepsize_shrink = o->stepsize_shrink; ch.o.tolerance = o->tolerance;
-  ch.g_kind = c->prox_kind == FH_PROX_SHRINK ? 1 : 0;
+  run_opts_in(o, &ch.o);
+  ch.g_kind = g_kind_of(c);
   ch.max_steps = max_steps;
   ch.st = (ChainState*)c->chain_state;
   ch.hist = c->run_hist_dev;

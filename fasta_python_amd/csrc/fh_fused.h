@@ -40,7 +40,7 @@
 // address, carry x = 0 and are masked out of every store (fh_host_launch.h:fused_shape_for picks the next shape up).
 #pragma once
 #include "fh_dense.h"
-#include "fh_loop.h"
+#include "fh_controller.h"
 
 #define FT_TEAM_MAX 32                              // members per team: 1, 2, 4, 8, 16 or 32 (template parameter TEAM)
 #define FT_SENTINEL_HI 0x7FF8DEADu                  // slot filler: the NaN 0x7FF8DEAD7FF8DEAD (hipMemsetD32)
@@ -137,7 +137,7 @@ __global__ __launch_bounds__(FH_WG, (fused_wpc<PPT, TEAM, XLDS, F32>())) void k_
 // accepted iteration rotates the roles exactly as fh_commit does and appends its record to the host-mapped history.  One launch = one
 // ATTEMPT; a launch that finds the solve stopped (stop rule, step budget, a hand-off timeout) returns at once.  The host enqueues K
 // launches, copies the state back once and adopts it as after fh_run -- same entry point (fh_run), same options / state / history.
-// Arithmetic: K-fused's sums, fh_run's controller (x * x where NumPy squares: histories rtol 1e-6 against the host-driven loop, counts equal).
+// Arithmetic: K-fused's sums, the shared controller of csrc/fh_controller.h (x * x where NumPy squares: histories rtol 1e-6 against the host-driven loop, counts equal).
 // Served: float64, teams of 1 / 2 / 4 members (n <= 16384), separable prox kinds -- where a launch is short enough for 5 us to matter.
 // =====================================================================================================================================
 struct ChainState {          // device memory; read by every workgroup at the start of a launch, rewritten by its finaliser
@@ -153,7 +153,7 @@ struct ChainP {
   double* G[2]; double* Z[2];
   double mu;
   RunOpts o;
-  int g_kind;                // g(x) for the objective: 0 = none, 1 = mu * sum|x|
+  int g_kind;                // g(x) for the objective: FC_G_* of fh_controller.h
   int max_steps;             // iterations this chain may complete
   ChainState* st;
   double* hist;              // [max_steps][FR_HIST], host-mapped
@@ -163,7 +163,7 @@ template <typename T> __device__ __forceinline__ T* chain_sel5(T* const (&b)[5],
   return i == 0 ? b[0] : (i == 1 ? b[1] : (i == 2 ? b[2] : (i == 3 ? b[3] : b[4])));
 }
 
-// the controller of csrc/fh_run.h (phase C), run by ONE thread: the finaliser of a chained launch
+// the loop's controller (csrc/fh_controller.h), run by ONE thread: the finaliser of a chained launch
 __device__ inline void chain_controller(const ChainP& ch, const FusedP& p, const double (&a)[8], const double (&bq)[5], double rdot, double timed_out) {
 #pragma clang fp contract(off)
   ChainState* st = ch.st;
@@ -176,78 +176,21 @@ __device__ inline void chain_controller(const ChainP& ch, const FusedP& p, const
     return;
   }
   st->attempts += 1;
-  const double fsq = a[0], dxg0 = a[1], dx2 = a[2], xh2 = a[3], g02 = a[4], gsum = a[5], gmax = a[6], fsq_adj = p.accel ? a[7] : a[0];
-  auto fval = [&](double s) -> double { if (p.loss != LOSS_LSQ) return s; const double q = sqrt(s); return .5 * (q * q); };
-  double f1 = fval(fsq);
-  const unsigned long long ita = rs.iteration;
-  if (o.backtrack) {                                                          // :195-217
-    const unsigned long long lo_ = ita + 1ull > (unsigned long long)o.window ? ita + 1ull - (unsigned long long)o.window : 0ull;
-    double M = rs.f_window[lo_ % FR_WINDOW_MAX];
-    for (unsigned long long j = lo_ + 1ull; j <= ita; ++j) { const double v = rs.f_window[j % FR_WINDOW_MAX]; M = v > M ? v : M; }
-    const double dxn = sqrt(dx2);
-    if (f1 - (M + dxg0 + (dxn * dxn) / (2.0 * tau)) > 1E-12 && st->bt < o.max_backtracks) {
-      rs.tau_next = tau * o.stepsize_shrink;                                  // same x0 / g0, smaller step (:204-215): the roles stay
-      st->bt += 1;
-      return;
-    }
+  const double sums[FC_NSUMS] = {a[0], a[1], a[2], a[3], a[4], a[5], a[6], rdot, bq[0], bq[1], a[7], bq[2], bq[3], bq[4]};
+  const bool lsq = p.loss == LOSS_LSQ;
+  if (fc_backtrack(o, rs.f_window, rs.iteration, fc_f(lsq, sums[FC_FSQ], FcSqMul()), sums[FC_DXG0], sums[FC_DX2], tau, st->bt, FcSqMul())) {
+    rs.tau_next = tau * o.stepsize_shrink;                                    // same x0 / g0, smaller step (:204-215): the roles stay
+    st->bt += 1;
+    return;
   }
-  double alpha0 = 0.0, alpha1_new = rs.alpha1;
-  bool restarted = false;
-  if (o.accelerate) {                                                         // :220-238 (the launch applied the same restart rule to its coefficient)
-    alpha0 = rs.alpha1;
-    if (o.restart && rdot > 1E-30) { alpha0 = 1.0; restarted = true; }
-    alpha1_new = (1.0 + sqrt(1.0 + 4.0 * (alpha0 * alpha0))) / 2.0;
-    f1 = fval(fsq_adj);                                                       // :245
-  }
-  const double xh2u = o.accelerate ? bq[2] : xh2, gsu = o.accelerate ? bq[3] : gsum, gmu = o.accelerate ? bq[4] : gmax;
-  double tau_nx = tau;                                                        // :249
-  const double dx_norm = sqrt(dx2);
-  if (o.adaptive) {                                                           // :253-270
-    const double dot = bq[0];
-    const double tau_s = (dx_norm * dx_norm) / dot;
-    const double sg = sqrt(bq[1]);
-    const double q = dot / (sg * sg);
-    const double tau_m = 0.0 > q ? 0.0 : q;                                   // Python's max(q, 0)
-    tau_nx = (2.0 * tau_m > tau_s) ? tau_m : tau_s - .5 * tau_m;
-    if (tau_nx <= 0.0 || isinf(tau_nx) || isnan(tau_nx)) tau_nx = tau * 1.5;
-  }
-  const double resid = dx_norm / tau;                                         // :272
-  const double a_ = sqrt(g02), b_ = sqrt(xh2u) / tau;
-  const double normalizer = (b_ > a_ ? b_ : a_) + 1E-12;                      // max(a, b) + EPSILON  (:274)
-  const double norm_resid = resid / normalizer;
-  if (resid > rs.max_residual) rs.max_residual = resid;                       // :281
-  double objective = 0.0, quality = resid;
-  if (o.evaluate_objective) {                                                 // :284-289
-    (void)gmu;
-    objective = f1 + (ch.g_kind == 1 ? ch.mu * gsu : 0.0);
-    quality = objective;
-  }
-  const bool better = quality < rs.best_quality;                              // :298-300
-  if (better) rs.best_quality = quality;
-  bool stop = false;                                                          // stopping.py:6-51
-  const bool ratio = resid / rs.max_residual < o.tolerance, normed = norm_resid < o.tolerance;
-  if (o.stop_rule == 0) stop = resid < o.tolerance;
-  else if (o.stop_rule == 1) stop = normed;
-  else if (o.stop_rule == 2) stop = ratio;
-  else stop = ratio || normed;
-  double* h = ch.hist + (uint64_t)st->steps_done * FR_HIST;
-  h[0] = resid; h[1] = norm_resid; h[2] = tau; h[3] = f1; h[4] = objective; h[5] = (double)st->bt; h[6] = alpha0;
-  h[7] = (better ? 1.0 : 0.0) + (restarted ? 2.0 : 0.0);
-  // commit: fh_commit's pointer bookkeeping on the roles
-  if (o.accelerate) { rs.alpha1 = alpha1_new; rs.pc ^= 1; rs.last_accel = 1; }
-  else { const int x_ = rs.perm[rs.ti], y_ = rs.perm[3 + (rs.pc ^ 1)]; rs.perm[rs.ti] = y_; rs.perm[3 + (rs.pc ^ 1)] = x_; rs.last_accel = 0; }      // std::swap(X[ti], P[pc ^ 1])
-  rs.xi = rs.ti;
-  if (better) rs.bi = rs.xi;
-  for (int k = 0; k < 3; ++k) if (k != rs.xi && k != rs.bi) { rs.ti = k; break; }
-  rs.zc ^= 1; rs.gc ^= 1;
-  rs.f_window[(ita + 1ull) % FR_WINDOW_MAX] = f1;
-  rs.tau_next = tau_nx;
-  st->tau_iter = tau_nx;
-  rs.iteration = ita + 1ull;
-  rs.backtracks += (unsigned long long)st->bt;
+  // (the launch applied the same restart rule to its coefficient)
+  const FcDecision d = fc_decide(o, lsq, ch.g_kind, ch.mu, sums, tau, st->bt, rs.alpha1, rs.max_residual, rs.best_quality,
+                                 ch.hist + (uint64_t)st->steps_done * FR_HIST, FcSqMul());
+  fc_rotate(o.accelerate != 0, d.better, rs.xi, rs.ti, rs.bi, rs.pc, rs.gc, rs.zc, rs.last_accel, rs.perm);      // fh_commit's pointer bookkeeping on the roles
+  fc_advance(rs, d, st->bt);
+  st->tau_iter = d.tau_next;
   st->bt = 0;
   st->steps_done += 1;
-  if (stop) rs.stopped = 1;
 }
 
 // the arguments of this attempt from the state block the previous launch's finaliser left (uniform: every workgroup reads the same block and
@@ -271,8 +214,7 @@ __device__ __forceinline__ bool chain_params(const FusedP& base, const ChainP& c
   p.z = zc ? ch.Z[0] : ch.Z[1];                                               // Z[zc ^ 1]
   p.g1 = gc ? ch.G[0] : ch.G[1];                                              // G[gc ^ 1]
   if (ch.o.accelerate) {
-    const double a1 = (1.0 + sqrt(1.0 + 4.0 * (alpha1 * alpha1))) / 2.0;
-    p.accel = 1; p.restart = ch.o.restart; p.coef = (alpha1 - 1.0) / a1;
+    p.accel = 1; p.restart = ch.o.restart; p.coef = (alpha1 - 1.0) / fc_alpha_next(alpha1, FcSqMul());
     p.xacc0 = chain_sel5(ch.nbuf, pcx ? perm[4] : perm[3]);                   // P[pc]
     p.zacc0 = zc ? ch.Z[1] : ch.Z[0];                                         // Z[zc]
     p.x1 = chain_sel5(ch.nbuf, ti == 0 ? perm[0] : (ti == 1 ? perm[1] : perm[2]));

@@ -38,7 +38,7 @@
 #else
 #define FR_STAMP(i) do { } while (0)
 #endif
-#include "fh_loop.h"
+#include "fh_controller.h"
 struct RunP {
   const double* A;
   uint32_t ld2, n, m, mp, ldp, nv2, nteams, rows_per_team;
@@ -48,7 +48,7 @@ struct RunP {
   int loss, prox_kind;
   int nt;                    // 1 = stream A with non-temporal loads, 0 = default cache policy (a matrix that fits the Infinity Cache is re-read from it)
   double mu, lo, hi;
-  int g_kind;                // g(x) for the objective: 0 = none, 1 = mu * sum|x|, 2 = mu * max|x|
+  int g_kind;                // g(x) for the objective: FC_G_* of fh_controller.h
   RunOpts o;
   int max_steps;
   RunState init;             // the state on entry, BY VALUE (kernel argument: no copy to order against the launch, no cache to go stale)
@@ -74,9 +74,6 @@ __device__ __forceinline__ double fr_sload_glc(const double* ptr) {
   asm volatile("s_load_dwordx2 %0, %1, 0x0 glc\n\ts_waitcnt lgkmcnt(0)" : "=s"(r) : "s"(u) : "memory");
   return __hiloint2double((int)r.y, (int)r.x);
 }
-
-// Python's max(a, b) on floats: a unless b > a (so a NaN in `a` stays)
-__device__ __forceinline__ double fr_pymax(double a, double b) { return b > a ? b : a; }
 
 template <int PPT>
 __global__ __launch_bounds__(FH_WG, 1) void k_run_dense(const RunP p) {
@@ -236,17 +233,8 @@ __global__ __launch_bounds__(FH_WG, 1) void k_run_dense(const RunP p) {
     }
     __syncthreads();
     const double dxg0 = s_ctl[0], dx2 = s_ctl[1], xh2 = s_ctl[2], g02 = s_ctl[3], gsum = s_ctl[4], gmax = s_ctl[5], rdot = s_ctl[6];
-    // FISTA (:220-238): the restart test and the alpha recursion of THIS attempt
-    double alpha0 = 0.0, coef = 0.0, alpha1_new = alpha1;
-    if (o.accelerate) {
-      alpha0 = alpha1;
-      if (o.restart && rdot > 1E-30) alpha0 = 1.0;
-      {
-#pragma clang fp contract(off)
-        alpha1_new = (1.0 + sqrt(1.0 + 4.0 * (alpha0 * alpha0))) / 2.0;
-        coef = (alpha0 - 1.0) / alpha1_new;
-      }
-    }
+    const FcAlpha al = fc_alpha(o, alpha1, rdot, FcSqMul());      // FISTA (:220-238): the restart test and the alpha recursion of THIS attempt
+    const double coef = al.coef;
     __syncthreads();                       // (s_ctl is reused below)
     FR_STAMP(0);
 
@@ -367,67 +355,19 @@ __global__ __launch_bounds__(FH_WG, 1) void k_run_dense(const RunP p) {
     }
     block_reduce<7>(w, s_scr, 6);
     if (tid == 0) {
-      // ---- the host driver's decisions (fasta_python_amd/solver.py:step, line for line), one thread per workgroup, identical everywhere
+      // ---- the host driver's decisions (csrc/fh_controller.h), one thread per workgroup, identical everywhere
 #pragma clang fp contract(off)
-      const double fsq = w[0], fsq_adj = o.accelerate ? w[1] : w[0];
-      auto fval = [&](double s) -> double { if (p.loss != LOSS_LSQ) return s; const double q = sqrt(s); return .5 * (q * q); };
-      double f1 = fval(fsq);
-      bool retry = false;
-      if (o.backtrack) {                                                          // :195-217
-        const unsigned long long ita = it0 + it;
-        const unsigned long long lo_ = ita + 1ull > (unsigned long long)o.window ? ita + 1ull - (unsigned long long)o.window : 0ull;
-        double M = s_win[lo_ % FR_WINDOW_MAX];
-        for (unsigned long long j = lo_ + 1ull; j <= ita; ++j) M = fr_pymax(M, s_win[j % FR_WINDOW_MAX]);
-        const double dxn = sqrt(dx2);
-        if (f1 - (M + dxg0 + (dxn * dxn) / (2.0 * tau)) > 1E-12 && bt < o.max_backtracks) retry = true;
-      }
-      double out[8];
-      if (retry) {
-        out[0] = 1.0; out[1] = tau * o.stepsize_shrink;
-      } else {
-        if (o.accelerate) f1 = fval(fsq_adj);                                    // :245
-        const double xh2u = o.accelerate ? w[4] : xh2, gsu = o.accelerate ? w[5] : gsum, gmu = o.accelerate ? w[6] : gmax;
-        double tau_nx = tau;                                                      // :249
-        const double dx_norm = sqrt(dx2);
-        if (o.adaptive) {                                                         // :253-270
-          const double dot = w[2];
-          const double tau_s = (dx_norm * dx_norm) / dot;
-          const double sg = sqrt(w[3]);
-          const double q = dot / (sg * sg);
-          const double tau_m = 0.0 > q ? 0.0 : q;                                 // Python's max(q, 0)
-          tau_nx = (2.0 * tau_m > tau_s) ? tau_m : tau_s - .5 * tau_m;
-          if (tau_nx <= 0.0 || isinf(tau_nx) || isnan(tau_nx)) tau_nx = tau * 1.5;
-        }
-        const double resid = dx_norm / tau;                                       // :272
-        const double a_ = sqrt(g02), b_ = sqrt(xh2u) / tau;
-        const double normalizer = (b_ > a_ ? b_ : a_) + 1E-12;                    // max(a, b) + EPSILON  (:274)
-        const double norm_resid = resid / normalizer;
-        max_residual = fr_pymax(max_residual, resid);                             // :281
-        double objective = 0.0, quality = resid;
-        if (o.evaluate_objective) {                                               // :284-289
-          const double gval = p.g_kind == 1 ? p.mu * gsu : (p.g_kind == 2 ? p.mu * gmu : 0.0);
-          objective = f1 + gval;
-          quality = objective;
-        }
-        const bool better = quality < best_quality;                               // :298-300
-        if (better) best_quality = quality;
-        bool stop = false;                                                        // stopping.py:6-51
-        const bool ratio = resid / max_residual < o.tolerance, normed = norm_resid < o.tolerance;
-        if (o.stop_rule == 0) stop = resid < o.tolerance;
-        else if (o.stop_rule == 1) stop = normed;
-        else if (o.stop_rule == 2) stop = ratio;
-        else stop = ratio || normed;
-        out[0] = 0.0; out[1] = tau_nx; out[2] = better ? 1.0 : 0.0; out[3] = stop ? 1.0 : 0.0; out[4] = f1;
-        if (team == 0) {
-          double* h = p.hist + (uint64_t)steps * FR_HIST;
-          const bool restarted = o.accelerate && o.restart && rdot > 1E-30;      // (:231-233; the reference prints "Restarted acceleration.")
-          h[0] = resid; h[1] = norm_resid; h[2] = tau; h[3] = f1; h[4] = objective; h[5] = (double)bt; h[6] = alpha0;
-          h[7] = (better ? 1.0 : 0.0) + (restarted ? 2.0 : 0.0);
-        }
+      const double sums[FC_NSUMS] = {w[0], dxg0, dx2, xh2, g02, gsum, gmax, rdot, w[2], w[3], w[1], w[4], w[5], w[6]};
+      const bool lsq = p.loss == LOSS_LSQ;
+      double out[7] = {1.0, tau * o.stepsize_shrink, 0.0, 0.0, 0.0, max_residual, best_quality};
+      if (!fc_backtrack(o, s_win, it0 + it, fc_f(lsq, sums[FC_FSQ], FcSqMul()), dxg0, dx2, tau, bt, FcSqMul())) {
+        const FcDecision d = fc_decide(o, lsq, p.g_kind, p.mu, sums, tau, bt, alpha1, max_residual, best_quality,
+                                       team == 0 ? p.hist + (uint64_t)steps * FR_HIST : nullptr, FcSqMul());
+        out[0] = 0.0; out[1] = d.tau_next; out[2] = d.better ? 1.0 : 0.0; out[3] = d.stop ? 1.0 : 0.0; out[4] = d.f1;
+        out[5] = d.max_residual; out[6] = d.best_quality;
       }
 #pragma unroll
-      for (int k = 0; k < 5; ++k) s_ctl[k] = out[k];
-      s_ctl[5] = max_residual; s_ctl[6] = best_quality;
+      for (int k = 0; k < 7; ++k) s_ctl[k] = out[k];
     }
     __syncthreads();
     FR_STAMP(5);
@@ -470,12 +410,8 @@ __global__ __launch_bounds__(FH_WG, 1) void k_run_dense(const RunP p) {
       s_x0[k * FH_WG + tid] = x1v;
     }
     load_g = true;
-    if (o.accelerate) { alpha1 = alpha1_new; pcx ^= 1; last_accel = 1; }
-    else { const int a_ = perm[ti], b_ = perm[3 + (pcx ^ 1)]; perm[ti] = b_; perm[3 + (pcx ^ 1)] = a_; last_accel = 0; }   // std::swap(X[ti], P[pc ^ 1])
-    xi = ti;
-    if (better) bi = xi;
-    for (int k = 0; k < 3; ++k) if (k != xi && k != bi) { ti = k; break; }
-    zc ^= 1; gc ^= 1;
+    alpha1 = al.alpha1;
+    fc_rotate(o.accelerate != 0, better, xi, ti, bi, pcx, gc, zc, last_accel, perm);      // fh_commit's pointer bookkeeping
     tau = s_ctl[1];
     tau_iter = tau;
     it += 1u;

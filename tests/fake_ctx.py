@@ -14,7 +14,9 @@ from oracle import problems as pr
 
 
 class FakeContext:
-    def __init__(self, fwd, adj, n_shape, m_shape, fused_kind=0):
+    def __init__(self, fwd, adj, n_shape, m_shape, fused_kind=0, controller="numpy"):
+        assert controller in ("numpy", "cxx")
+        self.controller = controller          # who takes the decisions of `iterate`: its NumPy restatement, or csrc/fh_controller.h itself
         self.fwd_op, self.adj_op = fwd, adj
         self.n_shape, self.m_shape = tuple(n_shape), tuple(m_shape)
         self.fused_kind = fused_kind
@@ -169,8 +171,16 @@ class FakeContext:
     def iterate(self, max_steps, o, st):
         """NumPy twin of fh_iterate: the same launches by the same policy, the expressions of fasta_python_amd/solver.py:FBSolver.step for the
         decisions, the same history records and state updates -- so that the CPU tier can drive `FBSolver._library_call` (history slices,
-        state carried from call to call, verbose lines, launch counters) without a GPU."""
+        state carried from call to call, verbose lines, launch counters) without a GPU.
+        With controller="cxx" the launch policy stays here and the two decisions -- the backtracking test, and everything after an accepted
+        attempt -- are taken by the shipped controller (csrc/fh_controller.h through tests/controller_shim.py), as fh_iterate takes them."""
         import math
+        cxx = self.controller == "cxx"
+        if cxx:
+            from tests import controller_shim as shim
+            co, lsq, g_kind = shim.opts_of(o), self.loss != "logistic", shim.G_KIND.get(self.prox_kind, 0)
+            cst = shim.State(**{k: getattr(st, k) for k in ("tau_next", "alpha1", "max_residual", "best_quality", "iteration", "backtracks")})
+            cst.f_window[:] = st.f_window[:]
         sq = lambda v: np.float64(math.sqrt(v))
         fval = (lambda s_: np.float64(s_)) if self.loss == "logistic" else (lambda s_: .5 * sq(s_) ** 2)
         gval = {hip.PROX_SHRINK: lambda gs, gm: self.mu * gs, hip.PROX_LINF: lambda gs, gm: self.mu * gm}.get(self.prox_kind, lambda gs, gm: 0)
@@ -212,7 +222,14 @@ class FakeContext:
                 st.spec_cooldown -= 1
             f1 = fval(s[hip.S_FSQ])
             bt = 0
-            if o.backtrack:
+            if cxx:
+                while shim.backtrack(co, cst, lsq, s, tau, bt):
+                    tau = tau * o.stepsize_shrink
+                    s, have_adj = forward(tau, always, np.float64(st.alpha1))
+                    bt += 1
+                if bt:
+                    st.spec_cooldown = 8
+            elif o.backtrack:
                 lo = max(i - o.window + 1, 0)
                 M = np.array([st.f_window[j % hip.RUN_WINDOW_MAX] for j in range(lo, i + 1)]).max()
                 while f1 - (M + s[hip.S_DXG0] + sq(s[hip.S_DX2]) ** 2 / (2 * tau)) > 1E-12 and bt < o.max_backtracks:
@@ -230,6 +247,19 @@ class FakeContext:
                 alpha1 = (1 + np.sqrt(1 + 4 * alpha0 ** 2)) / 2
                 coef = (alpha0 - 1) / alpha1
             a = s if have_adj else self.adj(tau, bool(o.accelerate), coef)
+            if cxx:
+                d, record = shim.decide(co, cst, lsq, g_kind, self.mu, a, tau, bt)
+                assert d.coef == coef and d.restarted == restarted          # (what K-adj was given is what the decision works with)
+                self.commit(save_best=d.better)
+                hist[step] = record
+                for k in ("tau_next", "alpha1", "max_residual", "best_quality", "iteration", "backtracks"):
+                    setattr(st, k, getattr(cst, k))
+                st.f_window[:] = cst.f_window[:]
+                done = step + 1
+                if d.stop:
+                    st.stopped = 1
+                    break
+                continue
             if o.accelerate:
                 f1 = fval(a[hip.S_FSQ_ADJ])
                 xh2, gsum, gmax = a[hip.S_XH2_ADJ], a[hip.S_GSUM_ADJ], a[hip.S_GMAX_ADJ]
@@ -281,16 +311,16 @@ class FakeContext:
 class FakeDenseMap(_DeviceMap):
     """Device-map look-alike over a host matrix (bypasses HipContext creation)."""
 
-    def __init__(self, A, fused_kind=0):
+    def __init__(self, A, fused_kind=0, controller="numpy"):
         A = np.asarray(A, dtype=float)
         self.matrix = A
         self.shape = A.shape
-        self.ctx = FakeContext(lambda x: A @ x, lambda y: A.T @ y, (A.shape[1],), (A.shape[0],), fused_kind)
+        self.ctx = FakeContext(lambda x: A @ x, lambda y: A.T @ y, (A.shape[1],), (A.shape[0],), fused_kind, controller)
         LinearMap.__init__(self, self.ctx.fwd_op, self.ctx.adj_op, (A.shape[1],), (A.shape[0],))
 
 
 class FakeStencilMap(_DeviceMap):
-    def __init__(self, image_shape, fused_kind=2):
+    def __init__(self, image_shape, fused_kind=2, controller="numpy"):
         H, W = image_shape
-        self.ctx = FakeContext(pr.div, pr.grad, (H, W, 2), (H, W), fused_kind)
+        self.ctx = FakeContext(pr.div, pr.grad, (H, W, 2), (H, W), fused_kind, controller)
         LinearMap.__init__(self, pr.div, pr.grad, (H, W, 2), (H, W))

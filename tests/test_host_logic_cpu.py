@@ -8,6 +8,7 @@ import pytest
 
 import fasta_python_amd as fa
 from fasta_python_amd import stopping as fstop
+from tests import controller_shim
 from tests import helpers as H
 from tests.fake_ctx import FakeDenseMap, FakeStencilMap
 from tests.gpu_util import TAGS
@@ -15,15 +16,21 @@ from tests.gpu_util import TAGS
 CASES = [n for n in H.golden_cases() if not n.startswith("c1_")]
 
 
-def _run(name, fused, dense_kind=1, **extra):
+@pytest.fixture(scope="session")
+def shipped_controller(tmp_path_factory):
+    """csrc/fh_controller.h built for the host, once per session (tests/controller_shim.py); a compiler that is missing or fails is an error"""
+    return controller_shim.build(tmp_path_factory.mktemp("controller_shim"))
+
+
+def _run(name, fused, dense_kind=1, controller="numpy", **extra):
     meta, z = H.load_case(name)
     data = H.case_data(meta, z)
     kind = meta["kind"]
     if kind == "tv":
-        A = FakeStencilMap(data["M"].shape, fused_kind=2 if fused else 0)
+        A = FakeStencilMap(data["M"].shape, fused_kind=2 if fused else 0, controller=controller)
         loss, x0 = fa.LeastSquares(data["M"] / float(data["mu"])), np.zeros(data["M"].shape + (2,))
     else:
-        A = FakeDenseMap(data["A"], fused_kind=dense_kind if fused else 0)
+        A = FakeDenseMap(data["A"], fused_kind=dense_kind if fused else 0, controller=controller)
         loss = fa.LogisticLoss(data["b"]) if kind == "logistic" else fa.LeastSquares(data["b"])
         x0 = np.zeros(data["A"].shape[1])
     reg = TAGS[kind](data)
@@ -74,18 +81,22 @@ def test_driver_reproduces_reference_run(name, fused):
         assert ctx.calls["pair"] == 0
 
 
-@pytest.mark.parametrize("fused", [False, True, 3])
+# (the "numpy" cases keep the ids they had before the controller became a parameter: name-False, name-True, name-3)
+@pytest.mark.parametrize("fused, controller", [pytest.param(f, c, id=str(f) + ("" if c == "numpy" else "-" + c))
+                                               for c in ("numpy", "cxx") for f in (False, True, 3)])
 @pytest.mark.parametrize("name", CASES)
-def test_library_loop_plumbing_equals_the_python_driver(name, fused):
+def test_library_loop_plumbing_equals_the_python_driver(name, fused, controller, shipped_controller):
     """Round 6: by default the decisions between two launches are taken by the library's host-side loop (fh_iterate) in calls of several
     iterations; `FBSolver._library_call` slices its history records into the reference's arrays and carries solver state and launch policy
     from call to call.  With the NumPy twin of fh_iterate on the stand-in context (tests/fake_ctx.py) that plumbing runs on the CPU tier:
     every fixture, calls of 7 iterations and time-sized calls, against the Python driver -- EQUAL histories, counts, solutions and launch
-    counters (the same launches produced the same numbers); options that need Python between iterations keep `step()`."""
+    counters (the same launches produced the same numbers); options that need Python between iterations keep `step()`.
+    controller="cxx": the twin keeps the launch policy and takes its decisions from the controller that ships (csrc/fh_controller.h, built for
+    the host with libm's pow as its square) -- the same equality, of the C++ itself."""
     meta, z, py, ctx_py = _run(name, bool(fused), dense_kind=3 if fused == 3 else 1, driver="python")
     needs_python = bool(meta["options"].get("record_iterates") or meta["options"].get("func"))
     for kw in (dict(driver="library", device_iters=7), {}):
-        _, _, lib, ctx = _run(name, bool(fused), dense_kind=3 if fused == 3 else 1, **kw)
+        _, _, lib, ctx = _run(name, bool(fused), dense_kind=3 if fused == 3 else 1, controller=controller, **kw)
         assert lib.library_steps == (0 if needs_python else lib.iteration_count) and py.library_steps == 0
         assert lib.iteration_count == py.iteration_count and lib.backtracks == py.backtracks
         for f in ("residuals", "norm_residuals", "stepsizes", "objectives", "function_hist", "iterates", "solution"):
@@ -94,6 +105,30 @@ def test_library_loop_plumbing_equals_the_python_driver(name, fused):
             if a is not None:
                 assert np.array_equal(a, b, equal_nan=True), f
         assert ctx.calls == ctx_py.calls
+
+
+@pytest.mark.parametrize("nan_at", range(5))
+def test_shipped_controller_window_with_a_nan_does_not_backtrack(nan_at, shipped_controller):
+    """The window maximum of the backtracking test is `f_hist[lo : i + 1].max()` (fasta/__init__.py:197): ndarray.max, where a NaN ANYWHERE in
+    the window wins, so the test compares against NaN and nothing backtracks -- wherever the NaN sits, also behind larger finite values
+    (a maximum by `v > M` alone would skip it there).  Same sums without the NaN: the attempt is rejected."""
+    window = [3.0, 1.0, 7.0, 2.0, 5.0]
+    o = controller_shim.Opts(backtrack=1, window=len(window), max_backtracks=20, stepsize_shrink=0.2)
+    s = np.zeros(16)
+    s[0], s[2] = 2 * 100.0, 1.0                        # f1 = .5 * sqrt(200) ** 2 = 100 > max(window) + <Dx, g0> + ||Dx||^2 / (2 tau)
+    for base in (0, 62):                               # ... also where the window wraps round the ring of 64
+        st = controller_shim.State(iteration=base + len(window) - 1)
+        for j, v in enumerate(window):
+            st.f_window[(base + j) % 64] = v
+        M = np.array(window).max()
+        assert controller_shim.backtrack(o, st, True, s, 1.0, 0) == bool(100.0 - (M + 0.0 + 1.0 / 2.0) > 1E-12) == True
+        st.f_window[(base + nan_at) % 64] = np.nan
+        poisoned = np.array(window)
+        poisoned[nan_at] = np.nan
+        with np.errstate(invalid="ignore"):
+            want = bool(100.0 - (poisoned.max() + 0.0 + 1.0 / 2.0) > 1E-12)
+        assert want is False
+        assert controller_shim.backtrack(o, st, True, s, 1.0, 0) == want
 
 
 @pytest.mark.parametrize("name", ["sparse_ls_64x128_accelerated", "sparse_ls_unnormalised_backtracks", "tv_32x32_adaptive"])
