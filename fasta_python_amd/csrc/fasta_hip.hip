@@ -16,6 +16,7 @@
 #include "../../include/fasta_hip.h"
 #include "fh_experimental.h"
 #include "fh_dense.h"
+#include "fh_multi.h"
 #include "fh_tv.h"
 #include "fh_prox.h"
 #include "fh_fused.h"
@@ -104,6 +105,12 @@ static const SetupEntry kSetupTable[] = {
 #undef SETUP_INST_0
 #undef SETUP_INST_1
 #undef SETUP_INST_2
+
+#ifdef FH_SINGLE_TU
+#define MC_INSTANTIATE(LB, CH, R) MC_KERNELS(template, LB, CH, R)
+MC_FOR_EACH(MC_INSTANTIATE)
+#undef MC_INSTANTIATE
+#endif
 
 #include "fh_host_ctx.h"
 #include "fh_host_launch.h"
@@ -538,10 +545,41 @@ extern "C" int fh_shape(fh_ctx* c, uint64_t* m, uint64_t* n) {
   return 0;
 }
 
+// ---- multi-column form: the unknown is an (n, L) matrix, B and Z are (m, L); one A for all columns (csrc/fh_multi.h) ----
+extern "C" int fh_set_rhs(fh_ctx* c, uint32_t L) {
+  if (!c) return fail(FH_E_ARG, "null context");
+  if (L > 16) return fail(FH_E_ARG, "fh_set_rhs: at most 16 columns (got %u)", L);
+  if (!c->shards.empty() || c->owner) return fail(FH_E_STATE, "fh_set_rhs: a multi-device context has no multi-column form");
+  if (c->comm) return fail(FH_E_STATE, "fh_set_rhs: a context with a communicator (row-sharded run) has no multi-column form");
+  if (c->pending_step) return fail(FH_E_STATE, "a step issued by fh_step_begin is still in flight on this context: call fh_step_end first");
+  if (c->op == OP_NONE) return fail(FH_E_STATE, "fh_set_rhs: set the dense operator first (fh_set_matrix / fh_generate_matrix)");
+  if (c->op != OP_DENSE) return fail(FH_E_STATE, "fh_set_rhs: the stencil operator has no multi-column form");
+  if (c->f32) return fail(FH_E_STATE, "fh_set_rhs: float32 storage of A has no multi-column form");
+  if (L && c->has_b && c->loss_kind != LOSS_LSQ) return fail(FH_E_STATE, "fh_set_rhs: the logistic loss has no multi-column form");
+  if (L && !mc_prox_ok(c->prox_kind)) return fail(FH_E_STATE, "fh_set_rhs: prox kind %d (LINF / L1BALL / TVBALL) has no multi-column form", c->prox_kind);
+  const uint32_t LB = L == 0 ? 0u : (L <= 2 ? 2u : (L <= 4 ? 4u : (L <= 8 ? 8u : 16u)));
+  FH_TRY(use_device(c));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  // every vector buffer changes its size: they start over as zeros (padding columns stay zero from here on), the loss has to be set again
+  free_vectors(c);
+  c->L = L; c->LB = LB;
+  c->has_b = false; c->loss_kind = LOSS_LSQ;
+  c->lazy = false; c->last_accel = false; c->commits = 0;
+  if (!L && c->prox_kind == FH_PROX_GROUP) { c->prox_kind = FH_PROX_IDENTITY; c->mu = 0.0; }
+  FH_TRY(alloc_vectors(c));
+  return finish(c);
+}
+extern "C" int fh_rhs(fh_ctx* c, uint32_t* L) {
+  if (!c || !L) return fail(FH_E_ARG, "null argument");
+  *L = c->LB ? c->L : 0u;
+  return 0;
+}
+
 static int set_loss(fh_ctx* c, int kind, const double* b, uint64_t len) {
   if (!c || !b) return fail(FH_E_ARG, "null argument");
   if (c->op == OP_NONE) return fail(FH_E_STATE, "set the operator before the loss");
-  if (len != c->m) return fail(FH_E_ARG, "b has %llu entries, operator has %llu rows", (unsigned long long)len, (unsigned long long)c->m);
+  if (len != c->m * l_of(c)) return fail(FH_E_ARG, "b has %llu entries, operator has %llu rows (x %llu columns)", (unsigned long long)len, (unsigned long long)c->m, (unsigned long long)l_of(c));
+  if (kind != LOSS_LSQ && c->LB) return fail(FH_E_STATE, "the logistic loss has no multi-column form (fh_set_rhs)");
   if (kind != LOSS_LSQ && c->op != OP_DENSE) return fail(FH_E_STATE, "the logistic loss is implemented for the dense operator");
   if (!c->shards.empty()) {          // shell: b is sharded like the rows
     for (int k = 0; k < nshards(c); ++k) FH_TRY(set_loss(c->shards[k], kind, b + c->shard_row0[k], shard_rows(c, k)));
@@ -549,7 +587,7 @@ static int set_loss(fh_ctx* c, int kind, const double* b, uint64_t len) {
     return 0;
   }
   FH_TRY(use_device(c));
-  HIP_TRY(hipMemcpyAsync(c->b, b, len * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  FH_TRY(copy_in(c, c->b, b, c->m));
   c->has_b = true;
   c->loss_kind = kind;
   return finish(c);
@@ -565,7 +603,9 @@ extern "C" int fh_set_loss_logistic(fh_ctx* c, const double* labels, uint64_t le
 
 extern "C" int fh_set_prox(fh_ctx* c, int kind, double mu, double lo, double hi) {
   if (!c) return fail(FH_E_ARG, "null context");
-  if (kind < FH_PROX_IDENTITY || kind > FH_PROX_BOX) return fail(FH_E_ARG, "unknown prox kind %d", kind);
+  if (kind < FH_PROX_IDENTITY || kind > FH_PROX_GROUP) return fail(FH_E_ARG, "unknown prox kind %d", kind);
+  if (kind == FH_PROX_GROUP && !c->LB) return fail(FH_E_ARG, "FH_PROX_GROUP (row-wise l2 shrink) needs the multi-column form: call fh_set_rhs first");
+  if (c->LB && !mc_prox_ok(kind)) return fail(FH_E_ARG, "prox kind %d (LINF / L1BALL / TVBALL) has no multi-column form", kind);
   if (kind == FH_PROX_BOX && !(lo <= hi)) return fail(FH_E_ARG, "box prox needs lo <= hi");
   for (fh_ctx* s : c->shards) { s->prox_kind = kind; s->mu = mu; s->lo = lo; s->hi = hi; }      // the prox is replicated work
   c->prox_kind = kind; c->mu = mu; c->lo = lo; c->hi = hi;
@@ -591,7 +631,7 @@ extern "C" int fh_set_vector(fh_ctx* c, int which, const double* host, uint64_t 
   if (!d) return fail(FH_E_ARG, "unknown vector id %d", which);
   if (len != want) return fail(FH_E_ARG, "vector %d has length %llu, got %llu", which, (unsigned long long)want, (unsigned long long)len);
   FH_TRY(use_device(c));
-  HIP_TRY(hipMemcpyAsync(d, host, len * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  FH_TRY(copy_in(c, d, host, len / l_of(c)));
   if (which == FH_VEC_B) c->has_b = true;
   return finish(c);
 }
@@ -617,7 +657,7 @@ extern "C" int fh_get_vector(fh_ctx* c, int which, double* host, uint64_t len) {
   }
   if (!d) return fail(FH_E_ARG, "unknown vector id %d", which);
   if (len != want) return fail(FH_E_ARG, "vector %d has length %llu, got %llu", which, (unsigned long long)want, (unsigned long long)len);
-  HIP_TRY(hipMemcpyAsync(host, d, len * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  FH_TRY(copy_out(c, host, d, len / l_of(c)));
   return finish(c);
 }
 
@@ -652,7 +692,7 @@ extern "C" int fh_init(fh_ctx* c, double* scalars) {
     FH_TRY(use_device(s));
     double* x0 = s->X[s->xi];
     // x_accel1 := x0, best := x0 ; g(x0) terms for objective_hist[0] (:143) come from the host wrapper via FH_VEC ops
-    HIP_TRY(hipMemcpyAsync(s->P[s->pc], x0, s->nv * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
+    HIP_TRY(hipMemcpyAsync(s->P[s->pc], x0, s->nv * lb_of(s) * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
     s->bi = s->xi;                         // best iterate := x0 (fasta/__init__.py:167), by reference
     for (int q = 0; q < 3; ++q) if (q != s->xi) { s->ti = q; break; }
     s->last_accel = false;
@@ -862,7 +902,7 @@ extern "C" int fh_gradient_at(fh_ctx* c, int src_vec, int dst_vec) {
     uint64_t l1 = 0, l2 = 0;
     double* src = vec_ptr(s, src_vec, &l1);
     double* dst = vec_ptr(s, dst_vec, &l2);
-    if (!src || !dst || l1 != s->n || l2 != s->n) return fail(FH_E_ARG, "fh_gradient_at needs two n-length vectors");
+    if (!src || !dst || l1 != s->n * l_of(s) || l2 != l1 || m_side(src_vec) || m_side(dst_vec)) return fail(FH_E_ARG, "fh_gradient_at needs two n-length vectors");
     if (plain_pair_fused_ok(s)) {
       bool ok = false;
       FH_TRY(plain_pair_fused(s, src, s->zt, dst, &ok));
@@ -889,6 +929,11 @@ static int diff_norm_sq(fh_ctx* c, int vec_a, int vec_b, double* sumsq) {
   double* a = vec_ptr(c, vec_a, &l1);
   double* b = vec_ptr(c, vec_b, &l2);
   if (!a || !b || l1 != l2) return fail(FH_E_ARG, "fh_diff_norm needs two vectors of equal length");
+  if (c->LB) {                                  // the whole device buffers: padding rows and columns are zero in both operands
+    if (m_side(vec_a) != m_side(vec_b)) return fail(FH_E_ARG, "fh_diff_norm needs two vectors of equal shape");
+    l1 = (m_side(vec_a) ? c->mv : c->nv) * c->LB;
+  }
+  if (l1 >= ((uint64_t)1 << 32)) return fail(FH_E_ARG, "fh_diff_norm: vector too long");
   const unsigned grid = (unsigned)std::min<uint64_t>((l1 + FH_WG - 1) / FH_WG, 1024);
   FH_TRY(ensure_ws(c, grid * sizeof(double)));
   k_diff_sq<<<dim3(grid), dim3(FH_WG), 0, c->stream>>>(a, b, (uint32_t)l1, c->ws, c->counters + CNT_AUX, c->dscal + FH_NSCALARS + 1);
@@ -1065,6 +1110,7 @@ static int dense_step(fh_ctx* c, double tau, int accel, double coef, int restart
 // Writes the complete FH_S_* block; scalars[15] != 0 reports a spin timeout (results invalid: use the two-launch path).
 static int step_body(fh_ctx* c, double tau, double* scalars, bool wait) {
   FH_TRY(check_ready(c, true));
+  if (c->LB) return fail(FH_E_STATE, "fh_step: the multi-column form (fh_set_rhs) has no one-pass kernel: use fh_fwd / fh_adj / fh_iterate");
   for (int k = 0; k < nshards(c); ++k) FH_TRY(not_lazy(shard_of(c, k), "fh_step"));
   if (c->op == OP_STENCIL) {
     if (row_sharded(c)) return fail(FH_E_STATE, "row sharding is implemented for the dense operator only");
@@ -1109,6 +1155,7 @@ extern "C" int fh_step_end(fh_ctx* c, double* scalars) {
 // travels to the separate n-side epilogue through a device scalar.
 extern "C" int fh_step_accel(fh_ctx* c, double tau, double coef, int restart, double* scalars) {
   FH_TRY(check_ready(c, true));
+  if (c->LB) return fail(FH_E_STATE, "fh_step_accel: the multi-column form (fh_set_rhs) has no one-pass kernel: use fh_fwd / fh_adj / fh_iterate");
   if (c->op == OP_STENCIL) {
     if (row_sharded(c)) return fail(FH_E_STATE, "row sharding is implemented for the dense operator only");
     if (!c->lazy) {      // first accelerated one-pass step after fh_init: x0 = X[xi] (c = 0), z(x0) = Z[zc], best = x0
@@ -1142,7 +1189,7 @@ static const RunEntry kRunTable[] = {{1, k_run_dense<1>}, {2, k_run_dense<2>}, {
 // (16 pieces per lane -- n in (7168, 8192] -- were measured and left out: 8192^2 158 us per iteration against 140 us on the per-iteration path,
 //  profiles/r05_device_loop.txt)
 static const RunEntry* run_entry(fh_ctx* c) {
-  if (c->op != OP_DENSE || c->f32 || row_sharded(c) || !c->shards.empty()) return nullptr;
+  if (c->op != OP_DENSE || c->f32 || c->LB || row_sharded(c) || !c->shards.empty()) return nullptr;
   if (c->prox_kind != FH_PROX_IDENTITY && c->prox_kind != FH_PROX_SHRINK && c->prox_kind != FH_PROX_NONNEG && c->prox_kind != FH_PROX_BOX) return nullptr;
   // a workgroup owns whole rows: 16-byte pieces per lane = the first table entry that covers the row (lanes past the row's end re-read its last piece)
   const uint64_t pieces = round_up(c->n, 16) / 2;
@@ -1212,7 +1259,7 @@ static void run_opts_in(const fh_run_opts* o, RunOpts* r) {
   r->stepsize_shrink = o->stepsize_shrink; r->tolerance = o->tolerance;
 }
 // g(x) from the prox's reductions (proximal.py: g_from_sums)
-static int g_kind_of(const fh_ctx* c) { return c->prox_kind == FH_PROX_SHRINK ? FC_G_SUM : (c->prox_kind == FH_PROX_LINF ? FC_G_MAX : FC_G_NONE); }
+static int g_kind_of(const fh_ctx* c) { return (c->prox_kind == FH_PROX_SHRINK || c->prox_kind == FH_PROX_GROUP) ? FC_G_SUM : (c->prox_kind == FH_PROX_LINF ? FC_G_MAX : FC_G_NONE); }
 static int run_adopt(fh_ctx* c, const fh_run_opts* o, const RunState* hs, double* const (&nb)[5], int max_steps, fh_run_state* state, double* history, int* steps_done, const char* what);
 static int run_chain(fh_ctx* c, int max_steps, const fh_run_opts* o, fh_run_state* state, double* history, int* steps_done);
 extern "C" int fh_run(fh_ctx* c, int max_steps, const fh_run_opts* o, fh_run_state* state, double* history, int* steps_done) {
@@ -1221,6 +1268,7 @@ extern "C" int fh_run(fh_ctx* c, int max_steps, const fh_run_opts* o, fh_run_sta
   if (max_steps < 0 || max_steps > 65536) return fail(FH_E_ARG, "fh_run: max_steps must be in [0, 65536]");
   if (o->window < 1 || o->window > FH_RUN_WINDOW_MAX) return fail(FH_E_ARG, "fh_run: window must be in [1, %d]", FH_RUN_WINDOW_MAX);
   if (o->stop_rule < 0 || o->stop_rule > 3) return fail(FH_E_ARG, "fh_run: stop_rule must be 0..3 (the four rules of fasta/stopping.py)");
+  if (c->LB) return fail(FH_E_STATE, "fh_run: the multi-column form (fh_set_rhs) has no device-side loop: use fh_iterate");
   const RunEntry* e = run_entry(c);
   if (!e && chain_ok(c) && co_resident(c)) return run_chain(c, max_steps, o, state, history, steps_done);
   if (!e || !co_resident(c)) return fail(FH_E_STATE, "fh_run: no device-side loop for this operator / loss / prox (see fh_run_supported)");
@@ -1416,11 +1464,11 @@ extern "C" int fh_apply(fh_ctx* c, int adjoint, const double* in, double* out) {
     const uint64_t r0 = shell ? c->shard_row0[k] : 0;       // rows of the whole operator this shard holds: [r0, r0 + s->m)
     FH_TRY(use_device(s));
     if (!adjoint) {
-      HIP_TRY(hipMemcpyAsync(s->T[3], in, s->n * sizeof(double), hipMemcpyHostToDevice, s->stream));
+      FH_TRY(copy_in(s, s->T[3], in, s->n));
       FH_TRY(op_fwd(s, 1, 0.0, s->T[3], nullptr, nullptr, nullptr, nullptr, s->zt, 0));
-      HIP_TRY(hipMemcpyAsync(out + r0, s->zt, s->m * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+      FH_TRY(copy_out(s, out + r0, s->zt, s->m));
     } else {
-      HIP_TRY(hipMemcpyAsync(s->zt, in + r0, s->m * sizeof(double), hipMemcpyHostToDevice, s->stream));
+      FH_TRY(copy_in(s, s->zt, in + r0, s->m));
       AdjIO io = {s->zt, nullptr, 0, 0, 0.0, 1, 1.0, nullptr, nullptr, nullptr, nullptr, nullptr, s->T[3]};
       FH_TRY(adj_local(s, io));
     }
@@ -1429,7 +1477,7 @@ extern "C" int fh_apply(fh_ctx* c, int adjoint, const double* in, double* out) {
     FH_TRY(adj_sum(c, [](fh_ctx* s) { return s->T[3]; }));
     fh_ctx* s0 = shard_of(c, 0);
     FH_TRY(use_device(s0));
-    HIP_TRY(hipMemcpyAsync(out, s0->T[3], s0->n * sizeof(double), hipMemcpyDeviceToHost, s0->stream));
+    FH_TRY(copy_out(s0, out, s0->T[3], s0->n));
   }
   return finish(c);
 }
@@ -1449,6 +1497,7 @@ extern "C" int fh_comm_unique_id(void* id128) {
 extern "C" int fh_comm_init(fh_ctx* c, int nranks, int rank, const void* id128) {
   if (!c || !id128) return fail(FH_E_ARG, "null argument");
   if (nranks < 1 || rank < 0 || rank >= nranks) return fail(FH_E_ARG, "bad rank %d of %d", rank, nranks);
+  if (c->LB) return fail(FH_E_STATE, "fh_comm_init: a context in multi-column form (fh_set_rhs) cannot be row-sharded");
   if (!c->shards.empty() || c->owner)
     return fail(FH_E_STATE, "fh_comm_init: a multi-device context (fh_create_ex, ndev > 1) already shards the rows in-process");
   FH_TRY(rccl_load());

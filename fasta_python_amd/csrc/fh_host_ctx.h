@@ -107,7 +107,8 @@ struct fh_ctx {
   uint64_t m = 0, n = 0;     // logical (local) rows / columns of A   (stencil: m = H*W, n = 2*H*W)
   uint64_t mp = 0, ld = 0;   // padded rows, device leading dimension in elements (dense)
   int f32 = 0;               // storage of A: 0 = float64, 1 = float32 (opt-in, fh_create_ex; vectors and arithmetic stay float64)
-  uint64_t nv = 0, mv = 0;   // allocated n-side / m-side vector lengths (doubles)
+  uint64_t nv = 0, mv = 0;   // allocated n-side / m-side vector lengths (doubles; rows of LB doubles in multi-column form)
+  uint32_t L = 0, LB = 0;    // multi-column form (fh_set_rhs, csrc/fh_multi.h): L columns per unknown, kept as LB in {2, 4, 8, 16} doubles per row; 0 = the vector form
   uint64_t H = 0, W = 0;
   double* A = nullptr;
   size_t a_block_bytes = 0;  // size of the block A lives in (>= the matrix: a kept block may be up to twice as large, see acquire_matrix_block)
@@ -119,6 +120,7 @@ struct fh_ctx {
   double* P[2] = {nullptr, nullptr};   // prox outputs: x_accel1 / x_accel0
   double* G[2] = {nullptr, nullptr};   // g0 / g1
   double* xhat = nullptr;
+  double* xs = nullptr;      // multi-column form: K-fwd's operand in its streaming layout (csrc/fh_multi.h: mc_pack_row)
   double* T[4] = {nullptr, nullptr, nullptr, nullptr};
   int pc = 0, gc = 0, zc = 0;
   bool last_accel = false;
@@ -247,6 +249,9 @@ enum { CNT_FWD = 0, CNT_ADJ_FIN = 1, CNT_AUX = 2, CNT_FUSED_BAR = 4, CNT_FUSED_E
        CNT_DIAG = kCounterWords - 8 };     // the last 8 words only ever grow: [0] level searches that fell back to one workgroup, [1] ... that found no level (fh_recovered_count)
 
 static inline uint64_t round_up(uint64_t v, uint64_t q) { return (v + q - 1) / q * q; }
+// multi-column form: doubles per device row of a vector buffer, columns per host row (both 1 in the vector form)
+static inline uint64_t lb_of(const fh_ctx* c) { return c->LB ? c->LB : 1u; }
+static inline uint64_t l_of(const fh_ctx* c) { return c->LB ? c->L : 1u; }
 
 // device scratch that is released on every exit path (the HIP_TRY macros return early)
 struct DevBuf {
@@ -344,15 +349,21 @@ static void release_cached_blocks(int device /* -1 = all */) {
   }
 }
 
+static void free_vectors(fh_ctx* c) {
+  auto fr = [](double*& p) { if (p) { (void)hipFree(p); p = nullptr; } };
+  for (int i = 0; i < 2; ++i) { fr(c->P[i]); fr(c->G[i]); fr(c->Z[i]); }
+  for (int i = 0; i < 3; ++i) fr(c->X[i]);
+  fr(c->xhat); fr(c->xs); fr(c->b); fr(c->zt); fr(c->ZX[0]); fr(c->ZX[1]);
+  for (int i = 0; i < 4; ++i) fr(c->T[i]);
+}
+
 static void free_operator(fh_ctx* c) {
   for (fh_ctx* s : c->shards) { (void)hipSetDevice(s->device); free_operator(s); }
   auto fr = [](double*& p) { if (p) { (void)hipFree(p); p = nullptr; } };
   if (c->A && c->op == OP_DENSE) { release_matrix_block(c->device, c->A, c->a_block_bytes); c->A = nullptr; c->a_block_bytes = 0; }
   fr(c->A);
-  for (int i = 0; i < 2; ++i) { fr(c->P[i]); fr(c->G[i]); fr(c->Z[i]); }
-  for (int i = 0; i < 3; ++i) fr(c->X[i]);
-  fr(c->xhat); fr(c->b); fr(c->zt); fr(c->ZX[0]); fr(c->ZX[1]);
-  for (int i = 0; i < 4; ++i) fr(c->T[i]);
+  free_vectors(c);
+  c->L = c->LB = 0;                  // a new operator starts in the vector form
   fr(c->ws); c->ws_bytes = 0;
   fr(c->slotbuf); c->slotbuf_bytes = 0; c->slots_sig = 0;
   c->op = OP_NONE; c->has_b = false;
@@ -365,18 +376,20 @@ static int alloc_zero(fh_ctx* c, double** p, uint64_t elems) {
 }
 
 static int alloc_vectors(fh_ctx* c) {
+  const uint64_t nvl = c->nv * lb_of(c), mvl = c->mv * lb_of(c);
   // +16 slack doubles on the n-side so sharded runs can append scalars to the all-reduce buffer
   for (int i = 0; i < 2; ++i) {
-    FH_TRY(alloc_zero(c, &c->P[i], c->nv + 16));
-    FH_TRY(alloc_zero(c, &c->G[i], c->nv + 16));
-    FH_TRY(alloc_zero(c, &c->Z[i], c->mv + 16));
+    FH_TRY(alloc_zero(c, &c->P[i], nvl + 16));
+    FH_TRY(alloc_zero(c, &c->G[i], nvl + 16));
+    FH_TRY(alloc_zero(c, &c->Z[i], mvl + 16));
   }
-  FH_TRY(alloc_zero(c, &c->xhat, c->nv + 16));
-  for (int i = 0; i < 3; ++i) FH_TRY(alloc_zero(c, &c->X[i], c->nv + 16));
-  for (int i = 0; i < 4; ++i) FH_TRY(alloc_zero(c, &c->T[i], c->nv + 16));
-  FH_TRY(alloc_zero(c, &c->b, c->mv + 16));
-  FH_TRY(alloc_zero(c, &c->zt, c->mv + 16));
-  if (c->op_pending_stencil) { FH_TRY(alloc_zero(c, &c->ZX[0], c->mv + 16)); FH_TRY(alloc_zero(c, &c->ZX[1], c->mv + 16)); }
+  FH_TRY(alloc_zero(c, &c->xhat, nvl + 16));
+  if (c->LB) FH_TRY(alloc_zero(c, &c->xs, nvl + 16));
+  for (int i = 0; i < 3; ++i) FH_TRY(alloc_zero(c, &c->X[i], nvl + 16));
+  for (int i = 0; i < 4; ++i) FH_TRY(alloc_zero(c, &c->T[i], nvl + 16));
+  FH_TRY(alloc_zero(c, &c->b, mvl + 16));
+  FH_TRY(alloc_zero(c, &c->zt, mvl + 16));
+  if (c->op_pending_stencil) { FH_TRY(alloc_zero(c, &c->ZX[0], mvl + 16)); FH_TRY(alloc_zero(c, &c->ZX[1], mvl + 16)); }
   c->pc = c->gc = c->zc = c->zxc = 0;
   c->xi = 0; c->ti = 1; c->bi = 0;
   c->zcur = nullptr;
@@ -582,7 +595,7 @@ static int sum_over_shards(fh_ctx* c, Sel sel, size_t count) {
 // ---- vector access --------------------------------------------------------------------------------
 static double* vec_ptr(fh_ctx* c, int which, uint64_t* len) {
   const bool acc = c->last_accel;
-  *len = c->n;
+  *len = c->n * l_of(c);             // host length: (n, L) row-major in multi-column form
   // the stencil path never materialises the gradient or xhat (fh_tv.h): those ids are not addressable there
   if (c->op == OP_STENCIL && (which == FH_VEC_G0 || which == FH_VEC_G1 || which == FH_VEC_XHAT)) return nullptr;
   switch (which) {
@@ -593,11 +606,38 @@ static double* vec_ptr(fh_ctx* c, int which, uint64_t* len) {
     case FH_VEC_X1: return acc ? c->X[c->ti] : c->P[c->pc ^ 1];
     case FH_VEC_G1: return c->G[c->gc ^ 1];
     case FH_VEC_BEST: return c->X[c->bi];
-    case FH_VEC_B: *len = c->m; return c->b;
-    case FH_VEC_Z: *len = c->m; return c->Z[c->zc ^ 1];
+    case FH_VEC_B: *len = c->m * l_of(c); return c->b;
+    case FH_VEC_Z: *len = c->m * l_of(c); return c->Z[c->zc ^ 1];
     case FH_VEC_T0: case FH_VEC_T1: case FH_VEC_T2: case FH_VEC_T3: return c->T[which - FH_VEC_T0];
     default: return nullptr;
   }
+}
+
+// `rows` logical rows between a contiguous row-major host array ((rows, L) in multi-column form) and a device buffer ((.., LB), whose padding
+// columns are never touched and therefore stay zero).  The multi-column form moves the array as ONE contiguous copy to / from the workspace
+// and re-strides it on the device (a strided copy of rows of 8..128 bytes would be one small transfer per row); everything is ordered on
+// the context's stream, like every other user of the workspace.
+static __global__ __launch_bounds__(FH_WG) void k_mc_restride(double* dst, uint32_t dst_ld, const double* src, uint32_t src_ld, uint32_t L, uint64_t count) {
+  for (uint64_t t = (uint64_t)blockIdx.x * FH_WG + threadIdx.x; t < count; t += (uint64_t)gridDim.x * FH_WG)
+    dst[t / L * dst_ld + t % L] = src[t / L * src_ld + t % L];
+}
+static int copy_in(fh_ctx* c, double* dev, const double* host, uint64_t rows) {
+  if (!c->LB) { HIP_TRY(hipMemcpyAsync(dev, host, rows * sizeof(double), hipMemcpyHostToDevice, c->stream)); return 0; }
+  const uint64_t count = rows * c->L;
+  FH_TRY(ensure_ws(c, count * sizeof(double)));
+  HIP_TRY(hipMemcpyAsync(c->ws, host, count * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  k_mc_restride<<<dim3((unsigned)std::min<uint64_t>((count + FH_WG - 1) / FH_WG, 4096)), dim3(FH_WG), 0, c->stream>>>(dev, c->LB, c->ws, c->L, c->L, count);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+static int copy_out(fh_ctx* c, double* host, const double* dev, uint64_t rows) {
+  if (!c->LB) { HIP_TRY(hipMemcpyAsync(host, dev, rows * sizeof(double), hipMemcpyDeviceToHost, c->stream)); return 0; }
+  const uint64_t count = rows * c->L;
+  FH_TRY(ensure_ws(c, count * sizeof(double)));
+  k_mc_restride<<<dim3((unsigned)std::min<uint64_t>((count + FH_WG - 1) / FH_WG, 4096)), dim3(FH_WG), 0, c->stream>>>(c->ws, c->L, dev, c->LB, c->L, count);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(host, c->ws, count * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  return 0;
 }
 
 static int launch_fwd_tv(fh_ctx* c, int mode, double tau, const double* x0, const double* g0, const double* xacc0,

@@ -144,6 +144,65 @@ static int launch_adj_dense(fh_ctx* c, const AdjIO& io) {
   return 0;
 }
 
+// ---- multi-column form (fh_set_rhs; kernels in csrc/fh_multi.h, instantiated by fh_multi_part.hip) ---------------------------------------
+#ifndef FH_SINGLE_TU
+#define MC_DECLARE(LB, CH, R) MC_KERNELS(extern template, LB, CH, R)
+MC_FOR_EACH(MC_DECLARE)
+#undef MC_DECLARE
+#endif
+struct McEntry {
+  int lb, rows; void (*pro)(const McProP); void (*pack)(const double*, double*, uint32_t, uint32_t);
+  void (*fwd[2])(const McFwdP); void (*adj[2])(const McAdjP);
+};
+#define MC_ROW(LB, CH, R) {LB, R, k_mc_prologue<LB>, k_mc_pack<LB>, {k_mc_fwd<LB, CH, R, 0>, k_mc_fwd<LB, CH, R, 1>}, {k_mc_adj<LB, MC_ADJ_CPT, 0>, k_mc_adj<LB, MC_ADJ_CPT, 1>}},
+static const McEntry kMcTable[] = { MC_FOR_EACH(MC_ROW) };
+#undef MC_ROW
+static const McEntry* mc_entry(const fh_ctx* c) {
+  for (const McEntry& e : kMcTable) if ((uint32_t)e.lb == c->LB) return &e;
+  return nullptr;
+}
+static inline bool mc_prox_ok(int kind) {
+  return kind == FH_PROX_IDENTITY || kind == FH_PROX_SHRINK || kind == FH_PROX_NONNEG || kind == FH_PROX_BOX || kind == FH_PROX_GROUP;
+}
+
+// Z := A * (mode 0: prox(X0 - tau G0), by the prologue launch ; mode 1: X0) for LB columns from one read of A
+static int launch_fwd_multi(fh_ctx* c, int mode, double tau, const double* x0, const double* g0, const double* xacc0,
+                            double* xhat, double* xp, double* z, int sub_b) {
+  const McEntry* e = mc_entry(c);
+  if (!e) return fail(FH_E_STATE, "multi-column form: no kernel for %u columns per row", c->LB);
+  if (c->loss_kind != LOSS_LSQ) return fail(FH_E_STATE, "the multi-column form serves the least-squares loss only");
+  if (mode == 0 && !mc_prox_ok(c->prox_kind)) return fail(FH_E_STATE, "prox kind %d has no multi-column form", c->prox_kind);
+  McFwdP p;
+  p.A = c->A; p.ld2 = (uint32_t)(c->ld / 2); p.m = (uint32_t)c->m; p.L = c->L;
+  p.nrg = (uint32_t)(c->mp / (uint64_t)e->rows);
+  const uint32_t npro = mode == 0 ? (uint32_t)((c->nv + FH_WG - 1) / FH_WG) : 0u;
+  p.nred_n = npro;
+  const unsigned grid = (unsigned)std::min<long long>(p.nrg, c->fwd_cap > 0 ? c->fwd_cap : 512);
+  FH_TRY(ensure_ws(c, ((size_t)npro * 8 + grid) * sizeof(double)));
+  p.red_n = c->ws; p.red_m = c->ws + (size_t)npro * 8;
+  p.x = c->xs;                       // the operand in K-fwd's streaming layout: written by the prologue, or packed from a plain operand below
+  p.b = c->b; p.z = z; p.sub_b = sub_b;
+  p.counter = c->counters + CNT_FWD;
+  p.out = scalar_out(c);
+  t_begin(c, FH_K_FWD);
+  if (mode == 0) {
+    McProP q;
+    q.n = (uint32_t)c->n; q.L = c->L; q.nv = (uint32_t)c->nv;
+    q.x0 = x0; q.g0 = g0; q.xacc0 = xacc0; q.xhat = xhat; q.xp = xp; q.tau = tau;
+    q.xs = c->xs; q.ld2 = p.ld2;
+    q.px = make_prox(c, tau);
+    q.red_n = c->ws;
+    e->pro<<<dim3(npro), dim3(FH_WG), 0, c->stream>>>(q);
+  } else {
+    e->pack<<<dim3((unsigned)((c->nv + FH_WG - 1) / FH_WG)), dim3(FH_WG), 0, c->stream>>>(x0, c->xs, (uint32_t)c->nv, p.ld2);
+  }
+  p.seq = seq_offer(c);
+  e->fwd[nt_for(c) ? 1 : 0]<<<dim3(grid), dim3(FH_WG), 0, c->stream>>>(p);
+  t_end(c, FH_K_FWD);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
 // n-side epilogue as its own launch (row-sharded runs, after the all-reduce of g1)
 static int bb_epilogue_only(fh_ctx* c, const AdjIO& io, const double* fsq_src, const double* coef_src = nullptr, const double* pack = nullptr) {
   AdjP p;
@@ -162,8 +221,54 @@ static int bb_epilogue_only(fh_ctx* c, const AdjIO& io, const double* fsq_src, c
   return 0;
 }
 
+static int launch_adj_multi(fh_ctx* c, const AdjIO& io) {
+  const McEntry* e = mc_entry(c);
+  if (!e) return fail(FH_E_STATE, "multi-column form: no kernel for %u columns per row", c->LB);
+  if (io.sub_b && c->loss_kind != LOSS_LSQ) return fail(FH_E_STATE, "the multi-column form serves the least-squares loss only");
+  if (io.mode != 0 && io.mode != 1) return fail(FH_E_STATE, "the multi-column form has no row-sharded adjoint");
+  McAdjP p;
+  p.A = c->A; p.ld2 = (uint32_t)(c->ld / 2); p.n = (uint32_t)c->n; p.L = c->L; p.mp = (uint32_t)c->mp; p.m = (uint32_t)c->m;
+  p.ncc = (p.ld2 + FH_WG * MC_ADJ_CPT - 1) / (FH_WG * MC_ADJ_CPT);
+  // the vector kernel's slab rule (about 32 slabs, more when there are few column chunks): a slab's rows are staged 2048 / LB at a time
+  uint32_t slab = (uint32_t)c->adj_slab;
+  if (slab == 0) {
+    const uint64_t target_slabs = std::max<uint64_t>(32, (128 + p.ncc - 1) / p.ncc);
+    const uint64_t slab_min = p.ncc >= 8 ? 128 : 32;
+    const uint64_t s = round_up((c->mp + target_slabs - 1) / target_slabs, 8);
+    slab = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(s, slab_min), ADJ_MAX_SLAB);
+  }
+  p.slab_rows = slab;
+  p.nslab = (uint32_t)((c->mp + slab - 1) / slab);
+  if (p.ncc + CNT_ADJ_CC > (uint32_t)CNT_DIAG) return fail(FH_E_ARG, "too many column chunks (%u)", p.ncc);
+  p.z = io.z; p.zacc0 = io.zacc0; p.b = c->b; p.sub_b = io.sub_b; p.accel = io.accel; p.coef = io.coef;
+  p.mode = io.mode; p.tau = io.tau; p.group = c->prox_kind == FH_PROX_GROUP ? 1 : 0;
+  p.x0 = io.x0; p.xp = io.xp; p.xacc0 = io.xacc0; p.xhat = io.xhat; p.x1 = io.x1; p.g1 = io.g1;
+  const size_t gpart_elems = (size_t)p.nslab * c->ld * c->LB;
+  if ((uint64_t)c->ld * c->LB / 2 >= ((uint64_t)1 << 27)) return fail(FH_E_ARG, "multi-column K-adj: n * LB too large for one slab partial");
+  FH_TRY(ensure_ws(c, (gpart_elems + (size_t)p.ncc * 8 + p.nslab) * sizeof(double)));
+  p.gpart = c->ws; p.red_bb = c->ws + gpart_elems; p.red_f = p.red_bb + (size_t)p.ncc * 8;
+  p.cc_counter = c->counters + CNT_ADJ_CC; p.fin_counter = c->counters + CNT_ADJ_FIN;
+  p.out = scalar_out(c);
+  const unsigned grid = p.ncc * p.nslab;
+  t_begin(c, FH_K_ADJ);
+  p.seq = io.mode == 0 ? seq_offer(c) : 0u;
+  e->adj[nt_for(c) ? 1 : 0]<<<dim3(grid), dim3(FH_WG), 0, c->stream>>>(p);
+  t_end(c, FH_K_ADJ);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
 // sum|x_i| and max|x_i| of an n-length device vector -> dscal[GSUM], dscal[GMAX]  (g(x0) for objective_hist[0], :143)
 static int launch_gterms(fh_ctx* c, const double* x) {
+  if (c->LB) {              // (n, L) matrix: the same two terms, or the sum of row norms for FH_PROX_GROUP
+    const unsigned mgrid = (unsigned)std::min<uint64_t>((c->n + FH_WG - 1) / FH_WG, 1024);
+    FH_TRY(ensure_ws(c, (size_t)mgrid * 2 * sizeof(double)));
+    t_begin(c, FH_K_AUX);
+    k_mc_gterms<<<dim3(mgrid), dim3(FH_WG), 0, c->stream>>>(x, (uint32_t)c->n, c->L, c->LB, c->prox_kind == FH_PROX_GROUP ? 1 : 0, c->ws, c->counters + CNT_AUX, scalar_out(c));
+    t_end(c, FH_K_AUX);
+    HIP_TRY(hipGetLastError());
+    return 0;
+  }
   const unsigned grid = (unsigned)std::min<uint64_t>((c->n + FH_WG - 1) / FH_WG, 1024);
   FH_TRY(ensure_ws(c, (size_t)grid * 2 * sizeof(double)));
   t_begin(c, FH_K_AUX);
@@ -394,7 +499,7 @@ static const FusedEntry* fused_lookup(const FusedShape& sh, int f32) {
 // on ONE device: two solves side by side, or -- in the tests -- the ranks of a row-sharded run that share a GPU (K ranks x ncu / K CUs).
 static int fused_ncu(fh_ctx* c) { return c->fused_cus > 0 ? std::min(c->fused_cus, std::max(1, c->ncu)) : c->ncu; }
 static FusedShape fused_shape(fh_ctx* c) {
-  if (c->op != OP_DENSE || c->prox_kind == FH_PROX_TVBALL) return FusedShape{0, 0, 0, 0, 0};
+  if (c->op != OP_DENSE || c->prox_kind == FH_PROX_TVBALL || c->LB) return FusedShape{0, 0, 0, 0, 0};      // (no one-pass kernel for the multi-column form)
   return fused_shape_for(c->n, c->ld, c->f32, c->fused_variant, fused_ncu(c));
 }
 static int fused_ppt(fh_ctx* c) { return fused_shape(c).ppt; }
@@ -577,6 +682,7 @@ static int plain_pair_fused(fh_ctx* c, const double* x, double* z, double* g, bo
 // ---- operator-generic wrappers ---------------------------------------------------------------------
 static int op_fwd(fh_ctx* c, int mode, double tau, const double* x0, const double* g0, const double* xacc0,
                   double* xhat, double* xp, double* z, int sub_b) {
+  if (c->op == OP_DENSE && c->LB) return launch_fwd_multi(c, mode, tau, x0, g0, xacc0, xhat, xp, z, sub_b);
   if (c->op == OP_DENSE) return launch_fwd_dense(c, mode, tau, x0, g0, xacc0, xhat, xp, z, sub_b);
   if (c->op == OP_STENCIL) return launch_fwd_tv(c, mode, tau, x0, g0, xacc0, xhat, xp, z, sub_b);
   return fail(FH_E_STATE, "no operator set");
@@ -588,6 +694,7 @@ static int adj_local(fh_ctx* c, const AdjIO& io_in) {
   AdjIO io = io_in;
   if (row_sharded(c) && c->op != OP_DENSE) return fail(FH_E_STATE, "row sharding is implemented for the dense operator only");
   if (row_sharded(c) && io.mode == 0) io.mode = 2;
+  if (c->op == OP_DENSE && c->LB) return launch_adj_multi(c, io);
   if (c->op == OP_DENSE) return launch_adj_dense(c, io);
   if (c->op == OP_STENCIL) return launch_adj_tv(c, io);
   return fail(FH_E_STATE, "no operator set");

@@ -35,10 +35,13 @@ def host_map(A, At, x0):
         return LinearMap.identity(np.shape(x0))
     if isinstance(A, np.ndarray):                    # sparse_least_squares.py:46 passes the raw matrix and its transpose
         assert A.ndim == 2                           # linalg.py:40
+        # a 2-D x0 of shape (n, L): a matrix unknown, `A @ X` column by column (examples/mmv.py)
+        cols = (np.shape(x0)[1],) if (np.ndim(x0) == 2 and np.shape(x0)[0] == A.shape[1]) else ()
+        V, W = (A.shape[1],) + cols, (A.shape[0],) + cols
         if isinstance(At, np.ndarray):
             assert At.shape == A.shape[::-1]
-            return LinearMap(lambda x: A @ x, lambda y: At @ y, (A.shape[1],), (A.shape[0],))
-        return LinearMap(lambda x: A @ x, lambda y: A.T @ y, (A.shape[1],), (A.shape[0],))      # linalg.py:41
+            return LinearMap(lambda x: A @ x, lambda y: At @ y, V, W)
+        return LinearMap(lambda x: A @ x, lambda y: A.T @ y, V, W)      # linalg.py:41
     if callable(A) and callable(At):                 # tv_denoising.py:99: bare functions, codomain found by probing
         return LinearMap(A, At, np.shape(x0), np.shape(A(np.zeros(np.shape(x0)))))
     raise TypeError("fasta(): operator A must be a LinearMap, a 2-D ndarray, a callable pair (A, At) or None")

@@ -15,7 +15,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FASTA_HIP_LIB") or os.path.join(_HERE, "libfasta_hip.so")
 
 # enums mirrored from include/fasta_hip.h ---------------------------------------------------------
-PROX_IDENTITY, PROX_SHRINK, PROX_NONNEG, PROX_LINF, PROX_L1BALL, PROX_TVBALL, PROX_BOX = range(7)
+PROX_IDENTITY, PROX_SHRINK, PROX_NONNEG, PROX_LINF, PROX_L1BALL, PROX_TVBALL, PROX_BOX, PROX_GROUP = range(8)
+MAX_RHS = 16                       # columns of a matrix unknown (fh_set_rhs)
 (VEC_X0, VEC_G0, VEC_XHAT, VEC_XPROX, VEC_X1, VEC_G1, VEC_BEST, VEC_B, VEC_Z,
  VEC_T0, VEC_T1, VEC_T2, VEC_T3) = range(13)
 (S_FSQ, S_DXG0, S_DX2, S_XH2, S_G02, S_GSUM, S_GMAX, S_RDOT, S_DXDG, S_DG2, S_FSQ_ADJ, S_XH2_ADJ,
@@ -80,6 +81,8 @@ SIGNATURES = {
     "fh_get_matrix_rows": (_i32, [_ctx, _u64, _u64, _pd]),
     "fh_set_stencil": (_i32, [_ctx, _u64, _u64]),
     "fh_shape": (_i32, [_ctx, C.POINTER(_u64), C.POINTER(_u64)]),
+    "fh_set_rhs": (_i32, [_ctx, C.c_uint32]),
+    "fh_rhs": (_i32, [_ctx, C.POINTER(C.c_uint32)]),
     "fh_set_loss_lsq": (_i32, [_ctx, _pd, _u64]),
     "fh_set_loss_logistic": (_i32, [_ctx, _pd, _u64]),
     "fh_set_prox": (_i32, [_ctx, _i32, _dbl, _dbl, _dbl]),
@@ -369,6 +372,18 @@ class HipContext:
         self._call("fh_shape", C.byref(m), C.byref(n))
         return m.value, n.value
 
+    def set_rhs(self, L):
+        """Multi-column form: the unknown becomes an (n, L) matrix, b and z (m, L) matrices, L in 1..16 (0: back to the vector form).
+        Plain single-device context with a dense float64 operator; vectors restart as zeros and the loss has to be set again."""
+        self._call("fh_set_rhs", int(L))
+
+    @property
+    def rhs(self):
+        """Columns of the matrix unknown (0 in the vector form)."""
+        L = C.c_uint32(0)
+        self._call("fh_rhs", C.byref(L))
+        return int(L.value)
+
     def set_loss_lsq(self, b):
         b, p = _as_f64(np.ravel(b))
         self._call("fh_set_loss_lsq", p, b.size)
@@ -512,9 +527,10 @@ class HipContext:
 
     def apply(self, v, adjoint=False):
         m, n = self.shape()
+        L = self.rhs or 1                              # multi-column form: (n, L) / (m, L) row-major, flattened
         v, p = _as_f64(np.ravel(v))
-        assert v.size == (m if adjoint else n)
-        out = np.empty(n if adjoint else m)
+        assert v.size == (m if adjoint else n) * L
+        out = np.empty((n if adjoint else m) * L)
         self._call("fh_apply", 1 if adjoint else 0, p, out.ctypes.data_as(_pd))
         return out
 

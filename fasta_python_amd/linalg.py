@@ -5,7 +5,9 @@ subclasses are *recognised* by `fasta()` and run on the device:
 
   DenseMatrixMap  -- row-major float64 matrix, resident in HBM (from a host ndarray, or generated
                      on the device by the counter-based synthetic generator, optionally one row
-                     block of a matrix sharded over GPUs, one process per GPU);
+                     block of a matrix sharded over GPUs, one process per GPU); with `rhs=L` it maps
+                     (n, L) matrices to (m, L) matrices -- one A for L columns, read once per pass
+                     (examples/mmv.py, multi-column LASSO / NNLS);
   ShardedDenseMatrixMap -- the same matrix split into contiguous row blocks over several devices
                      of THIS process (single call): `fasta(ShardedDenseMatrixMap(A,
                      devices=[0, 1, ...]), ls.f, ls.gradf, reg.g, reg.prox, x0)`;
@@ -204,13 +206,21 @@ class DenseMatrixMap(_DeviceMap):
     ranks (one process per GPU); the default is the whole matrix on one GPU.
     """
 
-    def __init__(self, A=None, device=0, tuning=None, _defer=False, storage="f64", _devices=None, _rccl_shell=False):
-        """storage="f32" (opt-in): keep the device copy of A in float32 -- half the bytes per pass, ~2x the iterations/s on
+    def __init__(self, A=None, device=0, tuning=None, _defer=False, storage="f64", _devices=None, _rccl_shell=False, rhs=None):
+        """rhs=L (1..16): the unknown is an (n, L) matrix and the data an (m, L) matrix (`Vshape = (n, L)`, `Wshape = (m, L)`): every
+        device pass reads A once for all L columns (csrc/fh_multi.h).  float64 storage, one device.
+        storage="f32" (opt-in): keep the device copy of A in float32 -- half the bytes per pass, ~2x the iterations/s on
         large matrices.  The solve is then the reference's solve on the ROUNDED matrix A.astype(float32) (all vectors and
         arithmetic stay float64), so iterates differ from the float64-matrix run by the effect of that rounding."""
         self.rows = None
         self.shape = None
         self.storage = storage
+        self.rhs = None if rhs is None else int(rhs)
+        if self.rhs is not None:
+            if not 1 <= self.rhs <= hip.MAX_RHS:
+                raise ValueError(f"rhs must be in 1..{hip.MAX_RHS} columns (got {rhs})")
+            if storage != "f64" or _devices is not None:
+                raise TypeError("a matrix unknown (rhs=L) needs float64 storage on a single device")
         self.matrix = None                 # host copy (a reference to the caller's array, like the closures of linalg.py:41)
         self._tuning = dict(tuning or {})
         if _defer:
@@ -219,7 +229,8 @@ class DenseMatrixMap(_DeviceMap):
             assert A is not None and A.ndim == 2
             self.matrix = A
             self.shape = tuple(A.shape)
-            _DeviceMap.__init__(self, (A.shape[1],), (A.shape[0],), device, storage, _devices, lazy=True, rccl_shell=_rccl_shell)
+            cols = () if self.rhs is None else (self.rhs,)
+            _DeviceMap.__init__(self, (A.shape[1],) + cols, (A.shape[0],) + cols, device, storage, _devices, lazy=True, rccl_shell=_rccl_shell)
 
     def _on_context(self, ctx):
         """First use of the device context: tuning, then the one H2D copy of the host matrix."""
@@ -227,6 +238,8 @@ class DenseMatrixMap(_DeviceMap):
             ctx.set_tuning(key, value)
         if self.matrix is not None:
             ctx.set_matrix(self.matrix)
+            if self.rhs is not None:
+                ctx.set_rhs(self.rhs)
 
     def _tune(self, tuning):
         self._tuning.update(tuning or {})
@@ -253,13 +266,16 @@ class DenseMatrixMap(_DeviceMap):
         return self._host_matrix().T @ w
 
     @classmethod
-    def synthetic(cls, m, n, seed, scale, row0=0, m_total=None, device=0, tuning=None, storage="f64", _devices=None):
-        """Rows [row0, row0+m) of the counter-based synthetic matrix, generated in HBM."""
+    def synthetic(cls, m, n, seed, scale, row0=0, m_total=None, device=0, tuning=None, storage="f64", _devices=None, rhs=None):
+        """Rows [row0, row0+m) of the counter-based synthetic matrix, generated in HBM; rhs=L as in the constructor."""
         from .synthetic import synth_coef
-        self = cls(_defer=True, device=device, storage=storage, _devices=_devices)
+        self = cls(_defer=True, device=device, storage=storage, _devices=_devices, rhs=rhs)
         self._tune(tuning)
         self.ctx.generate_matrix(m, n, row0, seed, synth_coef(scale))
-        self.Vshape, self.Wshape = (n,), (m,)
+        cols = () if self.rhs is None else (self.rhs,)
+        if self.rhs is not None:
+            self.ctx.set_rhs(self.rhs)
+        self.Vshape, self.Wshape = (n,) + cols, (m,) + cols
         self.shape = (m, n)
         self.rows = (row0, m if m_total is None else m_total)
         return self

@@ -19,7 +19,7 @@ import numpy as np
 
 from . import hip
 
-__all__ = ["Shrink", "NonNeg", "LinfProx", "L1Ball", "Box", "TVDualBall", "NoProx", "device_prox", "release_scratch",
+__all__ = ["Shrink", "NonNeg", "LinfProx", "L1Ball", "Box", "TVDualBall", "GroupShrink", "NoProx", "device_prox", "release_scratch",
            "shrink", "project_Linf_ball", "project_L1_ball", "project_Lnuc_ball"]
 
 
@@ -127,22 +127,65 @@ class TVDualBall(ProxTag):
         return Y / np.maximum(lengths, 1)[..., None]
 
 
+class GroupShrink(ProxTag):
+    """Row-sparsity regulariser of a matrix unknown X of shape (N, L) (examples/mmv.py:51-59):
+    g(X) = mu * (sum over the rows of their Euclidean norms), and proxg(X, t) shrinks every ROW's norm by t*mu -- a row whose norm is
+    below t*mu becomes zero, any other row keeps its direction and loses t*mu of its length.  Couples the columns of a row, so the
+    device serves it in the multi-column form only (FH_PROX_GROUP, csrc/fh_multi.h)."""
+    kind = hip.PROX_GROUP
+
+    def __init__(self, mu):
+        self.mu = float(mu)
+
+    def g_from_sums(self, gsum, gmax):
+        return self.mu * gsum                   # FH_S_GSUM carries the sum of row norms for this kind
+
+    def prox(self, X, t):
+        lengths = np.linalg.norm(X, axis=1)
+        # the shrunk length over the old one; an all-zero row is divided by one instead of zero and stays zero
+        factor = shrink(lengths, self.mu * t) / (lengths + (lengths == 0))
+        return X * factor[:, np.newaxis]
+
+    def g(self, X):
+        return self.mu * np.sum(np.sqrt(np.sum(X * X, axis=1)))
+
+
 # ---- the device prox on host arrays -----------------------------------------------------------------
 _scratch = {}            # (device, "dense", n) or (device, "tv", H, W) -> operator holding a scratch HipContext
 
 
-def _scratch_op(device, x, tv):
+_ELEMENTWISE = (hip.PROX_IDENTITY, hip.PROX_SHRINK, hip.PROX_NONNEG, hip.PROX_BOX)
+
+
+def _matrix_form(tag, x):
+    """Does device_prox take the multi-column kernels for `x`?  GroupShrink always (it couples the columns of a row, and refuses what the
+    device cannot hold); an elementwise kind for a 2-D array of at most 16 columns -- same bits as the vector kernels on the flattened
+    array.  Everything else (LinfProx / L1Ball on any shape, wider arrays, other ranks) is flattened and takes the vector kernels."""
+    if tag.kind == hip.PROX_GROUP:
+        if x.ndim != 2 or x.shape[1] > hip.MAX_RHS:
+            raise ValueError(f"GroupShrink needs a 2-D array of at most {hip.MAX_RHS} columns (got shape {x.shape})")
+        return True
+    return tag.kind in _ELEMENTWISE and x.ndim == 2 and 1 <= x.shape[1] <= hip.MAX_RHS
+
+
+def _scratch_op(device, x, tv, matrix=False):
     """One scratch operator per (device, shape), kept for the life of the process (`release_scratch()` frees them):
     a prox inside a caller's loop costs two small copies and one launch, not a context create/destroy."""
     from .linalg import DenseMatrixMap, GradDivMap
-    key = (device, "tv") + tuple(x.shape[:2]) if tv else (device, "dense", x.size)
+    rhs = x.shape[1] if matrix else None                         # a matrix unknown: (n, L) on a one-row operator with rhs = L
+    key = (device, "tv") + tuple(x.shape[:2]) if tv else ((device, "dense", x.size) if rhs is None else (device, "dense") + tuple(x.shape))
     op = _scratch.get(key)
     if op is None:
         if len(_scratch) >= 8:                                   # bounded: drop the oldest shape
             _scratch.pop(next(iter(_scratch))).close()
-        op = GradDivMap(x.shape[:2], device=device) if tv else DenseMatrixMap(np.zeros((1, x.size)), device=device)
+        if tv:
+            op = GradDivMap(x.shape[:2], device=device)
+        elif rhs is None:
+            op = DenseMatrixMap(np.zeros((1, x.size)), device=device)
+        else:
+            op = DenseMatrixMap(np.zeros((1, x.shape[0])), device=device, rhs=rhs)
         if not tv:
-            op.ctx.set_loss_lsq(np.zeros(1))
+            op.ctx.set_loss_lsq(np.zeros(1 if rhs is None else rhs))
             op.ctx.set_vector(hip.VEC_G0, np.zeros(x.size))
         _scratch[key] = op
     return op
@@ -156,13 +199,14 @@ def release_scratch():
 
 def device_prox(tag, x, t, device=0):
     """prox_{t g}(x) for a host array through the DEVICE kernels: one K-fwd with x0 := x and a zero gradient
-    gives xprox = prox(x, t)."""
+    gives xprox = prox(x, t).  GroupShrink takes a 2-D `x` of shape (n, L), L <= 16, and the multi-column kernels; so does an elementwise
+    tag on such an array (same bits as on the flattened array).  Every other call is flattened and takes the vector kernels."""
     x = np.asarray(x, dtype=np.float64)
     flat = x.ravel()
     tv = tag.kind == hip.PROX_TVBALL
     if tv:
         assert x.ndim == 3 and x.shape[-1] == 2
-    ctx = _scratch_op(device, x, tv).ctx
+    ctx = _scratch_op(device, x, tv, matrix=not tv and _matrix_form(tag, x)).ctx
     ctx.set_prox(tag.kind, tag.mu, tag.lo, tag.hi)
     ctx.set_vector(hip.VEC_X0, flat)
     if tv:

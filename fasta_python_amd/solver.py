@@ -71,7 +71,31 @@ def _tag_of(obj, cls):
     return owner if isinstance(owner, cls) else None
 
 
-def _unrecognised(A, At, f, gradf, g, proxg):
+def _matrix_form_refusal(A, loss, prox, x0):
+    """A 2-D x0 over a dense matrix is a MATRIX unknown (n, L): the device serves it in the multi-column form (csrc/fh_multi.h), which has
+    no level-search prox kinds, no logistic loss, no float32 storage and no row sharding, and at most 16 columns.  None, or the reason."""
+    from .linalg import ShardedDenseMatrixMap
+    from .proximal import GroupShrink, L1Ball, LinfProx, TVDualBall
+    dense = isinstance(A, np.ndarray) or isinstance(A, DenseMatrixMap)
+    matrix_form = dense and x0 is not None and np.ndim(x0) == 2
+    if isinstance(prox, GroupShrink) and not matrix_form:
+        return "proximal.GroupShrink couples the columns of a row: it needs a dense matrix operator and a 2-D x0 of shape (n, L)"
+    if not matrix_form:
+        return None
+    if np.shape(x0)[1] > hip.MAX_RHS:
+        return f"a matrix unknown has at most {hip.MAX_RHS} columns on the device (x0 has {np.shape(x0)[1]})"
+    if isinstance(prox, (LinfProx, L1Ball, TVDualBall)):
+        return f"proximal.{type(prox).__name__} has no matrix (multi-column) form on the device"
+    if isinstance(loss, LogisticLoss):
+        return "losses.LogisticLoss has no matrix (multi-column) form on the device"
+    if isinstance(A, ShardedDenseMatrixMap):
+        return "a row-sharded operator has no matrix (multi-column) form on the device"
+    if isinstance(A, DenseMatrixMap) and A.storage != "f64":
+        return 'storage="f32" has no matrix (multi-column) form on the device'
+    return None
+
+
+def _unrecognised(A, At, f, gradf, g, proxg, x0=None):
     """None when the seven operands can run on the device, else the reason they cannot (a sentence)."""
     if not isinstance(A, (np.ndarray, _DeviceMap)):
         return ("operator A is not device-resident (pass a 2-D float64 ndarray, a linalg.DenseMatrixMap / "
@@ -80,12 +104,12 @@ def _unrecognised(A, At, f, gradf, g, proxg):
     if loss_f is None or loss_f is not loss_g:
         return "f and gradf must be the `.f` / `.gradf` of one losses.LeastSquares(b) or losses.LogisticLoss(b) object"
     if g is None and proxg is None:
-        return None
+        return _matrix_form_refusal(A, loss_f, None, x0)
     prox, owner_g = _tag_of(proxg, ProxTag), _tag_of(g, ProxTag)
     if prox is None or (owner_g is not None and owner_g is not prox) or (owner_g is None and g is not None):
         return ("g and proxg must be the `.g` / `.prox` of one proximal.* tag object "
-                "(Shrink, NonNeg, LinfProx, L1Ball, Box, TVDualBall)")
-    return None
+                "(Shrink, NonNeg, LinfProx, L1Ball, Box, TVDualBall, GroupShrink)")
+    return _matrix_form_refusal(A, loss_f, prox, x0)
 
 
 def _recognise(A, At, f, gradf, g, proxg, x0):
@@ -95,7 +119,8 @@ def _recognise(A, At, f, gradf, g, proxg, x0):
             raise AssertionError("matrix operator must be 2-D")            # linalg.py:40
         if isinstance(At, np.ndarray) and At.shape != A.shape[::-1]:
             raise AssertionError("At must have the transposed shape of A")
-        A = DenseMatrixMap(A)
+        # a 2-D x0 of shape (n, L) over an (m, n) matrix: a matrix unknown, one A for its L columns
+        A = DenseMatrixMap(A, rhs=x0.shape[1] if (x0.ndim == 2 and x0.shape[0] == A.shape[1]) else None)
     loss_f = _tag_of(f, (LeastSquares, LogisticLoss))
     prox = NoProx() if (g is None and proxg is None) else _tag_of(proxg, ProxTag)      # :88-90
     if tuple(x0.shape) != A.Vshape:
@@ -507,7 +532,7 @@ def fasta(A, *operands, backend="auto", **options):
         raise TypeError("fasta() takes (A, f, gradf, g, proxg, x0) or (A, At, f, gradf, g, proxg, x0)")
     if backend not in ("auto", "hip", "numpy"):
         raise ValueError('backend must be "auto", "hip" or "numpy"')
-    why_not = "backend='numpy' was requested" if backend == "numpy" else _unrecognised(A, At, f, gradf, g, proxg)
+    why_not = "backend='numpy' was requested" if backend == "numpy" else _unrecognised(A, At, f, gradf, g, proxg, x0)
     if why_not is not None:
         if backend == "hip":
             raise TypeError("fasta(backend='hip'): " + why_not)

@@ -45,7 +45,10 @@ enum fh_prox_kind {
   FH_PROX_LINF     = 3,  /* proximal.project_Linf_ball(x, t*mu), fasta/proximal.py:12-31 */
   FH_PROX_L1BALL   = 4,  /* proximal.project_L1_ball(x, mu), fasta/proximal.py:34-41     */
   FH_PROX_TVBALL   = 5,  /* per-pixel 2-vector / max(norm,1), examples/tv_denoising.py:89-96 */
-  FH_PROX_BOX      = 6   /* clip to [lo, hi], examples/svm.py:71                         */
+  FH_PROX_BOX      = 6,  /* clip to [lo, hi], examples/svm.py:71                         */
+  FH_PROX_GROUP    = 7   /* row-wise l2 shrink of an (n, L) matrix, examples/mmv.py:51-59: with nu = ||xhat_j||_2 over the L entries of row j,
+                            xprox_j = xhat_j * max(nu - t*mu, 0) / (nu + (nu == 0)).  Multi-column form only (fh_set_rhs).  FH_S_GSUM /
+                            FH_S_GSUM_ADJ then carry sum_j ||xprox_j||_2 (of x1), so that g = mu * gsum; FH_S_GMAX is unchanged.            */
 };
 
 /* device vectors addressable through fh_set_vector / fh_get_vector                      */
@@ -179,6 +182,21 @@ int fh_get_matrix_rows(fh_ctx* ctx, uint64_t row0, uint64_t nrows, double* out /
 /* periodic difference stencil pair: A = div: (H,W,2)->(H,W), A^H = grad (examples/tv_denoising.py:26-63) */
 int fh_set_stencil(fh_ctx* ctx, uint64_t H, uint64_t W);
 int fh_shape(fh_ctx* ctx, uint64_t* m, uint64_t* n);
+
+/* ---- multi-column form: the unknown is an (n, L) MATRIX, one A for all L columns (examples/mmv.py; multi-column LASSO / NNLS) -----------
+ * fh_set_rhs(ctx, L), L in 1..16, on a plain single-device context with a dense float64 operator: every n-side vector (FH_VEC_X0 .. BEST,
+ * T0 .. T3) becomes an (n, L) matrix, FH_VEC_B and FH_VEC_Z (m, L) matrices; fh_set_vector, fh_get_vector, fh_set_loss_lsq and fh_apply
+ * take and return contiguous ROW-MAJOR host arrays of n*L or m*L doubles; fh_shape still reports (m, n) of A.  The call sequence and the
+ * meaning of every FH_S_* scalar (now sums over all n*L or m*L entries), fh_commit, fh_init, fh_setup (its three-pass route),
+ * fh_gradient_at, fh_diff_norm, fh_fwd, fh_adj (with accel / coef), fh_fwd_adj, fh_iterate and timing are those of the vector form; every
+ * pass reads A once for all L columns (csrc/fh_multi.h).  Prox kinds served: IDENTITY, SHRINK, NONNEG, BOX (elementwise) and GROUP.
+ * L = 0 returns the context to the vector form; a context that never calls fh_set_rhs behaves as before.  EVERY successful call -- also
+ * one that repeats the current L -- resets every vector to zero and forgets the loss (set it again).  Setting a new operator returns the context to the vector form.
+ * Refused (FH_E_ARG / FH_E_STATE): L > 16; a stencil operator; float32 storage; a multi-device context; a context with a communicator
+ * (and fh_comm_init on a multi-column context); the logistic loss; FH_PROX_LINF / L1BALL / TVBALL.  In multi-column form
+ * fh_fused_supported, fh_fused_agree and fh_run_supported report 0 and fh_step* / fh_run return FH_E_STATE.                               */
+int fh_set_rhs(fh_ctx* ctx, uint32_t L);
+int fh_rhs(fh_ctx* ctx, uint32_t* L);      /* L of the multi-column form, 0 in the vector form */
 
 /* ---- smooth term f(z) = .5||z - b||^2, grad f(z) = z - b (examples/sparse_least_squares.py:41-42) */
 int fh_set_loss_lsq(fh_ctx* ctx, const double* b, uint64_t len);

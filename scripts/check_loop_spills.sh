@@ -8,5 +8,6 @@ for part in 0 1 2 3; do python scripts/loop_spills.py fh_fused_part.hip k_fused_
 for part in 0 1 2; do python scripts/loop_spills.py fh_setup_part.hip k_setup_dense -DFH_PART=$part > $out/setup$part.txt 2>&1 & done
 wait
 python scripts/loop_spills.py fasta_hip.hip "k_run_dense|k_tv_onepass|k_fwd_dense|k_adj_dense" > $out/host.txt 2>&1
-cat $out/fused?.txt $out/setup?.txt $out/host.txt
+python scripts/loop_spills.py fh_multi_part.hip "k_mc_fwd|k_mc_adj" > $out/multi.txt 2>&1      # the multi-column kernels (make -C fasta_python_amd/csrc multi-spills)
+cat $out/fused?.txt $out/setup?.txt $out/host.txt $out/multi.txt
 rm -rf $out
