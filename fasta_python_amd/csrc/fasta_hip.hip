@@ -17,6 +17,7 @@
 #include "fh_experimental.h"
 #include "fh_dense.h"
 #include "fh_multi.h"
+#include "fh_sparse.h"
 #include "fh_tv.h"
 #include "fh_prox.h"
 #include "fh_fused.h"
@@ -110,6 +111,9 @@ static const SetupEntry kSetupTable[] = {
 #define MC_INSTANTIATE(LB, CH, R) MC_KERNELS(template, LB, CH, R)
 MC_FOR_EACH(MC_INSTANTIATE)
 #undef MC_INSTANTIATE
+#define SP_INSTANTIATE(G) SP_KERNELS(template, G)
+SP_FOR_EACH(SP_INSTANTIATE)
+#undef SP_INSTANTIATE
 #endif
 
 #include "fh_host_ctx.h"
@@ -486,8 +490,120 @@ extern "C" int fh_generate_matrix(fh_ctx* c, uint64_t m, uint64_t n, uint64_t ro
   return finish(c);
 }
 
+// ---- sparse operator: A in canonical CSR (csrc/fh_sparse.h) ---------------------------------------------------------------------------------
+// One side of the operator on the device: the arrays, the lanes per row G (from the mean row length), the rows longer than max(SP_LONG_FACTOR * G,
+// SP_LONG_MEANS mean rows) (a workgroup each) and the contiguous row ranges of the other workgroups, balanced by the trips a group of G lanes spends on a row.
+// Computed here, once; a launch only reads it.
+static int sp_upload_side(fh_ctx* c, int side, uint64_t rows, uint64_t nnz, const int64_t* ptr, const int32_t* idx, const double* val) {
+  const double mean = rows ? (double)nnz / (double)rows : 0.0;
+  int G = 4;
+  while (G < 64 && (double)G * 2.0 < mean) G *= 2;
+  const uint64_t groups = FH_WG / (uint64_t)G;
+  const uint64_t longer = std::max<uint64_t>((uint64_t)SP_LONG_FACTOR * (uint64_t)G, (uint64_t)((double)SP_LONG_MEANS * mean));
+  std::vector<uint32_t> longrows;
+  uint64_t total = 0;
+  auto cost = [&](uint64_t r) -> uint64_t {
+    const uint64_t len = (uint64_t)(ptr[r + 1] - ptr[r]);
+    return len > longer ? 1u : (len + G - 1) / G + 2u;
+  };
+  for (uint64_t r = 0; r < rows; ++r) {
+    if ((uint64_t)(ptr[r + 1] - ptr[r]) > longer) longrows.push_back((uint32_t)r);
+    total += cost(r);
+  }
+  const uint64_t cap = (uint64_t)std::max(1, c->ncu) * 8u;
+  const uint64_t nwg = std::max<uint64_t>(1, std::min<uint64_t>((rows + groups - 1) / groups, cap));
+  std::vector<uint32_t> part(nwg + 1, (uint32_t)rows);
+  part[0] = 0;
+  {
+    uint64_t run = 0, r = 0;
+    for (uint64_t w = 1; w < nwg; ++w) {
+      const uint64_t goal = (total * w + nwg - 1) / nwg;
+      while (r < rows && run < goal) { run += cost(r); ++r; }
+      part[w] = (uint32_t)r;
+    }
+  }
+  SpMatP a;
+  a.rows = (uint32_t)rows; a.nwg = (uint32_t)nwg; a.nlong = (uint32_t)longrows.size(); a.longer = (long long)longer;
+  void* d = nullptr;
+  HIP_TRY(hipMalloc(&d, (rows + 1) * sizeof(long long))); a.ptr = (const long long*)d; c->sp[side].ptr = a.ptr;
+  HIP_TRY(hipMalloc(&d, std::max<uint64_t>(nnz, 1) * sizeof(int))); a.idx = (const int*)d; c->sp[side].idx = a.idx;
+  HIP_TRY(hipMalloc(&d, std::max<uint64_t>(nnz, 1) * sizeof(double))); a.val = (const double*)d; c->sp[side].val = a.val;
+  HIP_TRY(hipMalloc(&d, (nwg + 1) * sizeof(uint32_t))); a.part = (const uint32_t*)d; c->sp[side].part = a.part;
+  HIP_TRY(hipMalloc(&d, std::max<size_t>(longrows.size(), 1) * sizeof(uint32_t))); a.longrows = (const uint32_t*)d; c->sp[side].longrows = a.longrows;
+  static_assert(sizeof(long long) == sizeof(int64_t), "entry offsets are 64-bit");
+  HIP_TRY(hipMemcpy((void*)a.ptr, ptr, (rows + 1) * sizeof(long long), hipMemcpyHostToDevice));
+  if (nnz) {
+    HIP_TRY(hipMemcpy((void*)a.idx, idx, nnz * sizeof(int), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy((void*)a.val, val, nnz * sizeof(double), hipMemcpyHostToDevice));
+  }
+  HIP_TRY(hipMemcpy((void*)a.part, part.data(), (nwg + 1) * sizeof(uint32_t), hipMemcpyHostToDevice));
+  if (!longrows.empty()) HIP_TRY(hipMemcpy((void*)a.longrows, longrows.data(), longrows.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+  c->sp[side] = a;
+  c->sp_G[side] = G;
+  return 0;
+}
+
+extern "C" int fh_set_matrix_csr(fh_ctx* c, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* indptr, const int32_t* indices, const double* values) {
+  if (!c || !indptr || (nnz && (!indices || !values))) return fail(FH_E_ARG, "fh_set_matrix_csr: null argument");
+  if (!c->shards.empty() || c->owner) return fail(FH_E_STATE, "fh_set_matrix_csr: a multi-device context has no sparse operator (row sharding is implemented for the dense operator only)");
+  if (c->comm) return fail(FH_E_STATE, "fh_set_matrix_csr: a context with a communicator (row-sharded run) has no sparse operator");
+  if (c->f32) return fail(FH_E_STATE, "fh_set_matrix_csr: float32 storage is not implemented for the sparse operator");
+  if (c->pending_step) return fail(FH_E_STATE, "a step issued by fh_step_begin is still in flight on this context: call fh_step_end first");
+  if (m == 0 || n == 0) return fail(FH_E_ARG, "matrix must be non-empty (got %llu x %llu)", (unsigned long long)m, (unsigned long long)n);
+  if (m >= (1ull << 31) || n >= (1ull << 31)) return fail(FH_E_ARG, "matrix dimension exceeds 2^31-1");
+  if (nnz >= (1ull << 62)) return fail(FH_E_ARG, "fh_set_matrix_csr: nnz out of range");
+  // canonical CSR, or the first offending row by name
+  if (indptr[0] != 0) return fail(FH_E_ARG, "fh_set_matrix_csr: indptr[0] is %lld, not 0 (row 0)", (long long)indptr[0]);
+  for (uint64_t r = 0; r < m; ++r) {
+    if (indptr[r + 1] < indptr[r] || (uint64_t)indptr[r + 1] > nnz)
+      return fail(FH_E_ARG, "fh_set_matrix_csr: indptr is decreasing or runs past nnz at row %llu", (unsigned long long)r);
+    for (int64_t k = indptr[r]; k < indptr[r + 1]; ++k) {
+      if (indices[k] < 0 || (uint64_t)indices[k] >= n)
+        return fail(FH_E_ARG, "fh_set_matrix_csr: column index %d out of range in row %llu (n = %llu)", indices[k], (unsigned long long)r, (unsigned long long)n);
+      if (k > indptr[r] && indices[k] <= indices[k - 1])
+        return fail(FH_E_ARG, "fh_set_matrix_csr: column indices of row %llu are not strictly increasing (sort them and sum duplicates)", (unsigned long long)r);
+    }
+  }
+  if ((uint64_t)indptr[m] != nnz) return fail(FH_E_ARG, "fh_set_matrix_csr: indptr ends at %lld, nnz is %llu (row %llu)", (long long)indptr[m], (unsigned long long)nnz, (unsigned long long)(m - 1));
+  FH_TRY(use_device(c));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  free_operator(c);
+  if (!sp_prox_ok(c->prox_kind)) { c->prox_kind = FH_PROX_IDENTITY; c->mu = 0.0; }
+  c->m = m; c->n = n;
+  c->mp = round_up(m, 16); c->ld = round_up(n, 16);      // vectors keep the vector form's padded layout
+  c->nv = c->ld; c->mv = c->mp;
+  c->nnz = nnz;
+  // A^T by rows: a stable counting sort over the columns, rows visited in order => every column lists its entries in ascending row order
+  std::vector<int64_t> tptr(n + 1, 0);
+  for (uint64_t k = 0; k < nnz; ++k) tptr[(size_t)indices[k] + 1] += 1;
+  for (uint64_t j = 0; j < n; ++j) tptr[j + 1] += tptr[j];
+  std::vector<int32_t> tidx(nnz);
+  std::vector<double> tval(nnz);
+  {
+    std::vector<int64_t> fill(tptr.begin(), tptr.end() - 1);
+    for (uint64_t r = 0; r < m; ++r)
+      for (int64_t k = indptr[r]; k < indptr[r + 1]; ++k) {
+        const int64_t q = fill[(size_t)indices[k]]++;
+        tidx[(size_t)q] = (int32_t)r; tval[(size_t)q] = values[k];
+      }
+  }
+  int rc = sp_upload_side(c, 0, m, nnz, indptr, indices, values);
+  if (rc == 0) rc = sp_upload_side(c, 1, n, nnz, tptr.data(), tidx.data(), tval.data());
+  if (rc == 0) rc = alloc_vectors(c);
+  if (rc == 0) rc = alloc_zero(c, &c->sp_r, c->mv + 16);
+  if (rc != 0) { free_operator(c); return rc; }
+  c->op = OP_SPARSE;
+  return finish(c);
+}
+extern "C" int fh_nnz(fh_ctx* c, uint64_t* nnz) {
+  if (!c || !nnz) return fail(FH_E_ARG, "null argument");
+  *nnz = c->op == OP_SPARSE ? c->nnz : 0u;
+  return 0;
+}
+
 extern "C" int fh_get_matrix_rows(fh_ctx* c, uint64_t row0, uint64_t nrows, double* out) {
   if (!c || !out) return fail(FH_E_ARG, "null argument");
+  if (c->op == OP_SPARSE) return fail(FH_E_STATE, "fh_get_matrix_rows: the sparse operator keeps no dense rows");
   if (c->op != OP_DENSE) return fail(FH_E_STATE, "no dense matrix set");
   if (row0 + nrows > c->m) return fail(FH_E_ARG, "rows [%llu,%llu) out of range (m=%llu)", (unsigned long long)row0,
                                        (unsigned long long)(row0 + nrows), (unsigned long long)c->m);
@@ -553,6 +669,7 @@ extern "C" int fh_set_rhs(fh_ctx* c, uint32_t L) {
   if (c->comm) return fail(FH_E_STATE, "fh_set_rhs: a context with a communicator (row-sharded run) has no multi-column form");
   if (c->pending_step) return fail(FH_E_STATE, "a step issued by fh_step_begin is still in flight on this context: call fh_step_end first");
   if (c->op == OP_NONE) return fail(FH_E_STATE, "fh_set_rhs: set the dense operator first (fh_set_matrix / fh_generate_matrix)");
+  if (c->op == OP_SPARSE) return fail(FH_E_STATE, "fh_set_rhs: the sparse operator has no multi-column form");
   if (c->op != OP_DENSE) return fail(FH_E_STATE, "fh_set_rhs: the stencil operator has no multi-column form");
   if (c->f32) return fail(FH_E_STATE, "fh_set_rhs: float32 storage of A has no multi-column form");
   if (L && c->has_b && c->loss_kind != LOSS_LSQ) return fail(FH_E_STATE, "fh_set_rhs: the logistic loss has no multi-column form");
@@ -580,7 +697,7 @@ static int set_loss(fh_ctx* c, int kind, const double* b, uint64_t len) {
   if (c->op == OP_NONE) return fail(FH_E_STATE, "set the operator before the loss");
   if (len != c->m * l_of(c)) return fail(FH_E_ARG, "b has %llu entries, operator has %llu rows (x %llu columns)", (unsigned long long)len, (unsigned long long)c->m, (unsigned long long)l_of(c));
   if (kind != LOSS_LSQ && c->LB) return fail(FH_E_STATE, "the logistic loss has no multi-column form (fh_set_rhs)");
-  if (kind != LOSS_LSQ && c->op != OP_DENSE) return fail(FH_E_STATE, "the logistic loss is implemented for the dense operator");
+  if (kind != LOSS_LSQ && c->op != OP_DENSE && c->op != OP_SPARSE) return fail(FH_E_STATE, "the logistic loss is implemented for the dense operator");
   if (!c->shards.empty()) {          // shell: b is sharded like the rows
     for (int k = 0; k < nshards(c); ++k) FH_TRY(set_loss(c->shards[k], kind, b + c->shard_row0[k], shard_rows(c, k)));
     c->has_b = true; c->loss_kind = kind;
@@ -606,6 +723,7 @@ extern "C" int fh_set_prox(fh_ctx* c, int kind, double mu, double lo, double hi)
   if (kind < FH_PROX_IDENTITY || kind > FH_PROX_GROUP) return fail(FH_E_ARG, "unknown prox kind %d", kind);
   if (kind == FH_PROX_GROUP && !c->LB) return fail(FH_E_ARG, "FH_PROX_GROUP (row-wise l2 shrink) needs the multi-column form: call fh_set_rhs first");
   if (c->LB && !mc_prox_ok(kind)) return fail(FH_E_ARG, "prox kind %d (LINF / L1BALL / TVBALL) has no multi-column form", kind);
+  if (c->op == OP_SPARSE && !sp_prox_ok(kind)) return fail(FH_E_ARG, "prox kind %d (LINF / L1BALL / TVBALL / GROUP) is not implemented for the sparse operator", kind);
   if (kind == FH_PROX_BOX && !(lo <= hi)) return fail(FH_E_ARG, "box prox needs lo <= hi");
   for (fh_ctx* s : c->shards) { s->prox_kind = kind; s->mu = mu; s->lo = lo; s->hi = hi; }      // the prox is replicated work
   c->prox_kind = kind; c->mu = mu; c->lo = lo; c->hi = hi;
@@ -1110,6 +1228,7 @@ static int dense_step(fh_ctx* c, double tau, int accel, double coef, int restart
 // Writes the complete FH_S_* block; scalars[15] != 0 reports a spin timeout (results invalid: use the two-launch path).
 static int step_body(fh_ctx* c, double tau, double* scalars, bool wait) {
   FH_TRY(check_ready(c, true));
+  if (c->op == OP_SPARSE) return fail(FH_E_STATE, "fh_step: the sparse operator has no one-pass kernel: use fh_fwd / fh_adj / fh_fwd_adj / fh_iterate");
   if (c->LB) return fail(FH_E_STATE, "fh_step: the multi-column form (fh_set_rhs) has no one-pass kernel: use fh_fwd / fh_adj / fh_iterate");
   for (int k = 0; k < nshards(c); ++k) FH_TRY(not_lazy(shard_of(c, k), "fh_step"));
   if (c->op == OP_STENCIL) {
@@ -1155,6 +1274,7 @@ extern "C" int fh_step_end(fh_ctx* c, double* scalars) {
 // travels to the separate n-side epilogue through a device scalar.
 extern "C" int fh_step_accel(fh_ctx* c, double tau, double coef, int restart, double* scalars) {
   FH_TRY(check_ready(c, true));
+  if (c->op == OP_SPARSE) return fail(FH_E_STATE, "fh_step_accel: the sparse operator has no one-pass kernel: use fh_fwd / fh_adj / fh_iterate");
   if (c->LB) return fail(FH_E_STATE, "fh_step_accel: the multi-column form (fh_set_rhs) has no one-pass kernel: use fh_fwd / fh_adj / fh_iterate");
   if (c->op == OP_STENCIL) {
     if (row_sharded(c)) return fail(FH_E_STATE, "row sharding is implemented for the dense operator only");
@@ -1268,6 +1388,7 @@ extern "C" int fh_run(fh_ctx* c, int max_steps, const fh_run_opts* o, fh_run_sta
   if (max_steps < 0 || max_steps > 65536) return fail(FH_E_ARG, "fh_run: max_steps must be in [0, 65536]");
   if (o->window < 1 || o->window > FH_RUN_WINDOW_MAX) return fail(FH_E_ARG, "fh_run: window must be in [1, %d]", FH_RUN_WINDOW_MAX);
   if (o->stop_rule < 0 || o->stop_rule > 3) return fail(FH_E_ARG, "fh_run: stop_rule must be 0..3 (the four rules of fasta/stopping.py)");
+  if (c->op == OP_SPARSE) return fail(FH_E_STATE, "fh_run: the sparse operator has no device-side loop: use fh_iterate");
   if (c->LB) return fail(FH_E_STATE, "fh_run: the multi-column form (fh_set_rhs) has no device-side loop: use fh_iterate");
   const RunEntry* e = run_entry(c);
   if (!e && chain_ok(c) && co_resident(c)) return run_chain(c, max_steps, o, state, history, steps_done);
@@ -1497,6 +1618,7 @@ extern "C" int fh_comm_unique_id(void* id128) {
 extern "C" int fh_comm_init(fh_ctx* c, int nranks, int rank, const void* id128) {
   if (!c || !id128) return fail(FH_E_ARG, "null argument");
   if (nranks < 1 || rank < 0 || rank >= nranks) return fail(FH_E_ARG, "bad rank %d of %d", rank, nranks);
+  if (c->op == OP_SPARSE) return fail(FH_E_STATE, "fh_comm_init: a context with a sparse operator cannot be row-sharded");
   if (c->LB) return fail(FH_E_STATE, "fh_comm_init: a context in multi-column form (fh_set_rhs) cannot be row-sharded");
   if (!c->shards.empty() || c->owner)
     return fail(FH_E_STATE, "fh_comm_init: a multi-device context (fh_create_ex, ndev > 1) already shards the rows in-process");
@@ -1686,6 +1808,7 @@ extern "C" int fh_shard(fh_ctx* c, int k, fh_ctx** shard, uint64_t* row0, uint64
 extern "C" int fh_stream_read_ms(fh_ctx* c, int reps, double* ms_per_pass, uint64_t* bytes_per_pass) {
   FH_TRY(check_ready(c, false));
   if (!c->shards.empty()) return fh_stream_read_ms(c->shards[0], reps, ms_per_pass, bytes_per_pass);     // shard 0's block on its device
+  if (c->op == OP_SPARSE) return fail(FH_E_STATE, "fh_stream_read_ms: the stream-read ceiling is measured on a dense matrix, not on the sparse operator");
   if (c->op != OP_DENSE) return fail(FH_E_STATE, "stream-read ceiling needs a dense matrix");
   if (reps < 1) reps = 1;
   // k_stream_probe<16,1> as described in include/fasta_hip.h: persistent workgroups, 1 per CU by default, three rotating buffers of 16 nt loads per lane

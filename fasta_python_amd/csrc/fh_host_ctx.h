@@ -97,7 +97,7 @@ static int rccl_load() {
 // ------------------------------------------------------------------------------------------------
 // context
 // ------------------------------------------------------------------------------------------------
-enum { OP_NONE = 0, OP_DENSE = 1, OP_STENCIL = 2 };
+enum { OP_NONE = 0, OP_DENSE = 1, OP_STENCIL = 2, OP_SPARSE = 3 };
 
 struct fh_ctx {
   int device = 0;
@@ -110,6 +110,12 @@ struct fh_ctx {
   uint64_t nv = 0, mv = 0;   // allocated n-side / m-side vector lengths (doubles; rows of LB doubles in multi-column form)
   uint32_t L = 0, LB = 0;    // multi-column form (fh_set_rhs, csrc/fh_multi.h): L columns per unknown, kept as LB in {2, 4, 8, 16} doubles per row; 0 = the vector form
   uint64_t H = 0, W = 0;
+  // sparse operator (fh_set_matrix_csr, csrc/fh_sparse.h): sp[0] = A by rows, sp[1] = A^T by rows, each with its non-zero-balanced row ranges,
+  // its list of long rows and the lanes-per-row G chosen from its mean row length; sp_r = the adjoint's residual (m-side)
+  SpMatP sp[2] = {};
+  int sp_G[2] = {0, 0};
+  uint64_t nnz = 0;
+  double* sp_r = nullptr;
   double* A = nullptr;
   size_t a_block_bytes = 0;  // size of the block A lives in (>= the matrix: a kept block may be up to twice as large, see acquire_matrix_block)
   // n-side
@@ -362,6 +368,15 @@ static void free_operator(fh_ctx* c) {
   auto fr = [](double*& p) { if (p) { (void)hipFree(p); p = nullptr; } };
   if (c->A && c->op == OP_DENSE) { release_matrix_block(c->device, c->A, c->a_block_bytes); c->A = nullptr; c->a_block_bytes = 0; }
   fr(c->A);
+  for (SpMatP& a : c->sp) {
+    if (a.ptr) (void)hipFree((void*)a.ptr);
+    if (a.idx) (void)hipFree((void*)a.idx);
+    if (a.val) (void)hipFree((void*)a.val);
+    if (a.part) (void)hipFree((void*)a.part);
+    if (a.longrows) (void)hipFree((void*)a.longrows);
+    a = SpMatP();
+  }
+  fr(c->sp_r); c->nnz = 0;
   free_vectors(c);
   c->L = c->LB = 0;                  // a new operator starts in the vector form
   fr(c->ws); c->ws_bytes = 0;

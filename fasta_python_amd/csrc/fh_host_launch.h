@@ -203,6 +203,61 @@ static int launch_fwd_multi(fh_ctx* c, int mode, double tau, const double* x0, c
   return 0;
 }
 
+// ---- sparse operator (fh_set_matrix_csr; kernels in csrc/fh_sparse.h, instantiated by fh_sparse_part.hip) -------------------------------
+#ifndef FH_SINGLE_TU
+#define SP_DECLARE(G) SP_KERNELS(extern template, G)
+SP_FOR_EACH(SP_DECLARE)
+#undef SP_DECLARE
+#endif
+struct SpEntry { int g; void (*fwd[2])(const SpFwdP); void (*adj[2])(const SpAdjP); };
+#define SP_ROW(G) {G, {k_sp_fwd<G, 0>, k_sp_fwd<G, 1>}, {k_sp_adj<G, 0>, k_sp_adj<G, 1>}},
+static const SpEntry kSpTable[] = { SP_FOR_EACH(SP_ROW) };
+#undef SP_ROW
+static const SpEntry* sp_entry(int g) {
+  for (const SpEntry& e : kSpTable) if (e.g == g) return &e;
+  return nullptr;
+}
+static inline bool sp_prox_ok(int kind) {
+  return kind == FH_PROX_IDENTITY || kind == FH_PROX_SHRINK || kind == FH_PROX_NONNEG || kind == FH_PROX_BOX;
+}
+// values and indices stream once and were the non-temporal candidates; measured (profiles/sparse_rows.txt), plain loads are as fast or faster at every
+// shape (65536^2: 0.1 % 0.129 against 0.147 ms per pair, 1 % 0.550 / 0.557, 5 % 2.063 / 2.162; 1048576^2, 16 per row: 0.522 / 0.523), so plain is the
+// default and FH_TUNE_NT_LOADS = 1 the opt-in
+static inline int sp_nt_for(const fh_ctx* c) { return c->nt_loads > 0 ? 1 : 0; }
+
+// z := A * (mode 0: prox(x0 - tau g0), by the prologue launch ; mode 1: x0)
+static int launch_fwd_sparse(fh_ctx* c, int mode, double tau, const double* x0, const double* g0, const double* xacc0,
+                             double* xhat, double* xp, double* z, int sub_b) {
+  const SpEntry* e = sp_entry(c->sp_G[0]);
+  if (!e) return fail(FH_E_STATE, "sparse operator: no kernel for %d lanes per row", c->sp_G[0]);
+  if (mode == 0 && !sp_prox_ok(c->prox_kind))
+    return fail(FH_E_STATE, "prox kind %d (LINF / L1BALL / TVBALL / GROUP) is not implemented for the sparse operator", c->prox_kind);
+  SpFwdP p;
+  p.a = c->sp[0]; p.m = (uint32_t)c->m;
+  const uint32_t npro = mode == 0 ? (uint32_t)((c->n + FH_WG - 1) / FH_WG) : 0u;
+  p.nred_n = npro;
+  const unsigned grid = p.a.nwg + p.a.nlong;
+  FH_TRY(ensure_ws(c, ((size_t)npro * 8 + grid) * sizeof(double)));
+  p.red_n = c->ws; p.red_m = c->ws + (size_t)npro * 8;
+  p.x = mode == 0 ? xp : x0;
+  p.b = c->b; p.z = z; p.sub_b = sub_b; p.loss = c->loss_kind;
+  p.counter = c->counters + CNT_FWD;
+  p.out = scalar_out(c);
+  t_begin(c, FH_K_FWD);
+  if (mode == 0) {
+    SpProP q;
+    q.n = (uint32_t)c->n; q.x0 = x0; q.g0 = g0; q.xacc0 = xacc0; q.xhat = xhat; q.xp = xp; q.tau = tau;
+    q.px = make_prox(c, tau);
+    q.red_n = c->ws;
+    k_sp_prologue<<<dim3(npro), dim3(FH_WG), 0, c->stream>>>(q);
+  }
+  p.seq = seq_offer(c);
+  e->fwd[sp_nt_for(c) ? 1 : 0]<<<dim3(grid), dim3(FH_WG), 0, c->stream>>>(p);
+  t_end(c, FH_K_FWD);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
 // n-side epilogue as its own launch (row-sharded runs, after the all-reduce of g1)
 static int bb_epilogue_only(fh_ctx* c, const AdjIO& io, const double* fsq_src, const double* coef_src = nullptr, const double* pack = nullptr) {
   AdjP p;
@@ -253,6 +308,36 @@ static int launch_adj_multi(fh_ctx* c, const AdjIO& io) {
   t_begin(c, FH_K_ADJ);
   p.seq = io.mode == 0 ? seq_offer(c) : 0u;
   e->adj[nt_for(c) ? 1 : 0]<<<dim3(grid), dim3(FH_WG), 0, c->stream>>>(p);
+  t_end(c, FH_K_ADJ);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// g1 := A^T grad f(z') by the gather over the A^T copy; the residual and the loss sum at z' come from the m-side prologue launch
+static int launch_adj_sparse(fh_ctx* c, const AdjIO& io) {
+  const SpEntry* e = sp_entry(c->sp_G[1]);
+  if (!e) return fail(FH_E_STATE, "sparse operator: no kernel for %d lanes per row", c->sp_G[1]);
+  if (io.mode != 0 && io.mode != 1) return fail(FH_E_STATE, "the sparse operator has no row-sharded adjoint");
+  SpAdjP p;
+  p.a = c->sp[1]; p.n = (uint32_t)c->n;
+  const uint32_t nres = (uint32_t)((c->m + FH_WG - 1) / FH_WG);
+  p.nred_f = nres;
+  const unsigned grid = p.a.nwg + p.a.nlong;
+  FH_TRY(ensure_ws(c, ((size_t)nres + (size_t)grid * 8) * sizeof(double)));
+  p.red_f = c->ws; p.red_bb = c->ws + nres;
+  p.r = c->sp_r;
+  p.accel = io.accel; p.mode = io.mode; p.coef = io.coef; p.tau = io.tau;
+  p.x0 = io.x0; p.xp = io.xp; p.xacc0 = io.xacc0; p.xhat = io.xhat; p.x1 = io.x1; p.g1 = io.g1;
+  p.counter = c->counters + CNT_ADJ_FIN;
+  p.out = scalar_out(c);
+  SpResP q;
+  q.m = (uint32_t)c->m; q.z = io.z; q.zacc0 = io.zacc0; q.b = c->b; q.r = c->sp_r;
+  q.sub_b = io.sub_b; q.loss = c->loss_kind; q.accel = io.accel; q.coef = io.coef;
+  q.red_f = c->ws;
+  t_begin(c, FH_K_ADJ);
+  k_sp_resid<<<dim3(nres), dim3(FH_WG), 0, c->stream>>>(q);
+  p.seq = io.mode == 0 ? seq_offer(c) : 0u;
+  e->adj[sp_nt_for(c) ? 1 : 0]<<<dim3(grid), dim3(FH_WG), 0, c->stream>>>(p);
   t_end(c, FH_K_ADJ);
   HIP_TRY(hipGetLastError());
   return 0;
@@ -685,6 +770,7 @@ static int op_fwd(fh_ctx* c, int mode, double tau, const double* x0, const doubl
   if (c->op == OP_DENSE && c->LB) return launch_fwd_multi(c, mode, tau, x0, g0, xacc0, xhat, xp, z, sub_b);
   if (c->op == OP_DENSE) return launch_fwd_dense(c, mode, tau, x0, g0, xacc0, xhat, xp, z, sub_b);
   if (c->op == OP_STENCIL) return launch_fwd_tv(c, mode, tau, x0, g0, xacc0, xhat, xp, z, sub_b);
+  if (c->op == OP_SPARSE) return launch_fwd_sparse(c, mode, tau, x0, g0, xacc0, xhat, xp, z, sub_b);
   return fail(FH_E_STATE, "no operator set");
 }
 
@@ -697,6 +783,7 @@ static int adj_local(fh_ctx* c, const AdjIO& io_in) {
   if (c->op == OP_DENSE && c->LB) return launch_adj_multi(c, io);
   if (c->op == OP_DENSE) return launch_adj_dense(c, io);
   if (c->op == OP_STENCIL) return launch_adj_tv(c, io);
+  if (c->op == OP_SPARSE) return launch_adj_sparse(c, io);
   return fail(FH_E_STATE, "no operator set");
 }
 // stage 2, exchange: A_k^T r_k partials (nv doubles at g1(shard)) and the local loss sums (FH_S_FSQ_ADJ) summed over the row blocks
@@ -725,7 +812,7 @@ static int reduce_fsq_over_ranks(fh_ctx* c) {
 static int check_ready(fh_ctx* c, bool need_b) {
   if (!c) return fail(FH_E_ARG, "null context");
   if (c->pending_step) return fail(FH_E_STATE, "a step issued by fh_step_begin is still in flight on this context: call fh_step_end first");
-  if (c->op == OP_NONE) return fail(FH_E_STATE, "no operator set (call fh_set_matrix / fh_generate_matrix / fh_set_stencil)");
+  if (c->op == OP_NONE) return fail(FH_E_STATE, "no operator set (call fh_set_matrix / fh_set_matrix_csr / fh_generate_matrix / fh_set_stencil)");
   if (need_b && !c->has_b) return fail(FH_E_STATE, "no loss set (call fh_set_loss_lsq)");
   return c->shards.empty() ? use_device(c) : 0;      // (a shell selects the device shard by shard)
 }

@@ -19,7 +19,7 @@ import numpy as np
 from numpy import linalg as la
 
 from . import stopping
-from .linalg import LinearMap
+from .linalg import LinearMap, is_sparse_matrix
 
 __all__ = ["HostFBS", "host_map"]
 
@@ -42,9 +42,15 @@ def host_map(A, At, x0):
             assert At.shape == A.shape[::-1]
             return LinearMap(lambda x: A @ x, lambda y: At @ y, V, W)
         return LinearMap(lambda x: A @ x, lambda y: A.T @ y, V, W)      # linalg.py:41
+    if is_sparse_matrix(A):                          # a scipy.sparse design matrix: the closures the reference is given for it
+        V, W = (A.shape[1],) + tuple(np.shape(x0)[1:]), (A.shape[0],) + tuple(np.shape(x0)[1:])
+        if At is not None and hasattr(At, "shape"):
+            assert tuple(At.shape) == tuple(A.shape)[::-1]
+            return LinearMap(lambda x: A @ x, lambda y: At @ y, V, W)
+        return LinearMap(lambda x: A @ x, lambda y: A.T @ y, V, W)
     if callable(A) and callable(At):                 # tv_denoising.py:99: bare functions, codomain found by probing
         return LinearMap(A, At, np.shape(x0), np.shape(A(np.zeros(np.shape(x0)))))
-    raise TypeError("fasta(): operator A must be a LinearMap, a 2-D ndarray, a callable pair (A, At) or None")
+    raise TypeError("fasta(): operator A must be a LinearMap, a 2-D ndarray, a scipy.sparse matrix, a callable pair (A, At) or None")
 
 
 def _flat_dot(u, v):

@@ -79,6 +79,8 @@ SIGNATURES = {
     "fh_set_matrix_f32": (_i32, [_ctx, C.POINTER(C.c_float), _u64, _u64, _u64]),
     "fh_generate_matrix": (_i32, [_ctx, _u64, _u64, _u64, _u64, _dbl]),
     "fh_get_matrix_rows": (_i32, [_ctx, _u64, _u64, _pd]),
+    "fh_set_matrix_csr": (_i32, [_ctx, _u64, _u64, _u64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _pd]),
+    "fh_nnz": (_i32, [_ctx, C.POINTER(_u64)]),
     "fh_set_stencil": (_i32, [_ctx, _u64, _u64]),
     "fh_shape": (_i32, [_ctx, C.POINTER(_u64), C.POINTER(_u64)]),
     "fh_set_rhs": (_i32, [_ctx, C.c_uint32]),
@@ -354,6 +356,29 @@ class HipContext:
             A = np.ascontiguousarray(A, dtype=np.float64)
         m, n = A.shape
         self._call("fh_set_matrix", A.ctypes.data_as(_pd), m, n, n)
+
+    def set_matrix_csr(self, indptr, indices, data, shape):
+        """Sparse operator from canonical CSR arrays (sorted, duplicates summed; fh_set_matrix_csr checks and names the first bad row)."""
+        m, n = (int(k) for k in shape)
+        indptr = np.ascontiguousarray(indptr, dtype=np.int64)
+        indices = np.asarray(indices)
+        if indices.dtype != np.int32:                  # narrowing must be exact: a wide column number may not wrap into the valid range
+            if indices.dtype.kind not in "iu":
+                raise TypeError("CSR indices must be integers")
+            if indices.size and (int(indices.min()) < 0 or int(indices.max()) >= min(n, 2 ** 31)):
+                raise ValueError(f"CSR column index out of range for {n} columns (32-bit column numbers)")
+        indices = np.ascontiguousarray(indices, dtype=np.int32)
+        data = np.ascontiguousarray(data, dtype=np.float64)
+        if indptr.size != m + 1 or indices.size != data.size:
+            raise ValueError(f"CSR arrays do not fit shape {(m, n)}: indptr {indptr.size}, indices {indices.size}, data {data.size}")
+        self._call("fh_set_matrix_csr", m, n, int(data.size), indptr.ctypes.data_as(C.POINTER(C.c_int64)),
+                   indices.ctypes.data_as(C.POINTER(C.c_int32)), data.ctypes.data_as(_pd))
+
+    def nnz(self):
+        """Stored entries of the sparse operator (0 for a dense matrix or the stencil)."""
+        k = _u64(0)
+        self._call("fh_nnz", C.byref(k))
+        return int(k.value)
 
     def generate_matrix(self, m, n, row0, seed, coef):
         self._call("fh_generate_matrix", int(m), int(n), int(row0), int(seed), float(coef))

@@ -11,6 +11,8 @@ subclasses are *recognised* by `fasta()` and run on the device:
   ShardedDenseMatrixMap -- the same matrix split into contiguous row blocks over several devices
                      of THIS process (single call): `fasta(ShardedDenseMatrixMap(A,
                      devices=[0, 1, ...]), ls.f, ls.gradf, reg.g, reg.prox, x0)`;
+  SparseMatrixMap -- a sparse design matrix (any scipy.sparse matrix / array, or CSR arrays), kept on the
+                     device by rows and by columns; both directions are gathers (csrc/fh_sparse.h);
   GradDivMap      -- the periodic div/grad stencil pair of examples/tv_denoising.py:26-63.
 
 A DenseMatrixMap built from a host ndarray uploads LAZILY: it keeps a reference to the array (as the
@@ -32,7 +34,7 @@ from . import hip
 Matrix = np.ndarray
 Vector = np.ndarray
 
-__all__ = ["LinearMap", "LinearOperator", "DenseMatrixMap", "ShardedDenseMatrixMap", "GradDivMap", "Matrix", "Vector"]
+__all__ = ["LinearMap", "LinearOperator", "DenseMatrixMap", "ShardedDenseMatrixMap", "SparseMatrixMap", "GradDivMap", "is_sparse_matrix", "Matrix", "Vector"]
 
 
 class LinearMap:
@@ -51,6 +53,10 @@ class LinearMap:
         """fasta/linalg.py:37-41.  Returns a DenseMatrixMap: `A @ x` / `A.T @ y` on host arrays (the reference's closures), the
         device-resident operator once the device loop adopts it (storage="f32": opt-in float32 storage of the device copy;
         devices=[...]: row blocks over several devices of this process, i.e. a ShardedDenseMatrixMap)."""
+        if is_sparse_matrix(A):                    # a scipy.sparse matrix: kept sparse on the device (one device, float64)
+            if storage != "f64" or devices is not None:
+                raise TypeError('storage="f32" and row sharding are not implemented for a sparse operator on the device')
+            return SparseMatrixMap(A, device=device)
         assert A.ndim == 2
         if devices is not None:
             return ShardedDenseMatrixMap(A, devices=devices, storage=storage)
@@ -325,6 +331,102 @@ class ShardedDenseMatrixMap(DenseMatrixMap):
     def row_blocks(self):
         """[(row0, rows)] of every block, in device-list order."""
         return [self.ctx.shard(k)[1:] for k in range(self.ctx.shard_count())]
+
+
+def is_sparse_matrix(A):
+    """A scipy.sparse matrix or array, told by its interface (SciPy is not imported here)."""
+    return not isinstance(A, np.ndarray) and callable(getattr(A, "tocsr", None)) and hasattr(A, "shape") and hasattr(A, "nnz")
+
+
+def canonical_csr(A):
+    """(data float64, indices int32, indptr int64, (m, n)) in canonical CSR -- rows in order, column indices strictly increasing, duplicates
+    summed, explicit zeros kept -- from a scipy.sparse matrix / array of any format, or from a raw `((data, indices, indptr), shape)` tuple,
+    which must already be canonical (ValueError otherwise: a raw triple is taken as it is, never silently re-sorted)."""
+    if is_sparse_matrix(A):
+        if len(A.shape) != 2:
+            raise AssertionError("matrix operator must be 2-D")
+        S = A.tocsr()
+        if S is A or S.data is getattr(A, "data", None):
+            S = S.copy()                                   # (sum_duplicates / sort_indices work in place: never on the caller's matrix)
+        S.sum_duplicates()
+        S.sort_indices()
+        data, indices, indptr, shape = S.data, S.indices, S.indptr, S.shape
+    else:
+        try:
+            (data, indices, indptr), shape = A
+        except (TypeError, ValueError):
+            raise TypeError("SparseMatrixMap takes a scipy.sparse matrix / array or a ((data, indices, indptr), shape) tuple") from None
+    m, n = (int(k) for k in shape)
+    if m < 1 or n < 1:
+        raise ValueError(f"matrix must be non-empty (got {m} x {n})")
+    if n >= 2 ** 31 or m >= 2 ** 31:
+        raise ValueError("matrix dimension exceeds 2^31 - 1: column / row numbers are kept as 32-bit integers")
+    data = np.ascontiguousarray(data, dtype=np.float64)
+    indices = np.asarray(indices)
+    indptr = np.ascontiguousarray(indptr, dtype=np.int64)
+    if indices.dtype.kind not in "iu":
+        raise TypeError("CSR indices must be integers")
+    if indices.size and (int(indices.min()) < 0 or int(indices.max()) >= n):
+        raise ValueError(f"CSR column index out of range for {n} columns")
+    indices = np.ascontiguousarray(indices, dtype=np.int32)           # (in range: the narrowing is exact)
+    if indptr.shape != (m + 1,) or indices.shape != data.shape or data.ndim != 1:
+        raise ValueError(f"CSR arrays do not fit shape {(m, n)}")
+    if indptr[0] != 0 or indptr[-1] != data.size or np.any(np.diff(indptr) < 0):
+        raise ValueError("CSR indptr must start at 0, be non-decreasing and end at nnz")
+    if data.size > 1:
+        step_ok = np.diff(indices.astype(np.int64)) > 0
+        starts = indptr[1:-1]
+        step_ok[starts[(starts > 0) & (starts < data.size)] - 1] = True    # (a row's first entry need not exceed the previous row's last)
+        if not step_ok.all():
+            bad = int(np.searchsorted(indptr, int(np.flatnonzero(~step_ok)[0]) + 1, side="right")) - 1
+            raise ValueError(f"CSR column indices of row {bad} are not strictly increasing (sort them and sum duplicates)")
+    return data, indices, indptr, (m, n)
+
+
+class SparseMatrixMap(_DeviceMap):
+    """Sparse matrix on the device (csrc/fh_sparse.h): `A` is any scipy.sparse matrix or array, or a `((data, indices, indptr), shape)`
+    tuple of canonical CSR arrays.  It is canonicalised on the host (float64, duplicates summed, indices sorted, explicit zeros kept);
+    the device keeps A by rows and A^T by rows and runs both directions as gathers -- no atomics, bitwise repeatable.
+
+    Lazy like a DenseMatrixMap built from a host matrix: the upload happens when the device loop first asks for the context, and on
+    host arrays the map is `S @ v` / `S.T @ w`, the closures the reference is given for such a matrix -- so `backend="numpy"` and the
+    generic host loop are the reference bit for bit.  One device, float64; prox kinds Shrink / NonNeg / Box / none; both losses."""
+
+    def __init__(self, A, device=0, tuning=None):
+        data, indices, indptr, shape = canonical_csr(A)
+        self.csr = (data, indices, indptr)
+        self.shape = shape
+        self.storage = "f64"
+        self.rhs = None
+        self._tuning = dict(tuning or {})
+        from scipy.sparse import csr_matrix            # (SciPy is needed from here on, not at module import)
+        self._host = csr_matrix((data, indices, indptr), shape=shape)
+        _DeviceMap.__init__(self, (shape[1],), (shape[0],), device, lazy=True)
+
+    @property
+    def nnz(self):
+        return int(self.csr[0].size)
+
+    @property
+    def matrix(self):
+        """The canonical host matrix (scipy.sparse.csr_matrix)."""
+        return self._host
+
+    def _on_context(self, ctx):
+        for key, value in self._tuning.items():
+            ctx.set_tuning(key, value)
+        data, indices, indptr = self.csr
+        ctx.set_matrix_csr(indptr, indices, data, self.shape)
+
+    def _apply_fwd(self, v):
+        return self._host @ v
+
+    def _apply_adj(self, w):
+        return self._host.T @ w
+
+    @property
+    def T(self):
+        return self.H
 
 
 class GradDivMap(_DeviceMap):

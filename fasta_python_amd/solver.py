@@ -30,13 +30,13 @@ from time import time
 import numpy as np
 
 from . import hip, stopping
-from .linalg import DenseMatrixMap, GradDivMap, LinearMap, _DeviceMap
+from .linalg import DenseMatrixMap, GradDivMap, LinearMap, SparseMatrixMap, _DeviceMap, is_sparse_matrix
 from .losses import LeastSquares, LogisticLoss
 from .proximal import NoProx, ProxTag
 
 __all__ = ["fasta", "Convergence", "FBSolver", "EPSILON"]
 
-PAIR_MAX_ELEMENTS = 1 << 26     # dense operators up to 64 Mi elements (<= ~0.1 ms per launch) take K-fwd + K-adj under one sync
+PAIR_MAX_ELEMENTS = 1 << 26     # operators up to 64 Mi (stored) elements (<= ~0.1 ms per launch) take K-fwd + K-adj under one sync
 EPSILON = 1E-12      # fasta/__init__.py:32
 
 
@@ -95,21 +95,34 @@ def _matrix_form_refusal(A, loss, prox, x0):
     return None
 
 
+def _sparse_form_refusal(A, prox, x0):
+    """A sparse operator (csrc/fh_sparse.h) serves vector unknowns and the elementwise prox kinds (float32 storage is refused where it
+    could be asked for: LinearMap.from_matrix).  None, or the reason."""
+    from .proximal import GroupShrink, L1Ball, LinfProx, TVDualBall
+    if not (isinstance(A, SparseMatrixMap) or is_sparse_matrix(A)):
+        return None
+    if isinstance(prox, (LinfProx, L1Ball, TVDualBall, GroupShrink)):
+        return f"proximal.{type(prox).__name__} is not implemented for a sparse operator on the device (Shrink, NonNeg, Box or no prox are)"
+    if x0 is not None and np.ndim(x0) == 2:
+        return "a sparse operator has no matrix (multi-column) form on the device: x0 must be a vector"
+    return None
+
+
 def _unrecognised(A, At, f, gradf, g, proxg, x0=None):
     """None when the seven operands can run on the device, else the reason they cannot (a sentence)."""
-    if not isinstance(A, (np.ndarray, _DeviceMap)):
-        return ("operator A is not device-resident (pass a 2-D float64 ndarray, a linalg.DenseMatrixMap / "
-                "LinearMap.from_matrix(A), or a linalg.GradDivMap); arbitrary Python callables cannot run inside the fused HIP kernels")
+    if not isinstance(A, (np.ndarray, _DeviceMap)) and not is_sparse_matrix(A):
+        return ("operator A is not device-resident (pass a 2-D float64 ndarray, a scipy.sparse matrix, a linalg.DenseMatrixMap / "
+                "LinearMap.from_matrix(A), a linalg.SparseMatrixMap or a linalg.GradDivMap); arbitrary Python callables cannot run inside the fused HIP kernels")
     loss_f, loss_g = _tag_of(f, (LeastSquares, LogisticLoss)), _tag_of(gradf, (LeastSquares, LogisticLoss))
     if loss_f is None or loss_f is not loss_g:
         return "f and gradf must be the `.f` / `.gradf` of one losses.LeastSquares(b) or losses.LogisticLoss(b) object"
     if g is None and proxg is None:
-        return _matrix_form_refusal(A, loss_f, None, x0)
+        return _sparse_form_refusal(A, None, x0) or _matrix_form_refusal(A, loss_f, None, x0)
     prox, owner_g = _tag_of(proxg, ProxTag), _tag_of(g, ProxTag)
     if prox is None or (owner_g is not None and owner_g is not prox) or (owner_g is None and g is not None):
         return ("g and proxg must be the `.g` / `.prox` of one proximal.* tag object "
                 "(Shrink, NonNeg, LinfProx, L1Ball, Box, TVDualBall, GroupShrink)")
-    return _matrix_form_refusal(A, loss_f, prox, x0)
+    return _sparse_form_refusal(A, prox, x0) or _matrix_form_refusal(A, loss_f, prox, x0)
 
 
 def _recognise(A, At, f, gradf, g, proxg, x0):
@@ -121,6 +134,10 @@ def _recognise(A, At, f, gradf, g, proxg, x0):
             raise AssertionError("At must have the transposed shape of A")
         # a 2-D x0 of shape (n, L) over an (m, n) matrix: a matrix unknown, one A for its L columns
         A = DenseMatrixMap(A, rhs=x0.shape[1] if (x0.ndim == 2 and x0.shape[0] == A.shape[1]) else None)
+    elif is_sparse_matrix(A):
+        if At is not None and hasattr(At, "shape") and tuple(At.shape) != tuple(A.shape)[::-1]:
+            raise AssertionError("At must have the transposed shape of A")
+        A = SparseMatrixMap(A)
     loss_f = _tag_of(f, (LeastSquares, LogisticLoss))
     prox = NoProx() if (g is None and proxg is None) else _tag_of(proxg, ProxTag)      # :88-90
     if tuple(x0.shape) != A.Vshape:
@@ -158,6 +175,8 @@ class FBSolver:
         printed after each call from its history records: same text and order as the reference's (:302-306), in bursts.  `times[i]`
         within one call are interpolated between its start and its end."""
         self.A, self.loss, self.prox = A, loss, prox
+        if isinstance(A, SparseMatrixMap) and fused is True:
+            raise ValueError("fused=True: a sparse operator has no one-pass kernel (csrc/fh_sparse.h: K-fwd and K-adj)")
         self.fused_opt = fused
         self.ctx = A.ctx
         self.x0 = np.asarray(x0, dtype=np.float64)
@@ -256,7 +275,7 @@ class FBSolver:
             self.mode = "speculative"
         elif (self.fused_opt == "auto" and kind in (0, 3) and not self.accelerate and hasattr(c, "fwd_adj")
               and getattr(self.A, "shape", None) is not None and len(self.A.shape) == 2
-              and self.A.shape[0] * self.A.shape[1] <= PAIR_MAX_ELEMENTS):
+              and (self.A.nnz if isinstance(self.A, SparseMatrixMap) else self.A.shape[0] * self.A.shape[1]) <= PAIR_MAX_ELEMENTS):
             self.mode = "pair"
         self.use_fused = self.mode in ("always", "speculative")
         self.fused_always = self.mode == "always"
@@ -543,7 +562,7 @@ def fasta(A, *operands, backend="auto", **options):
         x0 = np.asarray(x0)
         return HostFBS(host_map(A, At, x0), f, gradf, g, proxg, x0, **options).setup().run()
     x0 = np.asarray(x0, dtype=np.float64)
-    owns = isinstance(A, np.ndarray)
+    owns = isinstance(A, np.ndarray) or is_sparse_matrix(A)
     A, loss, prox = _recognise(A, At, f, gradf, g, proxg, x0)
     try:
         return FBSolver(A, loss, prox, x0, **options).setup().run()

@@ -179,6 +179,19 @@ int fh_set_matrix_f32(fh_ctx* ctx, const float* A, uint64_t m, uint64_t n, uint6
  * (device twin of oracle/problems.py:synth_values).                                            */
 int fh_generate_matrix(fh_ctx* ctx, uint64_t m, uint64_t n, uint64_t row0, uint64_t seed, double coef);
 int fh_get_matrix_rows(fh_ctx* ctx, uint64_t row0, uint64_t nrows, double* out /* nrows*n */);
+/* ---- sparse operator: A in canonical CSR (replaces the closures `S @ x`, `S.T @ y` of a scipy.sparse design matrix) ----------------------
+ * indptr has m + 1 entries, starts at 0, is non-decreasing and ends at nnz; the column indices of a row are strictly increasing and < n
+ * (sorted, duplicates summed); anything else is FH_E_ARG with a message naming the first offending row.  nnz == 0, empty rows and empty
+ * columns are legal; explicit zeros are kept as entries.  The library keeps two device copies, A by rows and A^T by rows (built here by a
+ * stable counting sort), and runs BOTH directions as gathers (csrc/fh_sparse.h): no atomics, fixed summation order, bitwise repeatable.
+ * Vectors keep the vector form's layout, so fh_set_vector / fh_get_vector, fh_diff_norm, fh_commit, both losses and the prox kinds
+ * IDENTITY / SHRINK / NONNEG / BOX work unchanged; served entry points: fh_init, fh_setup (its three-pass route), fh_gradient_at, fh_apply,
+ * fh_fwd, fh_adj (accel / coef), fh_fwd_adj, fh_iterate, fh_timing_* (FH_K_FWD / FH_K_ADJ / FH_K_AUX).
+ * Refused (FH_E_STATE / FH_E_ARG): fh_step*, fh_run, fh_set_rhs, fh_comm_init (and a context that has a communicator), multi-device
+ * contexts, float32 storage, fh_get_matrix_rows, fh_stream_read_ms, FH_PROX_LINF / L1BALL / TVBALL / GROUP (a context holding one of these
+ * returns to IDENTITY when the sparse operator is set).  fh_fused_supported, fh_fused_agree and fh_run_supported report 0.               */
+int fh_set_matrix_csr(fh_ctx* ctx, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* indptr, const int32_t* indices, const double* values);
+int fh_nnz(fh_ctx* ctx, uint64_t* nnz);     /* stored entries of the sparse operator; 0 for every other operator */
 /* periodic difference stencil pair: A = div: (H,W,2)->(H,W), A^H = grad (examples/tv_denoising.py:26-63) */
 int fh_set_stencil(fh_ctx* ctx, uint64_t H, uint64_t W);
 int fh_shape(fh_ctx* ctx, uint64_t* m, uint64_t* n);
@@ -201,7 +214,7 @@ int fh_rhs(fh_ctx* ctx, uint32_t* L);      /* L of the multi-column form, 0 in t
 /* ---- smooth term f(z) = .5||z - b||^2, grad f(z) = z - b (examples/sparse_least_squares.py:41-42) */
 int fh_set_loss_lsq(fh_ctx* ctx, const double* b, uint64_t len);
 /* ---- smooth term f(z) = sum log(1+exp(z)) - (b==1)*z, grad f(z) = -b/(1+exp(b*z)), labels b in {-1,+1}
- *      (examples/sparse_logistic.py:47-48); FH_S_FSQ / FH_S_FSQ_ADJ then carry f itself. Dense operator only.   */
+ *      (examples/sparse_logistic.py:47-48); FH_S_FSQ / FH_S_FSQ_ADJ then carry f itself. Dense and sparse operators.   */
 int fh_set_loss_logistic(fh_ctx* ctx, const double* labels, uint64_t len);
 /* ---- prox term (kinds above); mu as in the closures, lo/hi for FH_PROX_BOX only              */
 int fh_set_prox(fh_ctx* ctx, int kind, double mu, double lo, double hi);

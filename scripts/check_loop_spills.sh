@@ -9,5 +9,6 @@ for part in 0 1 2; do python scripts/loop_spills.py fh_setup_part.hip k_setup_de
 wait
 python scripts/loop_spills.py fasta_hip.hip "k_run_dense|k_tv_onepass|k_fwd_dense|k_adj_dense" > $out/host.txt 2>&1
 python scripts/loop_spills.py fh_multi_part.hip "k_mc_fwd|k_mc_adj" > $out/multi.txt 2>&1      # the multi-column kernels (make -C fasta_python_amd/csrc multi-spills)
-cat $out/fused?.txt $out/setup?.txt $out/host.txt $out/multi.txt
+python scripts/loop_spills.py fh_sparse_part.hip "k_sp_fwd|k_sp_adj" > $out/sparse.txt 2>&1    # the sparse-operator kernels (make -C fasta_python_amd/csrc sparse-spills)
+cat $out/fused?.txt $out/setup?.txt $out/host.txt $out/multi.txt $out/sparse.txt
 rm -rf $out
