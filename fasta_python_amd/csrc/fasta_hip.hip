@@ -18,6 +18,7 @@
 #include "fh_dense.h"
 #include "fh_multi.h"
 #include "fh_sparse.h"
+#include "fh_spmulti.h"
 #include "fh_tv.h"
 #include "fh_prox.h"
 #include "fh_fused.h"
@@ -114,6 +115,12 @@ MC_FOR_EACH(MC_INSTANTIATE)
 #define SP_INSTANTIATE(G) SP_KERNELS(template, G)
 SP_FOR_EACH(SP_INSTANTIATE)
 #undef SP_INSTANTIATE
+#define SPMC_INSTANTIATE_LB(LB) SPMC_LB_KERNELS(template, LB)
+SPMC_FOR_EACH_LB(SPMC_INSTANTIATE_LB)
+#undef SPMC_INSTANTIATE_LB
+#define SPMC_INSTANTIATE(G, LB) SPMC_KERNELS(template, G, LB)
+SPMC_FOR_EACH(SPMC_INSTANTIATE)
+#undef SPMC_INSTANTIATE
 #endif
 
 #include "fh_host_ctx.h"
@@ -490,21 +497,26 @@ extern "C" int fh_generate_matrix(fh_ctx* c, uint64_t m, uint64_t n, uint64_t ro
   return finish(c);
 }
 
-// ---- sparse operator: A in canonical CSR (csrc/fh_sparse.h) ---------------------------------------------------------------------------------
-// One side of the operator on the device: the arrays, the lanes per row G (from the mean row length), the rows longer than max(SP_LONG_FACTOR * G,
-// SP_LONG_MEANS mean rows) (a workgroup each) and the contiguous row ranges of the other workgroups, balanced by the trips a group of G lanes spends on a row.
-// Computed here, once; a launch only reads it.
-static int sp_upload_side(fh_ctx* c, int side, uint64_t rows, uint64_t nnz, const int64_t* ptr, const int32_t* idx, const double* val) {
+// ---- sparse operator: A in canonical CSR (csrc/fh_sparse.h; with a matrix unknown csrc/fh_spmulti.h) -----------------------------------------
+// One side of the operator on the device: the arrays, the lanes per row G, the long rows (a workgroup each) and the contiguous row ranges of
+// the other workgroups.  THE RULE, stated once: C lanes cover one gathered row of the operand (C = 1 for a vector unknown, LB / 2 column lanes
+// for a matrix unknown), so a group of G lanes works on E = G / C entries per trip;
+//   G       the smallest of max(4, C) .. 64 with 2 * E >= the mean row length;
+//   long    a row of more than max(SP_LONG_FACTOR * E, SP_LONG_MEANS mean rows) entries;
+//   ranges  balanced by the trips a group spends on a row, ceil(len / E) + 2, for at most 8 workgroups per CU.
+// Computed here, once (which is why the column count of a sparse operator is fixed when it is set); a launch only reads it.
+static int sp_upload_side(fh_ctx* c, int side, uint64_t rows, uint64_t nnz, const int64_t* ptr, const int32_t* idx, const double* val, int C) {
   const double mean = rows ? (double)nnz / (double)rows : 0.0;
-  int G = 4;
-  while (G < 64 && (double)G * 2.0 < mean) G *= 2;
+  int G = std::max(4, C);
+  while (G < 64 && (double)(G / C) * 2.0 < mean) G *= 2;
+  const uint64_t E = (uint64_t)(G / C);
   const uint64_t groups = FH_WG / (uint64_t)G;
-  const uint64_t longer = std::max<uint64_t>((uint64_t)SP_LONG_FACTOR * (uint64_t)G, (uint64_t)((double)SP_LONG_MEANS * mean));
+  const uint64_t longer = std::max<uint64_t>((uint64_t)SP_LONG_FACTOR * E, (uint64_t)((double)SP_LONG_MEANS * mean));
   std::vector<uint32_t> longrows;
   uint64_t total = 0;
   auto cost = [&](uint64_t r) -> uint64_t {
     const uint64_t len = (uint64_t)(ptr[r + 1] - ptr[r]);
-    return len > longer ? 1u : (len + G - 1) / G + 2u;
+    return len > longer ? 1u : (len + E - 1) / E + 2u;
   };
   for (uint64_t r = 0; r < rows; ++r) {
     if ((uint64_t)(ptr[r + 1] - ptr[r]) > longer) longrows.push_back((uint32_t)r);
@@ -543,32 +555,44 @@ static int sp_upload_side(fh_ctx* c, int side, uint64_t rows, uint64_t nnz, cons
   return 0;
 }
 
-extern "C" int fh_set_matrix_csr(fh_ctx* c, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* indptr, const int32_t* indices, const double* values) {
-  if (!c || !indptr || (nnz && (!indices || !values))) return fail(FH_E_ARG, "fh_set_matrix_csr: null argument");
-  if (!c->shards.empty() || c->owner) return fail(FH_E_STATE, "fh_set_matrix_csr: a multi-device context has no sparse operator (row sharding is implemented for the dense operator only)");
-  if (c->comm) return fail(FH_E_STATE, "fh_set_matrix_csr: a context with a communicator (row-sharded run) has no sparse operator");
-  if (c->f32) return fail(FH_E_STATE, "fh_set_matrix_csr: float32 storage is not implemented for the sparse operator");
-  if (c->pending_step) return fail(FH_E_STATE, "a step issued by fh_step_begin is still in flight on this context: call fh_step_end first");
+// canonical CSR, or the first offending row by name (fh_set_matrix_csr and fh_set_matrix_csr_rhs: one checker)
+static int csr_check(const char* who, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* indptr, const int32_t* indices) {
   if (m == 0 || n == 0) return fail(FH_E_ARG, "matrix must be non-empty (got %llu x %llu)", (unsigned long long)m, (unsigned long long)n);
   if (m >= (1ull << 31) || n >= (1ull << 31)) return fail(FH_E_ARG, "matrix dimension exceeds 2^31-1");
-  if (nnz >= (1ull << 62)) return fail(FH_E_ARG, "fh_set_matrix_csr: nnz out of range");
+  if (nnz >= (1ull << 62)) return fail(FH_E_ARG, "%s: nnz out of range", who);
   // canonical CSR, or the first offending row by name
-  if (indptr[0] != 0) return fail(FH_E_ARG, "fh_set_matrix_csr: indptr[0] is %lld, not 0 (row 0)", (long long)indptr[0]);
+  if (indptr[0] != 0) return fail(FH_E_ARG, "%s: indptr[0] is %lld, not 0 (row 0)", who, (long long)indptr[0]);
   for (uint64_t r = 0; r < m; ++r) {
     if (indptr[r + 1] < indptr[r] || (uint64_t)indptr[r + 1] > nnz)
-      return fail(FH_E_ARG, "fh_set_matrix_csr: indptr is decreasing or runs past nnz at row %llu", (unsigned long long)r);
+      return fail(FH_E_ARG, "%s: indptr is decreasing or runs past nnz at row %llu", who, (unsigned long long)r);
     for (int64_t k = indptr[r]; k < indptr[r + 1]; ++k) {
       if (indices[k] < 0 || (uint64_t)indices[k] >= n)
-        return fail(FH_E_ARG, "fh_set_matrix_csr: column index %d out of range in row %llu (n = %llu)", indices[k], (unsigned long long)r, (unsigned long long)n);
+        return fail(FH_E_ARG, "%s: column index %d out of range in row %llu (n = %llu)", who, indices[k], (unsigned long long)r, (unsigned long long)n);
       if (k > indptr[r] && indices[k] <= indices[k - 1])
-        return fail(FH_E_ARG, "fh_set_matrix_csr: column indices of row %llu are not strictly increasing (sort them and sum duplicates)", (unsigned long long)r);
+        return fail(FH_E_ARG, "%s: column indices of row %llu are not strictly increasing (sort them and sum duplicates)", who, (unsigned long long)r);
     }
   }
-  if ((uint64_t)indptr[m] != nnz) return fail(FH_E_ARG, "fh_set_matrix_csr: indptr ends at %lld, nnz is %llu (row %llu)", (long long)indptr[m], (unsigned long long)nnz, (unsigned long long)(m - 1));
+  if ((uint64_t)indptr[m] != nnz) return fail(FH_E_ARG, "%s: indptr ends at %lld, nnz is %llu (row %llu)", who, (long long)indptr[m], (unsigned long long)nnz, (unsigned long long)(m - 1));
+  return 0;
+}
+
+// L = 0: the vector form; L in 1..16: the multi-column form of csrc/fh_spmulti.h, set together with the operator
+static int set_matrix_csr(fh_ctx* c, const char* who, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* indptr, const int32_t* indices, const double* values, uint32_t L) {
+  if (!c || !indptr || (nnz && (!indices || !values))) return fail(FH_E_ARG, "%s: null argument", who);
+  if (L > 16) return fail(FH_E_ARG, "%s: at most 16 columns (got %u)", who, L);
+  if (!c->shards.empty() || c->owner) return fail(FH_E_STATE, "%s: a multi-device context has no sparse operator (row sharding is implemented for the dense operator only)", who);
+  if (c->comm) return fail(FH_E_STATE, "%s: a context with a communicator (row-sharded run) has no sparse operator", who);
+  if (c->f32) return fail(FH_E_STATE, "%s: float32 storage is not implemented for the sparse operator", who);
+  if (c->pending_step) return fail(FH_E_STATE, "a step issued by fh_step_begin is still in flight on this context: call fh_step_end first");
+  FH_TRY(csr_check(who, m, n, nnz, indptr, indices));
+  const uint32_t LB = L == 0 ? 0u : (L <= 2 ? 2u : (L <= 4 ? 4u : (L <= 8 ? 8u : 16u)));
+  const int C = LB ? (int)(LB / 2) : 1;                  // lanes per gathered row of the operand
   FH_TRY(use_device(c));
   HIP_TRY(hipStreamSynchronize(c->stream));
-  free_operator(c);
-  if (!sp_prox_ok(c->prox_kind)) { c->prox_kind = FH_PROX_IDENTITY; c->mu = 0.0; }
+  free_operator(c);                                      // (back to the vector form: L = LB = 0)
+  if (L ? !mc_prox_ok(c->prox_kind) : !sp_prox_ok(c->prox_kind)) { c->prox_kind = FH_PROX_IDENTITY; c->mu = 0.0; }
+  if (L) { c->loss_kind = LOSS_LSQ; c->lazy = false; c->last_accel = false; c->commits = 0; }
+  c->L = L; c->LB = LB;
   c->m = m; c->n = n;
   c->mp = round_up(m, 16); c->ld = round_up(n, 16);      // vectors keep the vector form's padded layout
   c->nv = c->ld; c->mv = c->mp;
@@ -587,13 +611,20 @@ extern "C" int fh_set_matrix_csr(fh_ctx* c, uint64_t m, uint64_t n, uint64_t nnz
         tidx[(size_t)q] = (int32_t)r; tval[(size_t)q] = values[k];
       }
   }
-  int rc = sp_upload_side(c, 0, m, nnz, indptr, indices, values);
-  if (rc == 0) rc = sp_upload_side(c, 1, n, nnz, tptr.data(), tidx.data(), tval.data());
+  int rc = sp_upload_side(c, 0, m, nnz, indptr, indices, values, C);
+  if (rc == 0) rc = sp_upload_side(c, 1, n, nnz, tptr.data(), tidx.data(), tval.data(), C);
   if (rc == 0) rc = alloc_vectors(c);
-  if (rc == 0) rc = alloc_zero(c, &c->sp_r, c->mv + 16);
+  if (rc == 0) rc = alloc_zero(c, &c->sp_r, c->mv * lb_of(c) + 16);
   if (rc != 0) { free_operator(c); return rc; }
   c->op = OP_SPARSE;
   return finish(c);
+}
+extern "C" int fh_set_matrix_csr(fh_ctx* c, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* indptr, const int32_t* indices, const double* values) {
+  return set_matrix_csr(c, "fh_set_matrix_csr", m, n, nnz, indptr, indices, values, 0);
+}
+// the sparse operator and the multi-column form in one call (G, the long-row threshold and the row ranges depend on LB: csrc/fh_spmulti.h); L = 0 is fh_set_matrix_csr
+extern "C" int fh_set_matrix_csr_rhs(fh_ctx* c, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* indptr, const int32_t* indices, const double* values, uint32_t L) {
+  return set_matrix_csr(c, L ? "fh_set_matrix_csr_rhs" : "fh_set_matrix_csr", m, n, nnz, indptr, indices, values, L);
 }
 extern "C" int fh_nnz(fh_ctx* c, uint64_t* nnz) {
   if (!c || !nnz) return fail(FH_E_ARG, "null argument");
@@ -669,7 +700,7 @@ extern "C" int fh_set_rhs(fh_ctx* c, uint32_t L) {
   if (c->comm) return fail(FH_E_STATE, "fh_set_rhs: a context with a communicator (row-sharded run) has no multi-column form");
   if (c->pending_step) return fail(FH_E_STATE, "a step issued by fh_step_begin is still in flight on this context: call fh_step_end first");
   if (c->op == OP_NONE) return fail(FH_E_STATE, "fh_set_rhs: set the dense operator first (fh_set_matrix / fh_generate_matrix)");
-  if (c->op == OP_SPARSE) return fail(FH_E_STATE, "fh_set_rhs: the sparse operator has no multi-column form");
+  if (c->op == OP_SPARSE) return fail(FH_E_STATE, "fh_set_rhs: the sparse operator has no multi-column form through fh_set_rhs: its column count is fixed when it is set (fh_set_matrix_csr_rhs)");
   if (c->op != OP_DENSE) return fail(FH_E_STATE, "fh_set_rhs: the stencil operator has no multi-column form");
   if (c->f32) return fail(FH_E_STATE, "fh_set_rhs: float32 storage of A has no multi-column form");
   if (L && c->has_b && c->loss_kind != LOSS_LSQ) return fail(FH_E_STATE, "fh_set_rhs: the logistic loss has no multi-column form");
@@ -696,7 +727,7 @@ static int set_loss(fh_ctx* c, int kind, const double* b, uint64_t len) {
   if (!c || !b) return fail(FH_E_ARG, "null argument");
   if (c->op == OP_NONE) return fail(FH_E_STATE, "set the operator before the loss");
   if (len != c->m * l_of(c)) return fail(FH_E_ARG, "b has %llu entries, operator has %llu rows (x %llu columns)", (unsigned long long)len, (unsigned long long)c->m, (unsigned long long)l_of(c));
-  if (kind != LOSS_LSQ && c->LB) return fail(FH_E_STATE, "the logistic loss has no multi-column form (fh_set_rhs)");
+  if (kind != LOSS_LSQ && c->LB) return fail(FH_E_STATE, "the logistic loss has no multi-column form (fh_set_rhs / fh_set_matrix_csr_rhs)");
   if (kind != LOSS_LSQ && c->op != OP_DENSE && c->op != OP_SPARSE) return fail(FH_E_STATE, "the logistic loss is implemented for the dense operator");
   if (!c->shards.empty()) {          // shell: b is sharded like the rows
     for (int k = 0; k < nshards(c); ++k) FH_TRY(set_loss(c->shards[k], kind, b + c->shard_row0[k], shard_rows(c, k)));
@@ -721,9 +752,9 @@ extern "C" int fh_set_loss_logistic(fh_ctx* c, const double* labels, uint64_t le
 extern "C" int fh_set_prox(fh_ctx* c, int kind, double mu, double lo, double hi) {
   if (!c) return fail(FH_E_ARG, "null context");
   if (kind < FH_PROX_IDENTITY || kind > FH_PROX_GROUP) return fail(FH_E_ARG, "unknown prox kind %d", kind);
-  if (kind == FH_PROX_GROUP && !c->LB) return fail(FH_E_ARG, "FH_PROX_GROUP (row-wise l2 shrink) needs the multi-column form: call fh_set_rhs first");
+  if (kind == FH_PROX_GROUP && !c->LB) return fail(FH_E_ARG, "FH_PROX_GROUP (row-wise l2 shrink) needs the multi-column form: call fh_set_rhs (dense operator) or fh_set_matrix_csr_rhs (sparse operator) first");
   if (c->LB && !mc_prox_ok(kind)) return fail(FH_E_ARG, "prox kind %d (LINF / L1BALL / TVBALL) has no multi-column form", kind);
-  if (c->op == OP_SPARSE && !sp_prox_ok(kind)) return fail(FH_E_ARG, "prox kind %d (LINF / L1BALL / TVBALL / GROUP) is not implemented for the sparse operator", kind);
+  if (c->op == OP_SPARSE && !c->LB && !sp_prox_ok(kind)) return fail(FH_E_ARG, "prox kind %d (LINF / L1BALL / TVBALL / GROUP) is not implemented for the sparse operator", kind);
   if (kind == FH_PROX_BOX && !(lo <= hi)) return fail(FH_E_ARG, "box prox needs lo <= hi");
   for (fh_ctx* s : c->shards) { s->prox_kind = kind; s->mu = mu; s->lo = lo; s->hi = hi; }      // the prox is replicated work
   c->prox_kind = kind; c->mu = mu; c->lo = lo; c->hi = hi;

@@ -108,10 +108,11 @@ struct fh_ctx {
   uint64_t mp = 0, ld = 0;   // padded rows, device leading dimension in elements (dense)
   int f32 = 0;               // storage of A: 0 = float64, 1 = float32 (opt-in, fh_create_ex; vectors and arithmetic stay float64)
   uint64_t nv = 0, mv = 0;   // allocated n-side / m-side vector lengths (doubles; rows of LB doubles in multi-column form)
-  uint32_t L = 0, LB = 0;    // multi-column form (fh_set_rhs, csrc/fh_multi.h): L columns per unknown, kept as LB in {2, 4, 8, 16} doubles per row; 0 = the vector form
+  uint32_t L = 0, LB = 0;    // multi-column form (fh_set_rhs, csrc/fh_multi.h; fh_set_matrix_csr_rhs, csrc/fh_spmulti.h): L columns per unknown, kept as LB in {2, 4, 8, 16} doubles per row; 0 = the vector form
   uint64_t H = 0, W = 0;
   // sparse operator (fh_set_matrix_csr, csrc/fh_sparse.h): sp[0] = A by rows, sp[1] = A^T by rows, each with its non-zero-balanced row ranges,
-  // its list of long rows and the lanes-per-row G chosen from its mean row length; sp_r = the adjoint's residual (m-side)
+  // its list of long rows and the lanes-per-row G chosen from its mean row length; sp_r = the adjoint's residual (m-side).  In multi-column form
+  // (fh_set_matrix_csr_rhs, csrc/fh_spmulti.h) G, the long-row threshold and the row ranges are those of LB / 2 column lanes per entry: fixed when the operator is set
   SpMatP sp[2] = {};
   int sp_G[2] = {0, 0};
   uint64_t nnz = 0;
@@ -399,7 +400,7 @@ static int alloc_vectors(fh_ctx* c) {
     FH_TRY(alloc_zero(c, &c->Z[i], mvl + 16));
   }
   FH_TRY(alloc_zero(c, &c->xhat, nvl + 16));
-  if (c->LB) FH_TRY(alloc_zero(c, &c->xs, nvl + 16));
+  if (c->LB && !c->sp[0].ptr) FH_TRY(alloc_zero(c, &c->xs, nvl + 16));      // (the sparse gather reads the row-major xprox itself)
   for (int i = 0; i < 3; ++i) FH_TRY(alloc_zero(c, &c->X[i], nvl + 16));
   for (int i = 0; i < 4; ++i) FH_TRY(alloc_zero(c, &c->T[i], nvl + 16));
   FH_TRY(alloc_zero(c, &c->b, mvl + 16));

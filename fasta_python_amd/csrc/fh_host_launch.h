@@ -343,6 +343,100 @@ static int launch_adj_sparse(fh_ctx* c, const AdjIO& io) {
   return 0;
 }
 
+// ---- matrix unknown over the sparse operator (fh_set_matrix_csr_rhs; kernels in csrc/fh_spmulti.h, instantiated by fh_spmulti_part.hip) ------
+#ifndef FH_SINGLE_TU
+#define SPMC_DECLARE_LB(LB) SPMC_LB_KERNELS(extern template, LB)
+SPMC_FOR_EACH_LB(SPMC_DECLARE_LB)
+#undef SPMC_DECLARE_LB
+#define SPMC_DECLARE(G, LB) SPMC_KERNELS(extern template, G, LB)
+SPMC_FOR_EACH(SPMC_DECLARE)
+#undef SPMC_DECLARE
+#endif
+struct SpmcLbEntry { int lb; void (*pro)(const SpmcProP); void (*resid)(const SpmcResP); };
+#define SPMC_LB_ROW(LB) {LB, k_spmc_prologue<LB>, k_spmc_resid<LB>},
+static const SpmcLbEntry kSpmcLbTable[] = { SPMC_FOR_EACH_LB(SPMC_LB_ROW) };
+#undef SPMC_LB_ROW
+struct SpmcEntry { int g, lb; void (*fwd[2])(const SpmcFwdP); void (*adj[2])(const SpmcAdjP); };
+#define SPMC_ROW(G, LB) {G, LB, {k_spmc_fwd<G, LB, 0>, k_spmc_fwd<G, LB, 1>}, {k_spmc_adj<G, LB, 0>, k_spmc_adj<G, LB, 1>}},
+static const SpmcEntry kSpmcTable[] = { SPMC_FOR_EACH(SPMC_ROW) };
+#undef SPMC_ROW
+static const SpmcLbEntry* spmc_lb_entry(const fh_ctx* c) {
+  for (const SpmcLbEntry& e : kSpmcLbTable) if ((uint32_t)e.lb == c->LB) return &e;
+  return nullptr;
+}
+static const SpmcEntry* spmc_entry(const fh_ctx* c, int side) {
+  for (const SpmcEntry& e : kSpmcTable) if (e.g == c->sp_G[side] && (uint32_t)e.lb == c->LB) return &e;
+  return nullptr;
+}
+
+// Z := A * (mode 0: prox(X0 - tau G0), by the prologue launch ; mode 1: X0), LB columns per gathered row
+static int launch_fwd_spmulti(fh_ctx* c, int mode, double tau, const double* x0, const double* g0, const double* xacc0,
+                              double* xhat, double* xp, double* z, int sub_b) {
+  const SpmcEntry* e = spmc_entry(c, 0);
+  const SpmcLbEntry* lbe = spmc_lb_entry(c);
+  if (!e || !lbe) return fail(FH_E_STATE, "sparse multi-column form: no kernel for %d lanes per row at %u columns per row", c->sp_G[0], c->LB);
+  if (c->loss_kind != LOSS_LSQ) return fail(FH_E_STATE, "the multi-column form serves the least-squares loss only");
+  if (mode == 0 && !mc_prox_ok(c->prox_kind)) return fail(FH_E_STATE, "prox kind %d has no multi-column form", c->prox_kind);
+  SpmcFwdP p;
+  p.a = c->sp[0]; p.m = (uint32_t)c->m; p.L = c->L;
+  const uint32_t npro = mode == 0 ? (uint32_t)((c->nv + FH_WG - 1) / FH_WG) : 0u;
+  p.nred_n = npro;
+  const unsigned grid = p.a.nwg + p.a.nlong;
+  FH_TRY(ensure_ws(c, ((size_t)npro * 8 + grid) * sizeof(double)));
+  p.red_n = c->ws; p.red_m = c->ws + (size_t)npro * 8;
+  p.x = mode == 0 ? xp : x0;
+  p.b = c->b; p.z = z; p.sub_b = sub_b;
+  p.counter = c->counters + CNT_FWD;
+  p.out = scalar_out(c);
+  t_begin(c, FH_K_FWD);
+  if (mode == 0) {
+    SpmcProP q;
+    q.n = (uint32_t)c->n; q.L = c->L; q.nv = (uint32_t)c->nv;
+    q.x0 = x0; q.g0 = g0; q.xacc0 = xacc0; q.xhat = xhat; q.xp = xp; q.tau = tau;
+    q.px = make_prox(c, tau);
+    q.red_n = c->ws;
+    lbe->pro<<<dim3(npro), dim3(FH_WG), 0, c->stream>>>(q);
+  }
+  p.seq = seq_offer(c);
+  e->fwd[sp_nt_for(c) ? 1 : 0]<<<dim3(grid), dim3(FH_WG), 0, c->stream>>>(p);
+  t_end(c, FH_K_FWD);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// G1 := A^T (Z' - B) by the gather over the A^T copy; the residual and the loss sum at Z' come from the m-side prologue launch
+static int launch_adj_spmulti(fh_ctx* c, const AdjIO& io) {
+  const SpmcEntry* e = spmc_entry(c, 1);
+  const SpmcLbEntry* lbe = spmc_lb_entry(c);
+  if (!e || !lbe) return fail(FH_E_STATE, "sparse multi-column form: no kernel for %d lanes per row at %u columns per row", c->sp_G[1], c->LB);
+  if (io.sub_b && c->loss_kind != LOSS_LSQ) return fail(FH_E_STATE, "the multi-column form serves the least-squares loss only");
+  if (io.mode != 0 && io.mode != 1) return fail(FH_E_STATE, "the sparse operator has no row-sharded adjoint");
+  SpmcAdjP p;
+  p.a = c->sp[1]; p.n = (uint32_t)c->n; p.L = c->L;
+  const uint64_t pairs = c->m * (uint64_t)(c->LB / 2);
+  const uint32_t nres = (uint32_t)((pairs + FH_WG - 1) / FH_WG);
+  p.nred_f = nres;
+  const unsigned grid = p.a.nwg + p.a.nlong;
+  FH_TRY(ensure_ws(c, ((size_t)nres + (size_t)grid * 8) * sizeof(double)));
+  p.red_f = c->ws; p.red_bb = c->ws + nres;
+  p.r = c->sp_r;
+  p.accel = io.accel; p.mode = io.mode; p.coef = io.coef; p.tau = io.tau; p.group = c->prox_kind == FH_PROX_GROUP ? 1 : 0;
+  p.x0 = io.x0; p.xp = io.xp; p.xacc0 = io.xacc0; p.xhat = io.xhat; p.x1 = io.x1; p.g1 = io.g1;
+  p.counter = c->counters + CNT_ADJ_FIN;
+  p.out = scalar_out(c);
+  SpmcResP q;
+  q.m = (uint32_t)c->m; q.L = c->L; q.z = io.z; q.zacc0 = io.zacc0; q.b = c->b; q.r = c->sp_r;
+  q.sub_b = io.sub_b; q.accel = io.accel; q.coef = io.coef;
+  q.red_f = c->ws;
+  t_begin(c, FH_K_ADJ);
+  lbe->resid<<<dim3(nres), dim3(FH_WG), 0, c->stream>>>(q);
+  p.seq = io.mode == 0 ? seq_offer(c) : 0u;
+  e->adj[sp_nt_for(c) ? 1 : 0]<<<dim3(grid), dim3(FH_WG), 0, c->stream>>>(p);
+  t_end(c, FH_K_ADJ);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
 // sum|x_i| and max|x_i| of an n-length device vector -> dscal[GSUM], dscal[GMAX]  (g(x0) for objective_hist[0], :143)
 static int launch_gterms(fh_ctx* c, const double* x) {
   if (c->LB) {              // (n, L) matrix: the same two terms, or the sum of row norms for FH_PROX_GROUP
@@ -770,7 +864,7 @@ static int op_fwd(fh_ctx* c, int mode, double tau, const double* x0, const doubl
   if (c->op == OP_DENSE && c->LB) return launch_fwd_multi(c, mode, tau, x0, g0, xacc0, xhat, xp, z, sub_b);
   if (c->op == OP_DENSE) return launch_fwd_dense(c, mode, tau, x0, g0, xacc0, xhat, xp, z, sub_b);
   if (c->op == OP_STENCIL) return launch_fwd_tv(c, mode, tau, x0, g0, xacc0, xhat, xp, z, sub_b);
-  if (c->op == OP_SPARSE) return launch_fwd_sparse(c, mode, tau, x0, g0, xacc0, xhat, xp, z, sub_b);
+  if (c->op == OP_SPARSE) return c->LB ? launch_fwd_spmulti(c, mode, tau, x0, g0, xacc0, xhat, xp, z, sub_b) : launch_fwd_sparse(c, mode, tau, x0, g0, xacc0, xhat, xp, z, sub_b);
   return fail(FH_E_STATE, "no operator set");
 }
 
@@ -783,7 +877,7 @@ static int adj_local(fh_ctx* c, const AdjIO& io_in) {
   if (c->op == OP_DENSE && c->LB) return launch_adj_multi(c, io);
   if (c->op == OP_DENSE) return launch_adj_dense(c, io);
   if (c->op == OP_STENCIL) return launch_adj_tv(c, io);
-  if (c->op == OP_SPARSE) return launch_adj_sparse(c, io);
+  if (c->op == OP_SPARSE) return c->LB ? launch_adj_spmulti(c, io) : launch_adj_sparse(c, io);
   return fail(FH_E_STATE, "no operator set");
 }
 // stage 2, exchange: A_k^T r_k partials (nv doubles at g1(shard)) and the local loss sums (FH_S_FSQ_ADJ) summed over the row blocks

@@ -1,4 +1,4 @@
-// fh_multi.h -- dense kernels for a MATRIX unknown: X is (n, L), B and Z are (m, L), one A for all L columns (fh_set_rhs).
+// fh_multi.h -- dense kernels for a MATRIX unknown: X is (n, L), B and Z are (m, L), one A for all L columns (fh_set_rhs; over a sparse A: fh_spmulti.h).
 //
 // The vector kernels of fh_dense.h are bound by the read of A: m*n*8 bytes per direction whatever the unknown.  Here every 16-byte piece
 // of A that a lane loads is used for LB columns, so L right-hand sides cost one read of A -- and the prox may couple the columns of a row

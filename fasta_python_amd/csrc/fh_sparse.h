@@ -1,4 +1,4 @@
-// fh_sparse.h -- kernels for a SPARSE operator (fh_set_matrix_csr): the library keeps A by rows (CSR) and A^T by rows (the CSC of A, built by
+// fh_sparse.h -- kernels for a SPARSE operator and a VECTOR unknown (fh_set_matrix_csr; a matrix unknown over the same two copies: fh_spmulti.h): the library keeps A by rows (CSR) and A^T by rows (the CSC of A, built by
 // a stable counting sort, so every column lists its entries in ascending row order), and BOTH directions are gathers over "rows" of one of the
 // two copies.  No atomics, every sum has a fixed order: bitwise repeatable, like every other kernel of the library.
 //

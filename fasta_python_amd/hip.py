@@ -16,7 +16,7 @@ LIB_PATH = os.environ.get("FASTA_HIP_LIB") or os.path.join(_HERE, "libfasta_hip.
 
 # enums mirrored from include/fasta_hip.h ---------------------------------------------------------
 PROX_IDENTITY, PROX_SHRINK, PROX_NONNEG, PROX_LINF, PROX_L1BALL, PROX_TVBALL, PROX_BOX, PROX_GROUP = range(8)
-MAX_RHS = 16                       # columns of a matrix unknown (fh_set_rhs)
+MAX_RHS = 16                       # columns of a matrix unknown (fh_set_rhs, fh_set_matrix_csr_rhs)
 (VEC_X0, VEC_G0, VEC_XHAT, VEC_XPROX, VEC_X1, VEC_G1, VEC_BEST, VEC_B, VEC_Z,
  VEC_T0, VEC_T1, VEC_T2, VEC_T3) = range(13)
 (S_FSQ, S_DXG0, S_DX2, S_XH2, S_G02, S_GSUM, S_GMAX, S_RDOT, S_DXDG, S_DG2, S_FSQ_ADJ, S_XH2_ADJ,
@@ -80,6 +80,7 @@ SIGNATURES = {
     "fh_generate_matrix": (_i32, [_ctx, _u64, _u64, _u64, _u64, _dbl]),
     "fh_get_matrix_rows": (_i32, [_ctx, _u64, _u64, _pd]),
     "fh_set_matrix_csr": (_i32, [_ctx, _u64, _u64, _u64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _pd]),
+    "fh_set_matrix_csr_rhs": (_i32, [_ctx, _u64, _u64, _u64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _pd, C.c_uint32]),
     "fh_nnz": (_i32, [_ctx, C.POINTER(_u64)]),
     "fh_set_stencil": (_i32, [_ctx, _u64, _u64]),
     "fh_shape": (_i32, [_ctx, C.POINTER(_u64), C.POINTER(_u64)]),
@@ -357,8 +358,9 @@ class HipContext:
         m, n = A.shape
         self._call("fh_set_matrix", A.ctypes.data_as(_pd), m, n, n)
 
-    def set_matrix_csr(self, indptr, indices, data, shape):
-        """Sparse operator from canonical CSR arrays (sorted, duplicates summed; fh_set_matrix_csr checks and names the first bad row)."""
+    def set_matrix_csr(self, indptr, indices, data, shape, rhs=None):
+        """Sparse operator from canonical CSR arrays (sorted, duplicates summed; fh_set_matrix_csr checks and names the first bad row).
+        rhs=L: fh_set_matrix_csr_rhs, the operator and the multi-column form in one call (see set_matrix_csr_rhs)."""
         m, n = (int(k) for k in shape)
         indptr = np.ascontiguousarray(indptr, dtype=np.int64)
         indices = np.asarray(indices)
@@ -371,8 +373,16 @@ class HipContext:
         data = np.ascontiguousarray(data, dtype=np.float64)
         if indptr.size != m + 1 or indices.size != data.size:
             raise ValueError(f"CSR arrays do not fit shape {(m, n)}: indptr {indptr.size}, indices {indices.size}, data {data.size}")
-        self._call("fh_set_matrix_csr", m, n, int(data.size), indptr.ctypes.data_as(C.POINTER(C.c_int64)),
-                   indices.ctypes.data_as(C.POINTER(C.c_int32)), data.ctypes.data_as(_pd))
+        args = (m, n, int(data.size), indptr.ctypes.data_as(C.POINTER(C.c_int64)), indices.ctypes.data_as(C.POINTER(C.c_int32)), data.ctypes.data_as(_pd))
+        if rhs is None:
+            self._call("fh_set_matrix_csr", *args)
+        else:
+            self._call("fh_set_matrix_csr_rhs", *args, int(rhs))
+
+    def set_matrix_csr_rhs(self, indptr, indices, data, shape, L):
+        """Sparse operator for a matrix unknown (csrc/fh_spmulti.h): the unknown is (n, L), b and z are (m, L), L in 1..16; L = 0 is
+        set_matrix_csr.  The lanes per row and the row ranges depend on L, so the column count is fixed here (set_rhs refuses a sparse context)."""
+        self.set_matrix_csr(indptr, indices, data, shape, rhs=int(L))
 
     def nnz(self):
         """Stored entries of the sparse operator (0 for a dense matrix or the stencil)."""

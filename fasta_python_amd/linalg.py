@@ -12,7 +12,8 @@ subclasses are *recognised* by `fasta()` and run on the device:
                      of THIS process (single call): `fasta(ShardedDenseMatrixMap(A,
                      devices=[0, 1, ...]), ls.f, ls.gradf, reg.g, reg.prox, x0)`;
   SparseMatrixMap -- a sparse design matrix (any scipy.sparse matrix / array, or CSR arrays), kept on the
-                     device by rows and by columns; both directions are gathers (csrc/fh_sparse.h);
+                     device by rows and by columns; both directions are gathers (csrc/fh_sparse.h; with `rhs=L`
+                     the unknown is an (n, L) matrix and every entry gathers a whole row of it, csrc/fh_spmulti.h);
   GradDivMap      -- the periodic div/grad stencil pair of examples/tv_denoising.py:26-63.
 
 A DenseMatrixMap built from a host ndarray uploads LAZILY: it keeps a reference to the array (as the
@@ -390,18 +391,25 @@ class SparseMatrixMap(_DeviceMap):
 
     Lazy like a DenseMatrixMap built from a host matrix: the upload happens when the device loop first asks for the context, and on
     host arrays the map is `S @ v` / `S.T @ w`, the closures the reference is given for such a matrix -- so `backend="numpy"` and the
-    generic host loop are the reference bit for bit.  One device, float64; prox kinds Shrink / NonNeg / Box / none; both losses."""
+    generic host loop are the reference bit for bit.  One device, float64; prox kinds Shrink / NonNeg / Box / none; both losses.
 
-    def __init__(self, A, device=0, tuning=None):
+    rhs=L (1..16): the unknown is an (n, L) matrix and the data an (m, L) matrix (`Vshape = (n, L)`, `Wshape = (m, L)`; on host arrays
+    `S @ X` / `S.T @ Y`).  On the device every stored entry then gathers a whole row of X and is paid once for all L columns
+    (csrc/fh_spmulti.h); least squares only, prox kinds Shrink / NonNeg / Box / GroupShrink / none."""
+
+    def __init__(self, A, device=0, tuning=None, rhs=None):
+        self.rhs = None if rhs is None else int(rhs)
+        if self.rhs is not None and not 1 <= self.rhs <= hip.MAX_RHS:
+            raise ValueError(f"rhs must be in 1..{hip.MAX_RHS} columns (got {rhs})")
         data, indices, indptr, shape = canonical_csr(A)
         self.csr = (data, indices, indptr)
         self.shape = shape
         self.storage = "f64"
-        self.rhs = None
         self._tuning = dict(tuning or {})
         from scipy.sparse import csr_matrix            # (SciPy is needed from here on, not at module import)
         self._host = csr_matrix((data, indices, indptr), shape=shape)
-        _DeviceMap.__init__(self, (shape[1],), (shape[0],), device, lazy=True)
+        cols = () if self.rhs is None else (self.rhs,)
+        _DeviceMap.__init__(self, (shape[1],) + cols, (shape[0],) + cols, device, lazy=True)
 
     @property
     def nnz(self):
@@ -416,7 +424,10 @@ class SparseMatrixMap(_DeviceMap):
         for key, value in self._tuning.items():
             ctx.set_tuning(key, value)
         data, indices, indptr = self.csr
-        ctx.set_matrix_csr(indptr, indices, data, self.shape)
+        if self.rhs is None:
+            ctx.set_matrix_csr(indptr, indices, data, self.shape)
+        else:
+            ctx.set_matrix_csr_rhs(indptr, indices, data, self.shape, self.rhs)
 
     def _apply_fwd(self, v):
         return self._host @ v

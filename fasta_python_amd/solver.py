@@ -76,6 +76,8 @@ def _matrix_form_refusal(A, loss, prox, x0):
     no level-search prox kinds, no logistic loss, no float32 storage and no row sharding, and at most 16 columns.  None, or the reason."""
     from .linalg import ShardedDenseMatrixMap
     from .proximal import GroupShrink, L1Ball, LinfProx, TVDualBall
+    if isinstance(A, SparseMatrixMap) or is_sparse_matrix(A):
+        return None                                    # (_sparse_form_refusal has the say)
     dense = isinstance(A, np.ndarray) or isinstance(A, DenseMatrixMap)
     matrix_form = dense and x0 is not None and np.ndim(x0) == 2
     if isinstance(prox, GroupShrink) and not matrix_form:
@@ -95,16 +97,27 @@ def _matrix_form_refusal(A, loss, prox, x0):
     return None
 
 
-def _sparse_form_refusal(A, prox, x0):
-    """A sparse operator (csrc/fh_sparse.h) serves vector unknowns and the elementwise prox kinds (float32 storage is refused where it
-    could be asked for: LinearMap.from_matrix).  None, or the reason."""
+def _sparse_form_refusal(A, loss, prox, x0):
+    """A sparse operator serves vector unknowns with the elementwise prox kinds and both losses (csrc/fh_sparse.h) and, as an explicit
+    SparseMatrixMap(S, rhs=L), matrix unknowns (n, L) with least squares and the elementwise kinds or GroupShrink (csrc/fh_spmulti.h).
+    (Float32 storage is refused where it could be asked for: LinearMap.from_matrix.)  None, or the reason."""
     from .proximal import GroupShrink, L1Ball, LinfProx, TVDualBall
     if not (isinstance(A, SparseMatrixMap) or is_sparse_matrix(A)):
         return None
-    if isinstance(prox, (LinfProx, L1Ball, TVDualBall, GroupShrink)):
-        return f"proximal.{type(prox).__name__} is not implemented for a sparse operator on the device (Shrink, NonNeg, Box or no prox are)"
+    matrix_form = isinstance(A, SparseMatrixMap) and A.rhs is not None
+    if isinstance(prox, (LinfProx, L1Ball, TVDualBall)):
+        return (f"proximal.{type(prox).__name__} is not implemented for a sparse operator on the device "
+                f"(Shrink, NonNeg, Box or no prox are{'; GroupShrink too over a matrix unknown' if matrix_form else ''})")
+    if matrix_form:
+        if isinstance(loss, LogisticLoss):
+            return "losses.LogisticLoss has no matrix (multi-column) form over a sparse operator on the device: least squares only"
+        return None                                    # (a shape that does not fit is _recognise's `x0 has shape` AssertionError)
+    if isinstance(prox, GroupShrink):
+        return ("proximal.GroupShrink is not implemented for a sparse operator with a vector unknown on the device: it couples the columns "
+                "of a row of a matrix unknown -- pass linalg.SparseMatrixMap(S, rhs=L) and a 2-D x0 of shape (n, L)")
     if x0 is not None and np.ndim(x0) == 2:
-        return "a sparse operator has no matrix (multi-column) form on the device: x0 must be a vector"
+        return ("a sparse operator takes a matrix (multi-column) unknown on the device only when it is told the column count: "
+                "pass linalg.SparseMatrixMap(S, rhs=L) in place of the raw matrix; otherwise x0 must be a vector")
     return None
 
 
@@ -117,12 +130,12 @@ def _unrecognised(A, At, f, gradf, g, proxg, x0=None):
     if loss_f is None or loss_f is not loss_g:
         return "f and gradf must be the `.f` / `.gradf` of one losses.LeastSquares(b) or losses.LogisticLoss(b) object"
     if g is None and proxg is None:
-        return _sparse_form_refusal(A, None, x0) or _matrix_form_refusal(A, loss_f, None, x0)
+        return _sparse_form_refusal(A, loss_f, None, x0) or _matrix_form_refusal(A, loss_f, None, x0)
     prox, owner_g = _tag_of(proxg, ProxTag), _tag_of(g, ProxTag)
     if prox is None or (owner_g is not None and owner_g is not prox) or (owner_g is None and g is not None):
         return ("g and proxg must be the `.g` / `.prox` of one proximal.* tag object "
                 "(Shrink, NonNeg, LinfProx, L1Ball, Box, TVDualBall, GroupShrink)")
-    return _sparse_form_refusal(A, prox, x0) or _matrix_form_refusal(A, loss_f, prox, x0)
+    return _sparse_form_refusal(A, loss_f, prox, x0) or _matrix_form_refusal(A, loss_f, prox, x0)
 
 
 def _recognise(A, At, f, gradf, g, proxg, x0):
@@ -176,7 +189,7 @@ class FBSolver:
         within one call are interpolated between its start and its end."""
         self.A, self.loss, self.prox = A, loss, prox
         if isinstance(A, SparseMatrixMap) and fused is True:
-            raise ValueError("fused=True: a sparse operator has no one-pass kernel (csrc/fh_sparse.h: K-fwd and K-adj)")
+            raise ValueError("fused=True: a sparse operator has no one-pass kernel (csrc/fh_sparse.h, csrc/fh_spmulti.h: K-fwd and K-adj)")
         self.fused_opt = fused
         self.ctx = A.ctx
         self.x0 = np.asarray(x0, dtype=np.float64)

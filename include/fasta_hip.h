@@ -47,7 +47,7 @@ enum fh_prox_kind {
   FH_PROX_TVBALL   = 5,  /* per-pixel 2-vector / max(norm,1), examples/tv_denoising.py:89-96 */
   FH_PROX_BOX      = 6,  /* clip to [lo, hi], examples/svm.py:71                         */
   FH_PROX_GROUP    = 7   /* row-wise l2 shrink of an (n, L) matrix, examples/mmv.py:51-59: with nu = ||xhat_j||_2 over the L entries of row j,
-                            xprox_j = xhat_j * max(nu - t*mu, 0) / (nu + (nu == 0)).  Multi-column form only (fh_set_rhs).  FH_S_GSUM /
+                            xprox_j = xhat_j * max(nu - t*mu, 0) / (nu + (nu == 0)).  Multi-column form only (fh_set_rhs, fh_set_matrix_csr_rhs).  FH_S_GSUM /
                             FH_S_GSUM_ADJ then carry sum_j ||xprox_j||_2 (of x1), so that g = mu * gsum; FH_S_GMAX is unchanged.            */
 };
 
@@ -187,17 +187,28 @@ int fh_get_matrix_rows(fh_ctx* ctx, uint64_t row0, uint64_t nrows, double* out /
  * Vectors keep the vector form's layout, so fh_set_vector / fh_get_vector, fh_diff_norm, fh_commit, both losses and the prox kinds
  * IDENTITY / SHRINK / NONNEG / BOX work unchanged; served entry points: fh_init, fh_setup (its three-pass route), fh_gradient_at, fh_apply,
  * fh_fwd, fh_adj (accel / coef), fh_fwd_adj, fh_iterate, fh_timing_* (FH_K_FWD / FH_K_ADJ / FH_K_AUX).
- * Refused (FH_E_STATE / FH_E_ARG): fh_step*, fh_run, fh_set_rhs, fh_comm_init (and a context that has a communicator), multi-device
+ * Refused (FH_E_STATE / FH_E_ARG): fh_step*, fh_run, fh_set_rhs (a matrix unknown: fh_set_matrix_csr_rhs below), fh_comm_init (and a context that has a communicator), multi-device
  * contexts, float32 storage, fh_get_matrix_rows, fh_stream_read_ms, FH_PROX_LINF / L1BALL / TVBALL / GROUP (a context holding one of these
  * returns to IDENTITY when the sparse operator is set).  fh_fused_supported, fh_fused_agree and fh_run_supported report 0.               */
 int fh_set_matrix_csr(fh_ctx* ctx, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* indptr, const int32_t* indices, const double* values);
 int fh_nnz(fh_ctx* ctx, uint64_t* nnz);     /* stored entries of the sparse operator; 0 for every other operator */
+/* ---- sparse operator with a MATRIX unknown: the sparse operator and the multi-column form in ONE call (csrc/fh_spmulti.h) ------------------
+ * L = 0 is fh_set_matrix_csr.  L in 1..16: the unknown is an (n, L) matrix, B and Z are (m, L); vectors, host formats (contiguous row-major
+ * (n, L) / (m, L) arrays), scalars and the call sequence are those of the multi-column form below; fh_rhs reports L, fh_nnz nnz, fh_shape (m, n).
+ * Every stored entry gathers one whole row of the operand and is read once for all L columns.  The lanes per row, the long-row threshold and
+ * the balanced row ranges computed here depend on L, so the column count of a sparse operator is fixed when it is set: fh_set_rhs on a sparse
+ * context stays FH_E_STATE.  CSR validation is that of fh_set_matrix_csr.  Served: fh_init, fh_setup (three-pass route), fh_gradient_at,
+ * fh_apply, fh_diff_norm, fh_commit, fh_fwd, fh_adj (accel / coef), fh_fwd_adj, fh_iterate, fh_timing_*; least squares; prox kinds IDENTITY,
+ * SHRINK, NONNEG, BOX, GROUP; FH_TUNE_NT_LOADS as for the vector form.  Refused: L > 16 (FH_E_ARG); fh_step* and fh_run (FH_E_STATE;
+ * fh_fused_supported, fh_fused_agree, fh_run_supported report 0); the logistic loss; FH_PROX_LINF / L1BALL / TVBALL; float32 storage,
+ * multi-device contexts and communicators.  Setting any new operator returns the context to the vector form.                              */
+int fh_set_matrix_csr_rhs(fh_ctx* ctx, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* indptr, const int32_t* indices, const double* values, uint32_t L);
 /* periodic difference stencil pair: A = div: (H,W,2)->(H,W), A^H = grad (examples/tv_denoising.py:26-63) */
 int fh_set_stencil(fh_ctx* ctx, uint64_t H, uint64_t W);
 int fh_shape(fh_ctx* ctx, uint64_t* m, uint64_t* n);
 
 /* ---- multi-column form: the unknown is an (n, L) MATRIX, one A for all L columns (examples/mmv.py; multi-column LASSO / NNLS) -----------
- * fh_set_rhs(ctx, L), L in 1..16, on a plain single-device context with a dense float64 operator: every n-side vector (FH_VEC_X0 .. BEST,
+ * fh_set_rhs(ctx, L), L in 1..16, on a plain single-device context with a dense float64 operator (a sparse one: fh_set_matrix_csr_rhs above): every n-side vector (FH_VEC_X0 .. BEST,
  * T0 .. T3) becomes an (n, L) matrix, FH_VEC_B and FH_VEC_Z (m, L) matrices; fh_set_vector, fh_get_vector, fh_set_loss_lsq and fh_apply
  * take and return contiguous ROW-MAJOR host arrays of n*L or m*L doubles; fh_shape still reports (m, n) of A.  The call sequence and the
  * meaning of every FH_S_* scalar (now sums over all n*L or m*L entries), fh_commit, fh_init, fh_setup (its three-pass route),

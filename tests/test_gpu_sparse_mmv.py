@@ -1,0 +1,518 @@
+"""GPU tests of a matrix unknown over a sparse operator (fh_set_matrix_csr_rhs, csrc/fh_spmulti.h): X is (n, L), every stored entry of A
+gathers one whole row of it -- through the C ABI and through fasta().
+
+Tolerances are the project's existing ones for the sparse operator: an apply is compared componentwise against SciPy with
+|error| <= 1e-12 * (|A| |V|) (a row's rounding bound k * u * sum |a v| stays under it for k <= 9000 entries); single-step scalars at the
+tolerances of tests/test_gpu_sparse.py:test_single_step_scalars_match_numpy; whole solves with equal iteration and backtrack counts,
+histories rtol 1e-6 / atol 1e-14, solution rtol 1e-5 with a floor of 1e-6 of its largest entry."""
+import os
+import warnings
+
+import numpy as np
+import pytest
+from scipy import sparse as sp
+
+import fasta_python_amd as fa
+from fasta_python_amd import hip, proximal
+from fasta_python_amd import stopping as fstop
+from tests import gpu_util as G
+from tests import helpers as H
+from tests.test_gpu_sparse import banded_random, long_both, long_col, random_sparse, skewed
+from tests.test_sparse_mmv_cpu import EXPECTED as CASES, capture_script, load
+
+pytestmark = pytest.mark.gpu
+
+FIELDS = ("residuals", "norm_residuals", "stepsizes", "objectives")
+ALL_L = [1, 2, 3, 4, 5, 8, 9, 16]                       # every LB (2, 4, 8, 16), with and without padding columns
+
+
+@pytest.fixture(autouse=True)
+def no_scratch_contexts_left_behind():
+    """device_prox caches a scratch context per shape; other test files count the entries."""
+    yield
+    proximal.release_scratch()
+
+
+# ---- the host's rule, restated -------------------------------------------------------------------------------------------------------------
+def long_rows_of(S, LB):
+    """(rows of A, rows of A^T) the host hands to whole workgroups at LB columns per row: its rule restated (csrc/fasta_hip.hip:
+    sp_upload_side).  C = LB / 2 column lanes per entry, a group of G lanes works on E = G / C entries per trip; G is the smallest of
+    max(4, C) .. 64 with 2 E >= the mean row length; a row is long beyond max(64 E, 16 mean rows) entries."""
+    C = LB // 2
+    out = []
+    for M in (S.tocsr(), S.T.tocsr()):
+        lens = np.diff(M.indptr)
+        mean = M.nnz / M.shape[0]
+        Gl = max(4, C)
+        while Gl < 64 and 2.0 * (Gl // C) < mean:
+            Gl *= 2
+        out.append(int((lens > max(64 * (Gl // C), int(16 * mean))).sum()))
+    return tuple(out)
+
+
+def test_the_long_row_cases_reach_the_whole_workgroup_path_on_both_copies():
+    for LB in (2, 16):
+        assert long_rows_of(long_col(), LB) == (0, 1) and long_rows_of(long_both(), LB) == (1, 1), LB
+        assert long_rows_of(random_sparse(4096, 4096, 0.01, 8), LB) == (0, 0)
+    assert long_rows_of(skewed(), 8) == (1, 1) and long_rows_of(skewed(), 2) == (1, 0)
+
+
+# ---- apply ---------------------------------------------------------------------------------------------------------------------------------
+SMALL = {
+    "1xn": lambda: random_sparse(1, 300, 0.3, 1), "mx1": lambda: random_sparse(300, 1, 0.3, 2), "1x1": lambda: sp.csr_matrix(np.array([[2.5]])),
+    "empty": lambda: sp.csr_matrix((37, 53)), "ragged": lambda: random_sparse(203, 1001, 0.02, 3), "tall": lambda: random_sparse(1030, 17, 0.2, 4),
+    "skewed": skewed,
+}
+LARGE = {"long_col": long_col, "long_both": long_both, "4096_1%": lambda: random_sparse(4096, 4096, 0.01, 8)}
+
+
+def assert_apply(got, S, V):
+    want = S @ V
+    bound = 1e-12 * (abs(S) @ np.abs(V))
+    err = np.abs(got - want)
+    worst = float(np.max(err / np.maximum(bound, 1e-300))) if err.size and err.max() > 0 else 0.0
+    print(f" worst |error| / (1e-12 |A||V|) = {worst:.3e}", end="")
+    assert got.shape == want.shape and np.all(err <= bound)
+
+
+def check_apply(S, L, nt):
+    m, n = S.shape
+    rng = np.random.RandomState(11)
+    V, W = rng.randn(n, L), rng.randn(m, L)
+    op = fa.SparseMatrixMap(S, rhs=L, tuning=None if nt is None else {hip.TUNE_NT_LOADS: nt})
+    try:
+        c = op.ctx
+        assert c.shape() == (m, n) and c.nnz() == S.nnz == op.nnz and c.rhs == L
+        Z, Gt = op.device_apply(V), op.device_apply(W, adjoint=True)
+        assert_apply(Z, S, V)
+        assert_apply(Gt, S.T.tocsr(), W)
+        lhs, rhs = float(np.sum(Z * W)), float(np.sum(V * Gt))           # <A U, V> = <U, A^T V> on the device's own products
+        print(f"; <AU,V> - <U,A^T V> = {lhs - rhs:.3e} of {lhs:.6e}")
+        assert abs(lhs - rhs) <= 1e-12 * max(abs(lhs), abs(rhs))
+        assert np.array_equal(op(V), S @ V) and np.array_equal(op.H(W), S.T @ W)          # host arrays: the reference's closures
+    finally:
+        op.close()
+
+
+@pytest.mark.parametrize("L", ALL_L)
+@pytest.mark.parametrize("shape", list(SMALL))
+def test_apply_matches_scipy_in_both_directions(shape, L):
+    print(f"\n{shape} L={L}:", end="")
+    check_apply(SMALL[shape](), L, None)
+
+
+@pytest.mark.parametrize("nt", [0, 1], ids=["nt0", "nt1"])
+@pytest.mark.parametrize("L", [2, 16])
+@pytest.mark.parametrize("shape", list(LARGE))
+def test_apply_on_the_long_row_matrices_with_both_load_policies(shape, L, nt):
+    print(f"\n{shape} L={L} nt={nt}:", end="")
+    check_apply(LARGE[shape](), L, nt)
+
+
+@pytest.mark.parametrize("L,full", [(3, 4), (5, 8)])
+def test_padding_never_leaks(L, full):
+    """fh_apply with L columns == the first L columns of the same apply with `full` = LB columns whose other columns are zero, bit for bit."""
+    S = random_sparse(203, 1001, 0.02, 3)
+    rng = np.random.RandomState(12)
+    V, W = rng.randn(1001, L), rng.randn(203, L)
+    Vf, Wf = np.zeros((1001, full)), np.zeros((203, full))
+    Vf[:, :L], Wf[:, :L] = V, W
+    outs = []
+    for cols, (v, w) in ((L, (V, W)), (full, (Vf, Wf))):
+        op = fa.SparseMatrixMap(S, rhs=cols)
+        try:
+            outs.append((op.device_apply(v), op.device_apply(w, adjoint=True)))
+        finally:
+            op.close()
+    assert np.array_equal(outs[0][0], outs[1][0][:, :L]) and np.array_equal(outs[0][1], outs[1][1][:, :L])
+    assert not outs[1][0][:, L:].any() and not outs[1][1][:, L:].any()
+
+
+def test_apply_is_bitwise_repeatable():
+    S = long_both()
+    V = np.random.RandomState(1).randn(6000, 5)
+    op = fa.SparseMatrixMap(S, rhs=5)
+    try:
+        a, b = op.device_apply(V), op.device_apply(V)
+        w = np.random.RandomState(2).randn(5000, 5)
+        c, d = op.device_apply(w, adjoint=True), op.device_apply(w, adjoint=True)
+    finally:
+        op.close()
+    assert np.array_equal(a, b) and np.array_equal(c, d)
+
+
+def test_offsets_and_partition_at_size():
+    """262 144^2 with 16 entries per row, L = 4: one apply each way against SciPy."""
+    n = 1 << 18
+    S = banded_random(n, 16, 41)
+    rng = np.random.RandomState(44)
+    V, W = rng.randn(n, 4), rng.randn(n, 4)
+    op = fa.SparseMatrixMap(S, rhs=4)
+    try:
+        print(f"\n{n}^2, 16 per row, L=4:", end="")
+        assert_apply(op.device_apply(V), S, V)
+        assert_apply(op.device_apply(W, adjoint=True), S.T.tocsr(), W)
+    finally:
+        op.close()
+
+
+# ---- one step ------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("tag", [fa.Shrink(0.3), fa.NonNeg(), fa.Box(-0.4, 0.7), fa.NoProx()], ids=lambda t: type(t).__name__)
+def test_elementwise_prox_outputs_are_the_vector_sparse_form_bit_for_bit(tag):
+    """Same x0, same g0 (set, not computed), same tau: xhat and xprox of every column == those of the vector sparse form run on that column."""
+    n, L, tau = 403, 5, 0.9
+    rng = np.random.RandomState(17)
+    X0, G0 = rng.randn(n, L), rng.randn(n, L)
+    S = random_sparse(40, n, 0.05, 18)
+
+    def one_fwd(op, x0, g0, b):
+        c = op.ctx
+        c.set_loss_lsq(b)
+        c.set_prox(tag.kind, tag.mu, tag.lo, tag.hi)
+        c.set_vector(hip.VEC_X0, x0)
+        c.init()
+        c.set_vector(hip.VEC_G0, g0)
+        c.fwd(tau)
+        return c.get_vector(hip.VEC_XHAT, x0.size).reshape(x0.shape), c.get_vector(hip.VEC_XPROX, x0.size).reshape(x0.shape)
+
+    op = fa.SparseMatrixMap(S, rhs=L)
+    try:
+        xh, xp = one_fwd(op, X0, G0, np.zeros((40, L)))
+    finally:
+        op.close()
+    vec = fa.SparseMatrixMap(S)
+    try:
+        for l in range(L):
+            vh, vp = one_fwd(vec, X0[:, l].copy(), G0[:, l].copy(), np.zeros(40))
+            assert np.array_equal(xh[:, l], vh) and np.array_equal(xp[:, l], vp), l
+    finally:
+        vec.close()
+    assert np.array_equal(xp, np.asarray(tag.prox(X0 - tau * G0, tau)) * np.ones((n, L)))
+
+
+def padding_is_zero(c, which, rows, L, m_side=False):
+    """fh_diff_norm adds up the WHOLE device buffers, so against a buffer that holds the same logical entries and untouched (zero) padding
+    the norm is exactly zero only if the padding of `which` is."""
+    v = c.get_vector(which, rows * L)
+    other = hip.VEC_B if m_side else hip.VEC_T0
+    c.set_vector(other, v)
+    return c.diff_norm(which, other) == 0.0
+
+
+STEP_MATRICES = {"uniform": lambda: random_sparse(190, 333, 0.06, 14), "long_both": lambda: long_both() * 0.05}
+
+
+@pytest.mark.parametrize("L,kind,matrix", [(5, "group", "uniform"), (16, "group", "uniform"), (3, "shrink", "uniform"), (2, "nonneg", "uniform"),
+                                           (9, "box", "uniform"), (1, "none", "uniform"), (8, "group", "long_both"), (2, "shrink", "long_both")])
+def test_single_step_scalars_match_numpy(L, kind, matrix):
+    """One K-fwd, one K-adj (mode 0, plain and accelerated), fh_init's mode-1 adjoint: matrices and all scalars against NumPy.  On long_both
+    the dense row's Z and the dense column's G1 with its n-side epilogue come from the whole-workgroup blocks."""
+    rng = np.random.RandomState(13 + L)
+    S = STEP_MATRICES[matrix]()
+    (m, n), mu, tau = S.shape, 0.05, 0.3
+    X0, B = rng.randn(n, L) * 0.1, rng.randn(m, L)
+    tag = {"group": fa.GroupShrink(mu), "shrink": fa.Shrink(mu), "nonneg": fa.NonNeg(), "box": fa.Box(-0.05, 0.08), "none": fa.NoProx()}[kind]
+    gsum = (lambda V: np.sum(np.sqrt(np.sum(V * V, axis=1)))) if kind == "group" else (lambda V: np.abs(V).sum())
+    mat = lambda which, rows: c.get_vector(which, rows * L).reshape(rows, L)
+    op = fa.SparseMatrixMap(S, rhs=L)
+    c = op.ctx
+    try:
+        c.set_loss_lsq(B)
+        c.set_prox(tag.kind, tag.mu, tag.lo, tag.hi)
+        c.set_vector(hip.VEC_X0, X0)
+        s0 = c.init()
+        G0 = S.T @ (S @ X0 - B)
+        np.testing.assert_allclose(mat(hip.VEC_G0, n), G0, rtol=1e-12, atol=1e-13)
+        np.testing.assert_allclose(s0[hip.S_FSQ], np.sum((S @ X0 - B) ** 2), rtol=1e-12)
+        np.testing.assert_allclose(s0[hip.S_GSUM], gsum(X0), rtol=1e-12)
+        s = c.fwd(tau)
+        Xh = X0 - tau * G0
+        Xp = np.asarray(tag.prox(Xh, tau))
+        np.testing.assert_allclose(mat(hip.VEC_XHAT, n), Xh, rtol=1e-12, atol=1e-14)
+        np.testing.assert_allclose(mat(hip.VEC_XPROX, n), Xp, rtol=1e-12, atol=1e-14)
+        dX, Z = Xp - X0, S @ Xp
+        np.testing.assert_allclose(mat(hip.VEC_Z, m), Z, rtol=1e-12, atol=1e-13)
+        want = {hip.S_FSQ: np.sum((Z - B) ** 2), hip.S_DXG0: np.sum(dX * G0), hip.S_DX2: np.sum(dX * dX), hip.S_XH2: np.sum((Xp - Xh) ** 2),
+                hip.S_G02: np.sum(G0 * G0), hip.S_GSUM: gsum(Xp), hip.S_GMAX: np.abs(Xp).max(), hip.S_RDOT: np.sum((X0 - Xp) * (Xp - X0))}
+        for k, v in want.items():
+            np.testing.assert_allclose(s[k], v, rtol=1e-11, atol=1e-13, err_msg=str(k))
+        a = c.adj(tau)
+        G1 = S.T @ (Z - B)
+        dG = G1 + (Xh - X0) / tau
+        np.testing.assert_allclose(mat(hip.VEC_G1, n), G1, rtol=1e-11, atol=1e-13)
+        np.testing.assert_allclose(a[hip.S_DXDG], np.sum(dX * dG), rtol=1e-10, atol=1e-13)
+        np.testing.assert_allclose(a[hip.S_DG2], np.sum(dG * dG), rtol=1e-10, atol=1e-13)
+        np.testing.assert_allclose(a[hip.S_FSQ_ADJ], np.sum((Z - B) ** 2), rtol=1e-11)
+        np.testing.assert_allclose(a[hip.S_GSUM_ADJ], gsum(Xp), rtol=1e-11)
+        np.testing.assert_allclose(a[hip.S_XH2_ADJ], np.sum((Xp - Xh) ** 2), rtol=1e-11, atol=1e-13)
+        np.testing.assert_allclose(a[hip.S_GMAX_ADJ], np.abs(Xp).max(), rtol=1e-12)
+        assert np.array_equal(a[:hip.S_DXDG], s[:hip.S_DXDG])                      # K-adj leaves the forward half of the block alone
+        pair = c.fwd_adj(tau)                                                    # both launches under one synchronisation: the same block
+        assert np.array_equal(pair[:hip.S_ALPHA], np.concatenate([s[:hip.S_DXDG], a[hip.S_DXDG:hip.S_ALPHA]]))
+        coef = 0.37                                                              # accelerated variant (fasta/__init__.py:242-245)
+        a2 = c.adj(tau, accel=True, coef=coef)
+        X1, Z1 = Xp + coef * (Xp - X0), Z + coef * (Z - S @ X0)
+        np.testing.assert_allclose(mat(hip.VEC_X1, n), X1, rtol=1e-12, atol=1e-14)
+        np.testing.assert_allclose(a2[hip.S_FSQ_ADJ], np.sum((Z1 - B) ** 2), rtol=1e-11)
+        np.testing.assert_allclose(mat(hip.VEC_G1, n), S.T @ (Z1 - B), rtol=1e-11, atol=1e-13)
+        np.testing.assert_allclose(a2[hip.S_XH2_ADJ], np.sum((X1 - Xh) ** 2), rtol=1e-11)
+        np.testing.assert_allclose(a2[hip.S_GSUM_ADJ], gsum(X1), rtol=1e-11)
+        np.testing.assert_allclose(a2[hip.S_GMAX_ADJ], np.abs(X1).max(), rtol=1e-12)
+        # padding columns (and rows) of everything the kernels wrote are exact zeros
+        for which in (hip.VEC_G0, hip.VEC_XHAT, hip.VEC_XPROX, hip.VEC_X1, hip.VEC_G1):
+            assert padding_is_zero(c, which, n, L), which
+        assert padding_is_zero(c, hip.VEC_Z, m, L, m_side=True)
+        # timing runs under the existing kernel ids
+        c.timing_enable(True)
+        c.fwd(tau), c.adj(tau), c.init()
+        assert c.timing_get(hip.K_FWD)[1] >= 2 and c.timing_get(hip.K_ADJ)[1] >= 2 and c.timing_get(hip.K_AUX)[1] >= 1
+        assert c.timing_get(hip.K_FUSED)[1] == 0
+    finally:
+        op.close()
+
+
+# ---- whole solves --------------------------------------------------------------------------------------------------------------------------
+def tags(kind, d):
+    """(loss, prox tag) of a fixture kind: the device-tagged twins of scripts/make_sparse_mmv_golden.py:closures."""
+    reg = {"mmv": lambda: fa.GroupShrink(float(d["mu"])), "lasso": lambda: fa.Shrink(float(d["mu"])), "skewed": lambda: fa.Shrink(float(d["mu"])),
+           "nnls": fa.NonNeg, "box": lambda: fa.Box(float(d["lo"]), float(d["hi"]))}[kind]()
+    return fa.LeastSquares(d["B"]), reg
+
+
+def solve(meta, d, op=None, **extra):
+    S = capture_script().matrix_of(d)
+    L = d["B"].shape[1]
+    own = op is None
+    op = fa.SparseMatrixMap(S, rhs=L) if own else op
+    try:
+        loss, reg = tags(meta["kind"], d)
+        o = H.resolve_options(dict(meta["options"], **extra), fstop)
+        np.random.seed(meta["solver_seed"])
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            return fa.fasta(op, op.H, loss.f, loss.gradf, reg.g, reg.prox, np.zeros((S.shape[1], L)), verbose=False, backend="hip", **o)
+    finally:
+        if own:
+            op.close()
+
+
+_runs = {}
+
+
+def library_run(name):
+    """The library-driven device solve of a fixture (its compared prefix), computed once and shared by the tests below; never modified."""
+    if name not in _runs:
+        meta, z, d = load(name)
+        k = min(int(meta.get("permuted_divergence", int(z["iteration_count"]))), int(z["iteration_count"]))
+        full = k == int(z["iteration_count"]) and "permuted_divergence" not in meta
+        extra = {} if full else dict(max_iters=k, tolerance=0.0)
+        _runs[name] = (solve(meta, d, driver="library", **extra), k, full, extra)
+    return _runs[name]
+
+
+def assert_solution(got, want):
+    np.testing.assert_allclose(got, want, rtol=1e-5, atol=1e-6 * float(np.max(np.abs(want))))
+
+
+def assert_same_bits(a, b):
+    assert a.iteration_count == b.iteration_count and a.backtracks == b.backtracks
+    for f in FIELDS:
+        if getattr(b, f) is not None:
+            assert np.array_equal(getattr(a, f), getattr(b, f), equal_nan=True), f
+    assert np.array_equal(a.solution, b.solution)
+
+
+@pytest.mark.parametrize("name", CASES)
+def test_fixture_solves_on_the_device(name):
+    meta, z, d = load(name)
+    lib, k, full, extra = library_run(name)
+    assert lib.library_steps == lib.iteration_count and lib.device_steps == 0
+    print(f"\n{name}: device {lib.iteration_count} iterations / {lib.backtracks} backtracks, reference {int(z['iteration_count'])} / {int(z['backtracks'])}", end="")
+    if full:
+        assert lib.iteration_count == int(z["iteration_count"]) and lib.backtracks == int(z["backtracks"])
+    else:
+        assert lib.iteration_count == k and lib.backtracks == meta["backtracks_at_divergence"]
+    worst = G.compare_histories(lib, lambda f: z[f] if f in z.files else None, k, rtol=1e-6, atol=1e-14)
+    print(f"; {k} iterations compared, worst relative deviation of a history entry {worst:.2e}")
+    if full:
+        assert_solution(lib.solution, z["solution"])
+
+
+@pytest.mark.parametrize("name", CASES)
+def test_library_and_python_drivers_are_bit_identical(name):
+    meta, z, d = load(name)
+    lib, k, full, extra = library_run(name)
+    py = solve(meta, d, driver="python", **extra)
+    assert py.library_steps == 0
+    assert_same_bits(py, lib)
+
+
+@pytest.mark.parametrize("name", ["mmv_60x90x5_adaptive", "mmv_60x90x5_accelerated", "nnls_150x80x16_accelerated", "skewed_257x515x8_adaptive"])
+def test_two_runs_are_bitwise_equal(name):
+    meta, z, d = load(name)
+    lib, k, full, extra = library_run(name)
+    assert_same_bits(solve(meta, d, driver="library", **extra), lib)
+
+
+@pytest.mark.parametrize("name", [n for n in CASES if "backtracks" not in n])
+def test_the_densified_matrix_agrees(name):
+    """The same matrix as a DenseMatrixMap(S.toarray(), rhs=L): equal counts, the first 40 iterations of every history at rtol 1e-6."""
+    meta, z, d = load(name)
+    sparse, k, full, extra = library_run(name)
+    dense_op = fa.DenseMatrixMap(capture_script().matrix_of(d).toarray(), rhs=d["B"].shape[1])
+    try:
+        dense = solve(meta, d, op=dense_op, fused=False)
+    finally:
+        dense_op.close()
+    print(f"\n{name}: sparse {sparse.iteration_count} / {sparse.backtracks}, dense {dense.iteration_count} / {dense.backtracks}")
+    assert sparse.iteration_count == dense.iteration_count and sparse.backtracks == dense.backtracks
+    G.compare_histories(sparse, lambda f: getattr(dense, f), min(40, sparse.iteration_count), rtol=1e-6, atol=1e-14)
+
+
+@pytest.mark.parametrize("name", ["mmv_60x90x5_adaptive", "mmv_60x90x5_accelerated"])
+def test_device_driver_falls_to_the_library_loop(name):
+    meta, z, d = load(name)
+    want, k, full, extra = library_run(name)
+    for how in (dict(driver="device"), dict(device_iters=7)):
+        c = solve(meta, d, **how)
+        assert c.device_steps == 0 and c.library_steps == c.iteration_count == want.iteration_count
+        assert np.array_equal(c.stepsizes, want.stepsizes) and np.array_equal(c.solution, want.solution)
+
+
+def test_fused_true_is_refused_as_on_the_vector_sparse_form():
+    meta, z, d = load("mmv_60x90x5_adaptive")
+    with pytest.raises(ValueError, match="one-pass"):
+        solve(meta, d, fused=True)
+
+
+def test_the_example_prints_the_same_iteration_counts_on_both_backends(capsys):
+    from fasta_python_amd.examples import test_modes
+    from fasta_python_amd.examples.sparse_mmv import SparseMMVProblem
+    counts = {}
+    for backend in ("numpy", "hip"):
+        problem, X0 = SparseMMVProblem.construct(M=200, N=300, L=5, K=8, density=0.05, backend=backend)
+        np.random.seed(1)
+        counts[backend] = [c.iteration_count for _, c in test_modes(problem, X0)]
+        problem.close()
+    assert counts["hip"] == counts["numpy"], counts
+    assert capsys.readouterr().out.count("Completed in") == 6            # print_info, once per mode and solve
+
+
+# ---- the C ABI -----------------------------------------------------------------------------------------------------------------------------
+def status_of(call):
+    with pytest.raises(hip.HipError) as e:
+        call()
+    assert len(str(e.value)) > 20                             # a sentence, not just a code
+    return int(str(e.value).split("]")[0][1:])
+
+
+def test_what_the_sparse_multi_column_form_does_not_serve_is_refused_with_its_code():
+    S = random_sparse(64, 96, 0.1, 31)
+    data, indices, indptr = S.data, S.indices, S.indptr
+    rng = np.random.RandomState(0)
+    op = fa.SparseMatrixMap(S, rhs=4)
+    try:
+        c = op.ctx
+        assert c.rhs == 4 and c.nnz() == S.nnz and c.shape() == S.shape
+        assert status_of(lambda: c.set_matrix_csr_rhs(indptr, indices, data, S.shape, 17)) == hip.E_ARG
+        assert c.rhs == 4 and c.nnz() == S.nnz                   # ... and left the operator as it was
+        for kind in (hip.PROX_LINF, hip.PROX_L1BALL, hip.PROX_TVBALL):
+            assert status_of(lambda: c.set_prox(kind, 1.0)) == hip.E_ARG
+        assert status_of(lambda: c.set_loss_logistic(np.ones(64 * 4))) == hip.E_STATE
+        assert status_of(lambda: c.set_rhs(2)) == hip.E_STATE
+        assert status_of(lambda: c.set_rhs(0)) == hip.E_STATE
+        assert status_of(lambda: c.comm_init(1, 0, bytes(hip.UNIQUE_ID_BYTES))) == hip.E_STATE
+        c.set_loss_lsq(rng.randn(64, 4))
+        c.set_prox(hip.PROX_GROUP, 0.1)
+        c.set_vector(hip.VEC_X0, np.zeros((96, 4)))
+        c.init()
+        assert c.fused_supported() == 0 and c.fused_agree() == 0 and not c.run_supported()
+        assert status_of(lambda: c.step(0.1)) == hip.E_STATE
+        assert status_of(lambda: c.step_begin(0.1)) == hip.E_STATE
+        assert status_of(lambda: c.step_accel(0.1, 0.5, True)) == hip.E_STATE
+        assert status_of(lambda: c.run(4, hip.RunOpts(window=10, stepsize_shrink=0.5), hip.RunState(tau_next=0.1, alpha1=1.0))) == hip.E_STATE
+        assert status_of(lambda: c.set_vector(hip.VEC_X0, np.zeros(96))) == hip.E_ARG           # the vector form's length
+        s = c.fwd(0.1)                                            # ... and the context still works
+        assert np.isfinite(s[hip.S_FSQ])
+        np.testing.assert_allclose(op.device_apply(np.ones((96, 4))), S @ np.ones((96, 4)), rtol=1e-12, atol=1e-13)
+    finally:
+        op.close()
+    with hip.HipContext(0, storage="f32") as c32:
+        assert status_of(lambda: c32.set_matrix_csr_rhs(indptr, indices, data, S.shape, 4)) == hip.E_STATE
+    with hip.HipContext(devices=[0, 0]) as shell:
+        assert status_of(lambda: shell.set_matrix_csr_rhs(indptr, indices, data, S.shape, 4)) == hip.E_STATE
+    with hip.HipContext(0) as c:
+        bad = indices.copy()                                      # CSR validation is fh_set_matrix_csr's: the first offending row by name
+        lo = int(indptr[5])
+        assert indptr[6] - lo >= 2
+        bad[lo], bad[lo + 1] = bad[lo + 1], bad[lo]
+        with pytest.raises(hip.HipError, match="row 5"):
+            c.set_matrix_csr_rhs(indptr, bad, data, S.shape, 4)
+        c.set_matrix_csr(indptr, indices, data, S.shape)          # a sparse VECTOR context: GROUP and fh_set_rhs stay refused
+        assert status_of(lambda: c.set_prox(hip.PROX_GROUP, 0.1)) == hip.E_ARG
+        assert status_of(lambda: c.set_rhs(2)) == hip.E_STATE
+        # a sparse multi-column operator, then a new dense one: back in the vector form
+        c.set_matrix_csr_rhs(indptr, indices, data, S.shape, 9)
+        assert c.rhs == 9 and c.nnz() == S.nnz
+        c.set_prox(hip.PROX_GROUP, 0.1)
+        c.set_matrix(np.eye(4))
+        assert c.rhs == 0 and c.nnz() == 0 and np.array_equal(c.apply(np.arange(4.0)), np.arange(4.0))
+        assert status_of(lambda: c.set_prox(hip.PROX_GROUP, 0.1)) == hip.E_ARG
+        # ... and a new sparse vector operator after a multi-column one
+        c.set_matrix_csr_rhs(indptr, indices, data, S.shape, 3)
+        c.set_matrix_csr(indptr, indices, data, S.shape)
+        assert c.rhs == 0
+        np.testing.assert_allclose(c.apply(np.ones(96)), S @ np.ones(96), rtol=1e-12, atol=1e-13)
+
+
+def test_a_communicator_refuses_the_sparse_multi_column_operator(tmp_path):
+    """A rank of a row-sharded run (fh_comm_init) has no sparse operator in either form.  A fresh process with the test-only RCCL stand-in."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    lib = str(tmp_path / "libmock_rccl.so")
+    subprocess.run(["/opt/rocm/bin/hipcc", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", lib, os.path.join(root, "tests", "mock_rccl", "mock_rccl.cpp"), "-lrt"],
+                   check=True, capture_output=True, timeout=300)
+    script = (
+        "import numpy as np\n"
+        "from fasta_python_amd import hip\n"
+        "with hip.HipContext(0) as c:\n"
+        "    c.set_matrix(np.arange(24.0).reshape(6, 4))\n"
+        "    c.comm_init(1, 0, hip.comm_unique_id())\n"
+        "    try:\n"
+        "        c.set_matrix_csr_rhs(np.array([0, 1, 2]), np.array([0, 1]), np.ones(2), (2, 2), 3)\n"
+        "    except hip.HipError as e:\n"
+        "        assert str(e).startswith('[%d]' % hip.E_STATE) and 'communicator' in str(e), str(e)\n"
+        "    else:\n"
+        "        raise SystemExit('fh_set_matrix_csr_rhs accepted a context with a communicator')\n"
+        "    y = c.apply(np.ones(4))\n"                              # still usable
+        "    assert np.allclose(y, np.arange(24.0).reshape(6, 4).sum(axis=1))\n"
+        "    c.comm_destroy()\n"
+        "print('refused')\n")
+    r = subprocess.run([sys.executable, "-c", script], env=dict(os.environ, FASTA_RCCL_LIB=lib), cwd=root, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "refused" in r.stdout, r.stdout[-1500:] + r.stderr[-3000:]
+
+
+def test_zero_columns_is_the_vector_form_bit_for_bit():
+    """fh_set_matrix_csr_rhs(..., 0) followed by a vector solve == fh_set_matrix_csr."""
+    from tests.test_gpu_sparse import load as load_vec, solve as solve_vec
+    from tests.test_sparse_cpu import capture_script as vec_script
+    meta, z, d = load_vec("lasso_200x400_adaptive")
+    want = solve_vec(meta, d)
+    S = vec_script().matrix_of(d)
+    op = fa.SparseMatrixMap(S)
+    try:
+        c = op.ctx
+        c.set_matrix_csr_rhs(S.indptr, S.indices, S.data, S.shape, 5)         # a multi-column operator first ...
+        c.set_loss_lsq(np.ones((200, 5)))
+        c.set_prox(hip.PROX_GROUP, 0.3)
+        c.set_vector(hip.VEC_X0, np.ones((400, 5)))
+        c.init()
+        c.fwd(0.01)
+        c.adj(0.01)
+        c.set_matrix_csr_rhs(S.indptr, S.indices, S.data, S.shape, 0)         # ... then the vector form through the new entry point
+        assert c.rhs == 0 and c.nnz() == S.nnz
+        got = solve_vec(meta, d, op=op)
+    finally:
+        op.close()
+    assert_same_bits(got, want)
