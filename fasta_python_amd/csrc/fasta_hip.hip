@@ -626,6 +626,16 @@ extern "C" int fh_set_matrix_csr(fh_ctx* c, uint64_t m, uint64_t n, uint64_t nnz
 extern "C" int fh_set_matrix_csr_rhs(fh_ctx* c, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* indptr, const int32_t* indices, const double* values, uint32_t L) {
   return set_matrix_csr(c, L ? "fh_set_matrix_csr_rhs" : "fh_set_matrix_csr", m, n, nnz, indptr, indices, values, L);
 }
+// what sp_upload_side chose for one copy of the operator (read-only; the tests assert which kernel instantiation ran)
+extern "C" int fh_sparse_lanes(fh_ctx* c, int side, int* G, uint32_t* nwg, uint32_t* nlong) {
+  if (!c) return fail(FH_E_ARG, "null context");
+  if (side != 0 && side != 1) return fail(FH_E_ARG, "fh_sparse_lanes: side is 0 (A by rows) or 1 (A^T by rows), got %d", side);
+  if (c->op != OP_SPARSE) return fail(FH_E_STATE, "fh_sparse_lanes: the context holds no sparse operator (fh_set_matrix_csr)");
+  if (G) *G = c->sp_G[side];
+  if (nwg) *nwg = c->sp[side].nwg;
+  if (nlong) *nlong = c->sp[side].nlong;
+  return 0;
+}
 extern "C" int fh_nnz(fh_ctx* c, uint64_t* nnz) {
   if (!c || !nnz) return fail(FH_E_ARG, "null argument");
   *nnz = c->op == OP_SPARSE ? c->nnz : 0u;

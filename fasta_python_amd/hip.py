@@ -82,6 +82,7 @@ SIGNATURES = {
     "fh_set_matrix_csr": (_i32, [_ctx, _u64, _u64, _u64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _pd]),
     "fh_set_matrix_csr_rhs": (_i32, [_ctx, _u64, _u64, _u64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _pd, C.c_uint32]),
     "fh_nnz": (_i32, [_ctx, C.POINTER(_u64)]),
+    "fh_sparse_lanes": (_i32, [_ctx, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "fh_set_stencil": (_i32, [_ctx, _u64, _u64]),
     "fh_shape": (_i32, [_ctx, C.POINTER(_u64), C.POINTER(_u64)]),
     "fh_set_rhs": (_i32, [_ctx, C.c_uint32]),
@@ -389,6 +390,13 @@ class HipContext:
         k = _u64(0)
         self._call("fh_nnz", C.byref(k))
         return int(k.value)
+
+    def sparse_lanes(self, side):
+        """(G, nwg, nlong) of one copy of the sparse operator (side 0: A by rows, 1: A^T by rows): the lanes per row -- which kernel
+        instantiation a launch takes -- the workgroups that share the ordinary rows, and the long rows that get a workgroup each."""
+        g, nwg, nlong = C.c_int(0), C.c_uint32(0), C.c_uint32(0)
+        self._call("fh_sparse_lanes", int(side), C.byref(g), C.byref(nwg), C.byref(nlong))
+        return int(g.value), int(nwg.value), int(nlong.value)
 
     def generate_matrix(self, m, n, row0, seed, coef):
         self._call("fh_generate_matrix", int(m), int(n), int(row0), int(seed), float(coef))

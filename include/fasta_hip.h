@@ -203,6 +203,10 @@ int fh_nnz(fh_ctx* ctx, uint64_t* nnz);     /* stored entries of the sparse oper
  * fh_fused_supported, fh_fused_agree, fh_run_supported report 0); the logistic loss; FH_PROX_LINF / L1BALL / TVBALL; float32 storage,
  * multi-device contexts and communicators.  Setting any new operator returns the context to the vector form.                              */
 int fh_set_matrix_csr_rhs(fh_ctx* ctx, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* indptr, const int32_t* indices, const double* values, uint32_t L);
+/* read-only: what fh_set_matrix_csr[_rhs] chose for one copy of the sparse operator (side 0: A by rows, 1: A^T by rows) -- the lanes per row G
+ * (which kernel instantiation a launch takes), the workgroups that share the ordinary rows and the long rows that get a workgroup each.  Any
+ * output pointer may be NULL.  FH_E_STATE without a sparse operator, FH_E_ARG for another side.                                            */
+int fh_sparse_lanes(fh_ctx* ctx, int side, int* G, uint32_t* nwg, uint32_t* nlong);
 /* periodic difference stencil pair: A = div: (H,W,2)->(H,W), A^H = grad (examples/tv_denoising.py:26-63) */
 int fh_set_stencil(fh_ctx* ctx, uint64_t H, uint64_t W);
 int fh_shape(fh_ctx* ctx, uint64_t* m, uint64_t* n);

@@ -18,6 +18,7 @@ from fasta_python_amd import hip
 from fasta_python_amd import stopping as fstop
 from tests import gpu_util as G
 from tests import helpers as H
+from tests import sparse_lanes as SL
 from tests.test_sparse_cpu import capture_script
 
 pytestmark = pytest.mark.gpu
@@ -85,16 +86,8 @@ def long_both():
 
 
 def long_rows_of(S):
-    """(rows of A, rows of A^T) the host hands to whole workgroups: its rule restated (csrc/fasta_hip.hip: sp_upload_side)."""
-    out = []
-    for M in (S.tocsr(), S.T.tocsr()):
-        lens = np.diff(M.indptr)
-        mean = M.nnz / M.shape[0]
-        G = 4
-        while G < 64 and 2.0 * G < mean:
-            G *= 2
-        out.append(int((lens > max(64 * G, int(16 * mean))).sum()))
-    return tuple(out)
+    """(rows of A, rows of A^T) the host hands to whole workgroups: its rule as tests/sparse_lanes.py restates it (csrc/fasta_hip.hip: sp_upload_side)."""
+    return tuple(int(la.long_rows.size) for la in SL.both_lanes(S, 0))
 
 
 def test_the_long_row_cases_reach_the_whole_workgroup_path_on_both_copies():

@@ -17,6 +17,7 @@ from fasta_python_amd import hip, proximal
 from fasta_python_amd import stopping as fstop
 from tests import gpu_util as G
 from tests import helpers as H
+from tests import sparse_lanes as SL
 from tests.test_gpu_sparse import banded_random, long_both, long_col, random_sparse, skewed
 from tests.test_sparse_mmv_cpu import EXPECTED as CASES, capture_script, load
 
@@ -35,19 +36,9 @@ def no_scratch_contexts_left_behind():
 
 # ---- the host's rule, restated -------------------------------------------------------------------------------------------------------------
 def long_rows_of(S, LB):
-    """(rows of A, rows of A^T) the host hands to whole workgroups at LB columns per row: its rule restated (csrc/fasta_hip.hip:
-    sp_upload_side).  C = LB / 2 column lanes per entry, a group of G lanes works on E = G / C entries per trip; G is the smallest of
-    max(4, C) .. 64 with 2 E >= the mean row length; a row is long beyond max(64 E, 16 mean rows) entries."""
-    C = LB // 2
-    out = []
-    for M in (S.tocsr(), S.T.tocsr()):
-        lens = np.diff(M.indptr)
-        mean = M.nnz / M.shape[0]
-        Gl = max(4, C)
-        while Gl < 64 and 2.0 * (Gl // C) < mean:
-            Gl *= 2
-        out.append(int((lens > max(64 * (Gl // C), int(16 * mean))).sum()))
-    return tuple(out)
+    """(rows of A, rows of A^T) the host hands to whole workgroups at LB columns per row: its rule as tests/sparse_lanes.py restates it
+    (csrc/fasta_hip.hip: sp_upload_side)."""
+    return tuple(int(la.long_rows.size) for la in SL.both_lanes(S, LB))
 
 
 def test_the_long_row_cases_reach_the_whole_workgroup_path_on_both_copies():
