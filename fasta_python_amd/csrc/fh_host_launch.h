@@ -20,10 +20,11 @@ static ProxP make_prox(fh_ctx* c, double tau) {
 // last-level cache, which the next launch finds there again if it was loaded with the default policy: 4096^2 K-adj 0.049 against 0.075 ms, 5120^2 0.063 / 0.088,
 // K-fwd 0.030 / 0.033; from 8192^2 (512 MiB) on the non-temporal form is the faster one again (profiles/r06_placement.txt, section 11).  The one-pass kernels
 // always load non-temporally (plain: +-3 % at these sizes, where their time is mostly fixed cost).
-static inline int nt_for(const fh_ctx* c) {
-  if (c->nt_loads >= 0) return c->nt_loads;
-  return (uint64_t)c->mp * c->ld * (c->f32 ? 4u : 8u) > ((uint64_t)256 << 20);
+static inline int nt_rule(int nt_loads, uint64_t mp, uint64_t ld, int f32) {
+  if (nt_loads >= 0) return nt_loads;
+  return mp * ld * (f32 ? 4u : 8u) > ((uint64_t)256 << 20);
 }
+static inline int nt_for(const fh_ctx* c) { return nt_rule(c->nt_loads, c->mp, c->ld, c->f32); }
 
 template <int R, int KIND>
 static void launch_fwd_rk(fh_ctx* c, const FwdP& p, unsigned grid) {
@@ -151,33 +152,107 @@ MC_FOR_EACH(MC_DECLARE)
 #undef MC_DECLARE
 #endif
 struct McEntry {
-  int lb, rows; void (*pro)(const McProP); void (*pack)(const double*, double*, uint32_t, uint32_t);
+  int lb, ch, rows; void (*pro)(const McProP); void (*pack)(const double*, double*, uint32_t, uint32_t);
   void (*fwd[2])(const McFwdP); void (*adj[2])(const McAdjP);
 };
-#define MC_ROW(LB, CH, R) {LB, R, k_mc_prologue<LB>, k_mc_pack<LB>, {k_mc_fwd<LB, CH, R, 0>, k_mc_fwd<LB, CH, R, 1>}, {k_mc_adj<LB, MC_ADJ_CPT, 0>, k_mc_adj<LB, MC_ADJ_CPT, 1>}},
+#define MC_ROW(LB, CH, R) {LB, CH, R, k_mc_prologue<LB>, k_mc_pack<LB>, {k_mc_fwd<LB, CH, R, 0>, k_mc_fwd<LB, CH, R, 1>}, {k_mc_adj<LB, MC_ADJ_CPT, 0>, k_mc_adj<LB, MC_ADJ_CPT, 1>}},
 static const McEntry kMcTable[] = { MC_FOR_EACH(MC_ROW) };
 #undef MC_ROW
-static const McEntry* mc_entry(const fh_ctx* c) {
-  for (const McEntry& e : kMcTable) if ((uint32_t)e.lb == c->LB) return &e;
+static const McEntry* mc_entry_lb(uint32_t LB) {
+  for (const McEntry& e : kMcTable) if ((uint32_t)e.lb == LB) return &e;
   return nullptr;
 }
+static const McEntry* mc_entry(const fh_ctx* c) { return mc_entry_lb(c->LB); }
 static inline bool mc_prox_ok(int kind) {
   return kind == FH_PROX_IDENTITY || kind == FH_PROX_SHRINK || kind == FH_PROX_NONNEG || kind == FH_PROX_BOX || kind == FH_PROX_GROUP;
+}
+
+// THE GEOMETRY of both multi-column launches, stated once: a pure function of the device shape (mp rows of ld doubles, nv rows of X), the
+// columns per row LB and the three tuning values (FH_TUNE_ADJ_SLAB_ROWS, FH_TUNE_FWD_GRID_CAP, FH_TUNE_NT_LOADS as the context keeps them:
+// 0 / 0 / -1 = auto).  The launchers below take every number from here; fh_multi_shape / fh_multi_shape_for export it so that a test can
+// assert the path it meant to reach (and the pure form needs no device).  `e` = nullptr when no kernel serves LB.
+struct McShape {
+  const McEntry* e;
+  int nt;                            // 1: the non-temporal instantiations
+  uint32_t ld2;                      // 16-byte pieces per device row of A = row pairs of X
+  uint32_t fwd_grid, nrg, ntrip;     // K-fwd: workgroups, row groups of R rows they stride over, trips of a lane group along a row
+  uint32_t npro;                     // workgroups of the n-side prologue (mode 0) / of the pack launch (mode 1)
+  uint32_t slab_rows, nslab, last_rows, sb, stages, ncc;   // K-adj: slabs, rows of the last one, rows per residual stage, stages of a full slab, column chunks
+};
+static McShape mc_shape_for(uint64_t mp, uint64_t ld, uint64_t nv, uint32_t LB, int adj_slab, long long fwd_cap, int nt_loads) {
+  McShape s;
+  memset(&s, 0, sizeof(s));
+  s.e = mc_entry_lb(LB);
+  if (!s.e) return s;
+  s.nt = nt_rule(nt_loads, mp, ld, 0) ? 1 : 0;
+  s.ld2 = (uint32_t)(ld / 2);
+  s.nrg = (uint32_t)(mp / (uint64_t)s.e->rows);
+  s.fwd_grid = (uint32_t)std::min<long long>(s.nrg, fwd_cap > 0 ? fwd_cap : 512);
+  const uint32_t GL = FH_WG / (uint32_t)(s.e->lb / s.e->ch);          // lanes of a column group (k_mc_fwd)
+  s.ntrip = (s.ld2 + GL - 1) / GL;
+  s.npro = (uint32_t)((nv + FH_WG - 1) / FH_WG);
+  s.ncc = (s.ld2 + FH_WG * MC_ADJ_CPT - 1) / (FH_WG * MC_ADJ_CPT);
+  // the vector kernel's slab rule (about 32 slabs, more when there are few column chunks): a slab's rows are staged 2048 / LB at a time
+  uint32_t slab = (uint32_t)adj_slab;
+  if (slab == 0) {
+    const uint64_t target_slabs = std::max<uint64_t>(32, (128 + s.ncc - 1) / s.ncc);
+    const uint64_t slab_min = s.ncc >= 8 ? 128 : 32;
+    const uint64_t r = round_up((mp + target_slabs - 1) / target_slabs, 8);
+    slab = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(r, slab_min), ADJ_MAX_SLAB);
+  }
+  s.slab_rows = slab;
+  s.nslab = (uint32_t)((mp + slab - 1) / slab);
+  s.last_rows = (uint32_t)(mp - (uint64_t)(s.nslab - 1) * slab);
+  s.sb = MC_LDS_DOUBLES / LB;
+  s.stages = (slab + s.sb - 1) / s.sb;
+  return s;
+}
+static McShape mc_shape(const fh_ctx* c) { return mc_shape_for(c->mp, c->ld, c->nv, c->LB, c->adj_slab, c->fwd_cap, c->nt_loads); }
+
+static void mc_shape_report(const McShape& s, uint32_t* out) {
+  const uint32_t v[FH_MULTI_SHAPE_LEN] = {(uint32_t)s.e->lb, (uint32_t)s.e->ch, (uint32_t)s.e->rows, (uint32_t)s.nt, s.fwd_grid, s.nrg, s.ntrip, s.npro,
+                                          s.slab_rows, s.nslab, s.last_rows, s.sb, s.stages, s.ncc};
+  memcpy(out, v, sizeof(v));
+}
+// read-only: the geometry the next fh_fwd / fh_adj of this context launches with
+extern "C" int fh_multi_shape(fh_ctx* c, uint32_t* out) {
+  if (!c || !out) return fail(FH_E_ARG, "fh_multi_shape: null argument");
+  if (c->op != OP_DENSE || !c->LB) return fail(FH_E_STATE, "fh_multi_shape: the context is not in multi-column dense form (fh_set_matrix + fh_set_rhs)");
+  const McShape s = mc_shape(c);
+  if (!s.e) return fail(FH_E_STATE, "multi-column form: no kernel for %u columns per row", c->LB);
+  mc_shape_report(s, out);
+  return 0;
+}
+// ... and the same rule for an (m, n) matrix with L columns that no context holds: a pure host function, no device needed
+extern "C" int fh_multi_shape_for(uint64_t m, uint64_t n, uint32_t L, int slab_rows, long long grid_cap, int nt_loads, uint32_t* out) {
+  if (!out) return fail(FH_E_ARG, "fh_multi_shape_for: null argument");
+  if (m == 0 || n == 0 || m >= (1ull << 31) || n >= (1ull << 31)) return fail(FH_E_ARG, "fh_multi_shape_for: matrix dimensions must be in [1, 2^31)");
+  if (L < 1 || L > 16) return fail(FH_E_ARG, "fh_multi_shape_for: 1 to 16 columns (got %u)", L);
+  if (slab_rows < 0 || slab_rows > ADJ_MAX_SLAB || slab_rows % 8) return fail(FH_E_ARG, "ADJ_SLAB_ROWS must be a multiple of 8 in [0,%d]", ADJ_MAX_SLAB);
+  if (grid_cap < 0) return fail(FH_E_ARG, "FWD_GRID_CAP must be >= 0");
+  if (nt_loads < -1 || nt_loads > 1) return fail(FH_E_ARG, "fh_multi_shape_for: nt_loads is -1 (auto), 0 or 1");
+  const uint32_t LB = L <= 2 ? 2u : (L <= 4 ? 4u : (L <= 8 ? 8u : 16u));
+  const uint64_t ld = round_up(n, 16);
+  const McShape s = mc_shape_for(round_up(m, 16), ld, ld, LB, slab_rows, grid_cap, nt_loads);
+  if (!s.e) return fail(FH_E_STATE, "multi-column form: no kernel for %u columns per row", LB);
+  mc_shape_report(s, out);
+  return 0;
 }
 
 // Z := A * (mode 0: prox(X0 - tau G0), by the prologue launch ; mode 1: X0) for LB columns from one read of A
 static int launch_fwd_multi(fh_ctx* c, int mode, double tau, const double* x0, const double* g0, const double* xacc0,
                             double* xhat, double* xp, double* z, int sub_b) {
-  const McEntry* e = mc_entry(c);
+  const McShape sh = mc_shape(c);
+  const McEntry* e = sh.e;
   if (!e) return fail(FH_E_STATE, "multi-column form: no kernel for %u columns per row", c->LB);
   if (c->loss_kind != LOSS_LSQ) return fail(FH_E_STATE, "the multi-column form serves the least-squares loss only");
   if (mode == 0 && !mc_prox_ok(c->prox_kind)) return fail(FH_E_STATE, "prox kind %d has no multi-column form", c->prox_kind);
   McFwdP p;
-  p.A = c->A; p.ld2 = (uint32_t)(c->ld / 2); p.m = (uint32_t)c->m; p.L = c->L;
-  p.nrg = (uint32_t)(c->mp / (uint64_t)e->rows);
-  const uint32_t npro = mode == 0 ? (uint32_t)((c->nv + FH_WG - 1) / FH_WG) : 0u;
+  p.A = c->A; p.ld2 = sh.ld2; p.m = (uint32_t)c->m; p.L = c->L;
+  p.nrg = sh.nrg;
+  const uint32_t npro = mode == 0 ? sh.npro : 0u;
   p.nred_n = npro;
-  const unsigned grid = (unsigned)std::min<long long>(p.nrg, c->fwd_cap > 0 ? c->fwd_cap : 512);
+  const unsigned grid = sh.fwd_grid;
   FH_TRY(ensure_ws(c, ((size_t)npro * 8 + grid) * sizeof(double)));
   p.red_n = c->ws; p.red_m = c->ws + (size_t)npro * 8;
   p.x = c->xs;                       // the operand in K-fwd's streaming layout: written by the prologue, or packed from a plain operand below
@@ -194,10 +269,10 @@ static int launch_fwd_multi(fh_ctx* c, int mode, double tau, const double* x0, c
     q.red_n = c->ws;
     e->pro<<<dim3(npro), dim3(FH_WG), 0, c->stream>>>(q);
   } else {
-    e->pack<<<dim3((unsigned)((c->nv + FH_WG - 1) / FH_WG)), dim3(FH_WG), 0, c->stream>>>(x0, c->xs, (uint32_t)c->nv, p.ld2);
+    e->pack<<<dim3(sh.npro), dim3(FH_WG), 0, c->stream>>>(x0, c->xs, (uint32_t)c->nv, p.ld2);
   }
   p.seq = seq_offer(c);
-  e->fwd[nt_for(c) ? 1 : 0]<<<dim3(grid), dim3(FH_WG), 0, c->stream>>>(p);
+  e->fwd[sh.nt]<<<dim3(grid), dim3(FH_WG), 0, c->stream>>>(p);
   t_end(c, FH_K_FWD);
   HIP_TRY(hipGetLastError());
   return 0;
@@ -277,23 +352,16 @@ static int bb_epilogue_only(fh_ctx* c, const AdjIO& io, const double* fsq_src, c
 }
 
 static int launch_adj_multi(fh_ctx* c, const AdjIO& io) {
-  const McEntry* e = mc_entry(c);
+  const McShape sh = mc_shape(c);
+  const McEntry* e = sh.e;
   if (!e) return fail(FH_E_STATE, "multi-column form: no kernel for %u columns per row", c->LB);
   if (io.sub_b && c->loss_kind != LOSS_LSQ) return fail(FH_E_STATE, "the multi-column form serves the least-squares loss only");
   if (io.mode != 0 && io.mode != 1) return fail(FH_E_STATE, "the multi-column form has no row-sharded adjoint");
   McAdjP p;
-  p.A = c->A; p.ld2 = (uint32_t)(c->ld / 2); p.n = (uint32_t)c->n; p.L = c->L; p.mp = (uint32_t)c->mp; p.m = (uint32_t)c->m;
-  p.ncc = (p.ld2 + FH_WG * MC_ADJ_CPT - 1) / (FH_WG * MC_ADJ_CPT);
-  // the vector kernel's slab rule (about 32 slabs, more when there are few column chunks): a slab's rows are staged 2048 / LB at a time
-  uint32_t slab = (uint32_t)c->adj_slab;
-  if (slab == 0) {
-    const uint64_t target_slabs = std::max<uint64_t>(32, (128 + p.ncc - 1) / p.ncc);
-    const uint64_t slab_min = p.ncc >= 8 ? 128 : 32;
-    const uint64_t s = round_up((c->mp + target_slabs - 1) / target_slabs, 8);
-    slab = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(s, slab_min), ADJ_MAX_SLAB);
-  }
-  p.slab_rows = slab;
-  p.nslab = (uint32_t)((c->mp + slab - 1) / slab);
+  p.A = c->A; p.ld2 = sh.ld2; p.n = (uint32_t)c->n; p.L = c->L; p.mp = (uint32_t)c->mp; p.m = (uint32_t)c->m;
+  p.ncc = sh.ncc;
+  p.slab_rows = sh.slab_rows;
+  p.nslab = sh.nslab;
   if (p.ncc + CNT_ADJ_CC > (uint32_t)CNT_DIAG) return fail(FH_E_ARG, "too many column chunks (%u)", p.ncc);
   p.z = io.z; p.zacc0 = io.zacc0; p.b = c->b; p.sub_b = io.sub_b; p.accel = io.accel; p.coef = io.coef;
   p.mode = io.mode; p.tau = io.tau; p.group = c->prox_kind == FH_PROX_GROUP ? 1 : 0;
@@ -307,7 +375,7 @@ static int launch_adj_multi(fh_ctx* c, const AdjIO& io) {
   const unsigned grid = p.ncc * p.nslab;
   t_begin(c, FH_K_ADJ);
   p.seq = io.mode == 0 ? seq_offer(c) : 0u;
-  e->adj[nt_for(c) ? 1 : 0]<<<dim3(grid), dim3(FH_WG), 0, c->stream>>>(p);
+  e->adj[sh.nt]<<<dim3(grid), dim3(FH_WG), 0, c->stream>>>(p);
   t_end(c, FH_K_ADJ);
   HIP_TRY(hipGetLastError());
   return 0;

@@ -4,6 +4,7 @@ This is the only module that talks to the GPU, and nothing in it falls back: if 
 no MI355X is visible, `load_library()` / `HipContext()` raise.
 """
 
+import collections
 import ctypes as C
 import os
 
@@ -87,6 +88,8 @@ SIGNATURES = {
     "fh_shape": (_i32, [_ctx, C.POINTER(_u64), C.POINTER(_u64)]),
     "fh_set_rhs": (_i32, [_ctx, C.c_uint32]),
     "fh_rhs": (_i32, [_ctx, C.POINTER(C.c_uint32)]),
+    "fh_multi_shape": (_i32, [_ctx, C.POINTER(C.c_uint32)]),
+    "fh_multi_shape_for": (_i32, [_u64, _u64, C.c_uint32, _i32, C.c_longlong, _i32, C.POINTER(C.c_uint32)]),
     "fh_set_loss_lsq": (_i32, [_ctx, _pd, _u64]),
     "fh_set_loss_logistic": (_i32, [_ctx, _pd, _u64]),
     "fh_set_prox": (_i32, [_ctx, _i32, _dbl, _dbl, _dbl]),
@@ -205,6 +208,19 @@ def fused_shape(n, storage="f64", variant=2, ncu=256):
     inst = _i32(0)
     _check(lib, lib.fh_fused_shape(int(n), STORAGE[storage], int(variant), int(ncu), shape, C.byref(inst)))
     return tuple(shape), bool(inst.value)
+
+
+MULTI_SHAPE_LEN = 14
+MultiShape = collections.namedtuple("MultiShape", "LB CH R NT fwd_grid nrg ntrip npro slab_rows nslab last_slab_rows SB stages ncc")
+
+
+def multi_shape(m, n, L, slab_rows=0, grid_cap=0, nt_loads=-1):
+    """MultiShape of the multi-column dense launches for an (m, n) matrix and L columns under the tuning values FH_TUNE_ADJ_SLAB_ROWS,
+    FH_TUNE_FWD_GRID_CAP (0 = auto) and FH_TUNE_NT_LOADS (-1 = auto): fh_multi_shape_for, the rule the launchers call.  Host-only."""
+    lib = load_library()
+    out = (C.c_uint32 * MULTI_SHAPE_LEN)()
+    _check(lib, lib.fh_multi_shape_for(int(m), int(n), int(L), int(slab_rows), int(grid_cap), int(nt_loads), out))
+    return MultiShape(*(int(v) for v in out))
 
 
 def comm_library():
@@ -426,6 +442,13 @@ class HipContext:
         L = C.c_uint32(0)
         self._call("fh_rhs", C.byref(L))
         return int(L.value)
+
+    def multi_shape(self):
+        """MultiShape the next fwd / adj of this context launches with (fh_multi_shape): which instantiation, how many passes, trips, slabs,
+        stages and column chunks.  E_STATE unless the context is in multi-column dense form."""
+        out = (C.c_uint32 * MULTI_SHAPE_LEN)()
+        self._call("fh_multi_shape", out)
+        return MultiShape(*(int(v) for v in out))
 
     def set_loss_lsq(self, b):
         b, p = _as_f64(np.ravel(b))

@@ -225,6 +225,17 @@ int fh_shape(fh_ctx* ctx, uint64_t* m, uint64_t* n);
  * fh_fused_supported, fh_fused_agree and fh_run_supported report 0 and fh_step* / fh_run return FH_E_STATE.                               */
 int fh_set_rhs(fh_ctx* ctx, uint32_t L);
 int fh_rhs(fh_ctx* ctx, uint32_t* L);      /* L of the multi-column form, 0 in the vector form */
+/* read-only: the geometry the multi-column dense launches take (csrc/fh_host_launch.h: mc_shape_for, the ONE rule both launchers call), so
+ * that a test can assert the path it meant to reach.  out[FH_MULTI_SHAPE_LEN] = { LB (device columns per row), CH (columns a lane of K-fwd
+ * carries), R (rows of A per K-fwd pass), NT (1: the non-temporal instantiations), K-fwd grid, nrg (row groups the grid strides over), ntrip
+ * (trips of a lane group along a row), prologue workgroups, slab_rows, nslab, rows of the last slab, SB (rows of the residual K-adj stages at
+ * a time), stages of a full slab, ncc (column chunks of K-adj) }.  fh_multi_shape reads the context's own device shape, column count and
+ * tuning values (FH_TUNE_ADJ_SLAB_ROWS, FH_TUNE_FWD_GRID_CAP, FH_TUNE_NT_LOADS) and is FH_E_STATE unless the context is in multi-column dense
+ * form; fh_multi_shape_for is the same rule as a pure host function (no device needed) of an (m, n) matrix, L columns and the three tuning
+ * values as fh_set_tuning takes them (0 = auto; nt_loads: -1 = auto, 0, 1).                                                              */
+#define FH_MULTI_SHAPE_LEN 14
+int fh_multi_shape(fh_ctx* ctx, uint32_t* out);
+int fh_multi_shape_for(uint64_t m, uint64_t n, uint32_t L, int slab_rows, long long grid_cap, int nt_loads, uint32_t* out);
 
 /* ---- smooth term f(z) = .5||z - b||^2, grad f(z) = z - b (examples/sparse_least_squares.py:41-42) */
 int fh_set_loss_lsq(fh_ctx* ctx, const double* b, uint64_t len);

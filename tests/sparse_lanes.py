@@ -163,7 +163,7 @@ def group_problem(S, L, seed=0):
     relative / absolute tolerances of tests/test_gpu_sparse_mmv.py.  Those were set for unit-scale data, so A = S / 8 (a power of two: the
     same pattern, the same lanes; the longest rows, 127 entries, then have the squared norm of that test's rows), X0 and the noise of B are
     of its sizes, and the threshold tau * mu sits at 0.8 of the median row norm of xhat: some rows vanish, the others shrink."""
-    A = (S * 0.125).tocsr()
+    A = (S * 0.125).tocsr() if sp.issparse(S) else np.asarray(S) * 0.125
     m, n = A.shape
     rng = np.random.RandomState(123 + 7919 * seed + L)
     X0 = rng.randn(n, L) * 0.1
@@ -181,6 +181,11 @@ def prox_tag(kind):
 
 
 # ---- the model -----------------------------------------------------------------------------------------------------------------------------
+def dense_of(S):
+    """The operator as a dense ndarray: a scipy matrix is expanded, a dense array (tests/mc_paths.py) is taken as it is."""
+    return np.asarray(S.todense()) if sp.issparse(S) else np.asarray(S)
+
+
 def _prox(tag, X, tau):
     dt = X.dtype.type
     if tag.kind == hip.PROX_SHRINK:
@@ -210,10 +215,11 @@ def row_norm_sum(X):
 
 
 def exact_step(S, X0, B, tag, tau=TAU, coef=COEF, dtype=np.float64):
-    """NumPy model of fh_init -> fh_fwd -> fh_adj (plain) -> fh_adj (accelerated) in `dtype`, least squares.  Returns a dict: the matrices
+    """NumPy model of fh_init -> fh_fwd -> fh_adj (plain) -> fh_adj (accelerated) in `dtype`, least squares; S a scipy matrix or a dense
+    array.  Returns a dict: the matrices
     G0, XHAT, XPROX, Z, G1 (plain adjoint), G1A and X1 (accelerated adjoint), and the scalar blocks `init`, `fwd`, `adj`, `adja`, each a
     dict from FH_S_* slot to value -- the slots tests/test_gpu_sparse*.py:test_single_step_scalars_match_numpy check."""
-    A = np.asarray(S.todense()).astype(dtype)
+    A = dense_of(S).astype(dtype)
     t = np.dtype(dtype).type
     X0, B = np.asarray(X0).astype(dtype), np.asarray(B).astype(dtype)
     tau, coef = t(tau), t(coef)

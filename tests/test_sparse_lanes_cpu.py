@@ -98,7 +98,7 @@ def imat(A, X):
 def integer_step(S, X0, B, tag):
     """exact_step restated in integers: matrices in units of 1/16, scalar sums of squares in units of 1/256, sums of magnitudes in 1/16.
     tau = 1/2 and coef = 1/4 are divisions by 2 and 4 that must come out even.  Returns (values, worst sum of magnitudes in units)."""
-    A = ints(S.toarray(), 1)
+    A = ints(SL.dense_of(S), 1)
     x0, b = ints(X0, 16), ints(B, 16)
     worst = [0]
 
@@ -197,7 +197,7 @@ def test_every_apply_is_exact_in_float64():
     for S, L in sets:
         V, W = SL.apply_operands(S, L)
         assert np.abs(V).max() == 4 and np.abs(W).max() == 4
-        A = ints(S.toarray(), 1)
+        A = ints(SL.dense_of(S), 1)
         for M, I, X in ((S, A, V), (S.T.tocsr(), A.T, W)):
             want = imat(I, ints(X, 1))
             assert np.array_equal(M @ X, want.astype(np.float64))
