@@ -20,6 +20,7 @@
 #include "fh_sparse.h"
 #include "fh_spmulti.h"
 #include "fh_tv.h"
+#include "fh_tv3d.h"
 #include "fh_prox.h"
 #include "fh_fused.h"
 #include "fh_setup.h"
@@ -121,6 +122,7 @@ SPMC_FOR_EACH_LB(SPMC_INSTANTIATE_LB)
 #define SPMC_INSTANTIATE(G, LB) SPMC_KERNELS(template, G, LB)
 SPMC_FOR_EACH(SPMC_INSTANTIATE)
 #undef SPMC_INSTANTIATE
+TV3_KERNELS(template)
 #endif
 
 #include "fh_host_ctx.h"
@@ -341,6 +343,9 @@ static int set_tuning_one(fh_ctx* c, int key, long long value) {
     case FH_TUNE_TV_NT:
       if (value < 0 || value > 3) return fail(FH_E_ARG, "TV_NT must be 0 (default), 1 (non-temporal loads and stores), 2 (non-temporal stores) or 3 (plain)");
       c->tv_nt = (int)value; return 0;
+    case FH_TUNE_TV3_PLANES:
+      if (value < 0 || value > (1ll << 30)) return fail(FH_E_ARG, "TV3_PLANES must be in [0, 2^30] planes per workgroup (0 = auto)");
+      c->tv3_planes = (int)value; return 0;
     case FH_TUNE_TV_PIPE:
       if (value < 0 || value > 3) return fail(FH_E_ARG, "TV_PIPE must be 0 (auto), 1 (load a trip, consume it) or 3 (three rotating trip buffers; 2 is taken as 3)");
       c->tv_pipe = (int)value; return 0;
@@ -645,6 +650,7 @@ extern "C" int fh_nnz(fh_ctx* c, uint64_t* nnz) {
 extern "C" int fh_get_matrix_rows(fh_ctx* c, uint64_t row0, uint64_t nrows, double* out) {
   if (!c || !out) return fail(FH_E_ARG, "null argument");
   if (c->op == OP_SPARSE) return fail(FH_E_STATE, "fh_get_matrix_rows: the sparse operator keeps no dense rows");
+  if (c->op == OP_STENCIL3D) return fail(FH_E_STATE, "fh_get_matrix_rows: the 3-D stencil operator keeps no dense rows");
   if (c->op != OP_DENSE) return fail(FH_E_STATE, "no dense matrix set");
   if (row0 + nrows > c->m) return fail(FH_E_ARG, "rows [%llu,%llu) out of range (m=%llu)", (unsigned long long)row0,
                                        (unsigned long long)(row0 + nrows), (unsigned long long)c->m);
@@ -695,6 +701,29 @@ extern "C" int fh_set_stencil(fh_ctx* c, uint64_t H, uint64_t W) {
   return finish(c);
 }
 
+// the 3-D stencil (csrc/fh_tv3d.h): vectors in the vector form's padded layout, every buffer stored like any other operator's
+extern "C" int fh_set_stencil3d(fh_ctx* c, uint64_t D, uint64_t H, uint64_t W) {
+  if (!c) return fail(FH_E_ARG, "null context");
+  if (!c->shards.empty() || c->owner) return fail(FH_E_STATE, "fh_set_stencil3d: a multi-device context has no 3-D stencil operator (row sharding is implemented for the dense operator only)");
+  if (c->comm) return fail(FH_E_STATE, "fh_set_stencil3d: a context with a communicator (row-sharded run) has no 3-D stencil operator");
+  if (c->pending_step) return fail(FH_E_STATE, "a step issued by fh_step_begin is still in flight on this context: call fh_step_end first");
+  Tv3Shape sh;
+  FH_TRY(tv3_shape_for(D, H, W, 0, 1, &sh));             // (dimensions >= 1, 3 * D * H * W < 2^31: FH_E_ARG with the sentence)
+  FH_TRY(use_device(c));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  free_operator(c);
+  if (!tv3_prox_ok(c->prox_kind)) { c->prox_kind = FH_PROX_IDENTITY; c->mu = 0.0; }
+  c->loss_kind = LOSS_LSQ; c->lazy = false; c->last_accel = false; c->commits = 0;
+  c->D = D; c->H = H; c->W = W;
+  c->m = D * H * W; c->n = 3 * c->m;
+  c->mp = c->m; c->ld = c->n;
+  c->nv = round_up(c->n, 16); c->mv = round_up(c->m, 16);
+  const int rc = alloc_vectors(c);
+  if (rc != 0) { free_operator(c); return rc; }
+  c->op = OP_STENCIL3D;
+  return finish(c);
+}
+
 extern "C" int fh_shape(fh_ctx* c, uint64_t* m, uint64_t* n) {
   if (!c || !m || !n) return fail(FH_E_ARG, "null argument");
   if (c->op == OP_NONE) return fail(FH_E_STATE, "no operator set");
@@ -711,6 +740,7 @@ extern "C" int fh_set_rhs(fh_ctx* c, uint32_t L) {
   if (c->pending_step) return fail(FH_E_STATE, "a step issued by fh_step_begin is still in flight on this context: call fh_step_end first");
   if (c->op == OP_NONE) return fail(FH_E_STATE, "fh_set_rhs: set the dense operator first (fh_set_matrix / fh_generate_matrix)");
   if (c->op == OP_SPARSE) return fail(FH_E_STATE, "fh_set_rhs: the sparse operator has no multi-column form through fh_set_rhs: its column count is fixed when it is set (fh_set_matrix_csr_rhs)");
+  if (c->op == OP_STENCIL3D) return fail(FH_E_STATE, "fh_set_rhs: the 3-D stencil operator has no multi-column form");
   if (c->op != OP_DENSE) return fail(FH_E_STATE, "fh_set_rhs: the stencil operator has no multi-column form");
   if (c->f32) return fail(FH_E_STATE, "fh_set_rhs: float32 storage of A has no multi-column form");
   if (L && c->has_b && c->loss_kind != LOSS_LSQ) return fail(FH_E_STATE, "fh_set_rhs: the logistic loss has no multi-column form");
@@ -738,6 +768,7 @@ static int set_loss(fh_ctx* c, int kind, const double* b, uint64_t len) {
   if (c->op == OP_NONE) return fail(FH_E_STATE, "set the operator before the loss");
   if (len != c->m * l_of(c)) return fail(FH_E_ARG, "b has %llu entries, operator has %llu rows (x %llu columns)", (unsigned long long)len, (unsigned long long)c->m, (unsigned long long)l_of(c));
   if (kind != LOSS_LSQ && c->LB) return fail(FH_E_STATE, "the logistic loss has no multi-column form (fh_set_rhs / fh_set_matrix_csr_rhs)");
+  if (kind != LOSS_LSQ && c->op == OP_STENCIL3D) return fail(FH_E_STATE, "the 3-D stencil operator serves the least-squares loss only (the logistic loss is implemented for the dense and sparse operators)");
   if (kind != LOSS_LSQ && c->op != OP_DENSE && c->op != OP_SPARSE) return fail(FH_E_STATE, "the logistic loss is implemented for the dense operator");
   if (!c->shards.empty()) {          // shell: b is sharded like the rows
     for (int k = 0; k < nshards(c); ++k) FH_TRY(set_loss(c->shards[k], kind, b + c->shard_row0[k], shard_rows(c, k)));
@@ -765,6 +796,7 @@ extern "C" int fh_set_prox(fh_ctx* c, int kind, double mu, double lo, double hi)
   if (kind == FH_PROX_GROUP && !c->LB) return fail(FH_E_ARG, "FH_PROX_GROUP (row-wise l2 shrink) needs the multi-column form: call fh_set_rhs (dense operator) or fh_set_matrix_csr_rhs (sparse operator) first");
   if (c->LB && !mc_prox_ok(kind)) return fail(FH_E_ARG, "prox kind %d (LINF / L1BALL / TVBALL) has no multi-column form", kind);
   if (c->op == OP_SPARSE && !c->LB && !sp_prox_ok(kind)) return fail(FH_E_ARG, "prox kind %d (LINF / L1BALL / TVBALL / GROUP) is not implemented for the sparse operator", kind);
+  if (c->op == OP_STENCIL3D && !tv3_prox_ok(kind)) return fail(FH_E_ARG, "prox kind %d (LINF / L1BALL / GROUP) is not implemented for the 3-D stencil operator", kind);
   if (kind == FH_PROX_BOX && !(lo <= hi)) return fail(FH_E_ARG, "box prox needs lo <= hi");
   for (fh_ctx* s : c->shards) { s->prox_kind = kind; s->mu = mu; s->lo = lo; s->hi = hi; }      // the prox is replicated work
   c->prox_kind = kind; c->mu = mu; c->lo = lo; c->hi = hi;
@@ -1270,6 +1302,7 @@ static int dense_step(fh_ctx* c, double tau, int accel, double coef, int restart
 static int step_body(fh_ctx* c, double tau, double* scalars, bool wait) {
   FH_TRY(check_ready(c, true));
   if (c->op == OP_SPARSE) return fail(FH_E_STATE, "fh_step: the sparse operator has no one-pass kernel: use fh_fwd / fh_adj / fh_fwd_adj / fh_iterate");
+  if (c->op == OP_STENCIL3D) return fail(FH_E_STATE, "fh_step: the 3-D stencil operator has no one-pass kernel: use fh_fwd / fh_adj / fh_fwd_adj / fh_iterate");
   if (c->LB) return fail(FH_E_STATE, "fh_step: the multi-column form (fh_set_rhs) has no one-pass kernel: use fh_fwd / fh_adj / fh_iterate");
   for (int k = 0; k < nshards(c); ++k) FH_TRY(not_lazy(shard_of(c, k), "fh_step"));
   if (c->op == OP_STENCIL) {
@@ -1316,6 +1349,7 @@ extern "C" int fh_step_end(fh_ctx* c, double* scalars) {
 extern "C" int fh_step_accel(fh_ctx* c, double tau, double coef, int restart, double* scalars) {
   FH_TRY(check_ready(c, true));
   if (c->op == OP_SPARSE) return fail(FH_E_STATE, "fh_step_accel: the sparse operator has no one-pass kernel: use fh_fwd / fh_adj / fh_iterate");
+  if (c->op == OP_STENCIL3D) return fail(FH_E_STATE, "fh_step_accel: the 3-D stencil operator has no one-pass kernel: use fh_fwd / fh_adj / fh_iterate");
   if (c->LB) return fail(FH_E_STATE, "fh_step_accel: the multi-column form (fh_set_rhs) has no one-pass kernel: use fh_fwd / fh_adj / fh_iterate");
   if (c->op == OP_STENCIL) {
     if (row_sharded(c)) return fail(FH_E_STATE, "row sharding is implemented for the dense operator only");
@@ -1430,6 +1464,7 @@ extern "C" int fh_run(fh_ctx* c, int max_steps, const fh_run_opts* o, fh_run_sta
   if (o->window < 1 || o->window > FH_RUN_WINDOW_MAX) return fail(FH_E_ARG, "fh_run: window must be in [1, %d]", FH_RUN_WINDOW_MAX);
   if (o->stop_rule < 0 || o->stop_rule > 3) return fail(FH_E_ARG, "fh_run: stop_rule must be 0..3 (the four rules of fasta/stopping.py)");
   if (c->op == OP_SPARSE) return fail(FH_E_STATE, "fh_run: the sparse operator has no device-side loop: use fh_iterate");
+  if (c->op == OP_STENCIL3D) return fail(FH_E_STATE, "fh_run: the 3-D stencil operator has no device-side loop: use fh_iterate");
   if (c->LB) return fail(FH_E_STATE, "fh_run: the multi-column form (fh_set_rhs) has no device-side loop: use fh_iterate");
   const RunEntry* e = run_entry(c);
   if (!e && chain_ok(c) && co_resident(c)) return run_chain(c, max_steps, o, state, history, steps_done);
@@ -1660,6 +1695,7 @@ extern "C" int fh_comm_init(fh_ctx* c, int nranks, int rank, const void* id128) 
   if (!c || !id128) return fail(FH_E_ARG, "null argument");
   if (nranks < 1 || rank < 0 || rank >= nranks) return fail(FH_E_ARG, "bad rank %d of %d", rank, nranks);
   if (c->op == OP_SPARSE) return fail(FH_E_STATE, "fh_comm_init: a context with a sparse operator cannot be row-sharded");
+  if (c->op == OP_STENCIL3D) return fail(FH_E_STATE, "fh_comm_init: a context with a 3-D stencil operator cannot be row-sharded");
   if (c->LB) return fail(FH_E_STATE, "fh_comm_init: a context in multi-column form (fh_set_rhs) cannot be row-sharded");
   if (!c->shards.empty() || c->owner)
     return fail(FH_E_STATE, "fh_comm_init: a multi-device context (fh_create_ex, ndev > 1) already shards the rows in-process");
@@ -1850,6 +1886,7 @@ extern "C" int fh_stream_read_ms(fh_ctx* c, int reps, double* ms_per_pass, uint6
   FH_TRY(check_ready(c, false));
   if (!c->shards.empty()) return fh_stream_read_ms(c->shards[0], reps, ms_per_pass, bytes_per_pass);     // shard 0's block on its device
   if (c->op == OP_SPARSE) return fail(FH_E_STATE, "fh_stream_read_ms: the stream-read ceiling is measured on a dense matrix, not on the sparse operator");
+  if (c->op == OP_STENCIL3D) return fail(FH_E_STATE, "fh_stream_read_ms: the stream-read ceiling is measured on a dense matrix, not on the 3-D stencil operator");
   if (c->op != OP_DENSE) return fail(FH_E_STATE, "stream-read ceiling needs a dense matrix");
   if (reps < 1) reps = 1;
   // k_stream_probe<16,1> as described in include/fasta_hip.h: persistent workgroups, 1 per CU by default, three rotating buffers of 16 nt loads per lane

@@ -97,7 +97,7 @@ static int rccl_load() {
 // ------------------------------------------------------------------------------------------------
 // context
 // ------------------------------------------------------------------------------------------------
-enum { OP_NONE = 0, OP_DENSE = 1, OP_STENCIL = 2, OP_SPARSE = 3 };
+enum { OP_NONE = 0, OP_DENSE = 1, OP_STENCIL = 2, OP_SPARSE = 3, OP_STENCIL3D = 4 };
 
 struct fh_ctx {
   int device = 0;
@@ -110,6 +110,7 @@ struct fh_ctx {
   uint64_t nv = 0, mv = 0;   // allocated n-side / m-side vector lengths (doubles; rows of LB doubles in multi-column form)
   uint32_t L = 0, LB = 0;    // multi-column form (fh_set_rhs, csrc/fh_multi.h; fh_set_matrix_csr_rhs, csrc/fh_spmulti.h): L columns per unknown, kept as LB in {2, 4, 8, 16} doubles per row; 0 = the vector form
   uint64_t H = 0, W = 0;
+  uint64_t D = 0;            // 3-D stencil (fh_set_stencil3d, csrc/fh_tv3d.h): the volume is (D, H, W), m = D*H*W, n = 3*m
   // sparse operator (fh_set_matrix_csr, csrc/fh_sparse.h): sp[0] = A by rows, sp[1] = A^T by rows, each with its non-zero-balanced row ranges,
   // its list of long rows and the lanes-per-row G chosen from its mean row length; sp_r = the adjoint's residual (m-side).  In multi-column form
   // (fh_set_matrix_csr_rhs, csrc/fh_spmulti.h) G, the long-row threshold and the row ranges are those of LB / 2 column lanes per entry: fixed when the operator is set
@@ -182,6 +183,7 @@ struct fh_ctx {
   int tv_xcd = 0;            // FH_TUNE_TV_XCD: workgroup ids of the one-pass sweep dealt out XCD by XCD (0 / 1 = on, 2 = off)
   int tv_slots = 0;          // FH_TUNE_TV_SLOTS: persistent one-pass sweep, workgroups per CU (0 = one workgroup per chunk)
   int tv_ring = 0;           // FH_TUNE_TV_RING: LDS-DMA trip ring of the one-pass sweep (0 = auto, 1 = off, 2 / 3 = slots per wave)
+  int tv3_planes = 0;        // FH_TUNE_TV3_PLANES: planes a workgroup of the 3-D stencil kernels marches over (0 = auto: tv3_shape_for)
   int tv_pipe = 0;           // FH_TUNE_TV_PIPE: rotating trip buffers of the one-pass sweep (0 = auto, 1 = burst, 2, 3)
   bool fused_variant_auto = true;   // cleared by FH_TUNE_FUSED_VARIANT: the caller's word is taken as it is (fused_variant_for)
   int fused_variant = 2 | 32;   // 2: team members 32 blocks apart (one XCD), best in profiles/r01b_tune_fused.txt; 32 (round 6): rows dealt cyclically to the teams -- the

@@ -1,4 +1,4 @@
-// fh_host_launch.h -- kernel launchers of libfasta_hip.so: shapes, grids and workspace of every kernel in fh_dense.h / fh_tv.h /
+// fh_host_launch.h -- kernel launchers of libfasta_hip.so: shapes, grids and workspace of every kernel in fh_dense.h / fh_tv.h / fh_tv3d.h /
 // fh_prox.h / fh_fused.h, the one-pass kernel's shape rule and dispatch table, the co-residency probe, and the three-stage form
 // (local launch / sum over row blocks / n-side epilogue) the C ABI in fasta_hip.hip builds its entry points from.
 #pragma once
@@ -505,6 +505,102 @@ static int launch_adj_spmulti(fh_ctx* c, const AdjIO& io) {
   return 0;
 }
 
+// ---- 3-D stencil operator (fh_set_stencil3d; kernels in csrc/fh_tv3d.h, instantiated by fh_tv3d_part.hip) -------------------------------
+#ifndef FH_SINGLE_TU
+TV3_KERNELS(extern template)
+#endif
+// THE launch geometry of both kernels, a pure function of the volume, FH_TUNE_TV3_PLANES (0 = auto) and the device's CU count: tiles of
+// TV3_TH x TV3_TW (h, w) positions, `planes` planes per workgroup along d, grid = chunks x tiles_h x tiles_w.  Auto: whole columns of planes
+// unless that leaves fewer than 8 workgroups per CU; then as many chunks as reach that, but at least 8 planes per chunk (a chunk computes
+// planes + 1: the d+1 halo of K-fwd, the d-1 halo of K-adj).
+struct Tv3Shape { uint32_t planes, tiles_h, tiles_w, chunks, grid; };
+static int tv3_shape_for(uint64_t D, uint64_t H, uint64_t W, int planes_tune, int ncu, Tv3Shape* sh) {
+  if (D < 1 || H < 1 || W < 1) return fail(FH_E_ARG, "the 3-D stencil needs D >= 1, H >= 1 and W >= 1 (got %llu x %llu x %llu)", (unsigned long long)D, (unsigned long long)H, (unsigned long long)W);
+  if (D >= (1ull << 31) || H >= (1ull << 31) || W >= (1ull << 31) || D * H >= (1ull << 31) || D * H * W * 3 >= (1ull << 31))
+    return fail(FH_E_ARG, "the 3-D stencil needs 3 * D * H * W < 2^31: the n-side sums and vector lengths count in 32 bits (got %llu x %llu x %llu)", (unsigned long long)D, (unsigned long long)H, (unsigned long long)W);
+  if (planes_tune < 0) return fail(FH_E_ARG, "TV3_PLANES must be >= 0 (0 = auto)");
+  const uint64_t tiles_h = (H + TV3_TH - 1) / TV3_TH, tiles_w = (W + TV3_TW - 1) / TV3_TW, tiles = tiles_h * tiles_w;
+  uint64_t planes;
+  if (planes_tune > 0) planes = std::min<uint64_t>((uint64_t)planes_tune, D);
+  else {
+    const uint64_t want = (uint64_t)std::max(1, ncu) * 8u;
+    const uint64_t chunks = std::max<uint64_t>(1, std::min<uint64_t>(D, (want + tiles - 1) / tiles));
+    planes = std::max<uint64_t>((D + chunks - 1) / chunks, std::min<uint64_t>(D, 8));
+  }
+  const uint64_t chunks = (D + planes - 1) / planes;
+  if (tiles * chunks >= (1ull << 31)) return fail(FH_E_ARG, "the 3-D stencil launch would need %llu workgroups", (unsigned long long)(tiles * chunks));
+  sh->planes = (uint32_t)planes; sh->tiles_h = (uint32_t)tiles_h; sh->tiles_w = (uint32_t)tiles_w; sh->chunks = (uint32_t)chunks;
+  sh->grid = (uint32_t)(tiles * chunks);
+  return 0;
+}
+static inline bool tv3_prox_ok(int kind) { return sp_prox_ok(kind) || kind == FH_PROX_TVBALL; }
+// plain stores are the default: the non-temporal ones measure within 1.4 % of them from 256^3 on; FH_TUNE_NT_LOADS = 1 opts in
+static inline int tv3_nt_for(const fh_ctx* c) { return c->nt_loads > 0 ? 1 : 0; }
+static void tv3_shape_out(const Tv3Shape& sh, int nt, uint32_t* out) {
+  out[0] = TV3_TH; out[1] = TV3_TW; out[2] = sh.planes; out[3] = sh.tiles_h; out[4] = sh.tiles_w; out[5] = sh.chunks; out[6] = sh.grid; out[7] = (uint32_t)nt;
+}
+extern "C" int fh_tv3d_shape(fh_ctx* c, uint32_t* out) {
+  if (!c || !out) return fail(FH_E_ARG, "fh_tv3d_shape: null argument");
+  if (c->op != OP_STENCIL3D) return fail(FH_E_STATE, "fh_tv3d_shape: the context holds no 3-D stencil operator (fh_set_stencil3d)");
+  Tv3Shape sh;
+  FH_TRY(tv3_shape_for(c->D, c->H, c->W, c->tv3_planes, c->ncu, &sh));
+  tv3_shape_out(sh, tv3_nt_for(c), out);
+  return 0;
+}
+extern "C" int fh_tv3d_shape_for(uint64_t D, uint64_t H, uint64_t W, int planes, int ncu, uint32_t* out) {
+  if (!out) return fail(FH_E_ARG, "fh_tv3d_shape_for: null argument");
+  Tv3Shape sh;
+  FH_TRY(tv3_shape_for(D, H, W, planes, ncu, &sh));
+  tv3_shape_out(sh, 0, out);
+  return 0;
+}
+
+// z := div(mode 0: prox(x0 - tau g0) ; mode 1: x0), ONE launch
+static int launch_fwd_tv3(fh_ctx* c, int mode, double tau, const double* x0, const double* g0, const double* xacc0,
+                          double* xhat, double* xp, double* z, int sub_b) {
+  if (c->loss_kind != LOSS_LSQ) return fail(FH_E_STATE, "the 3-D stencil operator serves the least-squares loss only (the logistic loss is implemented for the dense and sparse operators)");
+  if (mode == 0 && !tv3_prox_ok(c->prox_kind))
+    return fail(FH_E_STATE, "prox kind %d (LINF / L1BALL / GROUP) is not implemented for the 3-D stencil operator", c->prox_kind);
+  Tv3Shape sh;
+  FH_TRY(tv3_shape_for(c->D, c->H, c->W, c->tv3_planes, c->ncu, &sh));
+  Tv3FwdP p;
+  p.D = (uint32_t)c->D; p.H = (uint32_t)c->H; p.W = (uint32_t)c->W; p.planes = sh.planes; p.tiles_h = sh.tiles_h; p.tiles_w = sh.tiles_w;
+  p.mode = mode; p.sub_b = sub_b;
+  p.x0 = x0; p.g0 = g0; p.xacc0 = xacc0; p.xhat = xhat; p.xp = xp; p.b = c->b; p.z = z; p.tau = tau;
+  p.px = make_prox(c, tau);
+  FH_TRY(ensure_ws(c, (size_t)sh.grid * 8 * sizeof(double)));
+  p.red = c->ws; p.counter = c->counters + CNT_FWD; p.out = scalar_out(c);
+  const bool ball = mode == 0 && c->prox_kind == FH_PROX_TVBALL;
+  t_begin(c, FH_K_FWD);
+  p.seq = seq_offer(c);
+  if (tv3_nt_for(c)) { if (ball) k_tv3_fwd<0, 1><<<dim3(sh.grid), dim3(FH_WG), 0, c->stream>>>(p); else k_tv3_fwd<1, 1><<<dim3(sh.grid), dim3(FH_WG), 0, c->stream>>>(p); }
+  else { if (ball) k_tv3_fwd<0, 0><<<dim3(sh.grid), dim3(FH_WG), 0, c->stream>>>(p); else k_tv3_fwd<1, 0><<<dim3(sh.grid), dim3(FH_WG), 0, c->stream>>>(p); }
+  t_end(c, FH_K_FWD);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// g1 := grad(z' - b) with the residual, the loss at z' and the n-side epilogue in the same launch
+static int launch_adj_tv3(fh_ctx* c, const AdjIO& io) {
+  if (c->loss_kind != LOSS_LSQ) return fail(FH_E_STATE, "the 3-D stencil operator serves the least-squares loss only (the logistic loss is implemented for the dense and sparse operators)");
+  if (io.mode != 0 && io.mode != 1) return fail(FH_E_STATE, "the 3-D stencil operator has no row-sharded adjoint");
+  Tv3Shape sh;
+  FH_TRY(tv3_shape_for(c->D, c->H, c->W, c->tv3_planes, c->ncu, &sh));
+  Tv3AdjP p;
+  p.D = (uint32_t)c->D; p.H = (uint32_t)c->H; p.W = (uint32_t)c->W; p.planes = sh.planes; p.tiles_h = sh.tiles_h; p.tiles_w = sh.tiles_w;
+  p.z = io.z; p.zacc0 = io.zacc0; p.b = c->b; p.sub_b = io.sub_b; p.accel = io.accel; p.mode = io.mode; p.coef = io.coef; p.tau = io.tau;
+  p.x0 = io.x0; p.xp = io.xp; p.xacc0 = io.xacc0; p.xhat = io.xhat; p.x1 = io.x1; p.g1 = io.g1;
+  FH_TRY(ensure_ws(c, (size_t)sh.grid * 8 * sizeof(double)));
+  p.red = c->ws; p.counter = c->counters + CNT_ADJ_FIN; p.out = scalar_out(c);
+  t_begin(c, FH_K_ADJ);
+  p.seq = io.mode == 0 ? seq_offer(c) : 0u;
+  if (tv3_nt_for(c)) k_tv3_adj<1><<<dim3(sh.grid), dim3(FH_WG), 0, c->stream>>>(p);
+  else k_tv3_adj<0><<<dim3(sh.grid), dim3(FH_WG), 0, c->stream>>>(p);
+  t_end(c, FH_K_ADJ);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
 // sum|x_i| and max|x_i| of an n-length device vector -> dscal[GSUM], dscal[GMAX]  (g(x0) for objective_hist[0], :143)
 static int launch_gterms(fh_ctx* c, const double* x) {
   if (c->LB) {              // (n, L) matrix: the same two terms, or the sum of row norms for FH_PROX_GROUP
@@ -933,6 +1029,7 @@ static int op_fwd(fh_ctx* c, int mode, double tau, const double* x0, const doubl
   if (c->op == OP_DENSE) return launch_fwd_dense(c, mode, tau, x0, g0, xacc0, xhat, xp, z, sub_b);
   if (c->op == OP_STENCIL) return launch_fwd_tv(c, mode, tau, x0, g0, xacc0, xhat, xp, z, sub_b);
   if (c->op == OP_SPARSE) return c->LB ? launch_fwd_spmulti(c, mode, tau, x0, g0, xacc0, xhat, xp, z, sub_b) : launch_fwd_sparse(c, mode, tau, x0, g0, xacc0, xhat, xp, z, sub_b);
+  if (c->op == OP_STENCIL3D) return launch_fwd_tv3(c, mode, tau, x0, g0, xacc0, xhat, xp, z, sub_b);
   return fail(FH_E_STATE, "no operator set");
 }
 
@@ -946,6 +1043,7 @@ static int adj_local(fh_ctx* c, const AdjIO& io_in) {
   if (c->op == OP_DENSE) return launch_adj_dense(c, io);
   if (c->op == OP_STENCIL) return launch_adj_tv(c, io);
   if (c->op == OP_SPARSE) return c->LB ? launch_adj_spmulti(c, io) : launch_adj_sparse(c, io);
+  if (c->op == OP_STENCIL3D) return launch_adj_tv3(c, io);
   return fail(FH_E_STATE, "no operator set");
 }
 // stage 2, exchange: A_k^T r_k partials (nv doubles at g1(shard)) and the local loss sums (FH_S_FSQ_ADJ) summed over the row blocks
@@ -974,7 +1072,7 @@ static int reduce_fsq_over_ranks(fh_ctx* c) {
 static int check_ready(fh_ctx* c, bool need_b) {
   if (!c) return fail(FH_E_ARG, "null context");
   if (c->pending_step) return fail(FH_E_STATE, "a step issued by fh_step_begin is still in flight on this context: call fh_step_end first");
-  if (c->op == OP_NONE) return fail(FH_E_STATE, "no operator set (call fh_set_matrix / fh_set_matrix_csr / fh_generate_matrix / fh_set_stencil)");
+  if (c->op == OP_NONE) return fail(FH_E_STATE, "no operator set (call fh_set_matrix / fh_set_matrix_csr / fh_generate_matrix / fh_set_stencil / fh_set_stencil3d)");
   if (need_b && !c->has_b) return fail(FH_E_STATE, "no loss set (call fh_set_loss_lsq)");
   return c->shards.empty() ? use_device(c) : 0;      // (a shell selects the device shard by shard)
 }

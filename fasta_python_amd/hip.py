@@ -26,7 +26,7 @@ NSCALARS = 16
 K_FWD, K_ADJ, K_AUX, K_COMM, K_FUSED, K_HOST_ISSUE, K_LEVEL = range(7)
 (TUNE_FWD_ROWS, TUNE_FWD_GRID_CAP, TUNE_ADJ_SLAB_ROWS, TUNE_ADJ_CPT, TUNE_LD_PAD, TUNE_NT_LOADS,
  TUNE_TV_U, TUNE_TV_ROWS, TUNE_TV_NT, TUNE_FUSED_VARIANT, TUNE_TV_ZFREE, TUNE_TV_PIPE, TUNE_TV_XCD, TUNE_TV_LDS_PAD,
- TUNE_TV_RING, TUNE_TV_SLOTS, TUNE_FUSED_CUS, TUNE_RUN_MAX_N, TUNE_SEQ_POLL, TUNE_RUN_CHAIN, TUNE_ADJ_CYCLIC) = range(21)
+ TUNE_TV_RING, TUNE_TV_SLOTS, TUNE_FUSED_CUS, TUNE_RUN_MAX_N, TUNE_SEQ_POLL, TUNE_RUN_CHAIN, TUNE_ADJ_CYCLIC, TUNE_TV3_PLANES) = range(22)
 # keys 10, 13, 14, 15 (TUNE_TV_ZFREE / _LDS_PAD / _RING / _SLOTS) are NOT in include/fasta_hip.h: experimental forms of the stencil sweep,
 # accepted only by libfasta_hip_experimental.so (csrc/fh_experimental.h); the shipped library answers FH_E_ARG
 EXPERIMENTAL_KEYS = (TUNE_TV_ZFREE, TUNE_TV_LDS_PAD, TUNE_TV_RING, TUNE_TV_SLOTS)
@@ -85,6 +85,9 @@ SIGNATURES = {
     "fh_nnz": (_i32, [_ctx, C.POINTER(_u64)]),
     "fh_sparse_lanes": (_i32, [_ctx, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "fh_set_stencil": (_i32, [_ctx, _u64, _u64]),
+    "fh_set_stencil3d": (_i32, [_ctx, _u64, _u64, _u64]),
+    "fh_tv3d_shape": (_i32, [_ctx, C.POINTER(C.c_uint32)]),
+    "fh_tv3d_shape_for": (_i32, [_u64, _u64, _u64, _i32, _i32, C.POINTER(C.c_uint32)]),
     "fh_shape": (_i32, [_ctx, C.POINTER(_u64), C.POINTER(_u64)]),
     "fh_set_rhs": (_i32, [_ctx, C.c_uint32]),
     "fh_rhs": (_i32, [_ctx, C.POINTER(C.c_uint32)]),
@@ -221,6 +224,19 @@ def multi_shape(m, n, L, slab_rows=0, grid_cap=0, nt_loads=-1):
     out = (C.c_uint32 * MULTI_SHAPE_LEN)()
     _check(lib, lib.fh_multi_shape_for(int(m), int(n), int(L), int(slab_rows), int(grid_cap), int(nt_loads), out))
     return MultiShape(*(int(v) for v in out))
+
+
+TV3D_SHAPE_LEN = 8
+Tv3dShape = collections.namedtuple("Tv3dShape", "tile_h tile_w planes tiles_h tiles_w chunks grid NT")
+
+
+def tv3d_shape(D, H, W, planes=0, ncu=256):
+    """Tv3dShape of the 3-D stencil launches for a (D, H, W) volume under FH_TUNE_TV3_PLANES = planes (0 = auto) on a device of ncu compute
+    units: fh_tv3d_shape_for, the rule both launchers call.  Host-only."""
+    lib = load_library()
+    out = (C.c_uint32 * TV3D_SHAPE_LEN)()
+    _check(lib, lib.fh_tv3d_shape_for(int(D), int(H), int(W), int(planes), int(ncu), out))
+    return Tv3dShape(*(int(v) for v in out))
 
 
 def comm_library():
@@ -425,6 +441,16 @@ class HipContext:
 
     def set_stencil(self, H, W):
         self._call("fh_set_stencil", int(H), int(W))
+
+    def set_stencil3d(self, D, H, W):
+        """A = div : (D, H, W, 3) -> (D, H, W), A^H = grad, periodic (csrc/fh_tv3d.h)."""
+        self._call("fh_set_stencil3d", int(D), int(H), int(W))
+
+    def tv3d_shape(self):
+        """Tv3dShape the next fwd / adj of this context launches with (fh_tv3d_shape).  E_STATE without a 3-D stencil operator."""
+        out = (C.c_uint32 * TV3D_SHAPE_LEN)()
+        self._call("fh_tv3d_shape", out)
+        return Tv3dShape(*(int(v) for v in out))
 
     def shape(self):
         m, n = _u64(0), _u64(0)

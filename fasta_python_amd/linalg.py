@@ -440,11 +440,53 @@ class SparseMatrixMap(_DeviceMap):
         return self.H
 
 
+def _nd_grad(X):
+    """Periodic discrete gradient of an N-d array -> (N+1)-d (examples/tv_denoising.py:26-40): roll(X, +1, axis) - X per axis."""
+    out = np.zeros(X.shape + (X.ndim,))
+    for axis in range(X.ndim):
+        out[..., axis] = np.roll(X, 1, axis=axis) - X
+    return out
+
+
+def _nd_div(Y):
+    """Adjoint of `_nd_grad` (examples/tv_denoising.py:43-63): sum over axes of roll(Y[..., axis], -1, axis) - Y[..., axis]."""
+    out = np.zeros(Y.shape[:-1])
+    for axis in range(Y.shape[-1]):
+        comp = Y[..., axis]
+        out += np.roll(comp, -1, axis=axis) - comp
+    return out
+
+
 class GradDivMap(_DeviceMap):
-    """A = div : (H, W, 2) -> (H, W) and A^H = grad, periodic (examples/tv_denoising.py:26-63)."""
+    """A = div and A^H = grad, periodic (examples/tv_denoising.py:26-63), of an image or a volume:
+    (H, W):    div : (H, W, 2) -> (H, W), the 2-D stencil kernels (csrc/fh_tv.h);
+    (D, H, W): div : (D, H, W, 3) -> (D, H, W), the 3-D stencil kernels (csrc/fh_tv3d.h).  Lazy like a map built from a host matrix: the
+               device context is created when the device loop first asks for it, and on host arrays the map is the reference's N-d
+               `div` / `grad` closures -- so `backend="numpy"` and the generic host loop are the reference bit for bit."""
 
     def __init__(self, image_shape, device=0):
+        image_shape = tuple(int(k) for k in image_shape)
+        if len(image_shape) == 3:
+            self.image_shape = image_shape
+            _DeviceMap.__init__(self, image_shape + (3,), image_shape, device, lazy=True)
+            return
+        if len(image_shape) != 2:
+            raise ValueError(f"GradDivMap takes an image shape (H, W) or a volume shape (D, H, W); got {len(image_shape)} dimensions")
         H, W = image_shape
+        self.image_shape = (H, W)                      # (before the context: _on_context reads it)
         _DeviceMap.__init__(self, (H, W, 2), (H, W), device)
         self.ctx.set_stencil(H, W)
-        self.image_shape = (H, W)
+
+    def _on_context(self, ctx):
+        if len(self.image_shape) == 3:
+            ctx.set_stencil3d(*self.image_shape)
+
+    def _apply_fwd(self, v):
+        if len(self.image_shape) == 3:
+            return _nd_div(v)
+        return self.device_apply(v, adjoint=False)
+
+    def _apply_adj(self, w):
+        if len(self.image_shape) == 3:
+            return _nd_grad(w)
+        return self.device_apply(w, adjoint=True)

@@ -125,6 +125,9 @@ enum fh_tuning_key {
                                 65536^2; profiles/r06_placement.txt), so it stays an A/B switch                                                   */
   FH_TUNE_SEQ_POLL = 18,     /* 1 (default): a single-device step waits for its scalar block by the sequence number the launch writes behind
                                 it into host-mapped memory (~5 us sooner than the launch's completion signal); 0: hipStreamSynchronize (A/B)  */
+  FH_TUNE_TV3_PLANES = 21,   /* 3-D stencil kernels (fh_set_stencil3d): planes along d a workgroup marches over; 0 = auto (whole columns of planes unless
+                                that leaves fewer than 8 workgroups per CU, then at least 8 planes per workgroup).  A small value gives a small
+                                volume several workgroups along d (the tests); fh_tv3d_shape reports what a launch takes                        */
   FH_TUNE_FUSED_CUS = 16     /* dense one-pass kernel: launch it on at most this many CUs (one workgroup each; 0 = every CU the device
                                 reports).  The co-residency probe then asks for that many.  Lets several one-pass grids run side by side
                                 on one device: two solves at once, partitioned devices, ranks of a row-sharded run that share a GPU
@@ -209,6 +212,31 @@ int fh_set_matrix_csr_rhs(fh_ctx* ctx, uint64_t m, uint64_t n, uint64_t nnz, con
 int fh_sparse_lanes(fh_ctx* ctx, int side, int* G, uint32_t* nwg, uint32_t* nlong);
 /* periodic difference stencil pair: A = div: (H,W,2)->(H,W), A^H = grad (examples/tv_denoising.py:26-63) */
 int fh_set_stencil(fh_ctx* ctx, uint64_t H, uint64_t W);
+/* ---- 3-D periodic difference stencil pair: A = div : (D,H,W,3) -> (D,H,W), A^H = grad (the N = 3 case of examples/tv_denoising.py:26-63) ------
+ * m = P = D*H*W, n = 3*P (fh_shape reports them); every dimension >= 1 and 3*P < 2^31 (768^3 fits), anything else is FH_E_ARG with a sentence.
+ * n-side vectors are the C order of (D,H,W,3), flat index 3*p + c; m-side vectors the C order of (D,H,W); both live in the vector form's padded
+ * buffers, so fh_set_vector / fh_get_vector, fh_diff_norm, fh_commit, fh_set_loss_lsq and fh_set_prox work unchanged, and -- unlike the 2-D
+ * stencil -- FH_VEC_G0 / G1 / XHAT are stored and addressable like any other operator's.  With p = (d,h,w) and indices modulo the dimension
+ *   div(Y)[p]    = ((Y[d+1,h,w,0] - Y[p,0]) + (Y[d,h+1,w,1] - Y[p,1])) + (Y[d,h,w+1,2] - Y[p,2])       (NumPy's `out += ...` per axis, this order)
+ *   grad(X)[p,c] = X[p - e_c] - X[p]
+ * so a dimension of 1 contributes 0.0 and a dimension of 2 sees the same neighbour on both sides.  Two kernels (csrc/fh_tv3d.h), one launch per
+ * direction, no atomics, fixed summation order, bitwise repeatable; measured at 512^3: 6.9 ms per pair, 4.85 TB/s (profiles/tv3d_sizes.txt).  Prox kinds served: FH_PROX_TVBALL -- here the projection of each voxel's
+ * 3-vector, y / max(sqrt((y0*y0 + y1*y1) + y2*y2), 1) -- and IDENTITY, SHRINK, NONNEG, BOX (BOX(-1, 1): anisotropic TV); least squares only.
+ * Served entry points, the FH_S_* scalars meaning what they mean for the sparse operator: fh_init, fh_setup (its three-pass route), fh_gradient_at,
+ * fh_apply, fh_fwd, fh_adj (accel / coef), fh_fwd_adj, fh_iterate, fh_timing_* (FH_K_FWD / FH_K_ADJ).
+ * Refused (FH_E_STATE / FH_E_ARG): fh_step*, fh_run, fh_set_rhs, fh_comm_init (and a context that has a communicator), multi-device contexts,
+ * fh_get_matrix_rows, fh_stream_read_ms, the logistic loss, FH_PROX_LINF / L1BALL / GROUP (a context holding one of these returns to IDENTITY
+ * when the operator is set).  fh_fused_supported, fh_fused_agree and fh_run_supported report 0.  Setting any other operator leaves this form. */
+int fh_set_stencil3d(fh_ctx* ctx, uint64_t D, uint64_t H, uint64_t W);
+/* read-only: the geometry both 3-D stencil launches take (csrc/fh_host_launch.h: tv3_shape_for, the ONE rule both launchers call), so that a test
+ * can assert the path it meant to reach.  out[FH_TV3D_SHAPE_LEN] = { tile rows (h), tile columns (w), planes per workgroup, tiles along h, tiles
+ * along w, chunks along d, grid = chunks * tiles, NT (1: non-temporal stores, FH_TUNE_NT_LOADS) }.  Workgroup (chunk, th, tw) owns the voxels
+ * [chunk*planes, ...) x [th*tile rows, ...) x [tw*tile columns, ...), clipped to the volume: every voxel has exactly one owner.  fh_tv3d_shape
+ * reads the context's volume, FH_TUNE_TV3_PLANES and CU count and is FH_E_STATE without a 3-D stencil operator; fh_tv3d_shape_for is the same
+ * rule as a pure host function (no device needed; planes: 0 = auto; ncu: the device's compute units).                                        */
+#define FH_TV3D_SHAPE_LEN 8
+int fh_tv3d_shape(fh_ctx* ctx, uint32_t* out);
+int fh_tv3d_shape_for(uint64_t D, uint64_t H, uint64_t W, int planes, int ncu, uint32_t* out);
 int fh_shape(fh_ctx* ctx, uint64_t* m, uint64_t* n);
 
 /* ---- multi-column form: the unknown is an (n, L) MATRIX, one A for all L columns (examples/mmv.py; multi-column LASSO / NNLS) -----------
