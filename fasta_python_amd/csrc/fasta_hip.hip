@@ -1,5 +1,5 @@
 // fasta_hip.hip -- the C ABI of libfasta_hip.so (declared in include/fasta_hip.h): entry points only.  The context and its helpers are
-// in fh_host_ctx.h, the kernel launchers in fh_host_launch.h, the kernels in fh_dense.h / fh_tv.h / fh_prox.h / fh_fused.h.
+// in fh_host_ctx.h, the kernel launchers in fh_host_launch.h, the kernels in fh_dense.h / fh_multi.h / fh_quad.h / fh_tv.h / fh_prox.h / fh_fused.h.
 // gfx950 only.  No PyTorch, no rocBLAS: every device operation is a kernel from fh_dense.h / fh_tv.h,
 // plus RCCL (dlopen'ed on first use) for the row-sharded adjoint.
 #include <hip/hip_runtime.h>
@@ -17,6 +17,7 @@
 #include "fh_experimental.h"
 #include "fh_dense.h"
 #include "fh_multi.h"
+#include "fh_quad.h"
 #include "fh_sparse.h"
 #include "fh_spmulti.h"
 #include "fh_tv.h"
@@ -651,6 +652,7 @@ extern "C" int fh_get_matrix_rows(fh_ctx* c, uint64_t row0, uint64_t nrows, doub
   if (!c || !out) return fail(FH_E_ARG, "null argument");
   if (c->op == OP_SPARSE) return fail(FH_E_STATE, "fh_get_matrix_rows: the sparse operator keeps no dense rows");
   if (c->op == OP_STENCIL3D) return fail(FH_E_STATE, "fh_get_matrix_rows: the 3-D stencil operator keeps no dense rows");
+  if (c->op == OP_QUAD) return fail(FH_E_STATE, "fh_get_matrix_rows: the quadratic operator is not read back (the caller holds Q)");
   if (c->op != OP_DENSE) return fail(FH_E_STATE, "no dense matrix set");
   if (row0 + nrows > c->m) return fail(FH_E_ARG, "rows [%llu,%llu) out of range (m=%llu)", (unsigned long long)row0,
                                        (unsigned long long)(row0 + nrows), (unsigned long long)c->m);
@@ -741,6 +743,7 @@ extern "C" int fh_set_rhs(fh_ctx* c, uint32_t L) {
   if (c->op == OP_NONE) return fail(FH_E_STATE, "fh_set_rhs: set the dense operator first (fh_set_matrix / fh_generate_matrix)");
   if (c->op == OP_SPARSE) return fail(FH_E_STATE, "fh_set_rhs: the sparse operator has no multi-column form through fh_set_rhs: its column count is fixed when it is set (fh_set_matrix_csr_rhs)");
   if (c->op == OP_STENCIL3D) return fail(FH_E_STATE, "fh_set_rhs: the 3-D stencil operator has no multi-column form");
+  if (c->op == OP_QUAD) return fail(FH_E_STATE, "fh_set_rhs: the column count of a quadratic operator is fixed when it is set (fh_set_quadratic)");
   if (c->op != OP_DENSE) return fail(FH_E_STATE, "fh_set_rhs: the stencil operator has no multi-column form");
   if (c->f32) return fail(FH_E_STATE, "fh_set_rhs: float32 storage of A has no multi-column form");
   if (L && c->has_b && c->loss_kind != LOSS_LSQ) return fail(FH_E_STATE, "fh_set_rhs: the logistic loss has no multi-column form");
@@ -763,9 +766,60 @@ extern "C" int fh_rhs(fh_ctx* c, uint32_t* L) {
   return 0;
 }
 
+// ---- quadratic smooth term f(X) = .5 <X, Q X> + <C, X> on a symmetric Q, A = identity (csrc/fh_quad.h): operator and loss in one call ----
+// first (i, j), in row-major order of the upper triangle, with Q[i,j] != Q[j,i]; tiles keep both accesses in cache
+static bool first_asymmetry(const double* Q, uint64_t n, uint64_t ld, uint64_t* bi, uint64_t* bj) {
+  const uint64_t T = 64;
+  bool found = false;
+  for (uint64_t i0 = 0; i0 < n; i0 += T)
+    for (uint64_t j0 = i0; j0 < n; j0 += T)
+      for (uint64_t i = i0; i < std::min(i0 + T, n); ++i)
+        for (uint64_t j = std::max(j0, i + 1); j < std::min(j0 + T, n); ++j)
+          if (Q[i * ld + j] != Q[j * ld + i] && (!found || i < *bi || (i == *bi && j < *bj))) { found = true; *bi = i; *bj = j; }
+  return found;
+}
+extern "C" int fh_set_quadratic(fh_ctx* c, const double* Q, uint64_t n, uint64_t ld_host, const double* cvec, uint32_t L) {
+  if (!c || !Q) return fail(FH_E_ARG, "fh_set_quadratic: null argument");
+  if (L < 1 || L > 16) return fail(FH_E_ARG, "fh_set_quadratic: 1 to 16 columns (got %u)", L);
+  if (!c->shards.empty() || c->owner) return fail(FH_E_STATE, "fh_set_quadratic: a multi-device context has no quadratic operator (row sharding is implemented for the dense operator only)");
+  if (c->comm) return fail(FH_E_STATE, "fh_set_quadratic: a context with a communicator (row-sharded run) has no quadratic operator");
+  if (c->pending_step) return fail(FH_E_STATE, "a step issued by fh_step_begin is still in flight on this context: call fh_step_end first");
+  if (c->f32) return fail(FH_E_STATE, "fh_set_quadratic: float32 storage has no quadratic operator");
+  if (n == 0) return fail(FH_E_ARG, "fh_set_quadratic: the matrix must be non-empty");
+  if (n >= (1ull << 31)) return fail(FH_E_ARG, "fh_set_quadratic: matrix dimension exceeds 2^31-1");
+  if (ld_host < n) return fail(FH_E_ARG, "fh_set_quadratic: ld_host %llu < n %llu", (unsigned long long)ld_host, (unsigned long long)n);
+  uint64_t bi = 0, bj = 0;
+  if (first_asymmetry(Q, n, ld_host, &bi, &bj))
+    return fail(FH_E_ARG, "fh_set_quadratic: Q is not symmetric: Q[%llu,%llu] = %.17g but Q[%llu,%llu] = %.17g (pass (Q + Q^T) / 2, or S + S^T as examples/max_norm.py:50 does)",
+                (unsigned long long)bi, (unsigned long long)bj, Q[bi * ld_host + bj], (unsigned long long)bj, (unsigned long long)bi, Q[bj * ld_host + bi]);
+  FH_TRY(use_device(c));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  free_operator(c);
+  if (!qd_prox_ok(c->prox_kind)) { c->prox_kind = FH_PROX_IDENTITY; c->mu = 0.0; }
+  c->lazy = false; c->last_accel = false; c->commits = 0;
+  c->m = n; c->n = n;
+  c->mp = round_up(n, 16);
+  c->ld = round_up(n, 16) + (uint64_t)c->ld_pad;
+  c->nv = c->ld; c->mv = c->mp;
+  c->L = L; c->LB = L <= 2 ? 2u : (L <= 4 ? 4u : (L <= 8 ? 8u : 16u));
+  const size_t q_bytes = (size_t)c->mp * c->ld * sizeof(double);
+  HIP_TRY(acquire_matrix_block(c->device, q_bytes, &c->A, &c->a_block_bytes));
+  c->op = OP_QUAD;                                       // (from here on free_operator gives the block back)
+  int rc = alloc_vectors(c);
+  if (rc == 0 && hipMemsetAsync(c->A, 0, q_bytes, c->stream) != hipSuccess) rc = fail(FH_E_STATE, "fh_set_quadratic: clearing the device copy of Q failed");
+  if (rc == 0 && hipMemcpy2DAsync(c->A, c->ld * sizeof(double), Q, ld_host * sizeof(double), n * sizeof(double), n, hipMemcpyHostToDevice, c->stream) != hipSuccess)
+    rc = fail(FH_E_STATE, "fh_set_quadratic: the copy of Q to the device failed");
+  if (rc == 0 && cvec) rc = copy_in(c, c->b, cvec, n);   // (no C: the buffer stays the zeros it was allocated as)
+  if (rc == 0) rc = finish(c);
+  if (rc != 0) { free_operator(c); return rc; }
+  c->loss_kind = LOSS_QUAD; c->has_b = true;
+  return 0;
+}
+
 static int set_loss(fh_ctx* c, int kind, const double* b, uint64_t len) {
   if (!c || !b) return fail(FH_E_ARG, "null argument");
   if (c->op == OP_NONE) return fail(FH_E_STATE, "set the operator before the loss");
+  if (c->op == OP_QUAD) return fail(FH_E_STATE, "the quadratic operator carries its own loss (Q and the linear term of fh_set_quadratic): fh_set_loss_lsq / fh_set_loss_logistic do not apply");
   if (len != c->m * l_of(c)) return fail(FH_E_ARG, "b has %llu entries, operator has %llu rows (x %llu columns)", (unsigned long long)len, (unsigned long long)c->m, (unsigned long long)l_of(c));
   if (kind != LOSS_LSQ && c->LB) return fail(FH_E_STATE, "the logistic loss has no multi-column form (fh_set_rhs / fh_set_matrix_csr_rhs)");
   if (kind != LOSS_LSQ && c->op == OP_STENCIL3D) return fail(FH_E_STATE, "the 3-D stencil operator serves the least-squares loss only (the logistic loss is implemented for the dense and sparse operators)");
@@ -792,9 +846,11 @@ extern "C" int fh_set_loss_logistic(fh_ctx* c, const double* labels, uint64_t le
 
 extern "C" int fh_set_prox(fh_ctx* c, int kind, double mu, double lo, double hi) {
   if (!c) return fail(FH_E_ARG, "null context");
-  if (kind < FH_PROX_IDENTITY || kind > FH_PROX_GROUP) return fail(FH_E_ARG, "unknown prox kind %d", kind);
+  if (kind < FH_PROX_IDENTITY || kind > FH_PROX_ROWBALL) return fail(FH_E_ARG, "unknown prox kind %d", kind);
+  if (kind == FH_PROX_ROWBALL && c->op != OP_QUAD) return fail(FH_E_ARG, "FH_PROX_ROWBALL (row-wise projection onto the ball of radius mu) is served by the quadratic operator only: call fh_set_quadratic first");
+  if (c->op == OP_QUAD && !qd_prox_ok(kind)) return fail(FH_E_ARG, "prox kind %d (LINF / L1BALL / TVBALL) has no quadratic form", kind);
   if (kind == FH_PROX_GROUP && !c->LB) return fail(FH_E_ARG, "FH_PROX_GROUP (row-wise l2 shrink) needs the multi-column form: call fh_set_rhs (dense operator) or fh_set_matrix_csr_rhs (sparse operator) first");
-  if (c->LB && !mc_prox_ok(kind)) return fail(FH_E_ARG, "prox kind %d (LINF / L1BALL / TVBALL) has no multi-column form", kind);
+  if (c->LB && c->op != OP_QUAD && !mc_prox_ok(kind)) return fail(FH_E_ARG, "prox kind %d (LINF / L1BALL / TVBALL) has no multi-column form", kind);
   if (c->op == OP_SPARSE && !c->LB && !sp_prox_ok(kind)) return fail(FH_E_ARG, "prox kind %d (LINF / L1BALL / TVBALL / GROUP) is not implemented for the sparse operator", kind);
   if (c->op == OP_STENCIL3D && !tv3_prox_ok(kind)) return fail(FH_E_ARG, "prox kind %d (LINF / L1BALL / GROUP) is not implemented for the 3-D stencil operator", kind);
   if (kind == FH_PROX_BOX && !(lo <= hi)) return fail(FH_E_ARG, "box prox needs lo <= hi");
@@ -1303,6 +1359,7 @@ static int step_body(fh_ctx* c, double tau, double* scalars, bool wait) {
   FH_TRY(check_ready(c, true));
   if (c->op == OP_SPARSE) return fail(FH_E_STATE, "fh_step: the sparse operator has no one-pass kernel: use fh_fwd / fh_adj / fh_fwd_adj / fh_iterate");
   if (c->op == OP_STENCIL3D) return fail(FH_E_STATE, "fh_step: the 3-D stencil operator has no one-pass kernel: use fh_fwd / fh_adj / fh_fwd_adj / fh_iterate");
+  if (c->op == OP_QUAD) return fail(FH_E_STATE, "fh_step: the quadratic operator has no one-pass kernel: use fh_fwd / fh_adj / fh_fwd_adj / fh_iterate");
   if (c->LB) return fail(FH_E_STATE, "fh_step: the multi-column form (fh_set_rhs) has no one-pass kernel: use fh_fwd / fh_adj / fh_iterate");
   for (int k = 0; k < nshards(c); ++k) FH_TRY(not_lazy(shard_of(c, k), "fh_step"));
   if (c->op == OP_STENCIL) {
@@ -1350,6 +1407,7 @@ extern "C" int fh_step_accel(fh_ctx* c, double tau, double coef, int restart, do
   FH_TRY(check_ready(c, true));
   if (c->op == OP_SPARSE) return fail(FH_E_STATE, "fh_step_accel: the sparse operator has no one-pass kernel: use fh_fwd / fh_adj / fh_iterate");
   if (c->op == OP_STENCIL3D) return fail(FH_E_STATE, "fh_step_accel: the 3-D stencil operator has no one-pass kernel: use fh_fwd / fh_adj / fh_iterate");
+  if (c->op == OP_QUAD) return fail(FH_E_STATE, "fh_step_accel: the quadratic operator has no one-pass kernel: use fh_fwd / fh_adj / fh_iterate");
   if (c->LB) return fail(FH_E_STATE, "fh_step_accel: the multi-column form (fh_set_rhs) has no one-pass kernel: use fh_fwd / fh_adj / fh_iterate");
   if (c->op == OP_STENCIL) {
     if (row_sharded(c)) return fail(FH_E_STATE, "row sharding is implemented for the dense operator only");
@@ -1465,6 +1523,7 @@ extern "C" int fh_run(fh_ctx* c, int max_steps, const fh_run_opts* o, fh_run_sta
   if (o->stop_rule < 0 || o->stop_rule > 3) return fail(FH_E_ARG, "fh_run: stop_rule must be 0..3 (the four rules of fasta/stopping.py)");
   if (c->op == OP_SPARSE) return fail(FH_E_STATE, "fh_run: the sparse operator has no device-side loop: use fh_iterate");
   if (c->op == OP_STENCIL3D) return fail(FH_E_STATE, "fh_run: the 3-D stencil operator has no device-side loop: use fh_iterate");
+  if (c->op == OP_QUAD) return fail(FH_E_STATE, "fh_run: the quadratic operator has no device-side loop: use fh_iterate");
   if (c->LB) return fail(FH_E_STATE, "fh_run: the multi-column form (fh_set_rhs) has no device-side loop: use fh_iterate");
   const RunEntry* e = run_entry(c);
   if (!e && chain_ok(c) && co_resident(c)) return run_chain(c, max_steps, o, state, history, steps_done);
@@ -1660,6 +1719,7 @@ extern "C" int fh_apply(fh_ctx* c, int adjoint, const double* in, double* out) {
     fh_ctx* s = shard_of(c, k);
     const uint64_t r0 = shell ? c->shard_row0[k] : 0;       // rows of the whole operator this shard holds: [r0, r0 + s->m)
     FH_TRY(use_device(s));
+    if (s->op == OP_QUAD) adjoint = 0;                     // Q is symmetric: both flags are out = Q in
     if (!adjoint) {
       FH_TRY(copy_in(s, s->T[3], in, s->n));
       FH_TRY(op_fwd(s, 1, 0.0, s->T[3], nullptr, nullptr, nullptr, nullptr, s->zt, 0));
@@ -1696,6 +1756,7 @@ extern "C" int fh_comm_init(fh_ctx* c, int nranks, int rank, const void* id128) 
   if (nranks < 1 || rank < 0 || rank >= nranks) return fail(FH_E_ARG, "bad rank %d of %d", rank, nranks);
   if (c->op == OP_SPARSE) return fail(FH_E_STATE, "fh_comm_init: a context with a sparse operator cannot be row-sharded");
   if (c->op == OP_STENCIL3D) return fail(FH_E_STATE, "fh_comm_init: a context with a 3-D stencil operator cannot be row-sharded");
+  if (c->op == OP_QUAD) return fail(FH_E_STATE, "fh_comm_init: a context with a quadratic operator cannot be row-sharded");
   if (c->LB) return fail(FH_E_STATE, "fh_comm_init: a context in multi-column form (fh_set_rhs) cannot be row-sharded");
   if (!c->shards.empty() || c->owner)
     return fail(FH_E_STATE, "fh_comm_init: a multi-device context (fh_create_ex, ndev > 1) already shards the rows in-process");
@@ -1887,6 +1948,7 @@ extern "C" int fh_stream_read_ms(fh_ctx* c, int reps, double* ms_per_pass, uint6
   if (!c->shards.empty()) return fh_stream_read_ms(c->shards[0], reps, ms_per_pass, bytes_per_pass);     // shard 0's block on its device
   if (c->op == OP_SPARSE) return fail(FH_E_STATE, "fh_stream_read_ms: the stream-read ceiling is measured on a dense matrix, not on the sparse operator");
   if (c->op == OP_STENCIL3D) return fail(FH_E_STATE, "fh_stream_read_ms: the stream-read ceiling is measured on a dense matrix, not on the 3-D stencil operator");
+  if (c->op == OP_QUAD) return fail(FH_E_STATE, "fh_stream_read_ms: the stream-read ceiling is measured on a dense matrix, not on the quadratic operator");
   if (c->op != OP_DENSE) return fail(FH_E_STATE, "stream-read ceiling needs a dense matrix");
   if (reps < 1) reps = 1;
   // k_stream_probe<16,1> as described in include/fasta_hip.h: persistent workgroups, 1 per CU by default, three rotating buffers of 16 nt loads per lane

@@ -1,4 +1,4 @@
-// fh_host_launch.h -- kernel launchers of libfasta_hip.so: shapes, grids and workspace of every kernel in fh_dense.h / fh_tv.h / fh_tv3d.h /
+// fh_host_launch.h -- kernel launchers of libfasta_hip.so: shapes, grids and workspace of every kernel in fh_dense.h / fh_quad.h / fh_tv.h / fh_tv3d.h /
 // fh_prox.h / fh_fused.h, the one-pass kernel's shape rule and dispatch table, the co-residency probe, and the three-stage form
 // (local launch / sum over row blocks / n-side epilogue) the C ABI in fasta_hip.hip builds its entry points from.
 #pragma once
@@ -376,6 +376,147 @@ static int launch_adj_multi(fh_ctx* c, const AdjIO& io) {
   t_begin(c, FH_K_ADJ);
   p.seq = io.mode == 0 ? seq_offer(c) : 0u;
   e->adj[sh.nt]<<<dim3(grid), dim3(FH_WG), 0, c->stream>>>(p);
+  t_end(c, FH_K_ADJ);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// ---- quadratic smooth term on a symmetric matrix (fh_set_quadratic; kernels in csrc/fh_quad.h, instantiated by fh_quad_part.hip) ---------------
+#ifndef FH_SINGLE_TU
+#define QD_DECLARE(LB, CH, R) QD_KERNELS(extern template, LB, CH, R)
+MC_FOR_EACH(QD_DECLARE)
+#undef QD_DECLARE
+#endif
+struct QdEntry { int lb, ch, rows; void (*pro)(const McProP); void (*fwd[2])(const QdFwdP); void (*grad)(const QdGradP); };
+#define QD_ROW(LB, CH, R) {LB, CH, R, k_qd_prologue<LB>, {k_qd_fwd<LB, CH, R, 0>, k_qd_fwd<LB, CH, R, 1>}, k_qd_grad<LB>},
+static const QdEntry kQdTable[] = { MC_FOR_EACH(QD_ROW) };
+#undef QD_ROW
+static const QdEntry* qd_entry_lb(uint32_t LB) {
+  for (const QdEntry& e : kQdTable) if ((uint32_t)e.lb == LB) return &e;
+  return nullptr;
+}
+static inline bool qd_prox_ok(int kind) { return mc_prox_ok(kind) || kind == FH_PROX_ROWBALL; }
+
+// THE GEOMETRY of the quadratic launches, stated once: a pure function of the device shape (mp rows of ld doubles, nv rows of X), the columns per
+// row LB and the tuning values FH_TUNE_FWD_GRID_CAP and FH_TUNE_NT_LOADS as the context keeps them (0 / -1 = auto).  Both launchers take every
+// number from here; fh_quad_shape / fh_quad_shape_for export it.  `e` = nullptr when no kernel serves LB.
+struct QdShape {
+  const QdEntry* e;
+  int nt;
+  uint32_t ld2;                      // 16-byte pieces per device row of Q = row pairs of X
+  uint32_t fwd_grid, nrg, ntrip;     // K-fwd: workgroups, row groups of R rows they stride over, trips of a lane group along a row
+  uint32_t last_live;                // lanes of a lane group whose piece of the last trip lies inside the row
+  uint32_t pass_max, pass_min;       // passes of the busiest and of the idlest workgroup of K-fwd
+  uint32_t npro, ngrad;              // workgroups of the prologue (mode 0) / pack launch (mode 1), and of the elementwise gradient launch
+};
+static QdShape qd_shape_for(uint64_t mp, uint64_t ld, uint64_t nv, uint32_t LB, long long fwd_cap, int nt_loads) {
+  QdShape s;
+  memset(&s, 0, sizeof(s));
+  s.e = qd_entry_lb(LB);
+  if (!s.e) return s;
+  s.nt = nt_rule(nt_loads, mp, ld, 0) ? 1 : 0;
+  s.ld2 = (uint32_t)(ld / 2);
+  s.nrg = (uint32_t)(mp / (uint64_t)s.e->rows);
+  s.fwd_grid = (uint32_t)std::min<long long>(s.nrg, fwd_cap > 0 ? fwd_cap : 512);
+  const uint32_t GL = FH_WG / (uint32_t)(s.e->lb / s.e->ch);          // lanes of a column group (k_qd_fwd)
+  s.ntrip = (s.ld2 + GL - 1) / GL;
+  s.last_live = s.ld2 - (s.ntrip - 1) * GL;
+  s.pass_max = (s.nrg + s.fwd_grid - 1) / s.fwd_grid;
+  s.pass_min = s.nrg / s.fwd_grid;
+  s.npro = (uint32_t)((nv + FH_WG - 1) / FH_WG);
+  s.ngrad = (uint32_t)((mp + FH_WG - 1) / FH_WG);
+  return s;
+}
+static QdShape qd_shape(const fh_ctx* c) { return qd_shape_for(c->mp, c->ld, c->nv, c->LB, c->fwd_cap, c->nt_loads); }
+static void qd_shape_report(const QdShape& s, uint32_t* out) {
+  const uint32_t v[FH_QUAD_SHAPE_LEN] = {(uint32_t)s.e->lb, (uint32_t)s.e->ch, (uint32_t)s.e->rows, (uint32_t)s.nt, s.fwd_grid, s.nrg, s.ntrip, s.last_live,
+                                         s.pass_max, s.pass_min, s.npro, s.ngrad};
+  memcpy(out, v, sizeof(v));
+}
+// read-only: the geometry the next fh_fwd / fh_adj of this context launches with
+extern "C" int fh_quad_shape(fh_ctx* c, uint32_t* out) {
+  if (!c || !out) return fail(FH_E_ARG, "fh_quad_shape: null argument");
+  if (c->op != OP_QUAD) return fail(FH_E_STATE, "fh_quad_shape: the context holds no quadratic operator (fh_set_quadratic)");
+  const QdShape s = qd_shape(c);
+  if (!s.e) return fail(FH_E_STATE, "quadratic operator: no kernel for %u columns per row", c->LB);
+  qd_shape_report(s, out);
+  return 0;
+}
+// ... and the same rule for an (n, n) matrix with L columns that no context holds: a pure host function, no device needed
+extern "C" int fh_quad_shape_for(uint64_t n, uint32_t L, long long grid_cap, int nt_loads, uint32_t* out) {
+  if (!out) return fail(FH_E_ARG, "fh_quad_shape_for: null argument");
+  if (n == 0 || n >= (1ull << 31)) return fail(FH_E_ARG, "fh_quad_shape_for: the matrix dimension must be in [1, 2^31)");
+  if (L < 1 || L > 16) return fail(FH_E_ARG, "fh_quad_shape_for: 1 to 16 columns (got %u)", L);
+  if (grid_cap < 0) return fail(FH_E_ARG, "FWD_GRID_CAP must be >= 0");
+  if (nt_loads < -1 || nt_loads > 1) return fail(FH_E_ARG, "fh_quad_shape_for: nt_loads is -1 (auto), 0 or 1");
+  const uint32_t LB = L <= 2 ? 2u : (L <= 4 ? 4u : (L <= 8 ? 8u : 16u));
+  const uint64_t ld = round_up(n, 16);
+  const QdShape s = qd_shape_for(ld, ld, ld, LB, grid_cap, nt_loads);
+  if (!s.e) return fail(FH_E_STATE, "quadratic operator: no kernel for %u columns per row", LB);
+  qd_shape_report(s, out);
+  return 0;
+}
+
+// W := Q * (mode 0: prox(X0 - tau G0), by the prologue launch ; mode 1: X0) for LB columns from one read of Q; with_f: the loss sum over (n, L)
+static int launch_fwd_quad(fh_ctx* c, int mode, double tau, const double* x0, const double* g0, const double* xacc0,
+                           double* xhat, double* xp, double* w, int with_f) {
+  const QdShape sh = qd_shape(c);
+  const QdEntry* e = sh.e;
+  const McEntry* me = mc_entry_lb(c->LB);               // (k_mc_pack lays a plain operand out for the streaming loop)
+  if (!e || !me) return fail(FH_E_STATE, "quadratic operator: no kernel for %u columns per row", c->LB);
+  if (mode == 0 && !qd_prox_ok(c->prox_kind)) return fail(FH_E_STATE, "prox kind %d (LINF / L1BALL / TVBALL) has no quadratic form", c->prox_kind);
+  QdFwdP p;
+  p.Q = c->A; p.ld2 = sh.ld2; p.n = (uint32_t)c->n; p.L = c->L;
+  p.nrg = sh.nrg;
+  const uint32_t npro = mode == 0 ? sh.npro : 0u;
+  p.nred_n = npro;
+  const unsigned grid = sh.fwd_grid;
+  FH_TRY(ensure_ws(c, ((size_t)npro * 8 + grid) * sizeof(double)));
+  p.red_n = c->ws; p.red_m = c->ws + (size_t)npro * 8;
+  p.x = c->xs;
+  p.xrow = mode == 0 ? xp : x0;
+  p.c = c->b; p.w = w; p.with_f = with_f;
+  p.counter = c->counters + CNT_FWD;
+  p.out = scalar_out(c);
+  t_begin(c, FH_K_FWD);
+  if (mode == 0) {
+    McProP q;
+    q.n = (uint32_t)c->n; q.L = c->L; q.nv = (uint32_t)c->nv;
+    q.x0 = x0; q.g0 = g0; q.xacc0 = xacc0; q.xhat = xhat; q.xp = xp; q.tau = tau;
+    q.xs = c->xs; q.ld2 = p.ld2;
+    q.px = make_prox(c, tau);
+    if (c->prox_kind == FH_PROX_ROWBALL) q.px.thr = c->mu;         // the radius itself: this projection does not scale with the step
+    q.red_n = c->ws;
+    e->pro<<<dim3(npro), dim3(FH_WG), 0, c->stream>>>(q);
+  } else {
+    me->pack<<<dim3(sh.npro), dim3(FH_WG), 0, c->stream>>>(x0, c->xs, (uint32_t)c->nv, p.ld2);
+  }
+  p.seq = seq_offer(c);
+  e->fwd[sh.nt]<<<dim3(grid), dim3(FH_WG), 0, c->stream>>>(p);
+  t_end(c, FH_K_FWD);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// g1 := W' + C, elementwise (W' = W or its extrapolation), and the n-side epilogue; sub_b = 0 (fh_apply's adjoint flag) never gets here
+static int launch_adj_quad(fh_ctx* c, const AdjIO& io) {
+  const QdShape sh = qd_shape(c);
+  const QdEntry* e = sh.e;
+  if (!e) return fail(FH_E_STATE, "quadratic operator: no kernel for %u columns per row", c->LB);
+  if (io.mode != 0 && io.mode != 1) return fail(FH_E_STATE, "the quadratic operator has no row-sharded adjoint");
+  QdGradP p;
+  p.n = (uint32_t)c->n; p.L = c->L; p.rows = (uint32_t)c->mp;
+  p.w = io.z; p.wacc0 = io.zacc0; p.c = c->b;
+  p.accel = io.accel; p.mode = io.mode; p.group = c->prox_kind == FH_PROX_GROUP ? 1 : 0;
+  p.coef = io.coef; p.tau = io.tau;
+  p.x0 = io.x0; p.xp = io.xp; p.xacc0 = io.xacc0; p.xhat = io.xhat; p.x1 = io.x1; p.g1 = io.g1;
+  FH_TRY(ensure_ws(c, (size_t)sh.ngrad * 8 * sizeof(double)));
+  p.red = c->ws;
+  p.counter = c->counters + CNT_ADJ_FIN;
+  p.out = scalar_out(c);
+  t_begin(c, FH_K_ADJ);
+  p.seq = io.mode == 0 ? seq_offer(c) : 0u;
+  e->grad<<<dim3(sh.ngrad), dim3(FH_WG), 0, c->stream>>>(p);
   t_end(c, FH_K_ADJ);
   HIP_TRY(hipGetLastError());
   return 0;
@@ -1030,6 +1171,7 @@ static int op_fwd(fh_ctx* c, int mode, double tau, const double* x0, const doubl
   if (c->op == OP_STENCIL) return launch_fwd_tv(c, mode, tau, x0, g0, xacc0, xhat, xp, z, sub_b);
   if (c->op == OP_SPARSE) return c->LB ? launch_fwd_spmulti(c, mode, tau, x0, g0, xacc0, xhat, xp, z, sub_b) : launch_fwd_sparse(c, mode, tau, x0, g0, xacc0, xhat, xp, z, sub_b);
   if (c->op == OP_STENCIL3D) return launch_fwd_tv3(c, mode, tau, x0, g0, xacc0, xhat, xp, z, sub_b);
+  if (c->op == OP_QUAD) return launch_fwd_quad(c, mode, tau, x0, g0, xacc0, xhat, xp, z, sub_b);
   return fail(FH_E_STATE, "no operator set");
 }
 
@@ -1044,6 +1186,7 @@ static int adj_local(fh_ctx* c, const AdjIO& io_in) {
   if (c->op == OP_STENCIL) return launch_adj_tv(c, io);
   if (c->op == OP_SPARSE) return c->LB ? launch_adj_spmulti(c, io) : launch_adj_sparse(c, io);
   if (c->op == OP_STENCIL3D) return launch_adj_tv3(c, io);
+  if (c->op == OP_QUAD) return launch_adj_quad(c, io);
   return fail(FH_E_STATE, "no operator set");
 }
 // stage 2, exchange: A_k^T r_k partials (nv doubles at g1(shard)) and the local loss sums (FH_S_FSQ_ADJ) summed over the row blocks
@@ -1072,7 +1215,7 @@ static int reduce_fsq_over_ranks(fh_ctx* c) {
 static int check_ready(fh_ctx* c, bool need_b) {
   if (!c) return fail(FH_E_ARG, "null context");
   if (c->pending_step) return fail(FH_E_STATE, "a step issued by fh_step_begin is still in flight on this context: call fh_step_end first");
-  if (c->op == OP_NONE) return fail(FH_E_STATE, "no operator set (call fh_set_matrix / fh_set_matrix_csr / fh_generate_matrix / fh_set_stencil / fh_set_stencil3d)");
+  if (c->op == OP_NONE) return fail(FH_E_STATE, "no operator set (call fh_set_matrix / fh_set_matrix_csr / fh_generate_matrix / fh_set_stencil / fh_set_stencil3d / fh_set_quadratic)");
   if (need_b && !c->has_b) return fail(FH_E_STATE, "no loss set (call fh_set_loss_lsq)");
   return c->shards.empty() ? use_device(c) : 0;      // (a shell selects the device shard by shard)
 }

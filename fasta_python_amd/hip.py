@@ -16,8 +16,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FASTA_HIP_LIB") or os.path.join(_HERE, "libfasta_hip.so")
 
 # enums mirrored from include/fasta_hip.h ---------------------------------------------------------
-PROX_IDENTITY, PROX_SHRINK, PROX_NONNEG, PROX_LINF, PROX_L1BALL, PROX_TVBALL, PROX_BOX, PROX_GROUP = range(8)
-MAX_RHS = 16                       # columns of a matrix unknown (fh_set_rhs, fh_set_matrix_csr_rhs)
+PROX_IDENTITY, PROX_SHRINK, PROX_NONNEG, PROX_LINF, PROX_L1BALL, PROX_TVBALL, PROX_BOX, PROX_GROUP, PROX_ROWBALL = range(9)
+MAX_RHS = 16                       # columns of a matrix unknown (fh_set_rhs, fh_set_matrix_csr_rhs, fh_set_quadratic)
 (VEC_X0, VEC_G0, VEC_XHAT, VEC_XPROX, VEC_X1, VEC_G1, VEC_BEST, VEC_B, VEC_Z,
  VEC_T0, VEC_T1, VEC_T2, VEC_T3) = range(13)
 (S_FSQ, S_DXG0, S_DX2, S_XH2, S_G02, S_GSUM, S_GMAX, S_RDOT, S_DXDG, S_DG2, S_FSQ_ADJ, S_XH2_ADJ,
@@ -89,6 +89,9 @@ SIGNATURES = {
     "fh_tv3d_shape": (_i32, [_ctx, C.POINTER(C.c_uint32)]),
     "fh_tv3d_shape_for": (_i32, [_u64, _u64, _u64, _i32, _i32, C.POINTER(C.c_uint32)]),
     "fh_shape": (_i32, [_ctx, C.POINTER(_u64), C.POINTER(_u64)]),
+    "fh_set_quadratic": (_i32, [_ctx, _pd, _u64, _u64, _pd, C.c_uint32]),
+    "fh_quad_shape": (_i32, [_ctx, C.POINTER(C.c_uint32)]),
+    "fh_quad_shape_for": (_i32, [_u64, C.c_uint32, C.c_longlong, _i32, C.POINTER(C.c_uint32)]),
     "fh_set_rhs": (_i32, [_ctx, C.c_uint32]),
     "fh_rhs": (_i32, [_ctx, C.POINTER(C.c_uint32)]),
     "fh_multi_shape": (_i32, [_ctx, C.POINTER(C.c_uint32)]),
@@ -224,6 +227,19 @@ def multi_shape(m, n, L, slab_rows=0, grid_cap=0, nt_loads=-1):
     out = (C.c_uint32 * MULTI_SHAPE_LEN)()
     _check(lib, lib.fh_multi_shape_for(int(m), int(n), int(L), int(slab_rows), int(grid_cap), int(nt_loads), out))
     return MultiShape(*(int(v) for v in out))
+
+
+QUAD_SHAPE_LEN = 12
+QuadShape = collections.namedtuple("QuadShape", "LB CH R NT fwd_grid nrg ntrip last_live pass_max pass_min npro ngrad")
+
+
+def quad_shape(n, L, grid_cap=0, nt_loads=-1):
+    """QuadShape of the quadratic launches (csrc/fh_quad.h) for an (n, n) matrix and L columns under FH_TUNE_FWD_GRID_CAP (0 = auto) and
+    FH_TUNE_NT_LOADS (-1 = auto): fh_quad_shape_for, the rule the launchers call.  Host-only."""
+    lib = load_library()
+    out = (C.c_uint32 * QUAD_SHAPE_LEN)()
+    _check(lib, lib.fh_quad_shape_for(int(n), int(L), int(grid_cap), int(nt_loads), out))
+    return QuadShape(*(int(v) for v in out))
 
 
 TV3D_SHAPE_LEN = 8
@@ -451,6 +467,26 @@ class HipContext:
         out = (C.c_uint32 * TV3D_SHAPE_LEN)()
         self._call("fh_tv3d_shape", out)
         return Tv3dShape(*(int(v) for v in out))
+
+    def set_quadratic(self, Q, c=None, L=1):
+        """Operator and loss in one call (fh_set_quadratic): f(X) = .5 <X, Q X> + <c, X> with Q (n, n) float64 and EXACTLY symmetric, the unknown
+        (n, L), L in 1..16 (a vector unknown is L = 1), c of the unknown's shape or None.  The context takes the multi-column layout."""
+        Q = np.asarray(Q)
+        assert Q.ndim == 2 and Q.shape[0] == Q.shape[1]
+        if Q.dtype != np.float64 or not Q.flags.c_contiguous:
+            Q = np.ascontiguousarray(Q, dtype=np.float64)
+        n = Q.shape[0]
+        cp = None
+        if c is not None:
+            c, cp = _as_f64(np.ravel(c))
+            assert c.size == n * int(L)
+        self._call("fh_set_quadratic", Q.ctypes.data_as(_pd), n, n, cp, int(L))
+
+    def quad_shape(self):
+        """QuadShape the next fwd / adj of this context launches with (fh_quad_shape).  E_STATE without a quadratic operator."""
+        out = (C.c_uint32 * QUAD_SHAPE_LEN)()
+        self._call("fh_quad_shape", out)
+        return QuadShape(*(int(v) for v in out))
 
     def shape(self):
         m, n = _u64(0), _u64(0)

@@ -14,7 +14,8 @@ subclasses are *recognised* by `fasta()` and run on the device:
   SparseMatrixMap -- a sparse design matrix (any scipy.sparse matrix / array, or CSR arrays), kept on the
                      device by rows and by columns; both directions are gathers (csrc/fh_sparse.h; with `rhs=L`
                      the unknown is an (n, L) matrix and every entry gathers a whole row of it, csrc/fh_spmulti.h);
-  GradDivMap      -- the periodic div/grad stencil pair of examples/tv_denoising.py:26-63.
+  GradDivMap      -- the periodic div/grad stencil pair of examples/tv_denoising.py:26-63;
+  QuadraticMap    -- the identity operator of a quadratic smooth term (losses.Quadratic): what `fasta(None, None, q.f, q.gradf, ...)` runs on.
 
 A DenseMatrixMap built from a host ndarray uploads LAZILY: it keeps a reference to the array (as the
 closures of fasta/linalg.py:41 do) and copies it into HBM when the device loop first asks for its
@@ -35,7 +36,7 @@ from . import hip
 Matrix = np.ndarray
 Vector = np.ndarray
 
-__all__ = ["LinearMap", "LinearOperator", "DenseMatrixMap", "ShardedDenseMatrixMap", "SparseMatrixMap", "GradDivMap", "is_sparse_matrix", "Matrix", "Vector"]
+__all__ = ["LinearMap", "LinearOperator", "DenseMatrixMap", "ShardedDenseMatrixMap", "SparseMatrixMap", "GradDivMap", "QuadraticMap", "is_sparse_matrix", "Matrix", "Vector"]
 
 
 class LinearMap:
@@ -438,6 +439,37 @@ class SparseMatrixMap(_DeviceMap):
     @property
     def T(self):
         return self.H
+
+
+class QuadraticMap(_DeviceMap):
+    """The operator of `fasta(None, None, q.f, q.gradf, g, prox, x0)` with q = losses.Quadratic(Q, c): the identity on x0's shape.  Its device
+    context holds Q and c (fh_set_quadratic: operator and loss in one call, csrc/fh_quad.h) for an unknown of shape (n,) or (n, L), L <= 16.
+    Lazy like a map built from a host matrix; on host arrays it is the identity, as `A = None` is in the reference (examples/svm.py:74)."""
+
+    def __init__(self, loss, shape, device=0, tuning=None):
+        shape = tuple(int(k) for k in shape)
+        n = loss.Q.shape[0]
+        if len(shape) not in (1, 2) or shape[0] != n or (len(shape) == 2 and not 1 <= shape[1] <= hip.MAX_RHS):
+            raise ValueError(f"a quadratic loss on a {n} x {n} matrix takes an unknown of shape ({n},) or ({n}, L), L <= {hip.MAX_RHS} (got {shape})")
+        if loss.c is not None and loss.c.shape != shape:
+            raise ValueError(f"the linear term c has shape {loss.c.shape}, the unknown {shape}")
+        self.loss = loss
+        self.shape = (n, n)
+        self.rhs = shape[1] if len(shape) == 2 else 1
+        self.storage = "f64"
+        self._tuning = dict(tuning or {})
+        _DeviceMap.__init__(self, shape, shape, device, lazy=True)
+
+    def _on_context(self, ctx):
+        for key, value in self._tuning.items():
+            ctx.set_tuning(key, value)
+        ctx.set_quadratic(self.loss.Q, self.loss.c, self.rhs)
+
+    def _apply_fwd(self, v):
+        return v
+
+    def _apply_adj(self, w):
+        return w
 
 
 def _nd_grad(X):

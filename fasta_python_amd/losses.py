@@ -1,6 +1,6 @@
 """Smooth terms f(z) recognised by the device loop.
 
-LogisticLoss(b): see the class.  LeastSquares(b):  f(z) = .5*||z - b||^2,  gradf(z) = z - b   (examples/sparse_least_squares.py:41-42,
+LogisticLoss(b), Quadratic(Q, c): see the classes.  LeastSquares(b):  f(z) = .5*||z - b||^2,  gradf(z) = z - b   (examples/sparse_least_squares.py:41-42,
 same closures in lasso.py:42-43, nn_least_squares.py:39-40, tv_denoising.py:85-86 with b = M/mu).
 Pass `ls.f` and `ls.gradf` as the `f` / `gradf` arguments of `fasta()`.
 """
@@ -9,7 +9,7 @@ import math
 
 import numpy as np
 
-__all__ = ["LeastSquares", "LogisticLoss"]
+__all__ = ["LeastSquares", "LogisticLoss", "Quadratic"]
 
 
 class LeastSquares:
@@ -54,5 +54,43 @@ class LogisticLoss:
 
     def gradf(self, z):
         return -self.b / (1 + np.exp(self.b * z))
+
+    __call__ = f
+
+
+class Quadratic:
+    """f(x) = .5*<x, Q x> + <c, x>, gradf(x) = Q x + c on a SYMMETRIC float64 matrix Q, which may be indefinite; x is a vector (n,) or a
+    matrix (n, L), c has x's shape or is None.  The operator is the identity: `fasta(None, None, q.f, q.gradf, g, prox, x0)`.  Covers
+    examples/max_norm.py:49-50 (Q = S + S.T: sum(S * (X @ X.T)) = .5*<X, Q X>) and the dual of examples/svm.py:68-69
+    (Q = (l l^T) * (D D^T), c = -1), box-constrained QP and kernel-SVM duals in general.  On the device one product W = Q x gives both the
+    value and the gradient (csrc/fh_quad.h); on host arrays `f` / `gradf` are the closures below."""
+
+    def __init__(self, Q, c=None):
+        Q = np.asarray(Q)
+        if Q.ndim != 2 or Q.shape[0] != Q.shape[1]:
+            raise ValueError(f"Quadratic needs a square matrix Q (got shape {Q.shape})")
+        if Q.dtype != np.float64:
+            raise ValueError(f"Quadratic needs a float64 matrix Q (got {Q.dtype})")
+        if not np.array_equal(Q, Q.T):
+            i, j = (int(k) for k in np.argwhere(Q != Q.T)[0])
+            raise ValueError(f"Quadratic needs an exactly symmetric Q: Q[{i},{j}] = {float(Q[i, j])!r} but Q[{j},{i}] = {float(Q[j, i])!r} "
+                             "(pass (Q + Q.T) / 2, or S + S.T as examples/max_norm.py:50 does)")
+        self.Q = Q
+        self.c = None if c is None else np.ascontiguousarray(c, dtype=np.float64)
+
+    def bind(self, ctx):
+        """Nothing to do: Q and c reach the device with the operator (linalg.QuadraticMap: fh_set_quadratic is operator and loss in one call)."""
+
+    @staticmethod
+    def f_from_device(s):
+        return np.float64(s)                    # FH_S_FSQ carries f itself
+
+    def f(self, x):
+        v = .5 * np.sum(x * (self.Q @ x))
+        return v if self.c is None else v + np.sum(self.c * x)
+
+    def gradf(self, x):
+        w = self.Q @ x
+        return w if self.c is None else w + self.c
 
     __call__ = f

@@ -19,7 +19,7 @@ import numpy as np
 
 from . import hip
 
-__all__ = ["Shrink", "NonNeg", "LinfProx", "L1Ball", "Box", "TVDualBall", "GroupShrink", "NoProx", "device_prox", "release_scratch",
+__all__ = ["Shrink", "NonNeg", "LinfProx", "L1Ball", "Box", "TVDualBall", "GroupShrink", "RowBall", "NoProx", "device_prox", "release_scratch",
            "shrink", "project_Linf_ball", "project_L1_ball", "project_Lnuc_ball"]
 
 
@@ -150,6 +150,23 @@ class GroupShrink(ProxTag):
         return self.mu * np.sum(np.sqrt(np.sum(X * X, axis=1)))
 
 
+class RowBall(ProxTag):
+    """Max-norm constraint on a matrix unknown X of shape (N, K) (examples/max_norm.py:51-59): g = 0, and proxg(X, t) brings every ROW whose
+    Euclidean norm exceeds mu back to norm mu (rows inside the ball are kept; independent of t).  Couples the columns of a row; the device
+    serves it with a quadratic loss only (FH_PROX_ROWBALL, csrc/fh_quad.h)."""
+    kind = hip.PROX_ROWBALL
+    step_scaled = False
+
+    def __init__(self, mu):
+        self.mu = float(mu)
+
+    def prox(self, X, t):
+        norms = np.linalg.norm(X, axis=1)
+        # Shrink the norms that are too big, and ensure we don't divide by zero
+        scale = np.maximum(norms, self.mu) + (norms == 0)
+        return self.mu * X / scale[:, np.newaxis]
+
+
 # ---- the device prox on host arrays -----------------------------------------------------------------
 _scratch = {}            # (device, "dense", n) or (device, "tv", H, W) -> operator holding a scratch HipContext
 
@@ -161,6 +178,8 @@ def _matrix_form(tag, x):
     """Does device_prox take the multi-column kernels for `x`?  GroupShrink always (it couples the columns of a row, and refuses what the
     device cannot hold); an elementwise kind for a 2-D array of at most 16 columns -- same bits as the vector kernels on the flattened
     array.  Everything else (LinfProx / L1Ball on any shape, wider arrays, other ranks) is flattened and takes the vector kernels."""
+    if tag.kind == hip.PROX_ROWBALL:
+        raise ValueError("RowBall runs on the device with a quadratic loss only (losses.Quadratic): device_prox has no scratch operator for it")
     if tag.kind == hip.PROX_GROUP:
         if x.ndim != 2 or x.shape[1] > hip.MAX_RHS:
             raise ValueError(f"GroupShrink needs a 2-D array of at most {hip.MAX_RHS} columns (got shape {x.shape})")

@@ -15,7 +15,7 @@ of `FBSolver.step` below, bit for bit, without the interpreter between two launc
 Iterates, gradients and residual vectors never leave HBM unless `record_iterates` / `func` ask.
 
 Which loop runs is decided by the operand TYPES alone (`_recognise`), never by whether a GPU happens to be there:
-  * device-recognisable operands (matrix / DenseMatrixMap / GradDivMap + tagged loss + tagged prox) run the HIP loop
+  * device-recognisable operands (matrix / DenseMatrixMap / GradDivMap + tagged loss + tagged prox; `A=None` + losses.Quadratic) run the HIP loop
     below and RAISE when libfasta_hip.so or the GPU is missing -- there is no CPU fallback for them;
   * anything else -- Python closures, a callable pair, `A=None`, a host LinearMap: the forms the reference's own
     examples pass -- cannot execute inside a kernel and runs the generic host loop (generic.py, reference semantics,
@@ -30,8 +30,8 @@ from time import time
 import numpy as np
 
 from . import hip, stopping
-from .linalg import DenseMatrixMap, GradDivMap, LinearMap, SparseMatrixMap, _DeviceMap, is_sparse_matrix
-from .losses import LeastSquares, LogisticLoss
+from .linalg import DenseMatrixMap, GradDivMap, LinearMap, QuadraticMap, SparseMatrixMap, _DeviceMap, is_sparse_matrix
+from .losses import LeastSquares, LogisticLoss, Quadratic
 from .proximal import NoProx, ProxTag
 
 __all__ = ["fasta", "Convergence", "FBSolver", "EPSILON"]
@@ -121,8 +121,41 @@ def _sparse_form_refusal(A, loss, prox, x0):
     return None
 
 
+def _quadratic_form_refusal(A, At, loss_f, loss_g, g, proxg, x0):
+    """`fasta(None, None, q.f, q.gradf, g, prox, x0)` with q = losses.Quadratic(Q, c): the device serves it through fh_set_quadratic
+    (csrc/fh_quad.h) for a vector or a matrix unknown of at most 16 columns, with the elementwise prox kinds, GroupShrink and RowBall.
+    None, or the reason."""
+    from .proximal import GroupShrink, L1Ball, LinfProx, RowBall, TVDualBall
+    if loss_f is None or loss_f is not loss_g:
+        return "f and gradf must be the `.f` / `.gradf` of one losses.Quadratic(Q, c) object"
+    if A is not None or At is not None:
+        return "A must be None with a quadratic loss: losses.Quadratic(Q, c) holds the matrix, the operator is the identity"
+    n = loss_f.Q.shape[0]
+    shape = None if x0 is None else tuple(np.shape(x0))
+    if shape is not None and (len(shape) not in (1, 2) or shape[0] != n):
+        return f"x0 has shape {shape}: a quadratic loss on a {n} x {n} matrix takes an unknown of shape ({n},) or ({n}, L)"
+    if shape is not None and len(shape) == 2 and not 1 <= shape[1] <= hip.MAX_RHS:
+        return f"a 2-D x0 has at most {hip.MAX_RHS} columns on the device (x0 has {shape[1]})"
+    if shape is not None and loss_f.c is not None and loss_f.c.shape != shape:
+        return f"c must have x0's shape (c has {loss_f.c.shape}, x0 has {shape})"
+    if g is None and proxg is None:
+        return None
+    prox, owner_g = _tag_of(proxg, ProxTag), _tag_of(g, ProxTag)
+    if prox is None or (owner_g is not None and owner_g is not prox) or (owner_g is None and g is not None):
+        return ("g and proxg must be the `.g` / `.prox` of one proximal.* tag object "
+                "(Shrink, NonNeg, Box, GroupShrink, RowBall)")
+    if isinstance(prox, (LinfProx, L1Ball, TVDualBall)):
+        return f"proximal.{type(prox).__name__} has no quadratic form on the device (LinfProx, L1Ball and TVDualBall have no quadratic form)"
+    if isinstance(prox, (RowBall, GroupShrink)) and shape is not None and len(shape) != 2:
+        return f"proximal.{type(prox).__name__} couples the columns of a row: RowBall and GroupShrink need a 2-D x0 of shape (n, L)"
+    return None
+
+
 def _unrecognised(A, At, f, gradf, g, proxg, x0=None):
     """None when the seven operands can run on the device, else the reason they cannot (a sentence)."""
+    quad_f, quad_g = _tag_of(f, Quadratic), _tag_of(gradf, Quadratic)
+    if quad_f is not None or quad_g is not None:
+        return _quadratic_form_refusal(A, At, quad_f, quad_g, g, proxg, x0)
     if not isinstance(A, (np.ndarray, _DeviceMap)) and not is_sparse_matrix(A):
         return ("operator A is not device-resident (pass a 2-D float64 ndarray, a scipy.sparse matrix, a linalg.DenseMatrixMap / "
                 "LinearMap.from_matrix(A), a linalg.SparseMatrixMap or a linalg.GradDivMap); arbitrary Python callables cannot run inside the fused HIP kernels")
@@ -135,11 +168,17 @@ def _unrecognised(A, At, f, gradf, g, proxg, x0=None):
     if prox is None or (owner_g is not None and owner_g is not prox) or (owner_g is None and g is not None):
         return ("g and proxg must be the `.g` / `.prox` of one proximal.* tag object "
                 "(Shrink, NonNeg, LinfProx, L1Ball, Box, TVDualBall, GroupShrink)")
+    if prox.kind == hip.PROX_ROWBALL:
+        return "proximal.RowBall is served on the device with a quadratic loss only: fasta(None, None, q.f, q.gradf, ...) with q = losses.Quadratic(Q, c)"
     return _sparse_form_refusal(A, loss_f, prox, x0) or _matrix_form_refusal(A, loss_f, prox, x0)
 
 
 def _recognise(A, At, f, gradf, g, proxg, x0):
     """Map the reference's seven operands onto device objects (call only when `_unrecognised` returned None)."""
+    quad = _tag_of(f, Quadratic)
+    if quad is not None:                               # A = None: the identity; Q and c travel with the operator
+        prox = NoProx() if (g is None and proxg is None) else _tag_of(proxg, ProxTag)
+        return QuadraticMap(quad, x0.shape), quad, prox
     if isinstance(A, np.ndarray):
         if A.ndim != 2:
             raise AssertionError("matrix operator must be 2-D")            # linalg.py:40
@@ -575,7 +614,7 @@ def fasta(A, *operands, backend="auto", **options):
         x0 = np.asarray(x0)
         return HostFBS(host_map(A, At, x0), f, gradf, g, proxg, x0, **options).setup().run()
     x0 = np.asarray(x0, dtype=np.float64)
-    owns = isinstance(A, np.ndarray) or is_sparse_matrix(A)
+    owns = A is None or isinstance(A, np.ndarray) or is_sparse_matrix(A)
     A, loss, prox = _recognise(A, At, f, gradf, g, proxg, x0)
     try:
         return FBSolver(A, loss, prox, x0, **options).setup().run()

@@ -46,9 +46,12 @@ enum fh_prox_kind {
   FH_PROX_L1BALL   = 4,  /* proximal.project_L1_ball(x, mu), fasta/proximal.py:34-41     */
   FH_PROX_TVBALL   = 5,  /* per-pixel 2-vector / max(norm,1), examples/tv_denoising.py:89-96 */
   FH_PROX_BOX      = 6,  /* clip to [lo, hi], examples/svm.py:71                         */
-  FH_PROX_GROUP    = 7   /* row-wise l2 shrink of an (n, L) matrix, examples/mmv.py:51-59: with nu = ||xhat_j||_2 over the L entries of row j,
+  FH_PROX_GROUP    = 7,  /* row-wise l2 shrink of an (n, L) matrix, examples/mmv.py:51-59: with nu = ||xhat_j||_2 over the L entries of row j,
                             xprox_j = xhat_j * max(nu - t*mu, 0) / (nu + (nu == 0)).  Multi-column form only (fh_set_rhs, fh_set_matrix_csr_rhs).  FH_S_GSUM /
                             FH_S_GSUM_ADJ then carry sum_j ||xprox_j||_2 (of x1), so that g = mu * gsum; FH_S_GMAX is unchanged.            */
+  FH_PROX_ROWBALL  = 8   /* row-wise projection of an (n, L) matrix, examples/max_norm.py:53-59: with nu = ||xhat_j||_2 over the L entries of row j,
+                            xprox_j = (mu * xhat_j) / (max(nu, mu) + (nu == 0)) -- independent of the step; g = 0, so the objective adds nothing for it.
+                            Served by the quadratic operator only (fh_set_quadratic); every other operator refuses it with a sentence.        */
 };
 
 /* device vectors addressable through fh_set_vector / fh_get_vector                      */
@@ -238,6 +241,36 @@ int fh_set_stencil3d(fh_ctx* ctx, uint64_t D, uint64_t H, uint64_t W);
 int fh_tv3d_shape(fh_ctx* ctx, uint32_t* out);
 int fh_tv3d_shape_for(uint64_t D, uint64_t H, uint64_t W, int planes, int ncu, uint32_t* out);
 int fh_shape(fh_ctx* ctx, uint64_t* m, uint64_t* n);
+
+/* ---- quadratic smooth term on an explicit symmetric matrix: f(X) = .5 <X, Q X> + <C, X>, A = identity (csrc/fh_quad.h) -----------------------
+ * examples/max_norm.py:49-50 (Q = S + S^T, C = 0, X of shape (N, K)) and the dual of examples/svm.py:68-69 (Q = (l l^T) o (D D^T), C = -1, the box
+ * prox of :71); box-constrained QP and kernel-SVM duals in general.  Q may be indefinite, and C need not lie in any range: this is not
+ * .5 ||A x - b||^2 for any A.  ONE call sets the operator (m = n; fh_shape reports (n, n)) AND the loss: Q row-major float64 with leading dimension
+ * ld_host, stored like a dense A (padded, zero padding, through the kept-block allocator); C a contiguous (n, L) array or NULL for zero; L in 1..16
+ * columns of the unknown (L = 1: a vector unknown).  Q must be EXACTLY symmetric: checked on the host, FH_E_ARG names the first (i, j) with
+ * Q[i,j] != Q[j,i].  The context takes the multi-column layout (LB in {2, 4, 8, 16}, the smallest >= L; fh_rhs reports L): fh_set_vector,
+ * fh_get_vector and fh_apply take contiguous (n, L) arrays; fh_apply is out = Q in, whatever the adjoint flag; FH_VEC_Z holds W = Q xprox and
+ * FH_VEC_B holds C.  One product W = Q X gives the value .5 <X, W> + <C, X> and the gradient W + C: an attempt of the step reads Q once, the
+ * second direction is an elementwise launch.  FH_S_FSQ / FH_S_FSQ_ADJ carry f ITSELF (it may be negative), as for the logistic loss.
+ * Served: fh_init, fh_setup (its three-pass route), fh_gradient_at (dst = Q src + C), fh_diff_norm, fh_commit, fh_fwd, fh_adj (accel / coef),
+ * fh_fwd_adj, fh_iterate, fh_timing_*; prox kinds IDENTITY, SHRINK, NONNEG, BOX, GROUP and ROWBALL; FH_TUNE_FWD_GRID_CAP and FH_TUNE_NT_LOADS.
+ * Refused, each with a sentence: L = 0 or L > 16 (FH_E_ARG); a multi-device context, a context with a communicator (and fh_comm_init on a
+ * quadratic context), float32 storage (FH_E_STATE); fh_set_loss_lsq / fh_set_loss_logistic and fh_set_rhs on a quadratic context (FH_E_STATE: the
+ * loss and the column count are part of the operator); FH_PROX_LINF / L1BALL / TVBALL (FH_E_ARG; a context holding one of these returns to
+ * IDENTITY when the operator is set); fh_step* and fh_run (FH_E_STATE; fh_fused_supported, fh_fused_agree and fh_run_supported report 0);
+ * fh_get_matrix_rows, fh_stream_read_ms.  Setting any other operator returns the context to the vector form, the least-squares loss and -- if it
+ * held ROWBALL -- the IDENTITY prox.                                                                                                        */
+int fh_set_quadratic(fh_ctx* ctx, const double* Q, uint64_t n, uint64_t ld_host, const double* c, uint32_t L);
+/* read-only: the geometry the quadratic launches take (csrc/fh_host_launch.h: qd_shape_for, the ONE rule both launchers call).
+ * out[FH_QUAD_SHAPE_LEN] = { LB, CH (columns a lane of K-fwd carries), R (rows of Q per K-fwd pass), NT (1: the non-temporal instantiations),
+ * K-fwd grid, nrg (row groups the grid strides over), ntrip (trips of a lane group along a row), lanes of a lane group that hold a piece of
+ * the row in the LAST trip (the others are clamped), most and fewest passes a workgroup of K-fwd makes (they differ when the grid does not
+ * divide nrg), prologue workgroups, workgroups of the elementwise gradient launch }.  fh_quad_shape reads the context (FH_TUNE_FWD_GRID_CAP,
+ * FH_TUNE_NT_LOADS) and is FH_E_STATE without a quadratic operator; fh_quad_shape_for is the same rule as a pure host function (no device
+ * needed) of n, L and the two tuning values as fh_set_tuning takes them (0 = auto; nt_loads: -1 = auto, 0, 1).                          */
+#define FH_QUAD_SHAPE_LEN 12
+int fh_quad_shape(fh_ctx* ctx, uint32_t* out);
+int fh_quad_shape_for(uint64_t n, uint32_t L, long long grid_cap, int nt_loads, uint32_t* out);
 
 /* ---- multi-column form: the unknown is an (n, L) MATRIX, one A for all L columns (examples/mmv.py; multi-column LASSO / NNLS) -----------
  * fh_set_rhs(ctx, L), L in 1..16, on a plain single-device context with a dense float64 operator (a sparse one: fh_set_matrix_csr_rhs above): every n-side vector (FH_VEC_X0 .. BEST,
