@@ -1321,7 +1321,7 @@ static int launch_tv_onepass(fh_ctx* c, double tau, int accel, double coef, int 
     p.rows_wg = std::min(p.H, std::max(min_rows, (p.H + chunks - 1) / chunks));
   }
   // rows per trip / rotating trip buffers: 2 rows, load-then-consume for the plain sweep; 4 rows x 3 rotating buffers with FISTA
-  // (two streams to read): profiles/r03_tune_tv.txt.  Every combination produces the same bits (scripts/probes/tune_tvz.py).
+  // (two streams to read): profiles/r03_tune_tv.txt.  Every combination produces the same bits (tests/test_gpu_tv_paths.py).
   const int tvu = c->tv_u ? c->tv_u : (accel ? 4 : 2);
   if (accel) { p.p1 = nq(c, c->lq1); p.p0 = nq(c, c->lq0); p.pn = nq(c, c->lqn); p.cprev = c->lc; }
   else { p.p1 = c->X[c->xi]; p.p0 = c->X[c->xi]; p.pn = c->P[c->pc ^ 1]; p.cprev = 0.0; }
