@@ -1,5 +1,5 @@
 // fasta_hip.hip -- the C ABI of libfasta_hip.so (declared in include/fasta_hip.h): entry points only.  The context and its helpers are
-// in fh_host_ctx.h, the kernel launchers in fh_host_launch.h, the kernels in fh_dense.h / fh_multi.h / fh_quad.h / fh_tv.h / fh_prox.h / fh_fused.h.
+// in fh_host_ctx.h, the kernel launchers in fh_host_launch.h, the kernels in fh_dense.h / fh_multi.h / fh_quad.h / fh_bilinear.h / fh_tv.h / fh_prox.h / fh_fused.h.
 // gfx950 only.  No PyTorch, no rocBLAS: every device operation is a kernel from fh_dense.h / fh_tv.h,
 // plus RCCL (dlopen'ed on first use) for the row-sharded adjoint.
 #include <hip/hip_runtime.h>
@@ -18,6 +18,7 @@
 #include "fh_dense.h"
 #include "fh_multi.h"
 #include "fh_quad.h"
+#include "fh_bilinear.h"
 #include "fh_sparse.h"
 #include "fh_spmulti.h"
 #include "fh_tv.h"
@@ -653,6 +654,7 @@ extern "C" int fh_get_matrix_rows(fh_ctx* c, uint64_t row0, uint64_t nrows, doub
   if (c->op == OP_SPARSE) return fail(FH_E_STATE, "fh_get_matrix_rows: the sparse operator keeps no dense rows");
   if (c->op == OP_STENCIL3D) return fail(FH_E_STATE, "fh_get_matrix_rows: the 3-D stencil operator keeps no dense rows");
   if (c->op == OP_QUAD) return fail(FH_E_STATE, "fh_get_matrix_rows: the quadratic operator is not read back (the caller holds Q)");
+  if (c->op == OP_BILINEAR) return fail(FH_E_STATE, "fh_get_matrix_rows: the bilinear operator is not read back (the caller holds S)");
   if (c->op != OP_DENSE) return fail(FH_E_STATE, "no dense matrix set");
   if (row0 + nrows > c->m) return fail(FH_E_ARG, "rows [%llu,%llu) out of range (m=%llu)", (unsigned long long)row0,
                                        (unsigned long long)(row0 + nrows), (unsigned long long)c->m);
@@ -744,6 +746,7 @@ extern "C" int fh_set_rhs(fh_ctx* c, uint32_t L) {
   if (c->op == OP_SPARSE) return fail(FH_E_STATE, "fh_set_rhs: the sparse operator has no multi-column form through fh_set_rhs: its column count is fixed when it is set (fh_set_matrix_csr_rhs)");
   if (c->op == OP_STENCIL3D) return fail(FH_E_STATE, "fh_set_rhs: the 3-D stencil operator has no multi-column form");
   if (c->op == OP_QUAD) return fail(FH_E_STATE, "fh_set_rhs: the column count of a quadratic operator is fixed when it is set (fh_set_quadratic)");
+  if (c->op == OP_BILINEAR) return fail(FH_E_STATE, "fh_set_rhs: the column count of a bilinear operator is fixed when it is set (fh_set_factorization)");
   if (c->op != OP_DENSE) return fail(FH_E_STATE, "fh_set_rhs: the stencil operator has no multi-column form");
   if (c->f32) return fail(FH_E_STATE, "fh_set_rhs: float32 storage of A has no multi-column form");
   if (L && c->has_b && c->loss_kind != LOSS_LSQ) return fail(FH_E_STATE, "fh_set_rhs: the logistic loss has no multi-column form");
@@ -816,10 +819,65 @@ extern "C" int fh_set_quadratic(fh_ctx* c, const double* Q, uint64_t n, uint64_t
   return 0;
 }
 
+// ---- bilinear smooth term f(Z) = .5 ||S - X Y^T||^2, Z = [X; Y], A = identity (csrc/fh_bilinear.h): operator and loss in one call ----
+extern "C" int fh_set_factorization(fh_ctx* c, const double* S, uint64_t m, uint64_t n, uint64_t ld_host, uint32_t K) {
+  if (!c || !S) return fail(FH_E_ARG, "fh_set_factorization: null argument");
+  if (K < 1 || K > 16) return fail(FH_E_ARG, "fh_set_factorization: 1 to 16 columns (got %u)", K);
+  if (!c->shards.empty() || c->owner) return fail(FH_E_STATE, "fh_set_factorization: a multi-device context has no bilinear operator (row sharding is implemented for the dense operator only)");
+  if (c->comm) return fail(FH_E_STATE, "fh_set_factorization: a context with a communicator (row-sharded run) has no bilinear operator");
+  if (c->pending_step) return fail(FH_E_STATE, "a step issued by fh_step_begin is still in flight on this context: call fh_step_end first");
+  if (c->f32) return fail(FH_E_STATE, "fh_set_factorization: float32 storage has no bilinear operator");
+  if (m == 0 || n == 0) return fail(FH_E_ARG, "fh_set_factorization: the matrix must be non-empty");
+  if (ld_host < n) return fail(FH_E_ARG, "fh_set_factorization: ld_host %llu < n %llu", (unsigned long long)ld_host, (unsigned long long)n);
+  if (m >= (1ull << 27) || n >= (1ull << 27)) return fail(FH_E_ARG, "fh_set_factorization: m + n must be below 2^27 (the row offsets (m + n) * LB are kept in 31 bits)");
+  const uint32_t LB = lb_for(K);
+  const uint64_t ld = round_up(n, 16) + (uint64_t)c->ld_pad;
+  if (const char* why = bl_too_large(m, n, bl_shape_for(m, n, ld, LB, c->fwd_cap, c->nt_loads))) return fail(FH_E_ARG, "fh_set_factorization: %s", why);
+  FH_TRY(use_device(c));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  free_operator(c);
+  if (!bl_prox_ok(c->prox_kind)) { c->prox_kind = FH_PROX_IDENTITY; c->mu = 0.0; }
+  c->lazy = false; c->last_accel = false; c->commits = 0;
+  c->bl_m = m; c->bl_n = n;
+  c->m = m + n; c->n = m + n;
+  c->mp = round_up(m, 16);
+  c->ld = ld;
+  c->nv = round_up(m + n, 16); c->mv = c->nv;
+  c->L = K; c->LB = LB;
+  const size_t s_bytes = (size_t)c->mp * c->ld * sizeof(double);
+  HIP_TRY(acquire_matrix_block(c->device, s_bytes, &c->A, &c->a_block_bytes));
+  c->op = OP_BILINEAR;                                   // (from here on free_operator gives the block back)
+  int rc = alloc_vectors(c);
+  if (rc == 0 && hipMemsetAsync(c->A, 0, s_bytes, c->stream) != hipSuccess) rc = fail(FH_E_STATE, "fh_set_factorization: clearing the device copy of S failed");
+  if (rc == 0 && hipMemcpy2DAsync(c->A, c->ld * sizeof(double), S, ld_host * sizeof(double), n * sizeof(double), m, hipMemcpyHostToDevice, c->stream) != hipSuccess)
+    rc = fail(FH_E_STATE, "fh_set_factorization: the copy of S to the device failed");
+  if (rc == 0) rc = finish(c);
+  if (rc != 0) { free_operator(c); return rc; }
+  c->loss_kind = LOSS_BILINEAR; c->has_b = true;
+  return 0;
+}
+
+extern "C" int fh_set_prox_split(fh_ctx* c, uint64_t split, int kind_top, double mu_top, double lo_top, double hi_top,
+                                 int kind_bottom, double lo_bottom, double hi_bottom) {
+  if (!c) return fail(FH_E_ARG, "null context");
+  if (c->op != OP_BILINEAR) return fail(FH_E_STATE, "FH_PROX_ROWSPLIT (one elementwise prox on the top rows, another on the others) is served by the bilinear operator only: call fh_set_factorization first");
+  if (split != c->bl_m) return fail(FH_E_ARG, "fh_set_prox_split: split must equal m = %llu, the rows of the first factor (got %llu)", (unsigned long long)c->bl_m, (unsigned long long)split);
+  if (kind_top != FH_PROX_IDENTITY && kind_top != FH_PROX_SHRINK && kind_top != FH_PROX_NONNEG && kind_top != FH_PROX_BOX)
+    return fail(FH_E_ARG, "fh_set_prox_split: the top rows take IDENTITY, SHRINK, NONNEG or BOX (got kind %d)", kind_top);
+  if (kind_bottom != FH_PROX_IDENTITY && kind_bottom != FH_PROX_NONNEG && kind_bottom != FH_PROX_BOX)
+    return fail(FH_E_ARG, "fh_set_prox_split: the bottom rows take IDENTITY, NONNEG or BOX (got kind %d): the l1 term lives on the first factor only", kind_bottom);
+  if (kind_top == FH_PROX_BOX && !(lo_top <= hi_top)) return fail(FH_E_ARG, "box prox needs lo <= hi");
+  if (kind_bottom == FH_PROX_BOX && !(lo_bottom <= hi_bottom)) return fail(FH_E_ARG, "box prox needs lo <= hi");
+  c->prox_kind = FH_PROX_ROWSPLIT; c->mu = mu_top; c->lo = lo_top; c->hi = hi_top;
+  c->rs_split = split; c->rs_kind_top = kind_top; c->rs_kind_bot = kind_bottom; c->rs_lo_bot = lo_bottom; c->rs_hi_bot = hi_bottom;
+  return 0;
+}
+
 static int set_loss(fh_ctx* c, int kind, const double* b, uint64_t len) {
   if (!c || !b) return fail(FH_E_ARG, "null argument");
   if (c->op == OP_NONE) return fail(FH_E_STATE, "set the operator before the loss");
   if (c->op == OP_QUAD) return fail(FH_E_STATE, "the quadratic operator carries its own loss (Q and the linear term of fh_set_quadratic): fh_set_loss_lsq / fh_set_loss_logistic do not apply");
+  if (c->op == OP_BILINEAR) return fail(FH_E_STATE, "the bilinear operator carries its own loss (S of fh_set_factorization): fh_set_loss_lsq / fh_set_loss_logistic do not apply");
   if (len != c->m * l_of(c)) return fail(FH_E_ARG, "b has %llu entries, operator has %llu rows (x %llu columns)", (unsigned long long)len, (unsigned long long)c->m, (unsigned long long)l_of(c));
   if (kind != LOSS_LSQ && c->LB) return fail(FH_E_STATE, "the logistic loss has no multi-column form (fh_set_rhs / fh_set_matrix_csr_rhs)");
   if (kind != LOSS_LSQ && c->op == OP_STENCIL3D) return fail(FH_E_STATE, "the 3-D stencil operator serves the least-squares loss only (the logistic loss is implemented for the dense and sparse operators)");
@@ -846,7 +904,9 @@ extern "C" int fh_set_loss_logistic(fh_ctx* c, const double* labels, uint64_t le
 
 extern "C" int fh_set_prox(fh_ctx* c, int kind, double mu, double lo, double hi) {
   if (!c) return fail(FH_E_ARG, "null context");
+  if (kind == FH_PROX_ROWSPLIT) return fail(FH_E_ARG, "unknown prox kind %d for fh_set_prox: FH_PROX_ROWSPLIT takes two kinds and their parameters, set it with fh_set_prox_split (bilinear operator only)", kind);
   if (kind < FH_PROX_IDENTITY || kind > FH_PROX_ROWBALL) return fail(FH_E_ARG, "unknown prox kind %d", kind);
+  if (c->op == OP_BILINEAR && !bl_prox_ok(kind)) return fail(FH_E_ARG, "prox kind %d (LINF / L1BALL / TVBALL / GROUP / ROWBALL) has no bilinear form", kind);
   if (kind == FH_PROX_ROWBALL && c->op != OP_QUAD) return fail(FH_E_ARG, "FH_PROX_ROWBALL (row-wise projection onto the ball of radius mu) is served by the quadratic operator only: call fh_set_quadratic first");
   if (c->op == OP_QUAD && !qd_prox_ok(kind)) return fail(FH_E_ARG, "prox kind %d (LINF / L1BALL / TVBALL) has no quadratic form", kind);
   if (kind == FH_PROX_GROUP && !c->LB) return fail(FH_E_ARG, "FH_PROX_GROUP (row-wise l2 shrink) needs the multi-column form: call fh_set_rhs (dense operator) or fh_set_matrix_csr_rhs (sparse operator) first");
@@ -1360,6 +1420,7 @@ static int step_body(fh_ctx* c, double tau, double* scalars, bool wait) {
   if (c->op == OP_SPARSE) return fail(FH_E_STATE, "fh_step: the sparse operator has no one-pass kernel: use fh_fwd / fh_adj / fh_fwd_adj / fh_iterate");
   if (c->op == OP_STENCIL3D) return fail(FH_E_STATE, "fh_step: the 3-D stencil operator has no one-pass kernel: use fh_fwd / fh_adj / fh_fwd_adj / fh_iterate");
   if (c->op == OP_QUAD) return fail(FH_E_STATE, "fh_step: the quadratic operator has no one-pass kernel: use fh_fwd / fh_adj / fh_fwd_adj / fh_iterate");
+  if (c->op == OP_BILINEAR) return fail(FH_E_STATE, "fh_step: the bilinear operator has no one-pass kernel: use fh_fwd / fh_adj / fh_fwd_adj / fh_iterate");
   if (c->LB) return fail(FH_E_STATE, "fh_step: the multi-column form (fh_set_rhs) has no one-pass kernel: use fh_fwd / fh_adj / fh_iterate");
   for (int k = 0; k < nshards(c); ++k) FH_TRY(not_lazy(shard_of(c, k), "fh_step"));
   if (c->op == OP_STENCIL) {
@@ -1408,6 +1469,7 @@ extern "C" int fh_step_accel(fh_ctx* c, double tau, double coef, int restart, do
   if (c->op == OP_SPARSE) return fail(FH_E_STATE, "fh_step_accel: the sparse operator has no one-pass kernel: use fh_fwd / fh_adj / fh_iterate");
   if (c->op == OP_STENCIL3D) return fail(FH_E_STATE, "fh_step_accel: the 3-D stencil operator has no one-pass kernel: use fh_fwd / fh_adj / fh_iterate");
   if (c->op == OP_QUAD) return fail(FH_E_STATE, "fh_step_accel: the quadratic operator has no one-pass kernel: use fh_fwd / fh_adj / fh_iterate");
+  if (c->op == OP_BILINEAR) return fail(FH_E_STATE, "fh_step_accel: the bilinear operator has no one-pass kernel: use fh_fwd / fh_adj / fh_iterate");
   if (c->LB) return fail(FH_E_STATE, "fh_step_accel: the multi-column form (fh_set_rhs) has no one-pass kernel: use fh_fwd / fh_adj / fh_iterate");
   if (c->op == OP_STENCIL) {
     if (row_sharded(c)) return fail(FH_E_STATE, "row sharding is implemented for the dense operator only");
@@ -1512,7 +1574,7 @@ static void run_opts_in(const fh_run_opts* o, RunOpts* r) {
   r->stepsize_shrink = o->stepsize_shrink; r->tolerance = o->tolerance;
 }
 // g(x) from the prox's reductions (proximal.py: g_from_sums)
-static int g_kind_of(const fh_ctx* c) { return (c->prox_kind == FH_PROX_SHRINK || c->prox_kind == FH_PROX_GROUP) ? FC_G_SUM : (c->prox_kind == FH_PROX_LINF ? FC_G_MAX : FC_G_NONE); }
+static int g_kind_of(const fh_ctx* c) { return (c->prox_kind == FH_PROX_SHRINK || c->prox_kind == FH_PROX_GROUP || (c->prox_kind == FH_PROX_ROWSPLIT && c->rs_kind_top == FH_PROX_SHRINK)) ? FC_G_SUM : (c->prox_kind == FH_PROX_LINF ? FC_G_MAX : FC_G_NONE); }
 static int run_adopt(fh_ctx* c, const fh_run_opts* o, const RunState* hs, double* const (&nb)[5], int max_steps, fh_run_state* state, double* history, int* steps_done, const char* what);
 static int run_chain(fh_ctx* c, int max_steps, const fh_run_opts* o, fh_run_state* state, double* history, int* steps_done);
 extern "C" int fh_run(fh_ctx* c, int max_steps, const fh_run_opts* o, fh_run_state* state, double* history, int* steps_done) {
@@ -1524,6 +1586,7 @@ extern "C" int fh_run(fh_ctx* c, int max_steps, const fh_run_opts* o, fh_run_sta
   if (c->op == OP_SPARSE) return fail(FH_E_STATE, "fh_run: the sparse operator has no device-side loop: use fh_iterate");
   if (c->op == OP_STENCIL3D) return fail(FH_E_STATE, "fh_run: the 3-D stencil operator has no device-side loop: use fh_iterate");
   if (c->op == OP_QUAD) return fail(FH_E_STATE, "fh_run: the quadratic operator has no device-side loop: use fh_iterate");
+  if (c->op == OP_BILINEAR) return fail(FH_E_STATE, "fh_run: the bilinear operator has no device-side loop: use fh_iterate");
   if (c->LB) return fail(FH_E_STATE, "fh_run: the multi-column form (fh_set_rhs) has no device-side loop: use fh_iterate");
   const RunEntry* e = run_entry(c);
   if (!e && chain_ok(c) && co_resident(c)) return run_chain(c, max_steps, o, state, history, steps_done);
@@ -1712,6 +1775,7 @@ extern "C" int fh_commit(fh_ctx* c, int save_best) {
 
 extern "C" int fh_apply(fh_ctx* c, int adjoint, const double* in, double* out) {
   FH_TRY(check_ready(c, false));
+  if (c->op == OP_BILINEAR) return fail(FH_E_STATE, "fh_apply: the bilinear operator has no linear map to apply (A is the identity; S enters through the smooth term: fh_gradient_at)");
   if (!in || !out) return fail(FH_E_ARG, "null argument");
   const int ns = nshards(c);
   const bool shell = !c->shards.empty();
@@ -1757,6 +1821,7 @@ extern "C" int fh_comm_init(fh_ctx* c, int nranks, int rank, const void* id128) 
   if (c->op == OP_SPARSE) return fail(FH_E_STATE, "fh_comm_init: a context with a sparse operator cannot be row-sharded");
   if (c->op == OP_STENCIL3D) return fail(FH_E_STATE, "fh_comm_init: a context with a 3-D stencil operator cannot be row-sharded");
   if (c->op == OP_QUAD) return fail(FH_E_STATE, "fh_comm_init: a context with a quadratic operator cannot be row-sharded");
+  if (c->op == OP_BILINEAR) return fail(FH_E_STATE, "fh_comm_init: a context with a bilinear operator cannot be row-sharded");
   if (c->LB) return fail(FH_E_STATE, "fh_comm_init: a context in multi-column form (fh_set_rhs) cannot be row-sharded");
   if (!c->shards.empty() || c->owner)
     return fail(FH_E_STATE, "fh_comm_init: a multi-device context (fh_create_ex, ndev > 1) already shards the rows in-process");
@@ -1949,6 +2014,7 @@ extern "C" int fh_stream_read_ms(fh_ctx* c, int reps, double* ms_per_pass, uint6
   if (c->op == OP_SPARSE) return fail(FH_E_STATE, "fh_stream_read_ms: the stream-read ceiling is measured on a dense matrix, not on the sparse operator");
   if (c->op == OP_STENCIL3D) return fail(FH_E_STATE, "fh_stream_read_ms: the stream-read ceiling is measured on a dense matrix, not on the 3-D stencil operator");
   if (c->op == OP_QUAD) return fail(FH_E_STATE, "fh_stream_read_ms: the stream-read ceiling is measured on a dense matrix, not on the quadratic operator");
+  if (c->op == OP_BILINEAR) return fail(FH_E_STATE, "fh_stream_read_ms: the stream-read ceiling is measured on a dense matrix, not on the bilinear operator");
   if (c->op != OP_DENSE) return fail(FH_E_STATE, "stream-read ceiling needs a dense matrix");
   if (reps < 1) reps = 1;
   // k_stream_probe<16,1> as described in include/fasta_hip.h: persistent workgroups, 1 per CU by default, three rotating buffers of 16 nt loads per lane

@@ -97,7 +97,7 @@ static int rccl_load() {
 // ------------------------------------------------------------------------------------------------
 // context
 // ------------------------------------------------------------------------------------------------
-enum { OP_NONE = 0, OP_DENSE = 1, OP_STENCIL = 2, OP_SPARSE = 3, OP_STENCIL3D = 4, OP_QUAD = 5 };
+enum { OP_NONE = 0, OP_DENSE = 1, OP_STENCIL = 2, OP_SPARSE = 3, OP_STENCIL3D = 4, OP_QUAD = 5, OP_BILINEAR = 6 };
 
 struct fh_ctx {
   int device = 0;
@@ -109,6 +109,18 @@ struct fh_ctx {
   int f32 = 0;               // storage of A: 0 = float64, 1 = float32 (opt-in, fh_create_ex; vectors and arithmetic stay float64)
   uint64_t nv = 0, mv = 0;   // allocated n-side / m-side vector lengths (doubles; rows of LB doubles in multi-column form)
   uint32_t L = 0, LB = 0;    // multi-column form (fh_set_rhs, csrc/fh_multi.h; fh_set_matrix_csr_rhs, csrc/fh_spmulti.h; fh_set_quadratic, csrc/fh_quad.h): L columns per unknown, kept as LB in {2, 4, 8, 16} doubles per row; 0 = the vector form
+  // bilinear smooth term (fh_set_factorization, csrc/fh_bilinear.h): S is (bl_m, bl_n), stored like a dense A in `A` (mp rows of ld doubles); the unknown
+  // Z = [X; Y] has m = n = bl_m + bl_n rows.  bl_part: f of the latest pass (2 doubles), then the GX and the GY partials that pass wrote with the
+  // geometry bl_nct / bl_nrp -- a buffer of its own, because they live from the forward launch to the adjoint one; bl_have_grad: they are there.
+  // FH_PROX_ROWSPLIT (fh_set_prox_split): rows [0, rs_split) take rs_kind_top with mu / lo / hi, the other rows rs_kind_bot with rs_lo_bot / rs_hi_bot.
+  uint64_t bl_m = 0, bl_n = 0;
+  double* bl_part = nullptr;
+  size_t bl_part_bytes = 0;
+  uint32_t bl_nct = 0, bl_nrp = 0;
+  bool bl_have_grad = false;
+  uint64_t rs_split = 0;
+  int rs_kind_top = 0, rs_kind_bot = 0;
+  double rs_lo_bot = 0.0, rs_hi_bot = 0.0;
   uint64_t H = 0, W = 0;
   uint64_t D = 0;            // 3-D stencil (fh_set_stencil3d, csrc/fh_tv3d.h): the volume is (D, H, W), m = D*H*W, n = 3*m
   // sparse operator (fh_set_matrix_csr, csrc/fh_sparse.h): sp[0] = A by rows, sp[1] = A^T by rows, each with its non-zero-balanced row ranges,
@@ -369,7 +381,7 @@ static void free_vectors(fh_ctx* c) {
 static void free_operator(fh_ctx* c) {
   for (fh_ctx* s : c->shards) { (void)hipSetDevice(s->device); free_operator(s); }
   auto fr = [](double*& p) { if (p) { (void)hipFree(p); p = nullptr; } };
-  if (c->A && (c->op == OP_DENSE || c->op == OP_QUAD)) { release_matrix_block(c->device, c->A, c->a_block_bytes); c->A = nullptr; c->a_block_bytes = 0; }
+  if (c->A && (c->op == OP_DENSE || c->op == OP_QUAD || c->op == OP_BILINEAR)) { release_matrix_block(c->device, c->A, c->a_block_bytes); c->A = nullptr; c->a_block_bytes = 0; }
   fr(c->A);
   for (SpMatP& a : c->sp) {
     if (a.ptr) (void)hipFree((void*)a.ptr);
@@ -384,6 +396,9 @@ static void free_operator(fh_ctx* c) {
   c->L = c->LB = 0;                  // a new operator starts in the vector form
   if (c->loss_kind == LOSS_QUAD) c->loss_kind = LOSS_LSQ;                                        // ... and leaves the quadratic form (fh_set_quadratic) behind:
   if (c->prox_kind == FH_PROX_ROWBALL) { c->prox_kind = FH_PROX_IDENTITY; c->mu = 0.0; }      // its loss and the prox only it serves
+  if (c->loss_kind == LOSS_BILINEAR) c->loss_kind = LOSS_LSQ;                                    // ... and the bilinear form (fh_set_factorization) likewise
+  if (c->prox_kind == FH_PROX_ROWSPLIT) { c->prox_kind = FH_PROX_IDENTITY; c->mu = 0.0; }
+  fr(c->bl_part); c->bl_part_bytes = 0; c->bl_have_grad = false; c->bl_m = c->bl_n = 0;
   fr(c->ws); c->ws_bytes = 0;
   fr(c->slotbuf); c->slotbuf_bytes = 0; c->slots_sig = 0;
   c->op = OP_NONE; c->has_b = false;

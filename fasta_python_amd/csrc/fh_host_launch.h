@@ -1,4 +1,4 @@
-// fh_host_launch.h -- kernel launchers of libfasta_hip.so: shapes, grids and workspace of every kernel in fh_dense.h / fh_quad.h / fh_tv.h / fh_tv3d.h /
+// fh_host_launch.h -- kernel launchers of libfasta_hip.so: shapes, grids and workspace of every kernel in fh_dense.h / fh_quad.h / fh_bilinear.h / fh_tv.h / fh_tv3d.h /
 // fh_prox.h / fh_fused.h, the one-pass kernel's shape rule and dispatch table, the co-residency probe, and the three-stage form
 // (local launch / sum over row blocks / n-side epilogue) the C ABI in fasta_hip.hip builds its entry points from.
 #pragma once
@@ -522,6 +522,207 @@ static int launch_adj_quad(fh_ctx* c, const AdjIO& io) {
   return 0;
 }
 
+// ---- bilinear smooth term .5 ||S - X Y^T||^2 (fh_set_factorization; kernels in csrc/fh_bilinear.h, instantiated by fh_bilinear_part.hip) -------
+#ifndef FH_SINGLE_TU
+#define BL_DECLARE(LB) BL_KERNELS(extern template, LB)
+BL_FOR_EACH(BL_DECLARE)
+#undef BL_DECLARE
+#endif
+struct BlEntry { int lb; void (*pro)(const BlProP); void (*pass[2][2])(const BlPassP); void (*grad)(const BlGradP); };      // pass[GRAD][NT]
+#define BL_ROW(LB) {LB, k_bl_prologue<LB>, {{k_bl_pass<LB, 0, 0>, k_bl_pass<LB, 0, 1>}, {k_bl_pass<LB, 1, 0>, k_bl_pass<LB, 1, 1>}}, k_bl_grad<LB>},
+static const BlEntry kBlTable[] = { BL_FOR_EACH(BL_ROW) };
+#undef BL_ROW
+static const BlEntry* bl_entry_lb(uint32_t LB) {
+  for (const BlEntry& e : kBlTable) if ((uint32_t)e.lb == LB) return &e;
+  return nullptr;
+}
+static inline bool bl_prox_ok(int kind) { return kind == FH_PROX_IDENTITY || kind == FH_PROX_SHRINK || kind == FH_PROX_NONNEG || kind == FH_PROX_BOX || kind == FH_PROX_ROWSPLIT; }
+
+// THE GEOMETRY of the bilinear launches, stated once: a pure function of S's shape (m, n; device rows of ld doubles), the columns per row LB and
+// the tuning values FH_TUNE_FWD_GRID_CAP and FH_TUNE_NT_LOADS (0 / -1 = auto).  A work item of the pass is a row panel of PR rows x a column tile of
+// BL_TC = 512 columns.  PR is chosen so that the items reach the pass's grid of 512 workgroups where S is large enough -- panels = 512 / column
+// tiles, PR = m / panels rounded up to 16 -- and clamped to [16, 1024]: above 1024 rows a panel's GY partial is already 1 / 1024 of a column of S
+// per column of the factors, below 16 the chunks of RB rows would straddle S's padded rows.  Partial traffic, written once and read once each:
+// GX  LB / 512 and GY  LB / PR  of S's bytes (LB = 16, PR = 1024: 3.1 % + 1.6 %).
+struct BlShape {
+  const BlEntry* e;
+  int nt;
+  uint32_t ld2, pr, nrp, nct, rb;
+  uint32_t trips, last_rows, last_live_rows, last_live_lanes;
+  uint32_t grid, items_max, items_min, nelem;
+  uint64_t px_bytes, py_bytes;
+};
+static BlShape bl_shape_for(uint64_t m, uint64_t n, uint64_t ld, uint32_t LB, long long fwd_cap, int nt_loads) {
+  BlShape s;
+  memset(&s, 0, sizeof(s));
+  s.e = bl_entry_lb(LB);
+  if (!s.e) return s;
+  s.nt = nt_rule(nt_loads, round_up(m, 16), ld, 0) ? 1 : 0;
+  s.ld2 = (uint32_t)(ld / 2);
+  s.rb = (uint32_t)bl_ns((int)LB) / LB;
+  s.nct = (uint32_t)((n + BL_TC - 1) / BL_TC);
+  const uint64_t panels = std::max<uint64_t>(1, (512 + s.nct - 1) / s.nct);
+  s.pr = (uint32_t)std::min<uint64_t>(1024, std::max<uint64_t>(16, round_up((m + panels - 1) / panels, 16)));
+  s.nrp = (uint32_t)((m + s.pr - 1) / s.pr);
+  s.trips = s.pr / s.rb;
+  s.last_rows = (uint32_t)(m - (uint64_t)(s.nrp - 1) * s.pr);
+  s.last_live_rows = s.last_rows - (s.last_rows - 1) / s.rb * s.rb;
+  s.last_live_lanes = (uint32_t)((n + 1) / 2 - (uint64_t)(s.nct - 1) * (BL_TC / 2));
+  const uint64_t items = (uint64_t)s.nrp * s.nct;
+  s.grid = (uint32_t)std::min<uint64_t>(items, fwd_cap > 0 ? (uint64_t)fwd_cap : 512);
+  s.items_max = (uint32_t)((items + s.grid - 1) / s.grid);
+  s.items_min = (uint32_t)(items / s.grid);
+  s.nelem = (uint32_t)((round_up(m + n, 16) + FH_WG - 1) / FH_WG);
+  s.px_bytes = (uint64_t)s.nct * m * LB * sizeof(double);
+  s.py_bytes = (uint64_t)s.nrp * n * LB * sizeof(double);
+  return s;
+}
+static BlShape bl_shape(const fh_ctx* c) { return bl_shape_for(c->bl_m, c->bl_n, c->ld, c->LB, c->fwd_cap, c->nt_loads); }
+static void bl_shape_report(const BlShape& s, uint32_t* out) {
+  const uint32_t v[FH_BILINEAR_SHAPE_LEN] = {(uint32_t)s.e->lb, (uint32_t)s.nt, s.pr, BL_TC, s.nrp, s.nct, s.rb, s.trips, s.last_rows, s.last_live_rows,
+                                             s.last_live_lanes, s.grid, s.items_max, s.items_min, s.nelem, (uint32_t)s.px_bytes, (uint32_t)s.py_bytes};
+  memcpy(out, v, sizeof(v));
+}
+// the size limit of fh_set_factorization (include/fasta_hip.h), checked where the shape is known: nullptr, or what is too large
+static const char* bl_too_large(uint64_t m, uint64_t n, const BlShape& s) {
+  if (m + n >= (1ull << 27)) return "m + n must be below 2^27 (the row offsets (m + n) * LB are kept in 31 bits)";
+  if (s.px_bytes >= (1ull << 32) || s.py_bytes >= (1ull << 32)) return "a partial buffer (column tiles * m * LB or row panels * n * LB doubles) would reach 4 GiB";
+  return nullptr;
+}
+static inline uint32_t lb_for(uint32_t L) { return L <= 2 ? 2u : (L <= 4 ? 4u : (L <= 8 ? 8u : 16u)); }
+// read-only: the geometry the next fh_fwd / fh_adj of this context launches with
+extern "C" int fh_bilinear_shape(fh_ctx* c, uint32_t* out) {
+  if (!c || !out) return fail(FH_E_ARG, "fh_bilinear_shape: null argument");
+  if (c->op != OP_BILINEAR) return fail(FH_E_STATE, "fh_bilinear_shape: the context holds no bilinear operator (fh_set_factorization)");
+  const BlShape s = bl_shape(c);
+  if (!s.e) return fail(FH_E_STATE, "bilinear operator: no kernel for %u columns per row", c->LB);
+  bl_shape_report(s, out);
+  return 0;
+}
+// ... and the same rule for an (m, n) matrix with K columns that no context holds: a pure host function, no device needed
+extern "C" int fh_bilinear_shape_for(uint64_t m, uint64_t n, uint32_t K, long long grid_cap, int nt_loads, uint32_t* out) {
+  if (!out) return fail(FH_E_ARG, "fh_bilinear_shape_for: null argument");
+  if (m == 0 || n == 0) return fail(FH_E_ARG, "fh_bilinear_shape_for: the matrix must be non-empty");
+  if (K < 1 || K > 16) return fail(FH_E_ARG, "fh_bilinear_shape_for: 1 to 16 columns (got %u)", K);
+  if (grid_cap < 0) return fail(FH_E_ARG, "FWD_GRID_CAP must be >= 0");
+  if (nt_loads < -1 || nt_loads > 1) return fail(FH_E_ARG, "fh_bilinear_shape_for: nt_loads is -1 (auto), 0 or 1");
+  if (m >= (1ull << 27) || n >= (1ull << 27)) return fail(FH_E_ARG, "fh_bilinear_shape_for: m + n must be below 2^27 (the row offsets (m + n) * LB are kept in 31 bits)");
+  const BlShape s = bl_shape_for(m, n, round_up(n, 16), lb_for(K), grid_cap, nt_loads);
+  if (!s.e) return fail(FH_E_STATE, "bilinear operator: no kernel for %u columns per row", lb_for(K));
+  if (const char* why = bl_too_large(m, n, s)) return fail(FH_E_ARG, "fh_bilinear_shape_for: %s", why);
+  bl_shape_report(s, out);
+  return 0;
+}
+
+// the partial buffer: [0] f of the latest pass, from 2 doubles on the GX partials, behind them the GY partials (kept until the adjoint launch)
+static int bl_ensure_part(fh_ctx* c, const BlShape& sh) {
+  const size_t bytes = 16 + (size_t)sh.px_bytes + (size_t)sh.py_bytes;
+  if (bytes <= c->bl_part_bytes) return 0;
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (c->bl_part) { HIP_TRY(hipFree(c->bl_part)); c->bl_part = nullptr; c->bl_part_bytes = 0; }
+  HIP_TRY(hipMalloc((void**)&c->bl_part, bytes));
+  c->bl_part_bytes = bytes;
+  c->bl_have_grad = false;
+  return 0;
+}
+// one pass over S at `point`: f (and, grad = 1, the partials of both halves of the gradient); publish = 1: the forward half of the scalar block
+static int bl_launch_pass(fh_ctx* c, const BlShape& sh, const double* point, int grad, int publish, uint32_t npro) {
+  FH_TRY(bl_ensure_part(c, sh));
+  BlPassP p;
+  p.S = c->A; p.ld2 = sh.ld2; p.m = (uint32_t)c->bl_m; p.n = (uint32_t)c->bl_n; p.L = c->L;
+  p.pr = sh.pr; p.nrp = sh.nrp; p.nct = sh.nct;
+  p.z = point;
+  p.fout = c->bl_part; p.px = c->bl_part + 2; p.py = c->bl_part + 2 + sh.px_bytes / sizeof(double);
+  p.publish = publish; p.nred_n = npro;
+  p.red_n = c->ws; p.red_m = c->ws + (size_t)npro * 8;
+  p.counter = c->counters + CNT_FWD;
+  p.out = scalar_out(c);
+  p.seq = publish ? seq_offer(c) : 0u;
+  sh.e->pass[grad ? 1 : 0][sh.nt]<<<dim3(sh.grid), dim3(FH_WG), 0, c->stream>>>(p);
+  if (grad) { c->bl_have_grad = true; c->bl_nct = sh.nct; c->bl_nrp = sh.nrp; }
+  else c->bl_have_grad = false;
+  return 0;
+}
+static void bl_make_prox(fh_ctx* c, double tau, BlProP* q) {
+  q->a.px = make_prox(c, tau);
+  q->bot = q->a.px;
+  q->split = 0; q->rowsplit = 0;
+  if (c->prox_kind == FH_PROX_ROWSPLIT) {
+    q->rowsplit = 1; q->split = (uint32_t)c->rs_split;
+    q->a.px.kind = c->rs_kind_top;
+    q->bot.kind = c->rs_kind_bot; q->bot.thr = 0.0; q->bot.lo = c->rs_lo_bot; q->bot.hi = c->rs_hi_bot;
+  }
+}
+
+// mode 0: xhat, xprox = prox(X0 - tau G0) and the n-side sums by the prologue launch, then the pass at xprox; mode 1: the pass at X0.  The pass
+// of mode 0 leaves the gradient out when the context's latest adjoint launch was accelerated (the next one then wants the gradient at another
+// point anyway); launch_adj_bilinear makes up for a wrong guess, and f has the same bits either way.
+static int launch_fwd_bilinear(fh_ctx* c, int mode, double tau, const double* x0, const double* g0, const double* xacc0,
+                               double* xhat, double* xp, double* z, int with_f) {
+  (void)z;
+  const BlShape sh = bl_shape(c);
+  if (!sh.e) return fail(FH_E_STATE, "bilinear operator: no kernel for %u columns per row", c->LB);
+  if (mode == 0 && !bl_prox_ok(c->prox_kind)) return fail(FH_E_STATE, "prox kind %d (LINF / L1BALL / TVBALL / GROUP / ROWBALL) has no bilinear form", c->prox_kind);
+  if (!with_f) return fail(FH_E_STATE, "the bilinear operator has no linear map to apply");
+  const uint32_t npro = mode == 0 ? sh.nelem : 0u;
+  FH_TRY(ensure_ws(c, ((size_t)npro * 8 + sh.grid) * sizeof(double)));
+  FH_TRY(bl_ensure_part(c, sh));
+  t_begin(c, FH_K_FWD);
+  if (mode == 0) {
+    BlProP q;
+    q.a.n = (uint32_t)c->n; q.a.L = c->L; q.a.nv = (uint32_t)c->nv;
+    q.a.x0 = x0; q.a.g0 = g0; q.a.xacc0 = xacc0; q.a.xhat = xhat; q.a.xp = xp; q.a.tau = tau;
+    q.a.xs = nullptr; q.a.ld2 = 0;
+    bl_make_prox(c, tau, &q);
+    q.a.red_n = c->ws;
+    sh.e->pro<<<dim3(npro), dim3(FH_WG), 0, c->stream>>>(q);
+  }
+  const int rc = bl_launch_pass(c, sh, mode == 0 ? xp : x0, (mode == 1 || !c->last_accel) ? 1 : 0, 1, npro);
+  t_end(c, FH_K_FWD);
+  FH_TRY(rc);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// g1 := the gradient, summed from the partials of the latest pass, and the n-side epilogue.  With acceleration the gradient is wanted at the
+// extrapolated point: k_bl_extrap forms it, a second pass runs there, and FH_S_FSQ_ADJ is f at that point.
+static int launch_adj_bilinear(fh_ctx* c, const AdjIO& io) {
+  const BlShape sh = bl_shape(c);
+  if (!sh.e) return fail(FH_E_STATE, "bilinear operator: no kernel for %u columns per row", c->LB);
+  if (io.mode != 0 && io.mode != 1) return fail(FH_E_STATE, "the bilinear operator has no row-sharded adjoint");
+  if (!io.sub_b) return fail(FH_E_STATE, "the bilinear operator has no linear map to apply");
+  FH_TRY(ensure_ws(c, ((size_t)sh.nelem * 8 + sh.grid) * sizeof(double)));
+  t_begin(c, FH_K_ADJ);
+  int rc = 0;
+  if (io.mode == 0 && io.accel) {
+    const uint64_t count = c->nv * c->LB;
+    k_bl_extrap<<<dim3((unsigned)((count + FH_WG - 1) / FH_WG)), dim3(FH_WG), 0, c->stream>>>(io.xp, io.xacc0, io.coef, io.x1, (uint32_t)c->n, c->L, c->LB, count);
+    rc = bl_launch_pass(c, sh, io.x1, 1, 0, 0);
+  } else if (io.mode == 0 && !c->bl_have_grad) {
+    rc = bl_launch_pass(c, sh, io.xp, 1, 0, 0);
+  }
+  if (rc == 0 && !c->bl_have_grad) rc = fail(FH_E_STATE, "the bilinear operator: no pass has left its gradient partials (fh_fwd / fh_init first)");
+  if (rc == 0) {
+    BlGradP p;
+    p.m = (uint32_t)c->bl_m; p.n = (uint32_t)c->bl_n; p.L = c->L; p.rows = (uint32_t)c->nv;
+    p.nct = c->bl_nct; p.nrp = c->bl_nrp;
+    p.gtop = c->prox_kind == FH_PROX_ROWSPLIT ? (uint32_t)c->rs_split : (uint32_t)c->n;
+    p.fsrc = c->bl_part; p.px = c->bl_part + 2; p.py = c->bl_part + 2 + (uint64_t)c->bl_nct * c->bl_m * c->LB;
+    p.accel = io.accel; p.mode = io.mode; p.coef = io.coef; p.tau = io.tau;
+    p.x0 = io.x0; p.xp = io.xp; p.xacc0 = io.xacc0; p.xhat = io.xhat; p.g1 = io.g1;
+    p.red = c->ws;
+    p.counter = c->counters + CNT_ADJ_FIN;
+    p.out = scalar_out(c);
+    p.seq = io.mode == 0 ? seq_offer(c) : 0u;
+    sh.e->grad<<<dim3(sh.nelem), dim3(FH_WG), 0, c->stream>>>(p);
+    c->bl_have_grad = false;                 // (consumed: the next adjoint launch without a forward one makes its own pass)
+  }
+  t_end(c, FH_K_ADJ);
+  FH_TRY(rc);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
 // g1 := A^T grad f(z') by the gather over the A^T copy; the residual and the loss sum at z' come from the m-side prologue launch
 static int launch_adj_sparse(fh_ctx* c, const AdjIO& io) {
   const SpEntry* e = sp_entry(c->sp_G[1]);
@@ -747,8 +948,9 @@ static int launch_gterms(fh_ctx* c, const double* x) {
   if (c->LB) {              // (n, L) matrix: the same two terms, or the sum of row norms for FH_PROX_GROUP
     const unsigned mgrid = (unsigned)std::min<uint64_t>((c->n + FH_WG - 1) / FH_WG, 1024);
     FH_TRY(ensure_ws(c, (size_t)mgrid * 2 * sizeof(double)));
+    const uint64_t grows = c->prox_kind == FH_PROX_ROWSPLIT ? c->rs_split : c->n;      // (FH_PROX_ROWSPLIT: the l1 term lives on the top rows)
     t_begin(c, FH_K_AUX);
-    k_mc_gterms<<<dim3(mgrid), dim3(FH_WG), 0, c->stream>>>(x, (uint32_t)c->n, c->L, c->LB, c->prox_kind == FH_PROX_GROUP ? 1 : 0, c->ws, c->counters + CNT_AUX, scalar_out(c));
+    k_mc_gterms<<<dim3(mgrid), dim3(FH_WG), 0, c->stream>>>(x, (uint32_t)grows, c->L, c->LB, c->prox_kind == FH_PROX_GROUP ? 1 : 0, c->ws, c->counters + CNT_AUX, scalar_out(c));
     t_end(c, FH_K_AUX);
     HIP_TRY(hipGetLastError());
     return 0;
@@ -1172,6 +1374,7 @@ static int op_fwd(fh_ctx* c, int mode, double tau, const double* x0, const doubl
   if (c->op == OP_SPARSE) return c->LB ? launch_fwd_spmulti(c, mode, tau, x0, g0, xacc0, xhat, xp, z, sub_b) : launch_fwd_sparse(c, mode, tau, x0, g0, xacc0, xhat, xp, z, sub_b);
   if (c->op == OP_STENCIL3D) return launch_fwd_tv3(c, mode, tau, x0, g0, xacc0, xhat, xp, z, sub_b);
   if (c->op == OP_QUAD) return launch_fwd_quad(c, mode, tau, x0, g0, xacc0, xhat, xp, z, sub_b);
+  if (c->op == OP_BILINEAR) return launch_fwd_bilinear(c, mode, tau, x0, g0, xacc0, xhat, xp, z, sub_b);
   return fail(FH_E_STATE, "no operator set");
 }
 
@@ -1187,6 +1390,7 @@ static int adj_local(fh_ctx* c, const AdjIO& io_in) {
   if (c->op == OP_SPARSE) return c->LB ? launch_adj_spmulti(c, io) : launch_adj_sparse(c, io);
   if (c->op == OP_STENCIL3D) return launch_adj_tv3(c, io);
   if (c->op == OP_QUAD) return launch_adj_quad(c, io);
+  if (c->op == OP_BILINEAR) return launch_adj_bilinear(c, io);
   return fail(FH_E_STATE, "no operator set");
 }
 // stage 2, exchange: A_k^T r_k partials (nv doubles at g1(shard)) and the local loss sums (FH_S_FSQ_ADJ) summed over the row blocks
@@ -1215,7 +1419,7 @@ static int reduce_fsq_over_ranks(fh_ctx* c) {
 static int check_ready(fh_ctx* c, bool need_b) {
   if (!c) return fail(FH_E_ARG, "null context");
   if (c->pending_step) return fail(FH_E_STATE, "a step issued by fh_step_begin is still in flight on this context: call fh_step_end first");
-  if (c->op == OP_NONE) return fail(FH_E_STATE, "no operator set (call fh_set_matrix / fh_set_matrix_csr / fh_generate_matrix / fh_set_stencil / fh_set_stencil3d / fh_set_quadratic)");
+  if (c->op == OP_NONE) return fail(FH_E_STATE, "no operator set (call fh_set_matrix / fh_set_matrix_csr / fh_generate_matrix / fh_set_stencil / fh_set_stencil3d / fh_set_quadratic / fh_set_factorization)");
   if (need_b && !c->has_b) return fail(FH_E_STATE, "no loss set (call fh_set_loss_lsq)");
   return c->shards.empty() ? use_device(c) : 0;      // (a shell selects the device shard by shard)
 }

@@ -16,8 +16,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FASTA_HIP_LIB") or os.path.join(_HERE, "libfasta_hip.so")
 
 # enums mirrored from include/fasta_hip.h ---------------------------------------------------------
-PROX_IDENTITY, PROX_SHRINK, PROX_NONNEG, PROX_LINF, PROX_L1BALL, PROX_TVBALL, PROX_BOX, PROX_GROUP, PROX_ROWBALL = range(9)
-MAX_RHS = 16                       # columns of a matrix unknown (fh_set_rhs, fh_set_matrix_csr_rhs, fh_set_quadratic)
+PROX_IDENTITY, PROX_SHRINK, PROX_NONNEG, PROX_LINF, PROX_L1BALL, PROX_TVBALL, PROX_BOX, PROX_GROUP, PROX_ROWBALL, PROX_ROWSPLIT = range(10)
+MAX_RHS = 16                       # columns of a matrix unknown (fh_set_rhs, fh_set_matrix_csr_rhs, fh_set_quadratic, fh_set_factorization)
 (VEC_X0, VEC_G0, VEC_XHAT, VEC_XPROX, VEC_X1, VEC_G1, VEC_BEST, VEC_B, VEC_Z,
  VEC_T0, VEC_T1, VEC_T2, VEC_T3) = range(13)
 (S_FSQ, S_DXG0, S_DX2, S_XH2, S_G02, S_GSUM, S_GMAX, S_RDOT, S_DXDG, S_DG2, S_FSQ_ADJ, S_XH2_ADJ,
@@ -92,6 +92,10 @@ SIGNATURES = {
     "fh_set_quadratic": (_i32, [_ctx, _pd, _u64, _u64, _pd, C.c_uint32]),
     "fh_quad_shape": (_i32, [_ctx, C.POINTER(C.c_uint32)]),
     "fh_quad_shape_for": (_i32, [_u64, C.c_uint32, C.c_longlong, _i32, C.POINTER(C.c_uint32)]),
+    "fh_set_factorization": (_i32, [_ctx, _pd, _u64, _u64, _u64, C.c_uint32]),
+    "fh_set_prox_split": (_i32, [_ctx, _u64, _i32, C.c_double, C.c_double, C.c_double, _i32, C.c_double, C.c_double]),
+    "fh_bilinear_shape": (_i32, [_ctx, C.POINTER(C.c_uint32)]),
+    "fh_bilinear_shape_for": (_i32, [_u64, _u64, C.c_uint32, C.c_longlong, _i32, C.POINTER(C.c_uint32)]),
     "fh_set_rhs": (_i32, [_ctx, C.c_uint32]),
     "fh_rhs": (_i32, [_ctx, C.POINTER(C.c_uint32)]),
     "fh_multi_shape": (_i32, [_ctx, C.POINTER(C.c_uint32)]),
@@ -240,6 +244,20 @@ def quad_shape(n, L, grid_cap=0, nt_loads=-1):
     out = (C.c_uint32 * QUAD_SHAPE_LEN)()
     _check(lib, lib.fh_quad_shape_for(int(n), int(L), int(grid_cap), int(nt_loads), out))
     return QuadShape(*(int(v) for v in out))
+
+
+BILINEAR_SHAPE_LEN = 17
+BilinearShape = collections.namedtuple("BilinearShape", "LB NT tile_rows tile_cols row_panels col_tiles RB trips last_rows last_live_rows "
+                                       "last_live_lanes grid tiles_max tiles_min nelem gx_bytes gy_bytes")
+
+
+def bilinear_shape(m, n, K, grid_cap=0, nt_loads=-1):
+    """BilinearShape of the bilinear launches (csrc/fh_bilinear.h) for an (m, n) matrix S and K columns of the factors under
+    FH_TUNE_FWD_GRID_CAP (0 = auto) and FH_TUNE_NT_LOADS (-1 = auto): fh_bilinear_shape_for, the rule the launchers call.  Host-only."""
+    lib = load_library()
+    out = (C.c_uint32 * BILINEAR_SHAPE_LEN)()
+    _check(lib, lib.fh_bilinear_shape_for(int(m), int(n), int(K), int(grid_cap), int(nt_loads), out))
+    return BilinearShape(*(int(v) for v in out))
 
 
 TV3D_SHAPE_LEN = 8
@@ -487,6 +505,26 @@ class HipContext:
         out = (C.c_uint32 * QUAD_SHAPE_LEN)()
         self._call("fh_quad_shape", out)
         return QuadShape(*(int(v) for v in out))
+
+    def set_factorization(self, S, K):
+        """Operator and loss in one call (fh_set_factorization): f(Z) = .5 ||S - X Y^T||_F^2 with S (m, n) float64 and the unknown
+        Z = [X; Y] of shape (m + n, K), K in 1..16.  The context takes the multi-column layout."""
+        S = np.asarray(S)
+        assert S.ndim == 2
+        if S.dtype != np.float64 or not S.flags.c_contiguous:
+            S = np.ascontiguousarray(S, dtype=np.float64)
+        self._call("fh_set_factorization", S.ctypes.data_as(_pd), S.shape[0], S.shape[1], S.shape[1], int(K))
+
+    def set_prox_split(self, split, kind_top, mu_top=0.0, lo_top=0.0, hi_top=0.0, kind_bottom=PROX_IDENTITY, lo_bottom=0.0, hi_bottom=0.0):
+        """FH_PROX_ROWSPLIT (fh_set_prox_split): rows [0, split) take kind_top, the other rows kind_bottom.  Bilinear operator only."""
+        self._call("fh_set_prox_split", int(split), int(kind_top), float(mu_top), float(lo_top), float(hi_top),
+                   int(kind_bottom), float(lo_bottom), float(hi_bottom))
+
+    def bilinear_shape(self):
+        """BilinearShape the next fwd / adj of this context launches with (fh_bilinear_shape).  E_STATE without a bilinear operator."""
+        out = (C.c_uint32 * BILINEAR_SHAPE_LEN)()
+        self._call("fh_bilinear_shape", out)
+        return BilinearShape(*(int(v) for v in out))
 
     def shape(self):
         m, n = _u64(0), _u64(0)

@@ -15,7 +15,8 @@ subclasses are *recognised* by `fasta()` and run on the device:
                      device by rows and by columns; both directions are gathers (csrc/fh_sparse.h; with `rhs=L`
                      the unknown is an (n, L) matrix and every entry gathers a whole row of it, csrc/fh_spmulti.h);
   GradDivMap      -- the periodic div/grad stencil pair of examples/tv_denoising.py:26-63;
-  QuadraticMap    -- the identity operator of a quadratic smooth term (losses.Quadratic): what `fasta(None, None, q.f, q.gradf, ...)` runs on.
+  QuadraticMap    -- the identity operator of a quadratic smooth term (losses.Quadratic): what `fasta(None, None, q.f, q.gradf, ...)` runs on;
+  BilinearMap     -- the identity operator of a bilinear smooth term (losses.Factorization): what `fasta(None, None, fz.f, fz.gradf, ...)` runs on.
 
 A DenseMatrixMap built from a host ndarray uploads LAZILY: it keeps a reference to the array (as the
 closures of fasta/linalg.py:41 do) and copies it into HBM when the device loop first asks for its
@@ -36,7 +37,7 @@ from . import hip
 Matrix = np.ndarray
 Vector = np.ndarray
 
-__all__ = ["LinearMap", "LinearOperator", "DenseMatrixMap", "ShardedDenseMatrixMap", "SparseMatrixMap", "GradDivMap", "QuadraticMap", "is_sparse_matrix", "Matrix", "Vector"]
+__all__ = ["LinearMap", "LinearOperator", "DenseMatrixMap", "ShardedDenseMatrixMap", "SparseMatrixMap", "GradDivMap", "QuadraticMap", "BilinearMap", "is_sparse_matrix", "Matrix", "Vector"]
 
 
 class LinearMap:
@@ -464,6 +465,35 @@ class QuadraticMap(_DeviceMap):
         for key, value in self._tuning.items():
             ctx.set_tuning(key, value)
         ctx.set_quadratic(self.loss.Q, self.loss.c, self.rhs)
+
+    def _apply_fwd(self, v):
+        return v
+
+    def _apply_adj(self, w):
+        return w
+
+
+class BilinearMap(_DeviceMap):
+    """The operator of `fasta(None, None, fz.f, fz.gradf, g, prox, Z0)` with fz = losses.Factorization(S): the identity on Z0's shape
+    (m + n, K), K <= 16.  Its device context holds S (fh_set_factorization: operator and loss in one call, csrc/fh_bilinear.h).  Lazy like a
+    map built from a host matrix; on host arrays it is the identity, as `A = None` is in the reference (examples/nn_factorization.py:63)."""
+
+    def __init__(self, loss, shape, device=0, tuning=None):
+        shape = tuple(int(k) for k in shape)
+        rows = loss.m + loss.n
+        if len(shape) != 2 or shape[0] != rows or not 1 <= shape[1] <= hip.MAX_RHS:
+            raise ValueError(f"a factorization of a {loss.m} x {loss.n} matrix takes an unknown of shape ({rows}, K), K <= {hip.MAX_RHS} (got {shape})")
+        self.loss = loss
+        self.shape = (rows, rows)
+        self.rhs = shape[1]
+        self.storage = "f64"
+        self._tuning = dict(tuning or {})
+        _DeviceMap.__init__(self, shape, shape, device, lazy=True)
+
+    def _on_context(self, ctx):
+        for key, value in self._tuning.items():
+            ctx.set_tuning(key, value)
+        ctx.set_factorization(self.loss.S, self.rhs)
 
     def _apply_fwd(self, v):
         return v

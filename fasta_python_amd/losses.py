@@ -1,6 +1,6 @@
 """Smooth terms f(z) recognised by the device loop.
 
-LogisticLoss(b), Quadratic(Q, c): see the classes.  LeastSquares(b):  f(z) = .5*||z - b||^2,  gradf(z) = z - b   (examples/sparse_least_squares.py:41-42,
+LogisticLoss(b), Quadratic(Q, c), Factorization(S): see the classes.  LeastSquares(b):  f(z) = .5*||z - b||^2,  gradf(z) = z - b   (examples/sparse_least_squares.py:41-42,
 same closures in lasso.py:42-43, nn_least_squares.py:39-40, tv_denoising.py:85-86 with b = M/mu).
 Pass `ls.f` and `ls.gradf` as the `f` / `gradf` arguments of `fasta()`.
 """
@@ -9,7 +9,7 @@ import math
 
 import numpy as np
 
-__all__ = ["LeastSquares", "LogisticLoss", "Quadratic"]
+__all__ = ["LeastSquares", "LogisticLoss", "Quadratic", "Factorization"]
 
 
 class LeastSquares:
@@ -92,5 +92,41 @@ class Quadratic:
     def gradf(self, x):
         w = self.Q @ x
         return w if self.c is None else w + self.c
+
+    __call__ = f
+
+
+class Factorization:
+    """f(Z) = .5*||S - X Y^T||_F^2 with Z = [X; Y]: X = Z[:m] is (m, K), Y = Z[m:] is (n, K), S a 2-D float64 matrix (m, n)
+    (examples/nn_factorization.py:48-57).  gradf(Z) = [d Y; d^T X] with d = X Y^T - S.  The smooth term is BILINEAR in (X, Y), so the
+    problem is not convex; the operator is the identity: `fasta(None, None, fz.f, fz.gradf, g, prox, Z0)`.  On the device one pass over S
+    gives the value and both halves of the gradient (csrc/fh_bilinear.h); on host arrays `f` / `gradf` are the example's closures."""
+
+    def __init__(self, S):
+        S = np.asarray(S)
+        if S.ndim != 2:
+            raise ValueError(f"Factorization needs a 2-D matrix S (got shape {S.shape})")
+        if S.dtype != np.float64:
+            raise ValueError(f"Factorization needs a float64 matrix S (got {S.dtype})")
+        self.S = S
+        self.m, self.n = S.shape
+
+    def bind(self, ctx):
+        """Nothing to do: S reaches the device with the operator (linalg.BilinearMap: fh_set_factorization is operator and loss in one call)."""
+
+    @staticmethod
+    def f_from_device(s):
+        return np.float64(s)                    # FH_S_FSQ carries f itself
+
+    def f(self, Z):
+        N = self.m
+        return .5 * np.linalg.norm((self.S - Z[:N, ...] @ Z[N:, ...].T).ravel())**2
+
+    def gradf(self, Z):
+        N = self.m
+        X = Z[:N, ...]
+        Y = Z[N:, ...]
+        d = X @ Y.T - self.S
+        return np.concatenate((d @ Y, d.T @ X))
 
     __call__ = f

@@ -19,7 +19,7 @@ import numpy as np
 
 from . import hip
 
-__all__ = ["Shrink", "NonNeg", "LinfProx", "L1Ball", "Box", "TVDualBall", "GroupShrink", "RowBall", "NoProx", "device_prox", "release_scratch",
+__all__ = ["Shrink", "NonNeg", "LinfProx", "L1Ball", "Box", "TVDualBall", "GroupShrink", "RowBall", "RowSplit", "NoProx", "device_prox", "release_scratch",
            "shrink", "project_Linf_ball", "project_L1_ball", "project_Lnuc_ball"]
 
 
@@ -167,6 +167,37 @@ class RowBall(ProxTag):
         return self.mu * X / scale[:, np.newaxis]
 
 
+class RowSplit(ProxTag):
+    """Two elementwise terms on one matrix unknown Z = [top; bottom] (examples/nn_factorization.py:59-61): rows [0, split) take the tag `top`
+    (NoProx, Shrink, NonNeg or Box), the other rows the tag `bottom` (NoProx, NonNeg or Box: its g must be zero, the l1 term lives on the top
+    rows only).  `RowSplit(m, Shrink(mu), Box(0, 1))` is the example's pair.  The device serves it with losses.Factorization only
+    (FH_PROX_ROWSPLIT, csrc/fh_bilinear.h)."""
+    kind = hip.PROX_ROWSPLIT
+
+    def __init__(self, split, top, bottom):
+        if not isinstance(top, ProxTag) or not isinstance(bottom, ProxTag):
+            raise ValueError("RowSplit takes two proximal.* tag objects, e.g. RowSplit(m, Shrink(mu), Box(0, 1))")
+        if top.kind not in (hip.PROX_IDENTITY, hip.PROX_SHRINK, hip.PROX_NONNEG, hip.PROX_BOX):
+            raise ValueError(f"RowSplit: the top rows take NoProx, Shrink, NonNeg or Box (got proximal.{type(top).__name__})")
+        if bottom.kind not in (hip.PROX_IDENTITY, hip.PROX_NONNEG, hip.PROX_BOX):
+            raise ValueError(f"RowSplit: the bottom rows take NoProx, NonNeg or Box -- a tag whose g is zero (got proximal.{type(bottom).__name__})")
+        self.split, self.top, self.bottom = int(split), top, bottom
+        self.mu, self.lo, self.hi = top.mu, top.lo, top.hi
+
+    def bind_prox(self, ctx):
+        ctx.set_prox_split(self.split, self.top.kind, self.top.mu, self.top.lo, self.top.hi, self.bottom.kind, self.bottom.lo, self.bottom.hi)
+
+    def g_from_sums(self, gsum, gmax):
+        return self.top.g_from_sums(gsum, gmax)          # FH_S_GSUM runs over the top rows only for this kind
+
+    def prox(self, Z, t):
+        N = self.split
+        return np.concatenate((self.top.prox(Z[:N, ...], t), self.bottom.prox(Z[N:, ...], t)))
+
+    def g(self, Z):
+        return self.top.g(Z[:self.split, ...])
+
+
 # ---- the device prox on host arrays -----------------------------------------------------------------
 _scratch = {}            # (device, "dense", n) or (device, "tv", H, W) -> operator holding a scratch HipContext
 
@@ -178,6 +209,8 @@ def _matrix_form(tag, x):
     """Does device_prox take the multi-column kernels for `x`?  GroupShrink always (it couples the columns of a row, and refuses what the
     device cannot hold); an elementwise kind for a 2-D array of at most 16 columns -- same bits as the vector kernels on the flattened
     array.  Everything else (LinfProx / L1Ball on any shape, wider arrays, other ranks) is flattened and takes the vector kernels."""
+    if tag.kind == hip.PROX_ROWSPLIT:
+        raise ValueError("RowSplit runs on the device with losses.Factorization only: device_prox has no scratch operator for it")
     if tag.kind == hip.PROX_ROWBALL:
         raise ValueError("RowBall runs on the device with a quadratic loss only (losses.Quadratic): device_prox has no scratch operator for it")
     if tag.kind == hip.PROX_GROUP:

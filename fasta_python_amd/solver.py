@@ -15,7 +15,7 @@ of `FBSolver.step` below, bit for bit, without the interpreter between two launc
 Iterates, gradients and residual vectors never leave HBM unless `record_iterates` / `func` ask.
 
 Which loop runs is decided by the operand TYPES alone (`_recognise`), never by whether a GPU happens to be there:
-  * device-recognisable operands (matrix / DenseMatrixMap / GradDivMap + tagged loss + tagged prox; `A=None` + losses.Quadratic) run the HIP loop
+  * device-recognisable operands (matrix / DenseMatrixMap / GradDivMap + tagged loss + tagged prox; `A=None` + losses.Quadratic or losses.Factorization) run the HIP loop
     below and RAISE when libfasta_hip.so or the GPU is missing -- there is no CPU fallback for them;
   * anything else -- Python closures, a callable pair, `A=None`, a host LinearMap: the forms the reference's own
     examples pass -- cannot execute inside a kernel and runs the generic host loop (generic.py, reference semantics,
@@ -30,8 +30,8 @@ from time import time
 import numpy as np
 
 from . import hip, stopping
-from .linalg import DenseMatrixMap, GradDivMap, LinearMap, QuadraticMap, SparseMatrixMap, _DeviceMap, is_sparse_matrix
-from .losses import LeastSquares, LogisticLoss, Quadratic
+from .linalg import BilinearMap, DenseMatrixMap, GradDivMap, LinearMap, QuadraticMap, SparseMatrixMap, _DeviceMap, is_sparse_matrix
+from .losses import Factorization, LeastSquares, LogisticLoss, Quadratic
 from .proximal import NoProx, ProxTag
 
 __all__ = ["fasta", "Convergence", "FBSolver", "EPSILON"]
@@ -151,10 +151,45 @@ def _quadratic_form_refusal(A, At, loss_f, loss_g, g, proxg, x0):
     return None
 
 
+def _factorization_form_refusal(A, At, loss_f, loss_g, g, proxg, x0):
+    """`fasta(None, None, fz.f, fz.gradf, g, prox, Z0)` with fz = losses.Factorization(S), S of shape (m, n): the device serves it through
+    fh_set_factorization (csrc/fh_bilinear.h) for Z0 of shape (m + n, K), K <= 16, with the elementwise prox kinds on all rows or a
+    proximal.RowSplit at m.  None, or the reason."""
+    from .proximal import GroupShrink, L1Ball, LinfProx, RowBall, RowSplit, TVDualBall
+    if loss_f is None or loss_f is not loss_g:
+        return "f and gradf must be the `.f` / `.gradf` of one losses.Factorization(S) object"
+    if A is not None or At is not None:
+        return "A must be None with a factorization loss: losses.Factorization(S) holds the matrix, the operator is the identity"
+    m, n = loss_f.m, loss_f.n
+    shape = None if x0 is None else tuple(np.shape(x0))
+    if shape is not None and (len(shape) != 2 or shape[0] != m + n):
+        return f"Z0 has shape {shape}: a factorization of a {m} x {n} matrix takes Z0 = [X0; Y0] of shape ({m + n}, K)"
+    if shape is not None and not 1 <= shape[1] <= hip.MAX_RHS:
+        return f"Z0 has at most {hip.MAX_RHS} columns on the device (Z0 has {shape[1]})"
+    if g is None and proxg is None:
+        return None
+    prox, owner_g = _tag_of(proxg, ProxTag), _tag_of(g, ProxTag)
+    if prox is None or (owner_g is not None and owner_g is not prox) or (owner_g is None and g is not None):
+        return ("g and proxg must be the `.g` / `.prox` of one proximal.* tag object "
+                "(RowSplit, Shrink, NonNeg, Box)")
+    if isinstance(prox, (LinfProx, L1Ball, TVDualBall)):
+        return f"proximal.{type(prox).__name__} has no bilinear form on the device (the level-search kinds LinfProx, L1Ball and TVDualBall have none)"
+    if isinstance(prox, (GroupShrink, RowBall)):
+        return f"proximal.{type(prox).__name__} has no bilinear form on the device (the row-norm kinds GroupShrink and RowBall have none)"
+    if isinstance(prox, RowSplit) and prox.split != m:
+        return f"proximal.RowSplit splits at row {prox.split}, the factorization at m = {m} (the rows of the first factor): they must agree"
+    return None
+
+
 def _unrecognised(A, At, f, gradf, g, proxg, x0=None):
     """None when the seven operands can run on the device, else the reason they cannot (a sentence)."""
+    fz_f, fz_g = _tag_of(f, Factorization), _tag_of(gradf, Factorization)
+    if fz_f is not None or fz_g is not None:
+        return _factorization_form_refusal(A, At, fz_f, fz_g, g, proxg, x0)
     quad_f, quad_g = _tag_of(f, Quadratic), _tag_of(gradf, Quadratic)
     if quad_f is not None or quad_g is not None:
+        if _tag_of(proxg, ProxTag) is not None and _tag_of(proxg, ProxTag).kind == hip.PROX_ROWSPLIT:
+            return "proximal.RowSplit is served on the device with a factorization loss only: fasta(None, None, fz.f, fz.gradf, ...) with fz = losses.Factorization(S)"
         return _quadratic_form_refusal(A, At, quad_f, quad_g, g, proxg, x0)
     if not isinstance(A, (np.ndarray, _DeviceMap)) and not is_sparse_matrix(A):
         return ("operator A is not device-resident (pass a 2-D float64 ndarray, a scipy.sparse matrix, a linalg.DenseMatrixMap / "
@@ -170,11 +205,17 @@ def _unrecognised(A, At, f, gradf, g, proxg, x0=None):
                 "(Shrink, NonNeg, LinfProx, L1Ball, Box, TVDualBall, GroupShrink)")
     if prox.kind == hip.PROX_ROWBALL:
         return "proximal.RowBall is served on the device with a quadratic loss only: fasta(None, None, q.f, q.gradf, ...) with q = losses.Quadratic(Q, c)"
+    if prox.kind == hip.PROX_ROWSPLIT:
+        return "proximal.RowSplit is served on the device with a factorization loss only: fasta(None, None, fz.f, fz.gradf, ...) with fz = losses.Factorization(S)"
     return _sparse_form_refusal(A, loss_f, prox, x0) or _matrix_form_refusal(A, loss_f, prox, x0)
 
 
 def _recognise(A, At, f, gradf, g, proxg, x0):
     """Map the reference's seven operands onto device objects (call only when `_unrecognised` returned None)."""
+    fz = _tag_of(f, Factorization)
+    if fz is not None:                                 # A = None: the identity; S travels with the operator
+        prox = NoProx() if (g is None and proxg is None) else _tag_of(proxg, ProxTag)
+        return BilinearMap(fz, x0.shape), fz, prox
     quad = _tag_of(f, Quadratic)
     if quad is not None:                               # A = None: the identity; Q and c travel with the operator
         prox = NoProx() if (g is None and proxg is None) else _tag_of(proxg, ProxTag)
@@ -260,7 +301,10 @@ class FBSolver:
         self.loss.bind(c)
         fval = self.loss.f_from_device
         self._fval = fval
-        c.set_prox(self.prox.kind, self.prox.mu, self.prox.lo, self.prox.hi)
+        if hasattr(self.prox, "bind_prox"):                             # (proximal.RowSplit: two kinds, fh_set_prox_split)
+            self.prox.bind_prox(c)
+        else:
+            c.set_prox(self.prox.kind, self.prox.mu, self.prox.lo, self.prox.hi)
         L, tau0 = self.L, self.tau0
         probes = not L or not tau0
         if probes:                                                      # :100-113

@@ -49,9 +49,14 @@ enum fh_prox_kind {
   FH_PROX_GROUP    = 7,  /* row-wise l2 shrink of an (n, L) matrix, examples/mmv.py:51-59: with nu = ||xhat_j||_2 over the L entries of row j,
                             xprox_j = xhat_j * max(nu - t*mu, 0) / (nu + (nu == 0)).  Multi-column form only (fh_set_rhs, fh_set_matrix_csr_rhs).  FH_S_GSUM /
                             FH_S_GSUM_ADJ then carry sum_j ||xprox_j||_2 (of x1), so that g = mu * gsum; FH_S_GMAX is unchanged.            */
-  FH_PROX_ROWBALL  = 8   /* row-wise projection of an (n, L) matrix, examples/max_norm.py:53-59: with nu = ||xhat_j||_2 over the L entries of row j,
+  FH_PROX_ROWBALL  = 8,  /* row-wise projection of an (n, L) matrix, examples/max_norm.py:53-59: with nu = ||xhat_j||_2 over the L entries of row j,
                             xprox_j = (mu * xhat_j) / (max(nu, mu) + (nu == 0)) -- independent of the step; g = 0, so the objective adds nothing for it.
                             Served by the quadratic operator only (fh_set_quadratic); every other operator refuses it with a sentence.        */
+  FH_PROX_ROWSPLIT = 9   /* two elementwise kinds on one (n, L) matrix, examples/nn_factorization.py:60-61: rows [0, split) take one kind with its own
+                            parameters (IDENTITY, SHRINK, NONNEG or BOX), rows [split, n) another (IDENTITY, NONNEG or BOX), each half bit for bit what
+                            that kind gives alone.  Set by fh_set_prox_split, never by fh_set_prox.  FH_S_GSUM / FH_S_GSUM_ADJ sum |x| over the TOP rows
+                            only, so that g = mu_top * gsum (fh_init takes FH_S_GMAX over the same rows; no kind served here uses it).  Served by the bilinear operator only (fh_set_factorization); every other operator
+                            refuses it with a sentence.                                                                                          */
 };
 
 /* device vectors addressable through fh_set_vector / fh_get_vector                      */
@@ -271,6 +276,43 @@ int fh_set_quadratic(fh_ctx* ctx, const double* Q, uint64_t n, uint64_t ld_host,
 #define FH_QUAD_SHAPE_LEN 12
 int fh_quad_shape(fh_ctx* ctx, uint32_t* out);
 int fh_quad_shape_for(uint64_t n, uint32_t L, long long grid_cap, int nt_loads, uint32_t* out);
+
+/* ---- bilinear smooth term: f(Z) = .5 ||S - X Y^T||_F^2, Z = [X; Y], A = identity (csrc/fh_bilinear.h) -------------------------------------
+ * examples/nn_factorization.py:48-61: X is (m, K), Y is (n, K), the unknown Z = [X; Y] is (m + n, K), S is (m, n);
+ * gradf(Z) = [d Y; d^T X] with d = X Y^T - S.  Sparse dictionary learning, topic models and sparse NMF have this form.  ONE call sets the operator
+ * (fh_shape reports (m + n, m + n)) AND the loss: S row-major float64 with leading dimension ld_host, stored like a dense A (padded, zero padding,
+ * through the kept-block allocator); K in 1..16.  The context takes the multi-column layout (LB in {2, 4, 8, 16}, the smallest >= K; fh_rhs
+ * reports K): fh_set_vector and fh_get_vector take contiguous (m + n, K) arrays.  One pass over S at a point gives f and both halves of the
+ * gradient: an attempt of the step reads S once (fh_fwd: the prox point; its gradient becomes g1 in fh_adj); with acceleration fh_adj makes a second
+ * pass at the extrapolated point, because the form is not linear.  FH_S_FSQ / FH_S_FSQ_ADJ carry f ITSELF.  FH_VEC_B and FH_VEC_Z hold nothing.
+ * SIZE LIMIT: m + n < 2^27 (row offsets (m + n) * LB fit 31 bits) and each of the two partial buffers -- column tiles * m * LB and
+ * row panels * n * LB doubles, fh_bilinear_shape -- below 4 GiB; anything larger is FH_E_ARG.
+ * Served: fh_init, fh_setup (its Lipschitz probes are two gradient passes), fh_gradient_at, fh_diff_norm, fh_commit, fh_fwd, fh_adj
+ * (accel / coef), fh_fwd_adj, fh_iterate, fh_timing_*; fh_set_prox with IDENTITY, SHRINK, NONNEG or BOX (all rows) and fh_set_prox_split;
+ * FH_TUNE_FWD_GRID_CAP and FH_TUNE_NT_LOADS.
+ * Refused, each with a sentence naming what was asked: K = 0 or K > 16, an empty S, the size limit (FH_E_ARG); fh_apply (there is no linear operator
+ * to apply); fh_set_loss_lsq / fh_set_loss_logistic and fh_set_rhs (the loss and the column count are part of the operator); FH_PROX_LINF / L1BALL /
+ * TVBALL / GROUP / ROWBALL (a context holding one of these returns to IDENTITY when the operator is set); fh_step* and fh_run (fh_fused_supported,
+ * fh_fused_agree and fh_run_supported report 0); multi-device contexts, communicators (and fh_comm_init on such a context), float32 storage;
+ * fh_get_matrix_rows, fh_stream_read_ms.  Setting any other operator returns the context to the vector form, the least-squares loss and -- if it
+ * held ROWSPLIT -- the IDENTITY prox.                                                                                                        */
+int fh_set_factorization(fh_ctx* ctx, const double* S, uint64_t m, uint64_t n, uint64_t ld_host, uint32_t K);
+/* FH_PROX_ROWSPLIT: rows [0, split) take kind_top (IDENTITY, SHRINK with mu_top, NONNEG, BOX with lo_top / hi_top), rows [split, ..) take
+ * kind_bottom (IDENTITY, NONNEG, BOX with lo_bottom / hi_bottom).  On the bilinear operator split must equal m (the rows of X); every other
+ * operator refuses the call (FH_E_STATE).                                                                                                    */
+int fh_set_prox_split(fh_ctx* ctx, uint64_t split, int kind_top, double mu_top, double lo_top, double hi_top,
+                      int kind_bottom, double lo_bottom, double hi_bottom);
+/* read-only: the geometry the bilinear launches take (csrc/fh_host_launch.h: bl_shape_for, the ONE rule the launchers call).
+ * out[FH_BILINEAR_SHAPE_LEN] = { LB, NT (1: the non-temporal instantiations), tile rows PR (rows of a row panel), tile columns (512), row panels,
+ * column tiles, RB (rows of S per trip down a panel), trips down a full panel, rows of the LAST panel, live rows of its last trip, lanes that
+ * hold a live column in the LAST column tile (of 256), workgroups of the pass, most and fewest tiles a workgroup takes (they differ when the
+ * grid does not divide the tile count), workgroups of the elementwise launches, bytes of the GX partials, bytes of the GY partials }.
+ * fh_bilinear_shape reads the context (FH_TUNE_FWD_GRID_CAP, FH_TUNE_NT_LOADS) and is FH_E_STATE without a bilinear operator;
+ * fh_bilinear_shape_for is the same rule as a pure host function (no device needed) of m, n, K and the two tuning values as fh_set_tuning
+ * takes them (0 = auto; nt_loads: -1 = auto, 0, 1).                                                                                          */
+#define FH_BILINEAR_SHAPE_LEN 17
+int fh_bilinear_shape(fh_ctx* ctx, uint32_t* out);
+int fh_bilinear_shape_for(uint64_t m, uint64_t n, uint32_t K, long long grid_cap, int nt_loads, uint32_t* out);
 
 /* ---- multi-column form: the unknown is an (n, L) MATRIX, one A for all L columns (examples/mmv.py; multi-column LASSO / NNLS) -----------
  * fh_set_rhs(ctx, L), L in 1..16, on a plain single-device context with a dense float64 operator (a sparse one: fh_set_matrix_csr_rhs above): every n-side vector (FH_VEC_X0 .. BEST,
