@@ -1503,24 +1503,86 @@ static const RunEntry kRunTable[] = {{1, k_run_dense<1>}, {2, k_run_dense<2>}, {
                                      {10, k_run_dense<10>}, {12, k_run_dense<12>}, {14, k_run_dense<14>}};
 // (16 pieces per lane -- n in (7168, 8192] -- were measured and left out: 8192^2 158 us per iteration against 140 us on the per-iteration path,
 //  profiles/r05_device_loop.txt)
-static const RunEntry* run_entry(fh_ctx* c) {
-  if (c->op != OP_DENSE || c->f32 || c->LB || row_sharded(c) || !c->shards.empty()) return nullptr;
-  if (c->prox_kind != FH_PROX_IDENTITY && c->prox_kind != FH_PROX_SHRINK && c->prox_kind != FH_PROX_NONNEG && c->prox_kind != FH_PROX_BOX) return nullptr;
+// THE GEOMETRY of the persistent launch, stated once: a pure function of the matrix (m rows, mp = round_up(m, 16) rows on the device, n columns,
+// rows of ld doubles), the CUs the launch may take (fused_ncu: FH_TUNE_FUSED_CUS capped by the device's count) and three tuning values as the
+// context keeps them (min_rows: the rows-per-team floor, 0 = none; run_max_n: FH_TUNE_RUN_MAX_N; nt_loads: FH_TUNE_NT_LOADS, -1 = auto).  fh_run
+// takes every number from here; fh_run_shape / fh_run_shape_for export it so that a test can assert the path it meant to reach.  e = nullptr: no kernel.
+struct RunShape {
+  const RunEntry* e;
+  int need;                          // 16-byte pieces per lane the row needs (the entry is the first of the table with ppt >= need)
+  int nt;
+  uint32_t ld2, nteams, rows_per_team;
+};
+static RunShape run_shape_for(uint64_t m, uint64_t mp, uint64_t n, uint64_t ld, int ncu, int min_rows, int run_max_n, int nt_loads) {
+  RunShape s;
+  memset(&s, 0, sizeof(s));
   // a workgroup owns whole rows: 16-byte pieces per lane = the first table entry that covers the row (lanes past the row's end re-read its last piece)
-  const uint64_t pieces = round_up(c->n, 16) / 2;
-  if (c->ld % 2 || pieces == 0 || pieces > (uint64_t)FH_WG * 14) return nullptr;
+  const uint64_t pieces = round_up(n, 16) / 2;
+  if (ld % 2 || pieces == 0 || pieces > (uint64_t)FH_WG * 14 || ncu < 1) return s;
   // ... and it is OFFERED only where it beats one launch per iteration issued by fh_iterate (profiles/r06_device_loop.txt: a grid of 36 shapes, ratio
   // device / library loop): whole rows in LDS (n <= 4096) up to 32 Mi elements -- beyond, the launches are long enough to hide their fixed cost and the
   // team kernel streams faster (4096 x 16384: 0.96, 2048 x 32768: 0.95); the wide shapes (n <= 6144) from 4096 rows on -- below, the redundant n-side
   // work of every workgroup costs more than a launch (1024 x 6144: 0.94) -- up to 40 Mi elements (8192 x 6144: 0.97; 6144^2: 1.08, 4096 x 6144: 1.19).
   // FH_TUNE_RUN_MAX_N = N replaces the window by "n <= N, any m" (tests, probes).
-  if (c->run_max_n > 0) { if (c->n > (uint64_t)c->run_max_n) return nullptr; }
-  else if (c->n <= 4096) { if (c->m * c->n > ((uint64_t)1 << 25)) return nullptr; }
-  else if (c->n <= (uint64_t)kRunDefaultMaxN) { if (c->m < 4096 || c->m * c->n > ((uint64_t)40 << 20)) return nullptr; }
-  else return nullptr;
-  const int need = (int)((pieces + FH_WG - 1) / FH_WG);
-  for (const RunEntry& e : kRunTable) if (e.ppt >= need) return &e;
-  return nullptr;
+  if (run_max_n > 0) { if (n > (uint64_t)run_max_n) return s; }
+  else if (n <= 4096) { if (m * n > ((uint64_t)1 << 25)) return s; }
+  else if (n <= (uint64_t)kRunDefaultMaxN) { if (m < 4096 || m * n > ((uint64_t)40 << 20)) return s; }
+  else return s;
+  s.need = (int)((pieces + FH_WG - 1) / FH_WG);
+  for (const RunEntry& e : kRunTable) if (e.ppt >= s.need) { s.e = &e; break; }
+  if (!s.e) return s;
+  s.nt = nt_rule(nt_loads, mp, ld, 0) ? 1 : 0;
+  s.ld2 = (uint32_t)pieces;
+  // one workgroup per CU; fewer when m is small: at least `min_rows` rows per workgroup, in steps of 8 workgroups
+  s.nteams = (uint32_t)ncu;
+  if (min_rows > 0) {
+    const uint64_t want = std::max<uint64_t>(8, round_up((mp + min_rows - 1) / min_rows, 8));
+    s.nteams = (uint32_t)std::min<uint64_t>(s.nteams, want);
+  }
+  s.rows_per_team = (uint32_t)((mp + s.nteams - 1) / s.nteams);
+  return s;
+}
+static RunShape run_shape(fh_ctx* c) {
+  const bool form = c->op == OP_DENSE && !c->f32 && !c->LB && !row_sharded(c) && c->shards.empty() &&
+                    (c->prox_kind == FH_PROX_IDENTITY || c->prox_kind == FH_PROX_SHRINK || c->prox_kind == FH_PROX_NONNEG || c->prox_kind == FH_PROX_BOX);
+  if (!form) { RunShape s; memset(&s, 0, sizeof(s)); return s; }
+  return run_shape_for(c->m, c->mp, c->n, c->ld, fused_ncu(c), c->fused_min_rows, c->run_max_n, c->nt_loads);
+}
+static const RunEntry* run_entry(fh_ctx* c) { return run_shape(c).e; }
+// What k_run_dense<PPT> derives from that shape, for the report (csrc/fh_run.h: its constants XLDS / BIG / NB, the row blocks from
+// `rows_per_team`, phase B's split of the columns): out[FH_RUN_SHAPE_LEN] as include/fasta_hip.h lists it.
+static void run_shape_report(const RunShape& s, uint64_t mp, uint32_t* out) {
+  const uint32_t ppt = (uint32_t)s.e->ppt, G = s.nteams;
+  const uint32_t xlds = ppt >= 7 ? 1u : 0u, big = ppt > 8 ? 1u : 0u, nb = big ? 3u : (ppt >= 7 ? 4u : (ppt >= 5 ? 5u : 6u));
+  const uint32_t live = (uint32_t)((mp + s.rows_per_team - 1) / s.rows_per_team);          // workgroups that own rows
+  const uint32_t share = (s.ld2 + G - 1) / G;
+  const uint32_t slices = share < FH_WG ? std::min<uint32_t>(FH_WG / std::max(share, 1u), G) : 1u;
+  const uint32_t v[FH_RUN_SHAPE_LEN] = {ppt, (uint32_t)s.need, xlds, big, nb, G, s.rows_per_team, G - live,
+                                        (uint32_t)(mp - (uint64_t)(live - 1) * s.rows_per_team), share, slices, (G + slices - 1) / slices,
+                                        (share + FH_WG - 1) / FH_WG, (uint32_t)s.nt, s.ld2};
+  memcpy(out, v, sizeof(v));
+}
+// read-only: the geometry the next fh_run of this context launches with, in its persistent form (FH_E_STATE where that form has no kernel)
+extern "C" int fh_run_shape(fh_ctx* c, uint32_t* out) {
+  if (!c || !out) return fail(FH_E_ARG, "fh_run_shape: null argument");
+  const RunShape s = run_shape(c);
+  if (!s.e) return fail(FH_E_STATE, "fh_run_shape: no persistent launch for this operator / prox / shape (see fh_run_supported)");
+  run_shape_report(s, c->mp, out);
+  return 0;
+}
+// ... and the same rule for an (m, n) dense float64 matrix that no context holds: a pure host function, no device needed
+extern "C" int fh_run_shape_for(uint64_t m, uint64_t n, int cus, int min_rows, int run_max_n, int nt_loads, uint32_t* out) {
+  if (!out) return fail(FH_E_ARG, "fh_run_shape_for: null argument");
+  if (m == 0 || n == 0 || m >= (1ull << 31) || n >= (1ull << 31)) return fail(FH_E_ARG, "fh_run_shape_for: matrix dimensions must be in [1, 2^31)");
+  if (cus < 1 || cus > 65536) return fail(FH_E_ARG, "fh_run_shape_for: cus (the CUs the launch may take) must be in [1, 65536]");
+  if (min_rows < 0 || min_rows >= 0xFFFF) return fail(FH_E_ARG, "fh_run_shape_for: min_rows must be in [0, 65535) (0 = no floor)");
+  if (run_max_n < 0 || run_max_n > 7168) return fail(FH_E_ARG, "RUN_MAX_N must be in [0, 7168] (0 = the measured default; 7168 = the widest row fh_run has a kernel for)");
+  if (nt_loads < -1 || nt_loads > 1) return fail(FH_E_ARG, "fh_run_shape_for: nt_loads is -1 (auto), 0 or 1");
+  const uint64_t mp = round_up(m, 16);
+  const RunShape s = run_shape_for(m, mp, n, round_up(n, 16), cus, min_rows, run_max_n, nt_loads);
+  if (!s.e) return fail(FH_E_STATE, "fh_run_shape_for: no persistent launch for a %llu x %llu matrix (see fh_run_supported)", (unsigned long long)m, (unsigned long long)n);
+  run_shape_report(s, mp, out);
+  return 0;
 }
 // The chained form (k_fused_chain, csrc/fh_fused.h) can serve what the persistent launch does not: float64 shapes of 1 / 2 / 4 team members
 // (n <= 16384) outside fh_run's window -- same prox kinds, single context.  OPT-IN (FH_TUNE_RUN_CHAIN = 1): it removes the gap between two
@@ -1588,7 +1650,8 @@ extern "C" int fh_run(fh_ctx* c, int max_steps, const fh_run_opts* o, fh_run_sta
   if (c->op == OP_QUAD) return fail(FH_E_STATE, "fh_run: the quadratic operator has no device-side loop: use fh_iterate");
   if (c->op == OP_BILINEAR) return fail(FH_E_STATE, "fh_run: the bilinear operator has no device-side loop: use fh_iterate");
   if (c->LB) return fail(FH_E_STATE, "fh_run: the multi-column form (fh_set_rhs) has no device-side loop: use fh_iterate");
-  const RunEntry* e = run_entry(c);
+  const RunShape sh = run_shape(c);
+  const RunEntry* e = sh.e;
   if (!e && chain_ok(c) && co_resident(c)) return run_chain(c, max_steps, o, state, history, steps_done);
   if (!e || !co_resident(c)) return fail(FH_E_STATE, "fh_run: no device-side loop for this operator / loss / prox (see fh_run_supported)");
   FH_TRY(use_device(c));
@@ -1597,18 +1660,13 @@ extern "C" int fh_run(fh_ctx* c, int max_steps, const fh_run_opts* o, fh_run_sta
   RunP p;
   run_state_in(c, state, &p.init);                      // the state on entry travels as a kernel argument
   p.A = c->A; p.n = (uint32_t)c->n; p.m = (uint32_t)c->m; p.mp = (uint32_t)c->mp;
-  p.ld2 = (uint32_t)(round_up(c->n, 16) / 2); p.ldp = (uint32_t)(c->ld / 2); p.nv2 = p.ld2;
-  p.nteams = (uint32_t)fused_ncu(c);
-  if (c->fused_min_rows > 0) {
-    const uint64_t want = std::max<uint64_t>(8, round_up((c->mp + c->fused_min_rows - 1) / c->fused_min_rows, 8));
-    p.nteams = (uint32_t)std::min<uint64_t>(p.nteams, want);
-  }
-  p.rows_per_team = (uint32_t)((c->mp + p.nteams - 1) / p.nteams);
+  p.ld2 = sh.ld2; p.ldp = (uint32_t)(c->ld / 2); p.nv2 = p.ld2;
+  p.nteams = sh.nteams; p.rows_per_team = sh.rows_per_team;      // (the geometry: run_shape_for above, what fh_run_shape reports)
   double* nb[5] = {c->X[0], c->X[1], c->X[2], c->P[0], c->P[1]};
   for (int q = 0; q < 5; ++q) p.nbuf[q] = nb[q];
   p.G[0] = c->G[0]; p.G[1] = c->G[1]; p.Z[0] = c->Z[0]; p.Z[1] = c->Z[1]; p.xhat = c->xhat; p.b = c->b;
   p.loss = c->loss_kind; p.prox_kind = c->prox_kind; p.mu = c->mu; p.lo = c->lo; p.hi = c->hi;
-  p.nt = nt_for(c);
+  p.nt = sh.nt;
   p.g_kind = g_kind_of(c);
   run_opts_in(o, &p.o);
   p.max_steps = max_steps;

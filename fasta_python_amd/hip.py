@@ -115,6 +115,8 @@ SIGNATURES = {
     "fh_abi_sizes": (_i32, [C.POINTER(_u64)]),
     "fh_run_supported": (_i32, [_ctx, C.POINTER(_i32)]),
     "fh_run": (_i32, [_ctx, _i32, C.POINTER(RunOpts), C.POINTER(RunState), _pd, C.POINTER(_i32)]),
+    "fh_run_shape": (_i32, [_ctx, C.POINTER(C.c_uint32)]),
+    "fh_run_shape_for": (_i32, [_u64, _u64, _i32, _i32, _i32, _i32, C.POINTER(C.c_uint32)]),
     "fh_iterate": (_i32, [_ctx, _i32, C.POINTER(RunOpts), C.POINTER(RunState), _pd, C.POINTER(_i32)]),
     "fh_recovered_count": (_i32, [_ctx, _i32, C.POINTER(_u64)]),
     "fh_fused_supported": (_i32, [_ctx, C.POINTER(_i32)]),
@@ -260,8 +262,22 @@ def bilinear_shape(m, n, K, grid_cap=0, nt_loads=-1):
     return BilinearShape(*(int(v) for v in out))
 
 
+RUN_SHAPE_LEN = 15
+RunShape = collections.namedtuple("RunShape", "PPT need XLDS BIG NB G rows_per_team empty_wgs last_rows share slices tps trips NT ld2")
+
+
+def run_shape_for(m, n, cus=256, min_rows=16, run_max_n=0, nt_loads=-1):
+    """RunShape of fh_run's persistent launch (csrc/fh_run.h) for an (m, n) dense float64 matrix on `cus` CUs (FH_TUNE_FUSED_CUS capped by the
+    device's count) under the rows-per-team floor `min_rows` (the high half of FH_TUNE_FUSED_VARIANT; 16 by default, 0 = none),
+    FH_TUNE_RUN_MAX_N and FH_TUNE_NT_LOADS (-1 = auto): fh_run_shape_for, the rule fh_run itself calls.  Host-only."""
+    lib = load_library()
+    out = (C.c_uint32 * RUN_SHAPE_LEN)()
+    _check(lib, lib.fh_run_shape_for(int(m), int(n), int(cus), int(min_rows), int(run_max_n), int(nt_loads), out))
+    return RunShape(*(int(v) for v in out))
+
+
 TV3D_SHAPE_LEN = 8
-Tv3dShape = collections.namedtuple("Tv3dShape", "tile_h tile_w planes tiles_h tiles_w chunks grid NT")
+Tv3dShape =collections.namedtuple("Tv3dShape", "tile_h tile_w planes tiles_h tiles_w chunks grid NT")
 
 
 def tv3d_shape(D, H, W, planes=0, ncu=256):
@@ -653,6 +669,13 @@ class HipContext:
         yes = _i32(0)
         self._call("fh_run_supported", C.byref(yes))
         return bool(yes.value)
+
+    def run_shape(self):
+        """RunShape the next run() of this context launches with (fh_run_shape): which instantiation, the grid, the row blocks and phase B's
+        split.  E_STATE where the persistent launch has no kernel for the context."""
+        out = (C.c_uint32 * RUN_SHAPE_LEN)()
+        self._call("fh_run_shape", out)
+        return RunShape(*(int(v) for v in out))
 
     def run(self, max_steps, opts, state):
         """Up to `max_steps` FBS iterations in one persistent launch.  `opts`: RunOpts, `state`: RunState (updated in place).

@@ -471,6 +471,19 @@ int fh_run_supported(fh_ctx* ctx, int* yes);
  * the context and `state` are those of the last COMPLETED iteration (state->tau_next = the step the interrupted iteration started with),
  * `history` / `steps_done` describe the completed ones -- the caller continues with fh_iterate or fh_step.  Any other failure: FH_E_STATE. */
 int fh_run(fh_ctx* ctx, int max_steps, const fh_run_opts* opts, fh_run_state* state, double* history, int* steps_done);
+/* The geometry of fh_run's persistent launch, from the one host function the launcher itself takes it from (csrc/fasta_hip.hip: run_shape_for),
+ * so that a test can assert the path it meant to reach.  out[FH_RUN_SHAPE_LEN] = { PPT (16-byte pieces per lane: the instantiation
+ * k_run_dense<PPT>), the pieces per lane the row needs (PPT is the next table entry: 1, 2, 4, 5, 6, 7, 8, 10, 12, 14), XLDS (1: the dot products
+ * read the prox output from LDS), BIG (1: g0 and x_accel0 come from L2 in every attempt), NB (row buffers), G (workgroups), rows per workgroup,
+ * workgroups with no rows, rows of the last workgroup that has any, phase B: columns pairs per workgroup (share), slices of the workgroup
+ * range a workgroup sums side by side, workgroups per slice (tps), trips over its share; NT (1: A is streamed with non-temporal loads), ld2
+ * (16-byte pieces per row) }.  fh_run_shape reads the context (its matrix, prox kind, FH_TUNE_FUSED_CUS capped by the device's CUs, the
+ * rows-per-team floor of FH_TUNE_FUSED_VARIANT, FH_TUNE_RUN_MAX_N, FH_TUNE_NT_LOADS) and is FH_E_STATE where the persistent launch has no kernel;
+ * fh_run_shape_for is the same rule as a pure host function (no device needed) of an (m, n) dense float64 matrix, `cus` = the CUs the launch
+ * may take, `min_rows` = the rows-per-team floor (16 by default, 0 = none) and the two tuning values as fh_set_tuning takes them.       */
+#define FH_RUN_SHAPE_LEN 15
+int fh_run_shape(fh_ctx* ctx, uint32_t* out);
+int fh_run_shape_for(uint64_t m, uint64_t n, int cus, int min_rows, int run_max_n, int nt_loads, uint32_t* out);
 /* The same loop driven from the HOST side of the library (csrc/fh_host_iterate.h), for EVERY operator, loss, prox and sharding form the
  * step entry points serve -- a dense matrix of any width, the level-search prox kinds, the stencil, float32 storage, row blocks in this
  * process, a rank of a row-sharded run (every rank calls it with the same arguments).  Per iteration it issues what the Python driver of

@@ -48,6 +48,10 @@ def build(directory):
     lib.fc_shim_backtrack.argtypes = [C.POINTER(Opts), C.POINTER(State), C.c_int, _pd, C.c_double, C.c_int]
     lib.fc_shim_decide.restype = None
     lib.fc_shim_decide.argtypes = [C.POINTER(Opts), C.POINTER(State), C.c_int, C.c_int, C.c_double, _pd, C.c_double, C.c_int, _pd, C.POINTER(Decision)]
+    lib.fc_shim_backtrack_mul.restype, lib.fc_shim_backtrack_mul.argtypes = C.c_int, lib.fc_shim_backtrack.argtypes
+    lib.fc_shim_decide_mul.restype, lib.fc_shim_decide_mul.argtypes = None, lib.fc_shim_decide.argtypes
+    lib.fc_shim_alpha_mul.restype, lib.fc_shim_alpha_mul.argtypes = None, [C.POINTER(Opts), C.c_double, C.c_double, _pd]
+    lib.fc_shim_rotate.restype, lib.fc_shim_rotate.argtypes = None, [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     sizes = (C.c_ulonglong * 3)()
     lib.fc_shim_sizes(sizes)
     assert list(sizes) == [C.sizeof(Opts), C.sizeof(State), C.sizeof(Decision)], "struct layouts of fh_loop.h / fh_controller.h moved"
@@ -66,15 +70,31 @@ def opts_of(o):
     return Opts(**{k: getattr(o, k) for k, _ in Opts._fields_})
 
 
-def backtrack(o, st, lsq, scalars, tau, bt):
-    """the accept test: True = reject this attempt"""
+def backtrack(o, st, lsq, scalars, tau, bt, mul=False):
+    """the accept test: True = reject this attempt (mul: squares as the device forms them, FcSqMul)"""
     s = (C.c_double * len(scalars))(*scalars)
-    return bool(get().fc_shim_backtrack(C.byref(o), C.byref(st), int(lsq), s, float(tau), int(bt)))
+    fn = get().fc_shim_backtrack_mul if mul else get().fc_shim_backtrack
+    return bool(fn(C.byref(o), C.byref(st), int(lsq), s, float(tau), int(bt)))
 
 
-def decide(o, st, lsq, g_kind, mu, scalars, tau, bt):
+def decide(o, st, lsq, g_kind, mu, scalars, tau, bt, mul=False):
     """the decision after an accepted attempt: advances `st`, returns (Decision, history record)"""
     s = (C.c_double * len(scalars))(*scalars)
     rec, d = (C.c_double * hip.RUN_HIST)(), Decision()
-    get().fc_shim_decide(C.byref(o), C.byref(st), int(lsq), int(g_kind), float(mu), s, float(tau), int(bt), rec, C.byref(d))
+    fn = get().fc_shim_decide_mul if mul else get().fc_shim_decide
+    fn(C.byref(o), C.byref(st), int(lsq), int(g_kind), float(mu), s, float(tau), int(bt), rec, C.byref(d))
     return d, list(rec)
+
+
+def alpha_mul(o, alpha1, rdot):
+    """(alpha0, alpha1, coef) of fc_alpha with the device's square"""
+    out = (C.c_double * 3)()
+    get().fc_shim_alpha_mul(C.byref(o), float(alpha1), float(rdot), out)
+    return tuple(out)
+
+
+def rotate(accelerate, better, roles, perm):
+    """fc_rotate on roles = [xi, ti, bi, pc, gc, zc, last_accel] and perm[5]: the new (roles, perm)"""
+    r, p = (C.c_int * 7)(*roles), (C.c_int * 5)(*perm)
+    get().fc_shim_rotate(int(accelerate), int(better), r, p)
+    return list(r), list(p)

@@ -13,3 +13,23 @@ extern "C" void fc_shim_decide(const RunOpts* o, RunState* st, int lsq, int g_ki
   *d = fc_decide(*o, lsq != 0, g_kind, mu, s, tau, bt, st->alpha1, st->max_residual, st->best_quality, record, ShimSq());
   fc_advance(*st, *d, bt);
 }
+// ... and instantiated as the DEVICE instantiates it (FcSqMul: a square is a product), for the exact-arithmetic tier of the persistent launch
+// (tests/run_paths.py restates the controller in Python; tests/test_run_paths_cpu.py proves the restatement equal to these)
+extern "C" int fc_shim_backtrack_mul(const RunOpts* o, const RunState* st, int lsq, const double* s, double tau, int bt) {
+  return fc_backtrack(*o, st->f_window, st->iteration, fc_f(lsq != 0, s[FC_FSQ], FcSqMul()), s[FC_DXG0], s[FC_DX2], tau, bt, FcSqMul()) ? 1 : 0;
+}
+extern "C" void fc_shim_decide_mul(const RunOpts* o, RunState* st, int lsq, int g_kind, double mu, const double* s, double tau, int bt, double* record, FcDecision* d) {
+  *d = fc_decide(*o, lsq != 0, g_kind, mu, s, tau, bt, st->alpha1, st->max_residual, st->best_quality, record, FcSqMul());
+  fc_advance(*st, *d, bt);
+}
+extern "C" void fc_shim_alpha_mul(const RunOpts* o, double alpha1, double rdot, double* out3) {
+  const FcAlpha a = fc_alpha(*o, alpha1, rdot, FcSqMul());
+  out3[0] = a.alpha0; out3[1] = a.alpha1; out3[2] = a.coef;
+}
+// roles = {xi, ti, bi, pc, gc, zc, last_accel}
+extern "C" void fc_shim_rotate(int accelerate, int better, int* roles, int* perm) {
+  int p[5];
+  for (int k = 0; k < 5; ++k) p[k] = perm[k];
+  fc_rotate(accelerate != 0, better != 0, roles[0], roles[1], roles[2], roles[3], roles[4], roles[5], roles[6], p);
+  for (int k = 0; k < 5; ++k) perm[k] = p[k];
+}
