@@ -14,11 +14,11 @@ loss + tagged prox) run the HIP loop and raise when the built `libfasta_hip.so` 
 """
 
 from . import generic, hip, linalg, losses, proximal, stopping
-from .linalg import BilinearMap, DenseMatrixMap, GradDivMap, LinearMap, LinearOperator, QuadraticMap, ShardedDenseMatrixMap, SparseMatrixMap
+from .linalg import BilinearMap, DCTMap, DenseMatrixMap, GradDivMap, LinearMap, LinearOperator, QuadraticMap, ShardedDenseMatrixMap, SparseMatrixMap
 from .losses import Factorization, LeastSquares, LogisticLoss, Quadratic
 from .proximal import Box, GroupShrink, L1Ball, LinfProx, NonNeg, NoProx, RowBall, RowSplit, Shrink, TVDualBall
 from .solver import EPSILON, Convergence, FBSolver, fasta
 
 __all__ = ["fasta", "Convergence", "FBSolver", "EPSILON", "linalg", "proximal", "stopping", "losses", "hip",
-           "LinearMap", "LinearOperator", "DenseMatrixMap", "ShardedDenseMatrixMap", "SparseMatrixMap", "GradDivMap", "QuadraticMap", "BilinearMap", "LeastSquares", "LogisticLoss", "Quadratic", "Factorization",
+           "LinearMap", "LinearOperator", "DenseMatrixMap", "ShardedDenseMatrixMap", "SparseMatrixMap", "GradDivMap", "DCTMap", "QuadraticMap", "BilinearMap", "LeastSquares", "LogisticLoss", "Quadratic", "Factorization",
            "Shrink", "NonNeg", "LinfProx", "L1Ball", "Box", "TVDualBall", "GroupShrink", "RowBall", "RowSplit", "NoProx"]

@@ -23,6 +23,7 @@
 #include "fh_spmulti.h"
 #include "fh_tv.h"
 #include "fh_tv3d.h"
+#include "fh_dct.h"
 #include "fh_prox.h"
 #include "fh_fused.h"
 #include "fh_setup.h"
@@ -125,6 +126,10 @@ SPMC_FOR_EACH_LB(SPMC_INSTANTIATE_LB)
 SPMC_FOR_EACH(SPMC_INSTANTIATE)
 #undef SPMC_INSTANTIATE
 TV3_KERNELS(template)
+#define DCT_INSTANTIATE(LDSN) DCT_KERNELS(template, LDSN)
+DCT_FOR_EACH(DCT_INSTANTIATE)
+#undef DCT_INSTANTIATE
+DCT_TILE_KERNELS(template)
 #endif
 
 #include "fh_host_ctx.h"
@@ -348,6 +353,9 @@ static int set_tuning_one(fh_ctx* c, int key, long long value) {
     case FH_TUNE_TV3_PLANES:
       if (value < 0 || value > (1ll << 30)) return fail(FH_E_ARG, "TV3_PLANES must be in [0, 2^30] planes per workgroup (0 = auto)");
       c->tv3_planes = (int)value; return 0;
+    case FH_TUNE_DCT_ROW_CAP:
+      if (value != 0 && (value < 2 || value > DCT_ROW_CAP)) return fail(FH_E_ARG, "DCT_ROW_CAP must be 0 (default: %d) or in [2, %d] elements per row transform", DCT_ROW_CAP, DCT_ROW_CAP);
+      c->dct_row_cap = (int)value; return 0;
     case FH_TUNE_TV_PIPE:
       if (value < 0 || value > 3) return fail(FH_E_ARG, "TV_PIPE must be 0 (auto), 1 (load a trip, consume it) or 3 (three rotating trip buffers; 2 is taken as 3)");
       c->tv_pipe = (int)value; return 0;
@@ -653,6 +661,7 @@ extern "C" int fh_get_matrix_rows(fh_ctx* c, uint64_t row0, uint64_t nrows, doub
   if (!c || !out) return fail(FH_E_ARG, "null argument");
   if (c->op == OP_SPARSE) return fail(FH_E_STATE, "fh_get_matrix_rows: the sparse operator keeps no dense rows");
   if (c->op == OP_STENCIL3D) return fail(FH_E_STATE, "fh_get_matrix_rows: the 3-D stencil operator keeps no dense rows");
+  if (c->op == OP_DCT) return fail(FH_E_STATE, "fh_get_matrix_rows: the DCT operator keeps no dense rows");
   if (c->op == OP_QUAD) return fail(FH_E_STATE, "fh_get_matrix_rows: the quadratic operator is not read back (the caller holds Q)");
   if (c->op == OP_BILINEAR) return fail(FH_E_STATE, "fh_get_matrix_rows: the bilinear operator is not read back (the caller holds S)");
   if (c->op != OP_DENSE) return fail(FH_E_STATE, "no dense matrix set");
@@ -728,6 +737,33 @@ extern "C" int fh_set_stencil3d(fh_ctx* c, uint64_t D, uint64_t H, uint64_t W) {
   return finish(c);
 }
 
+// the subsampled DCT (csrc/fh_dct.h): A = diag(d) * C, m = n = N; vectors in the vector form's padded layout, no matrix stored: two twiddle
+// tables built here in long double, a copy of d, and two work buffers of N double2 when the transform takes two levels
+extern "C" int fh_set_dct(fh_ctx* c, uint64_t N, const double* diag) {
+  if (!c) return fail(FH_E_ARG, "null context");
+  if (!c->shards.empty() || c->owner) return fail(FH_E_STATE, "fh_set_dct: a multi-device context has no DCT operator (row sharding is implemented for the dense operator only)");
+  if (c->comm) return fail(FH_E_STATE, "fh_set_dct: a context with a communicator (row-sharded run) has no DCT operator");
+  if (c->f32) return fail(FH_E_STATE, "fh_set_dct: float32 storage is a storage mode of a dense matrix; the DCT operator stores no matrix and computes in float64");
+  if (c->pending_step) return fail(FH_E_STATE, "a step issued by fh_step_begin is still in flight on this context: call fh_step_end first");
+  DctShape sh;
+  FH_TRY(dct_shape_for(N, c->dct_row_cap, c->ncu, &sh));   // (N >= 1, prime factors in {2, 3, 5}, a split within the row cap: FH_E_ARG with the sentence)
+  FH_TRY(use_device(c));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  free_operator(c);
+  if (!dct_prox_ok(c->prox_kind)) { c->prox_kind = FH_PROX_IDENTITY; c->mu = 0.0; }
+  c->loss_kind = LOSS_LSQ; c->lazy = false; c->last_accel = false; c->commits = 0;
+  c->m = c->n = N;
+  c->mp = c->m; c->ld = c->n;
+  c->nv = round_up(c->n, 16); c->mv = round_up(c->m, 16);
+  c->dct_sh = sh;
+  c->dct_sc0 = (double)sqrtl(1.0L / (long double)N); c->dct_sck = (double)sqrtl(2.0L / (long double)N);
+  c->op = OP_DCT;                                         // (from here on free_operator gives the tables back)
+  int rc = alloc_vectors(c);
+  if (rc == 0) rc = dct_alloc_tables(c, sh, diag);
+  if (rc != 0) { free_operator(c); return rc; }
+  return finish(c);
+}
+
 extern "C" int fh_shape(fh_ctx* c, uint64_t* m, uint64_t* n) {
   if (!c || !m || !n) return fail(FH_E_ARG, "null argument");
   if (c->op == OP_NONE) return fail(FH_E_STATE, "no operator set");
@@ -745,6 +781,7 @@ extern "C" int fh_set_rhs(fh_ctx* c, uint32_t L) {
   if (c->op == OP_NONE) return fail(FH_E_STATE, "fh_set_rhs: set the dense operator first (fh_set_matrix / fh_generate_matrix)");
   if (c->op == OP_SPARSE) return fail(FH_E_STATE, "fh_set_rhs: the sparse operator has no multi-column form through fh_set_rhs: its column count is fixed when it is set (fh_set_matrix_csr_rhs)");
   if (c->op == OP_STENCIL3D) return fail(FH_E_STATE, "fh_set_rhs: the 3-D stencil operator has no multi-column form");
+  if (c->op == OP_DCT) return fail(FH_E_STATE, "fh_set_rhs: the DCT operator has no multi-column form");
   if (c->op == OP_QUAD) return fail(FH_E_STATE, "fh_set_rhs: the column count of a quadratic operator is fixed when it is set (fh_set_quadratic)");
   if (c->op == OP_BILINEAR) return fail(FH_E_STATE, "fh_set_rhs: the column count of a bilinear operator is fixed when it is set (fh_set_factorization)");
   if (c->op != OP_DENSE) return fail(FH_E_STATE, "fh_set_rhs: the stencil operator has no multi-column form");
@@ -881,6 +918,7 @@ static int set_loss(fh_ctx* c, int kind, const double* b, uint64_t len) {
   if (len != c->m * l_of(c)) return fail(FH_E_ARG, "b has %llu entries, operator has %llu rows (x %llu columns)", (unsigned long long)len, (unsigned long long)c->m, (unsigned long long)l_of(c));
   if (kind != LOSS_LSQ && c->LB) return fail(FH_E_STATE, "the logistic loss has no multi-column form (fh_set_rhs / fh_set_matrix_csr_rhs)");
   if (kind != LOSS_LSQ && c->op == OP_STENCIL3D) return fail(FH_E_STATE, "the 3-D stencil operator serves the least-squares loss only (the logistic loss is implemented for the dense and sparse operators)");
+  if (kind != LOSS_LSQ && c->op == OP_DCT) return fail(FH_E_STATE, "the DCT operator serves the least-squares loss only (the logistic loss is implemented for the dense and sparse operators)");
   if (kind != LOSS_LSQ && c->op != OP_DENSE && c->op != OP_SPARSE) return fail(FH_E_STATE, "the logistic loss is implemented for the dense operator");
   if (!c->shards.empty()) {          // shell: b is sharded like the rows
     for (int k = 0; k < nshards(c); ++k) FH_TRY(set_loss(c->shards[k], kind, b + c->shard_row0[k], shard_rows(c, k)));
@@ -913,6 +951,7 @@ extern "C" int fh_set_prox(fh_ctx* c, int kind, double mu, double lo, double hi)
   if (c->LB && c->op != OP_QUAD && !mc_prox_ok(kind)) return fail(FH_E_ARG, "prox kind %d (LINF / L1BALL / TVBALL) has no multi-column form", kind);
   if (c->op == OP_SPARSE && !c->LB && !sp_prox_ok(kind)) return fail(FH_E_ARG, "prox kind %d (LINF / L1BALL / TVBALL / GROUP) is not implemented for the sparse operator", kind);
   if (c->op == OP_STENCIL3D && !tv3_prox_ok(kind)) return fail(FH_E_ARG, "prox kind %d (LINF / L1BALL / GROUP) is not implemented for the 3-D stencil operator", kind);
+  if (c->op == OP_DCT && !dct_prox_ok(kind)) return fail(FH_E_ARG, "prox kind %d (TVBALL / GROUP) is not implemented for the DCT operator", kind);
   if (kind == FH_PROX_BOX && !(lo <= hi)) return fail(FH_E_ARG, "box prox needs lo <= hi");
   for (fh_ctx* s : c->shards) { s->prox_kind = kind; s->mu = mu; s->lo = lo; s->hi = hi; }      // the prox is replicated work
   c->prox_kind = kind; c->mu = mu; c->lo = lo; c->hi = hi;
@@ -1419,6 +1458,7 @@ static int step_body(fh_ctx* c, double tau, double* scalars, bool wait) {
   FH_TRY(check_ready(c, true));
   if (c->op == OP_SPARSE) return fail(FH_E_STATE, "fh_step: the sparse operator has no one-pass kernel: use fh_fwd / fh_adj / fh_fwd_adj / fh_iterate");
   if (c->op == OP_STENCIL3D) return fail(FH_E_STATE, "fh_step: the 3-D stencil operator has no one-pass kernel: use fh_fwd / fh_adj / fh_fwd_adj / fh_iterate");
+  if (c->op == OP_DCT) return fail(FH_E_STATE, "fh_step: the DCT operator has no one-pass kernel: use fh_fwd / fh_adj / fh_fwd_adj / fh_iterate");
   if (c->op == OP_QUAD) return fail(FH_E_STATE, "fh_step: the quadratic operator has no one-pass kernel: use fh_fwd / fh_adj / fh_fwd_adj / fh_iterate");
   if (c->op == OP_BILINEAR) return fail(FH_E_STATE, "fh_step: the bilinear operator has no one-pass kernel: use fh_fwd / fh_adj / fh_fwd_adj / fh_iterate");
   if (c->LB) return fail(FH_E_STATE, "fh_step: the multi-column form (fh_set_rhs) has no one-pass kernel: use fh_fwd / fh_adj / fh_iterate");
@@ -1468,6 +1508,7 @@ extern "C" int fh_step_accel(fh_ctx* c, double tau, double coef, int restart, do
   FH_TRY(check_ready(c, true));
   if (c->op == OP_SPARSE) return fail(FH_E_STATE, "fh_step_accel: the sparse operator has no one-pass kernel: use fh_fwd / fh_adj / fh_iterate");
   if (c->op == OP_STENCIL3D) return fail(FH_E_STATE, "fh_step_accel: the 3-D stencil operator has no one-pass kernel: use fh_fwd / fh_adj / fh_iterate");
+  if (c->op == OP_DCT) return fail(FH_E_STATE, "fh_step_accel: the DCT operator has no one-pass kernel: use fh_fwd / fh_adj / fh_iterate");
   if (c->op == OP_QUAD) return fail(FH_E_STATE, "fh_step_accel: the quadratic operator has no one-pass kernel: use fh_fwd / fh_adj / fh_iterate");
   if (c->op == OP_BILINEAR) return fail(FH_E_STATE, "fh_step_accel: the bilinear operator has no one-pass kernel: use fh_fwd / fh_adj / fh_iterate");
   if (c->LB) return fail(FH_E_STATE, "fh_step_accel: the multi-column form (fh_set_rhs) has no one-pass kernel: use fh_fwd / fh_adj / fh_iterate");
@@ -1647,6 +1688,7 @@ extern "C" int fh_run(fh_ctx* c, int max_steps, const fh_run_opts* o, fh_run_sta
   if (o->stop_rule < 0 || o->stop_rule > 3) return fail(FH_E_ARG, "fh_run: stop_rule must be 0..3 (the four rules of fasta/stopping.py)");
   if (c->op == OP_SPARSE) return fail(FH_E_STATE, "fh_run: the sparse operator has no device-side loop: use fh_iterate");
   if (c->op == OP_STENCIL3D) return fail(FH_E_STATE, "fh_run: the 3-D stencil operator has no device-side loop: use fh_iterate");
+  if (c->op == OP_DCT) return fail(FH_E_STATE, "fh_run: the DCT operator has no device-side loop: use fh_iterate");
   if (c->op == OP_QUAD) return fail(FH_E_STATE, "fh_run: the quadratic operator has no device-side loop: use fh_iterate");
   if (c->op == OP_BILINEAR) return fail(FH_E_STATE, "fh_run: the bilinear operator has no device-side loop: use fh_iterate");
   if (c->LB) return fail(FH_E_STATE, "fh_run: the multi-column form (fh_set_rhs) has no device-side loop: use fh_iterate");
@@ -1878,6 +1920,7 @@ extern "C" int fh_comm_init(fh_ctx* c, int nranks, int rank, const void* id128) 
   if (nranks < 1 || rank < 0 || rank >= nranks) return fail(FH_E_ARG, "bad rank %d of %d", rank, nranks);
   if (c->op == OP_SPARSE) return fail(FH_E_STATE, "fh_comm_init: a context with a sparse operator cannot be row-sharded");
   if (c->op == OP_STENCIL3D) return fail(FH_E_STATE, "fh_comm_init: a context with a 3-D stencil operator cannot be row-sharded");
+  if (c->op == OP_DCT) return fail(FH_E_STATE, "fh_comm_init: a context with a DCT operator cannot be row-sharded");
   if (c->op == OP_QUAD) return fail(FH_E_STATE, "fh_comm_init: a context with a quadratic operator cannot be row-sharded");
   if (c->op == OP_BILINEAR) return fail(FH_E_STATE, "fh_comm_init: a context with a bilinear operator cannot be row-sharded");
   if (c->LB) return fail(FH_E_STATE, "fh_comm_init: a context in multi-column form (fh_set_rhs) cannot be row-sharded");
@@ -2071,6 +2114,7 @@ extern "C" int fh_stream_read_ms(fh_ctx* c, int reps, double* ms_per_pass, uint6
   if (!c->shards.empty()) return fh_stream_read_ms(c->shards[0], reps, ms_per_pass, bytes_per_pass);     // shard 0's block on its device
   if (c->op == OP_SPARSE) return fail(FH_E_STATE, "fh_stream_read_ms: the stream-read ceiling is measured on a dense matrix, not on the sparse operator");
   if (c->op == OP_STENCIL3D) return fail(FH_E_STATE, "fh_stream_read_ms: the stream-read ceiling is measured on a dense matrix, not on the 3-D stencil operator");
+  if (c->op == OP_DCT) return fail(FH_E_STATE, "fh_stream_read_ms: the stream-read ceiling is measured on a dense matrix, not on the DCT operator");
   if (c->op == OP_QUAD) return fail(FH_E_STATE, "fh_stream_read_ms: the stream-read ceiling is measured on a dense matrix, not on the quadratic operator");
   if (c->op == OP_BILINEAR) return fail(FH_E_STATE, "fh_stream_read_ms: the stream-read ceiling is measured on a dense matrix, not on the bilinear operator");
   if (c->op != OP_DENSE) return fail(FH_E_STATE, "stream-read ceiling needs a dense matrix");

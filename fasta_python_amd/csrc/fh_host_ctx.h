@@ -94,10 +94,13 @@ static int rccl_load() {
     if (r_ != 0) return fail(20000 + r_, "%s failed: %s", #expr, g_rccl.GetErrorString(r_));  \
   } while (0)
 
+// geometry of the DCT operator's launches (csrc/fh_host_launch.h: dct_shape_for fills it)
+struct DctShape { uint32_t levels, N1, N2, cap; DctRad r1, r2; uint32_t ldsn1, rpw1, grid1, ldsn2, rpw2, grid2, tiles, launches, lds_bytes; };
+
 // ------------------------------------------------------------------------------------------------
 // context
 // ------------------------------------------------------------------------------------------------
-enum { OP_NONE = 0, OP_DENSE = 1, OP_STENCIL = 2, OP_SPARSE = 3, OP_STENCIL3D = 4, OP_QUAD = 5, OP_BILINEAR = 6 };
+enum { OP_NONE = 0, OP_DENSE = 1, OP_STENCIL = 2, OP_SPARSE = 3, OP_STENCIL3D = 4, OP_QUAD = 5, OP_BILINEAR = 6, OP_DCT = 7 };
 
 struct fh_ctx {
   int device = 0;
@@ -122,6 +125,12 @@ struct fh_ctx {
   int rs_kind_top = 0, rs_kind_bot = 0;
   double rs_lo_bot = 0.0, rs_hi_bot = 0.0;
   uint64_t H = 0, W = 0;
+  // subsampled DCT (fh_set_dct, csrc/fh_dct.h): m = n = N; tw[j] = e^{-2 pi i j / N}, pw[k] = e^{-i pi k / 2N}, the diagonal d (nullptr: all ones),
+  // two work buffers of N double2 (two-level transforms only), and what is derived once when the operator is set
+  d2* dct_tw = nullptr; d2* dct_pw = nullptr; double* dct_diag = nullptr;
+  d2* dct_w0 = nullptr; d2* dct_w1 = nullptr;
+  DctShape dct_sh = {};      // the geometry dct_shape_for gave when the operator was set (every launch reads it; fh_dct_shape reports it)
+  double dct_sc0 = 0.0, dct_sck = 0.0;   // sqrt(1/N), sqrt(2/N)
   uint64_t D = 0;            // 3-D stencil (fh_set_stencil3d, csrc/fh_tv3d.h): the volume is (D, H, W), m = D*H*W, n = 3*m
   // sparse operator (fh_set_matrix_csr, csrc/fh_sparse.h): sp[0] = A by rows, sp[1] = A^T by rows, each with its non-zero-balanced row ranges,
   // its list of long rows and the lanes-per-row G chosen from its mean row length; sp_r = the adjoint's residual (m-side).  In multi-column form
@@ -196,6 +205,7 @@ struct fh_ctx {
   int tv_slots = 0;          // FH_TUNE_TV_SLOTS: persistent one-pass sweep, workgroups per CU (0 = one workgroup per chunk)
   int tv_ring = 0;           // FH_TUNE_TV_RING: LDS-DMA trip ring of the one-pass sweep (0 = auto, 1 = off, 2 / 3 = slots per wave)
   int tv3_planes = 0;        // FH_TUNE_TV3_PLANES: planes a workgroup of the 3-D stencil kernels marches over (0 = auto: tv3_shape_for)
+  int dct_row_cap = 0;       // FH_TUNE_DCT_ROW_CAP: longest row transform of the DCT operator (0 = DCT_ROW_CAP); read when fh_set_dct sets the operator
   int tv_pipe = 0;           // FH_TUNE_TV_PIPE: rotating trip buffers of the one-pass sweep (0 = auto, 1 = burst, 2, 3)
   bool fused_variant_auto = true;   // cleared by FH_TUNE_FUSED_VARIANT: the caller's word is taken as it is (fused_variant_for)
   int fused_variant = 2 | 32;   // 2: team members 32 blocks apart (one XCD), best in profiles/r01b_tune_fused.txt; 32 (round 6): rows dealt cyclically to the teams -- the
@@ -392,6 +402,8 @@ static void free_operator(fh_ctx* c) {
     a = SpMatP();
   }
   fr(c->sp_r); c->nnz = 0;
+  for (d2** q : {&c->dct_tw, &c->dct_pw, &c->dct_w0, &c->dct_w1}) if (*q) { (void)hipFree(*q); *q = nullptr; }
+  fr(c->dct_diag);
   free_vectors(c);
   c->L = c->LB = 0;                  // a new operator starts in the vector form
   if (c->loss_kind == LOSS_QUAD) c->loss_kind = LOSS_LSQ;                                        // ... and leaves the quadratic form (fh_set_quadratic) behind:

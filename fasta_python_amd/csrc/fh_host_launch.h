@@ -1,4 +1,4 @@
-// fh_host_launch.h -- kernel launchers of libfasta_hip.so: shapes, grids and workspace of every kernel in fh_dense.h / fh_quad.h / fh_bilinear.h / fh_tv.h / fh_tv3d.h /
+// fh_host_launch.h -- kernel launchers of libfasta_hip.so: shapes, grids and workspace of every kernel in fh_dense.h / fh_quad.h / fh_bilinear.h / fh_tv.h / fh_tv3d.h / fh_dct.h /
 // fh_prox.h / fh_fused.h, the one-pass kernel's shape rule and dispatch table, the co-residency probe, and the three-stage form
 // (local launch / sum over row blocks / n-side epilogue) the C ABI in fasta_hip.hip builds its entry points from.
 #pragma once
@@ -943,6 +943,204 @@ static int launch_adj_tv3(fh_ctx* c, const AdjIO& io) {
   return 0;
 }
 
+// ---- subsampled DCT operator (fh_set_dct; kernels in csrc/fh_dct.h, instantiated by fh_dct_part.hip) -------------------------------------
+#ifndef FH_SINGLE_TU
+#define DCT_DECLARE(LDSN) DCT_KERNELS(extern template, LDSN)
+DCT_FOR_EACH(DCT_DECLARE)
+#undef DCT_DECLARE
+DCT_TILE_KERNELS(extern template)
+#endif
+// THE geometry of every launch of both directions, a pure function of N, the row cap (FH_TUNE_DCT_ROW_CAP; 0 = DCT_ROW_CAP) and the device's CU
+// count.  N <= cap: one row of length N1 = N, N2 = 1, one workgroup, one launch.  Otherwise N = N1 * N2 with N2 the largest divisor of N that is
+// at most the cap and leaves N1 = N / N2 at most the cap too (4096 = 2 * 2048, 6000 = 3 * 2000, 2^22 = 2048 * 2048): five launches, the row
+// transforms of length N1 (N2 rows) and N2 (N1 rows) between three tile launches of ceil(N1 / 32) * ceil(N2 / 32) workgroups.  A row length takes
+// the radices 5, 3, 4, 2 in that order; its LDS class is the smallest of 128 / 512 / 2048 that holds it; a workgroup takes as many rows as the
+// class holds, at most DCT_MAX_ROWS, and fewer where that would leave fewer workgroups than CUs.
+static bool dct_radices(uint64_t L, DctRad* rd) {
+  rd->n = 0; memset(rd->r, 0, sizeof(rd->r));
+  for (uint32_t r : {5u, 3u, 4u, 2u})
+    while (L % r == 0 && L > 1) { if (rd->n == DCT_MAXRAD) return false; rd->r[rd->n++] = (uint8_t)r; L /= r; }
+  return L == 1;
+}
+static inline uint32_t dct_ldsn(uint64_t L) { return L <= 128 ? 128u : (L <= 512 ? 512u : 2048u); }
+static void dct_rows_geometry(uint64_t L, uint64_t nrows, int ncu, uint32_t* ldsn, uint32_t* rpw, uint32_t* grid) {
+  *ldsn = dct_ldsn(L);
+  uint64_t r = std::min<uint64_t>(std::min<uint64_t>(*ldsn / L, DCT_MAX_ROWS), nrows);
+  r = std::max<uint64_t>(1, std::min<uint64_t>(r, nrows / (uint64_t)std::max(1, ncu)));
+  *rpw = (uint32_t)r; *grid = (uint32_t)((nrows + r - 1) / r);
+}
+static int dct_shape_for(uint64_t N, int row_cap, int ncu, DctShape* sh) {
+  memset(sh, 0, sizeof(*sh));
+  if (row_cap != 0 && (row_cap < 2 || row_cap > DCT_ROW_CAP)) return fail(FH_E_ARG, "DCT_ROW_CAP must be 0 (default: %d) or in [2, %d] elements per row transform", DCT_ROW_CAP, DCT_ROW_CAP);
+  const uint64_t cap = row_cap ? (uint64_t)row_cap : DCT_ROW_CAP;
+  sh->cap = (uint32_t)cap;                                // (set from here on: a refusal below is about N, not about the cap)
+  if (N == 0) return fail(FH_E_ARG, "the DCT operator needs N >= 1");
+  uint64_t rest = N;
+  for (uint64_t r : {2u, 3u, 5u}) while (rest % r == 0) rest /= r;
+  if (rest != 1) return fail(FH_E_ARG, "the DCT operator serves lengths whose prime factors are 2, 3 and 5 only: N = %llu has a prime factor above 5", (unsigned long long)N);
+  uint64_t N1 = N, N2 = 1;
+  if (N > cap) {
+    N2 = 0;
+    if (N <= cap * cap)
+      for (uint64_t d = cap; d >= 2; --d) if (N % d == 0 && N / d <= cap) { N2 = d; break; }
+    if (!N2) return fail(FH_E_ARG, "the DCT operator needs N <= the row cap or a split N = N1 * N2 with both factors at most the row cap (%llu): N = %llu has none", (unsigned long long)cap, (unsigned long long)N);
+    N1 = N / N2;
+  }
+  sh->levels = N2 > 1 ? 2u : 1u; sh->N1 = (uint32_t)N1; sh->N2 = (uint32_t)N2; sh->cap = (uint32_t)cap;
+  if (!dct_radices(N1, &sh->r1) || !dct_radices(N2, &sh->r2)) return fail(FH_E_ARG, "the DCT operator: N = %llu needs more than %d radix passes per row", (unsigned long long)N, DCT_MAXRAD);
+  if (sh->levels == 1) {
+    sh->ldsn1 = dct_ldsn(N1); sh->rpw1 = 1; sh->grid1 = 1; sh->launches = 1;
+    sh->lds_bytes = sh->ldsn1 * 2u * (uint32_t)sizeof(d2);
+    return 0;
+  }
+  dct_rows_geometry(N1, N2, ncu, &sh->ldsn1, &sh->rpw1, &sh->grid1);
+  dct_rows_geometry(N2, N1, ncu, &sh->ldsn2, &sh->rpw2, &sh->grid2);
+  sh->tiles = (uint32_t)(((N1 + DCT_TT - 1) / DCT_TT) * ((N2 + DCT_TT - 1) / DCT_TT));
+  sh->launches = 5;
+  sh->lds_bytes = std::max(sh->ldsn1, sh->ldsn2) * 2u * (uint32_t)sizeof(d2);
+  return 0;
+}
+static inline bool dct_prox_ok(int kind) { return sp_prox_ok(kind) || kind == FH_PROX_LINF || kind == FH_PROX_L1BALL; }
+static void dct_shape_out(const DctShape& sh, uint32_t* out) {
+  memset(out, 0, FH_DCT_SHAPE_LEN * sizeof(uint32_t));
+  out[0] = sh.levels; out[1] = sh.N1; out[2] = sh.N2; out[3] = sh.cap;
+  out[4] = sh.r1.n; for (uint32_t i = 0; i < sh.r1.n; ++i) out[5 + i] = sh.r1.r[i];
+  out[17] = sh.r2.n; for (uint32_t i = 0; i < sh.r2.n; ++i) out[18 + i] = sh.r2.r[i];
+  out[30] = sh.ldsn1; out[31] = sh.rpw1; out[32] = sh.grid1; out[33] = sh.ldsn2; out[34] = sh.rpw2; out[35] = sh.grid2;
+  out[36] = FH_WG; out[37] = sh.lds_bytes; out[38] = sh.tiles; out[39] = sh.launches;
+}
+extern "C" int fh_dct_shape(fh_ctx* c, uint32_t* out) {
+  if (!c || !out) return fail(FH_E_ARG, "fh_dct_shape: null argument");
+  if (c->op != OP_DCT) return fail(FH_E_STATE, "fh_dct_shape: the context holds no DCT operator (fh_set_dct)");
+  dct_shape_out(c->dct_sh, out);                          // (what dct_shape_for gave when fh_set_dct set the operator: the launchers read the same copy)
+  return 0;
+}
+extern "C" int fh_dct_shape_for(uint64_t N, int row_cap, int ncu, uint32_t* out) {
+  if (!out) return fail(FH_E_ARG, "fh_dct_shape_for: null argument");
+  DctShape sh;
+  const int rc = dct_shape_for(N, row_cap, ncu, &sh);
+  dct_shape_out(sh, out);                                 // (a refused N: levels = 0, "not served", beside the error and its sentence)
+  return rc;
+}
+
+// the two twiddle tables (long double on the host, rounded once), the diagonal and, for two levels, the work buffers.  A set-up cost, paid once
+// per fh_set_dct: 4 N cosl / sinl calls and a host vector of 16 N bytes (N = 2^22: about 17 M long-double calls, of the order of a second)
+static int dct_alloc_tables(fh_ctx* c, const DctShape& sh, const double* diag) {
+  const uint64_t N = c->n;
+  const long double pi = 3.14159265358979323846264338327950288L;
+  std::vector<double> t(2 * N);
+  HIP_TRY(hipMalloc((void**)&c->dct_tw, N * sizeof(d2)));
+  HIP_TRY(hipMalloc((void**)&c->dct_pw, N * sizeof(d2)));
+  for (uint64_t j = 0; j < N; ++j) { const long double a = 2.0L * pi * (long double)j / (long double)N; t[2 * j] = (double)cosl(a); t[2 * j + 1] = (double)-sinl(a); }
+  HIP_TRY(hipMemcpy(c->dct_tw, t.data(), N * sizeof(d2), hipMemcpyHostToDevice));
+  for (uint64_t k = 0; k < N; ++k) { const long double a = pi * (long double)k / (2.0L * (long double)N); t[2 * k] = (double)cosl(a); t[2 * k + 1] = (double)-sinl(a); }
+  HIP_TRY(hipMemcpy(c->dct_pw, t.data(), N * sizeof(d2), hipMemcpyHostToDevice));
+  if (diag) {
+    HIP_TRY(hipMalloc((void**)&c->dct_diag, N * sizeof(double)));
+    HIP_TRY(hipMemcpy(c->dct_diag, diag, N * sizeof(double), hipMemcpyHostToDevice));
+  }
+  if (sh.levels == 2) {
+    HIP_TRY(hipMalloc((void**)&c->dct_w0, N * sizeof(d2)));
+    HIP_TRY(hipMalloc((void**)&c->dct_w1, N * sizeof(d2)));
+  }
+  return 0;
+}
+static DctOpP dct_op_params(fh_ctx* c, const DctShape& sh) {
+  DctOpP o;
+  o.N = (uint32_t)c->n; o.N1 = sh.N1; o.N2 = sh.N2; o.r1 = sh.r1; o.r2 = sh.r2;
+  o.tw = c->dct_tw; o.pw = c->dct_pw; o.diag = c->dct_diag;
+  o.sc0 = c->dct_sc0; o.sck = c->dct_sck;
+  o.w0 = c->dct_w0; o.w1 = c->dct_w1;
+  return o;
+}
+template <int CONJ>
+static void dct_launch_rows_c(fh_ctx* c, uint32_t ldsn, uint32_t grid, const DctRowsP& q) {
+  if (ldsn == 128u) k_dct_rows<128, CONJ><<<dim3(grid), dim3(FH_WG), 0, c->stream>>>(q);
+  else if (ldsn == 512u) k_dct_rows<512, CONJ><<<dim3(grid), dim3(FH_WG), 0, c->stream>>>(q);
+  else k_dct_rows<2048, CONJ><<<dim3(grid), dim3(FH_WG), 0, c->stream>>>(q);
+}
+// the three middle launches of a two-level transform: rows of length N1 (with the six-step twiddle), transpose, rows of length N2.
+// K-fwd: real rows in w0 -> w1 -> w0 (in place); K-adj: complex rows in w0 (in place) -> w1 (in place).  A workgroup owns whole rows, so a
+// row launch may write where it read.
+static void dct_launch_middle(fh_ctx* c, const DctShape& sh, int conj) {
+  DctRowsP q;
+  q.N = (uint32_t)c->n; q.tw = c->dct_tw;
+  q.L = sh.N1; q.nrows = sh.N2; q.rpw = sh.rpw1; q.rd = sh.r1; q.in = c->dct_w0; q.out = conj ? c->dct_w0 : c->dct_w1; q.real_in = conj ? 0 : 1; q.tw6 = 1;
+  if (conj) dct_launch_rows_c<1>(c, sh.ldsn1, sh.grid1, q); else dct_launch_rows_c<0>(c, sh.ldsn1, sh.grid1, q);
+  d2* tin = conj ? c->dct_w0 : c->dct_w1; d2* tout = conj ? c->dct_w1 : c->dct_w0;
+  k_dct_tr<DCT_TT><<<dim3(sh.tiles), dim3(FH_WG), 0, c->stream>>>(tin, tout, sh.N2, sh.N1);
+  q.L = sh.N2; q.nrows = sh.N1; q.rpw = sh.rpw2; q.rd = sh.r2; q.in = tout; q.out = tout; q.real_in = 0; q.tw6 = 0;
+  if (conj) dct_launch_rows_c<1>(c, sh.ldsn2, sh.grid2, q); else dct_launch_rows_c<0>(c, sh.ldsn2, sh.grid2, q);
+}
+
+// z := d * C (mode 0: prox(x0 - tau g0) ; mode 1: x0): one launch (N <= row cap) or five
+static int launch_fwd_dct(fh_ctx* c, int mode, double tau, const double* x0, const double* g0, const double* xacc0,
+                          double* xhat, double* xp, double* z, int sub_b) {
+  if (c->loss_kind != LOSS_LSQ) return fail(FH_E_STATE, "the DCT operator serves the least-squares loss only (the logistic loss is implemented for the dense and sparse operators)");
+  if (mode == 0 && !dct_prox_ok(c->prox_kind))
+    return fail(FH_E_STATE, "prox kind %d (TVBALL / GROUP) is not implemented for the DCT operator", c->prox_kind);
+  const DctShape& sh = c->dct_sh;
+  DctFwdP p;
+  p.op = dct_op_params(c, sh);
+  p.mode = mode; p.sub_b = sub_b;
+  p.x0 = x0; p.g0 = g0; p.xacc0 = xacc0; p.xhat = xhat; p.xp = xp; p.b = c->b; p.z = z; p.tau = tau;
+  p.px = make_prox(c, tau);
+  p.seq = 0u; p.nred_n = 0u; p.red_n = nullptr;
+  const uint32_t grid = sh.levels == 1 ? 1u : sh.tiles;
+  FH_TRY(ensure_ws(c, (size_t)grid * 16 * sizeof(double)));
+  p.red = c->ws; p.counter = c->counters + CNT_FWD; p.out = scalar_out(c);
+  t_begin(c, FH_K_FWD);
+  if (sh.levels == 1) {
+    p.seq = seq_offer(c);
+    if (sh.ldsn1 == 128u) k_dct1_fwd<128><<<dim3(1), dim3(FH_WG), 0, c->stream>>>(p);
+    else if (sh.ldsn1 == 512u) k_dct1_fwd<512><<<dim3(1), dim3(FH_WG), 0, c->stream>>>(p);
+    else k_dct1_fwd<2048><<<dim3(1), dim3(FH_WG), 0, c->stream>>>(p);
+  } else {
+    p.red_n = c->ws + (size_t)grid * 8;
+    k_dct_pre_fwd<DCT_TT><<<dim3(grid), dim3(FH_WG), 0, c->stream>>>(p);
+    dct_launch_middle(c, sh, 0);
+    p.nred_n = mode == 0 ? grid : 0u;
+    p.seq = seq_offer(c);
+    k_dct_post_fwd<DCT_TT><<<dim3(grid), dim3(FH_WG), 0, c->stream>>>(p);
+  }
+  t_end(c, FH_K_FWD);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// g1 := C^T (d * (z' - b)) with the residual, the loss at z' and the n-side epilogue: one launch (N <= row cap) or five
+static int launch_adj_dct(fh_ctx* c, const AdjIO& io) {
+  if (c->loss_kind != LOSS_LSQ) return fail(FH_E_STATE, "the DCT operator serves the least-squares loss only (the logistic loss is implemented for the dense and sparse operators)");
+  if (io.mode != 0 && io.mode != 1) return fail(FH_E_STATE, "the DCT operator has no row-sharded adjoint");
+  const DctShape& sh = c->dct_sh;
+  DctAdjP p;
+  p.op = dct_op_params(c, sh);
+  p.z = io.z; p.zacc0 = io.zacc0; p.b = c->b; p.sub_b = io.sub_b; p.accel = io.accel; p.mode = io.mode; p.coef = io.coef; p.tau = io.tau;
+  p.x0 = io.x0; p.xp = io.xp; p.xacc0 = io.xacc0; p.xhat = io.xhat; p.x1 = io.x1; p.g1 = io.g1;
+  p.seq = 0u; p.nred_f = 0u; p.red_f = nullptr;
+  const uint32_t grid = sh.levels == 1 ? 1u : sh.tiles;
+  FH_TRY(ensure_ws(c, (size_t)grid * 16 * sizeof(double)));
+  p.red = c->ws; p.counter = c->counters + CNT_ADJ_FIN; p.out = scalar_out(c);
+  t_begin(c, FH_K_ADJ);
+  if (sh.levels == 1) {
+    p.seq = io.mode == 0 ? seq_offer(c) : 0u;
+    if (sh.ldsn1 == 128u) k_dct1_adj<128><<<dim3(1), dim3(FH_WG), 0, c->stream>>>(p);
+    else if (sh.ldsn1 == 512u) k_dct1_adj<512><<<dim3(1), dim3(FH_WG), 0, c->stream>>>(p);
+    else k_dct1_adj<2048><<<dim3(1), dim3(FH_WG), 0, c->stream>>>(p);
+  } else {
+    p.red_f = c->ws + (size_t)grid * 8;
+    k_dct_pre_adj<DCT_TT><<<dim3(grid), dim3(FH_WG), 0, c->stream>>>(p);
+    dct_launch_middle(c, sh, 1);
+    p.nred_f = grid;
+    p.op.w0 = c->dct_w1;                                  // (where the second row launch left the transform)
+    p.seq = io.mode == 0 ? seq_offer(c) : 0u;
+    k_dct_post_adj<DCT_TT><<<dim3(grid), dim3(FH_WG), 0, c->stream>>>(p);
+  }
+  t_end(c, FH_K_ADJ);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
 // sum|x_i| and max|x_i| of an n-length device vector -> dscal[GSUM], dscal[GMAX]  (g(x0) for objective_hist[0], :143)
 static int launch_gterms(fh_ctx* c, const double* x) {
   if (c->LB) {              // (n, L) matrix: the same two terms, or the sum of row norms for FH_PROX_GROUP
@@ -966,7 +1164,7 @@ static int launch_gterms(fh_ctx* c, const double* x) {
 
 // clipping level alpha for FH_PROX_LINF (radius tau*mu) / FH_PROX_L1BALL (radius mu) -> dscal[FH_NSCALARS]
 static int launch_level_search(fh_ctx* c, double tau) {
-  if (c->op != OP_DENSE) return fail(FH_E_STATE, "LINF / L1BALL prox need the dense operator");
+  if (c->op != OP_DENSE && c->op != OP_DCT) return fail(FH_E_STATE, "LINF / L1BALL prox need the dense operator");      // (the search reads x0, g0 and n only)
   const double radius = c->prox_kind == FH_PROX_L1BALL ? c->mu : tau * c->mu;
   const double* x0 = c->X[c->xi];
   const double* g0 = c->G[c->gc];
@@ -1373,6 +1571,7 @@ static int op_fwd(fh_ctx* c, int mode, double tau, const double* x0, const doubl
   if (c->op == OP_STENCIL) return launch_fwd_tv(c, mode, tau, x0, g0, xacc0, xhat, xp, z, sub_b);
   if (c->op == OP_SPARSE) return c->LB ? launch_fwd_spmulti(c, mode, tau, x0, g0, xacc0, xhat, xp, z, sub_b) : launch_fwd_sparse(c, mode, tau, x0, g0, xacc0, xhat, xp, z, sub_b);
   if (c->op == OP_STENCIL3D) return launch_fwd_tv3(c, mode, tau, x0, g0, xacc0, xhat, xp, z, sub_b);
+  if (c->op == OP_DCT) return launch_fwd_dct(c, mode, tau, x0, g0, xacc0, xhat, xp, z, sub_b);
   if (c->op == OP_QUAD) return launch_fwd_quad(c, mode, tau, x0, g0, xacc0, xhat, xp, z, sub_b);
   if (c->op == OP_BILINEAR) return launch_fwd_bilinear(c, mode, tau, x0, g0, xacc0, xhat, xp, z, sub_b);
   return fail(FH_E_STATE, "no operator set");
@@ -1389,6 +1588,7 @@ static int adj_local(fh_ctx* c, const AdjIO& io_in) {
   if (c->op == OP_STENCIL) return launch_adj_tv(c, io);
   if (c->op == OP_SPARSE) return c->LB ? launch_adj_spmulti(c, io) : launch_adj_sparse(c, io);
   if (c->op == OP_STENCIL3D) return launch_adj_tv3(c, io);
+  if (c->op == OP_DCT) return launch_adj_dct(c, io);
   if (c->op == OP_QUAD) return launch_adj_quad(c, io);
   if (c->op == OP_BILINEAR) return launch_adj_bilinear(c, io);
   return fail(FH_E_STATE, "no operator set");
@@ -1419,7 +1619,7 @@ static int reduce_fsq_over_ranks(fh_ctx* c) {
 static int check_ready(fh_ctx* c, bool need_b) {
   if (!c) return fail(FH_E_ARG, "null context");
   if (c->pending_step) return fail(FH_E_STATE, "a step issued by fh_step_begin is still in flight on this context: call fh_step_end first");
-  if (c->op == OP_NONE) return fail(FH_E_STATE, "no operator set (call fh_set_matrix / fh_set_matrix_csr / fh_generate_matrix / fh_set_stencil / fh_set_stencil3d / fh_set_quadratic / fh_set_factorization)");
+  if (c->op == OP_NONE) return fail(FH_E_STATE, "no operator set (call fh_set_matrix / fh_set_matrix_csr / fh_generate_matrix / fh_set_stencil / fh_set_stencil3d / fh_set_dct / fh_set_quadratic / fh_set_factorization)");
   if (need_b && !c->has_b) return fail(FH_E_STATE, "no loss set (call fh_set_loss_lsq)");
   return c->shards.empty() ? use_device(c) : 0;      // (a shell selects the device shard by shard)
 }

@@ -26,7 +26,7 @@ NSCALARS = 16
 K_FWD, K_ADJ, K_AUX, K_COMM, K_FUSED, K_HOST_ISSUE, K_LEVEL = range(7)
 (TUNE_FWD_ROWS, TUNE_FWD_GRID_CAP, TUNE_ADJ_SLAB_ROWS, TUNE_ADJ_CPT, TUNE_LD_PAD, TUNE_NT_LOADS,
  TUNE_TV_U, TUNE_TV_ROWS, TUNE_TV_NT, TUNE_FUSED_VARIANT, TUNE_TV_ZFREE, TUNE_TV_PIPE, TUNE_TV_XCD, TUNE_TV_LDS_PAD,
- TUNE_TV_RING, TUNE_TV_SLOTS, TUNE_FUSED_CUS, TUNE_RUN_MAX_N, TUNE_SEQ_POLL, TUNE_RUN_CHAIN, TUNE_ADJ_CYCLIC, TUNE_TV3_PLANES) = range(22)
+ TUNE_TV_RING, TUNE_TV_SLOTS, TUNE_FUSED_CUS, TUNE_RUN_MAX_N, TUNE_SEQ_POLL, TUNE_RUN_CHAIN, TUNE_ADJ_CYCLIC, TUNE_TV3_PLANES, TUNE_DCT_ROW_CAP) = range(23)
 # keys 10, 13, 14, 15 (TUNE_TV_ZFREE / _LDS_PAD / _RING / _SLOTS) are NOT in include/fasta_hip.h: experimental forms of the stencil sweep,
 # accepted only by libfasta_hip_experimental.so (csrc/fh_experimental.h); the shipped library answers FH_E_ARG
 EXPERIMENTAL_KEYS = (TUNE_TV_ZFREE, TUNE_TV_LDS_PAD, TUNE_TV_RING, TUNE_TV_SLOTS)
@@ -88,6 +88,9 @@ SIGNATURES = {
     "fh_set_stencil3d": (_i32, [_ctx, _u64, _u64, _u64]),
     "fh_tv3d_shape": (_i32, [_ctx, C.POINTER(C.c_uint32)]),
     "fh_tv3d_shape_for": (_i32, [_u64, _u64, _u64, _i32, _i32, C.POINTER(C.c_uint32)]),
+    "fh_set_dct": (_i32, [_ctx, _u64, _pd]),
+    "fh_dct_shape": (_i32, [_ctx, C.POINTER(C.c_uint32)]),
+    "fh_dct_shape_for": (_i32, [_u64, _i32, _i32, C.POINTER(C.c_uint32)]),
     "fh_shape": (_i32, [_ctx, C.POINTER(_u64), C.POINTER(_u64)]),
     "fh_set_quadratic": (_i32, [_ctx, _pd, _u64, _u64, _pd, C.c_uint32]),
     "fh_quad_shape": (_i32, [_ctx, C.POINTER(C.c_uint32)]),
@@ -287,6 +290,37 @@ def tv3d_shape(D, H, W, planes=0, ncu=256):
     out = (C.c_uint32 * TV3D_SHAPE_LEN)()
     _check(lib, lib.fh_tv3d_shape_for(int(D), int(H), int(W), int(planes), int(ncu), out))
     return Tv3dShape(*(int(v) for v in out))
+
+
+DCT_SHAPE_LEN = 40
+DCT_ROW_CAP = 2048
+DctShape = collections.namedtuple("DctShape", "levels N1 N2 cap radices1 radices2 lds1 rows1 grid1 lds2 rows2 grid2 threads lds_bytes tiles launches")
+
+
+def _dct_shape(out):
+    v = [int(k) for k in out]
+    return DctShape(v[0], v[1], v[2], v[3], tuple(v[5:5 + v[4]]), tuple(v[18:18 + v[17]]), *v[30:40])
+
+
+def dct_shape(N, row_cap=0, ncu=256):
+    """DctShape of the DCT operator's launches for length N under FH_TUNE_DCT_ROW_CAP = row_cap (0 = 2048) on a device of ncu compute units:
+    fh_dct_shape_for, the rule the launchers call.  Host-only.  HipError with the library's sentence for an N the device refuses."""
+    lib = load_library()
+    out = (C.c_uint32 * DCT_SHAPE_LEN)()
+    _check(lib, lib.fh_dct_shape_for(int(N), int(row_cap), int(ncu), out))
+    return _dct_shape(out)
+
+
+def dct_refusal(N, row_cap=0, ncu=256):
+    """None when the device serves length N under that row cap, else the library's sentence about N (N = 0, a prime factor above 5, no split
+    within the cap).  Only those are refusals: a row cap out of range, a library that is missing or does not load, or any other status raises."""
+    lib = load_library()
+    out = (C.c_uint32 * DCT_SHAPE_LEN)()
+    status = lib.fh_dct_shape_for(int(N), int(row_cap), int(ncu), out)
+    if status == E_ARG and out[3] != 0:                  # (the cap was accepted -- the rule reports it -- so the sentence is about N)
+        return f"[{status}] " + lib.fh_last_error().decode(errors="replace")
+    _check(lib, status)
+    return None
 
 
 def comm_library():
@@ -541,6 +575,22 @@ class HipContext:
         out = (C.c_uint32 * BILINEAR_SHAPE_LEN)()
         self._call("fh_bilinear_shape", out)
         return BilinearShape(*(int(v) for v in out))
+
+    def set_dct(self, N, diag=None):
+        """A = diag(d) * C, A^H = C^T * diag(d), C the orthonormal DCT-II of length N (csrc/fh_dct.h); diag=None: all ones."""
+        if diag is None:
+            self._call("fh_set_dct", int(N), None)
+            return
+        d, pd = _as_f64(diag)
+        if d.shape != (int(N),):
+            raise ValueError(f"diag has shape {d.shape}, the DCT operator of length {int(N)} takes ({int(N)},)")
+        self._call("fh_set_dct", int(N), pd)
+
+    def dct_shape(self):
+        """DctShape the next fwd / adj of this context launches with (fh_dct_shape).  E_STATE without a DCT operator."""
+        out = (C.c_uint32 * DCT_SHAPE_LEN)()
+        self._call("fh_dct_shape", out)
+        return _dct_shape(out)
 
     def shape(self):
         m, n = _u64(0), _u64(0)

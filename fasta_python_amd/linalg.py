@@ -15,6 +15,7 @@ subclasses are *recognised* by `fasta()` and run on the device:
                      device by rows and by columns; both directions are gathers (csrc/fh_sparse.h; with `rhs=L`
                      the unknown is an (n, L) matrix and every entry gathers a whole row of it, csrc/fh_spmulti.h);
   GradDivMap      -- the periodic div/grad stencil pair of examples/tv_denoising.py:26-63;
+  DCTMap          -- the subsampled orthonormal DCT of examples/democratic_representation.py:80-82, an implicit fast transform (csrc/fh_dct.h);
   QuadraticMap    -- the identity operator of a quadratic smooth term (losses.Quadratic): what `fasta(None, None, q.f, q.gradf, ...)` runs on;
   BilinearMap     -- the identity operator of a bilinear smooth term (losses.Factorization): what `fasta(None, None, fz.f, fz.gradf, ...)` runs on.
 
@@ -37,7 +38,7 @@ from . import hip
 Matrix = np.ndarray
 Vector = np.ndarray
 
-__all__ = ["LinearMap", "LinearOperator", "DenseMatrixMap", "ShardedDenseMatrixMap", "SparseMatrixMap", "GradDivMap", "QuadraticMap", "BilinearMap", "is_sparse_matrix", "Matrix", "Vector"]
+__all__ = ["LinearMap", "LinearOperator", "DenseMatrixMap", "ShardedDenseMatrixMap", "SparseMatrixMap", "GradDivMap", "DCTMap", "QuadraticMap", "BilinearMap", "is_sparse_matrix", "Matrix", "Vector"]
 
 
 class LinearMap:
@@ -552,3 +553,41 @@ class GradDivMap(_DeviceMap):
         if len(self.image_shape) == 3:
             return _nd_grad(w)
         return self.device_apply(w, adjoint=True)
+
+
+class DCTMap(_DeviceMap):
+    """A = mask * DCT and A^H = IDCT(mask * .), the orthonormal DCT-II / DCT-III of length N (examples/democratic_representation.py:80-82):
+    an implicit operator -- no matrix is stored, the device runs the transform itself (fh_set_dct, csrc/fh_dct.h), so N = 2^16 ... 2^22 is in
+    reach where a dense N x N matrix is not.  `mask`: any float64 vector of length N (the reference's is 0/1), None = all ones.
+    On host arrays the map is exactly the reference's closures, `mask * scipy.fftpack.dct(x, norm='ortho')` and
+    `scipy.fftpack.idct(mask * w, norm='ortho')`, so `backend="numpy"` and the generic host loop are the reference bit for bit.
+    lazy=True: the device context is created when the device loop first asks for it.  An N the device refuses (a prime factor above 5, no
+    split within the row cap: `refusal` holds the library's sentence) stays a host map: `fasta()` runs it on the generic host loop, and
+    `backend="hip"` raises with that sentence.  tuning (a keyword of this build, as DenseMatrixMap has one): {hip.TUNE_DCT_ROW_CAP: cap} lowers
+    the row cap (set before the operator); a cap out of range raises."""
+
+    def __init__(self, N, mask=None, device=0, lazy=False, tuning=None):
+        N = int(N)
+        self.N = N
+        self.mask = None if mask is None else np.ascontiguousarray(mask, dtype=np.float64)
+        if self.mask is not None and self.mask.shape != (N,):
+            raise ValueError(f"mask has shape {self.mask.shape}, a DCT of length {N} takes ({N},)")
+        self._tuning = dict(tuning or {})
+        cap = self._tuning.get(hip.TUNE_DCT_ROW_CAP, 0)
+        self.refusal = hip.dct_refusal(N, cap)           # (a row cap out of range or a library that does not load raises: only a sentence about N is a refusal)
+        self.geometry = None if self.refusal is not None else hip.dct_shape(N, cap)
+        _DeviceMap.__init__(self, (N,), (N,), device, lazy=lazy or self.refusal is not None)
+
+    def _on_context(self, ctx):
+        for key, value in self._tuning.items():
+            ctx.set_tuning(key, value)
+        ctx.set_dct(self.N, self.mask)
+
+    def _apply_fwd(self, v):
+        from scipy.fftpack import dct
+        y = dct(v, norm='ortho')
+        return y if self.mask is None else self.mask * y
+
+    def _apply_adj(self, w):
+        from scipy.fftpack import idct
+        return idct(w if self.mask is None else self.mask * w, norm='ortho')

@@ -136,6 +136,9 @@ enum fh_tuning_key {
   FH_TUNE_TV3_PLANES = 21,   /* 3-D stencil kernels (fh_set_stencil3d): planes along d a workgroup marches over; 0 = auto (whole columns of planes unless
                                 that leaves fewer than 8 workgroups per CU, then at least 8 planes per workgroup).  A small value gives a small
                                 volume several workgroups along d (the tests); fh_tv3d_shape reports what a launch takes                        */
+  FH_TUNE_DCT_ROW_CAP = 22,  /* DCT operator (fh_set_dct): longest row transform, 0 = default (2048) or 2..2048.  A small value gives a small N the
+                                two-level form (the tests: N = 60 at a cap of 16).  Read when fh_set_dct sets the operator: set it before; fh_dct_shape
+                                reports what the launches take                                                                                    */
   FH_TUNE_FUSED_CUS = 16     /* dense one-pass kernel: launch it on at most this many CUs (one workgroup each; 0 = every CU the device
                                 reports).  The co-residency probe then asks for that many.  Lets several one-pass grids run side by side
                                 on one device: two solves at once, partitioned devices, ranks of a row-sharded run that share a GPU
@@ -245,6 +248,34 @@ int fh_set_stencil3d(fh_ctx* ctx, uint64_t D, uint64_t H, uint64_t W);
 #define FH_TV3D_SHAPE_LEN 8
 int fh_tv3d_shape(fh_ctx* ctx, uint32_t* out);
 int fh_tv3d_shape_for(uint64_t D, uint64_t H, uint64_t W, int planes, int ncu, uint32_t* out);
+/* ---- subsampled DCT: A = diag(d) * C, A^H = C^T * diag(d) (examples/democratic_representation.py:80-82 is the case of a 0/1 mask d) ------------
+ * C is the orthonormal DCT-II of length N, scipy.fftpack.dct(x, norm='ortho'): C[k,n] = s_k cos(pi k (2n+1) / (2N)), s_0 = sqrt(1/N), s_k = sqrt(2/N).
+ * m = n = N (fh_shape reports them).  d: N float64 values copied to the device, NULL = all ones; d[k] == 0.0 gives z[k] == 0.0 exactly.  No matrix is
+ * stored: both directions are one complex FFT of length N done in LDS (Makhoul; Stockham autosort, radices 2, 3, 4, 5; csrc/fh_dct.h), from two
+ * twiddle tables built on the host in long double when the operator is set (4 N cosl / sinl calls: of the order of a second at N = 2^22).  N <= the row cap (2048; FH_TUNE_DCT_ROW_CAP lowers it): one launch per direction; beyond:
+ * N = N1 * N2, both at most the cap, five launches per direction (so N <= 2^22).  Vectors live in the vector form's padded buffers, so
+ * fh_set_vector / fh_get_vector, fh_diff_norm, fh_commit, fh_set_loss_lsq, fh_set_prox and fh_shape work unchanged.  No atomics on floats, fixed
+ * summation order, bitwise repeatable.  Prox kinds served: IDENTITY, SHRINK, NONNEG, BOX, LINF and L1BALL (the level search of the dense operator
+ * reads x0, g0 and n only); least squares only.
+ * Served entry points, the FH_S_* scalars meaning what they mean for the sparse operator: fh_init, fh_setup (its three-pass route), fh_gradient_at,
+ * fh_apply, fh_fwd, fh_adj (accel / coef), fh_fwd_adj, fh_iterate, fh_commit, fh_timing_* (FH_K_FWD / FH_K_ADJ / FH_K_LEVEL).
+ * Refused (FH_E_ARG with a sentence): N = 0, an N with a prime factor above 5, an N above the row cap that has no split N1 * N2 with both factors at
+ * most the cap; FH_PROX_TVBALL / GROUP (a context holding one returns to IDENTITY when the operator is set) and fh_set_prox_split.  Refused
+ * (FH_E_STATE): multi-device contexts, a context with a communicator and fh_comm_init, fh_set_rhs, float32 storage, the logistic loss, fh_step*,
+ * fh_run, fh_get_matrix_rows, fh_stream_read_ms.  fh_fused_supported, fh_fused_agree and fh_run_supported report 0.  Setting any other operator
+ * leaves this form.                                                                                                                            */
+int fh_set_dct(fh_ctx* ctx, uint64_t N, const double* diag);
+/* read-only: the geometry the DCT launches take (csrc/fh_host_launch.h: dct_shape_for, the ONE rule the launchers call), so that a test can assert
+ * the path it meant to reach.  out[FH_DCT_SHAPE_LEN]: [0] levels (1: one row, one launch; 2: N1 x N2, five launches; 0: N is not served -- the call
+ * then returns FH_E_ARG and the sentence), [1] N1, [2] N2 (1 for one level), [3] the row cap, [4] number of radix passes of a row of length N1,
+ * [5..16] its radices in pass order, [17] and [18..29] the same for N2, [30] LDS class (double2 per ping-pong buffer: 128 / 512 / 2048), [31] rows
+ * per workgroup and [32] grid of the row launch of length N1, [33..35] the same for N2, [36] threads per workgroup, [37] static LDS bytes of the
+ * largest row kernel, [38] grid of each of the three tile launches (32 x 32 tiles of the N1 x N2 matrix), [39] launches per direction.
+ * fh_dct_shape reads the context's N, the row cap it was set with and its CU count and is FH_E_STATE without a DCT operator; fh_dct_shape_for is
+ * the same rule as a pure host function (no device needed; row_cap: 0 = 2048; ncu: the device's compute units).                              */
+#define FH_DCT_SHAPE_LEN 40
+int fh_dct_shape(fh_ctx* ctx, uint32_t* out);
+int fh_dct_shape_for(uint64_t N, int row_cap, int ncu, uint32_t* out);
 int fh_shape(fh_ctx* ctx, uint64_t* m, uint64_t* n);
 
 /* ---- quadratic smooth term on an explicit symmetric matrix: f(X) = .5 <X, Q X> + <C, X>, A = identity (csrc/fh_quad.h) -----------------------
