@@ -24,6 +24,7 @@
 #include "fh_tv.h"
 #include "fh_tv3d.h"
 #include "fh_dct.h"
+#include "fh_nuclear.h"
 #include "fh_prox.h"
 #include "fh_fused.h"
 #include "fh_setup.h"
@@ -356,6 +357,9 @@ static int set_tuning_one(fh_ctx* c, int key, long long value) {
     case FH_TUNE_DCT_ROW_CAP:
       if (value != 0 && (value < 2 || value > DCT_ROW_CAP)) return fail(FH_E_ARG, "DCT_ROW_CAP must be 0 (default: %d) or in [2, %d] elements per row transform", DCT_ROW_CAP, DCT_ROW_CAP);
       c->dct_row_cap = (int)value; return 0;
+    case FH_TUNE_NUC_BLOCK_ROWS:
+      if (value != 0 && value != 1 && value != 2 && value != 4 && value != 8) return fail(FH_E_ARG, "NUC_BLOCK_ROWS must be 0 (auto), 1, 2, 4 or 8 rows per block");
+      c->nuc_block_rows = (int)value; return 0;
     case FH_TUNE_TV_PIPE:
       if (value < 0 || value > 3) return fail(FH_E_ARG, "TV_PIPE must be 0 (auto), 1 (load a trip, consume it) or 3 (three rotating trip buffers; 2 is taken as 3)");
       c->tv_pipe = (int)value; return 0;
@@ -662,6 +666,7 @@ extern "C" int fh_get_matrix_rows(fh_ctx* c, uint64_t row0, uint64_t nrows, doub
   if (c->op == OP_SPARSE) return fail(FH_E_STATE, "fh_get_matrix_rows: the sparse operator keeps no dense rows");
   if (c->op == OP_STENCIL3D) return fail(FH_E_STATE, "fh_get_matrix_rows: the 3-D stencil operator keeps no dense rows");
   if (c->op == OP_DCT) return fail(FH_E_STATE, "fh_get_matrix_rows: the DCT operator keeps no dense rows");
+  if (c->op == OP_IDENTITY) return fail(FH_E_STATE, "fh_get_matrix_rows: the identity operator keeps no matrix");
   if (c->op == OP_QUAD) return fail(FH_E_STATE, "fh_get_matrix_rows: the quadratic operator is not read back (the caller holds Q)");
   if (c->op == OP_BILINEAR) return fail(FH_E_STATE, "fh_get_matrix_rows: the bilinear operator is not read back (the caller holds S)");
   if (c->op != OP_DENSE) return fail(FH_E_STATE, "no dense matrix set");
@@ -764,6 +769,66 @@ extern "C" int fh_set_dct(fh_ctx* c, uint64_t N, const double* diag) {
   return finish(c);
 }
 
+// the identity operator with an elementwise loss (csrc/fh_nuclear.h): the unknown is an (M, N) matrix in the vector form's buffers, m = n = M * N;
+// nothing is stored for the operator itself
+extern "C" int fh_set_identity(fh_ctx* c, uint64_t M, uint64_t N) {
+  if (!c) return fail(FH_E_ARG, "null context");
+  if (!c->shards.empty() || c->owner) return fail(FH_E_STATE, "fh_set_identity: a multi-device context has no identity operator (row sharding is implemented for the dense operator only)");
+  if (c->comm) return fail(FH_E_STATE, "fh_set_identity: a context with a communicator (row-sharded run) has no identity operator");
+  if (c->f32) return fail(FH_E_STATE, "fh_set_identity: float32 storage is a storage mode of a dense matrix; the identity operator stores no matrix and computes in float64");
+  if (c->pending_step) return fail(FH_E_STATE, "a step issued by fh_step_begin is still in flight on this context: call fh_step_end first");
+  if (M == 0 || N == 0) return fail(FH_E_ARG, "fh_set_identity: the matrix unknown must be non-empty (got %llu x %llu)", (unsigned long long)M, (unsigned long long)N);
+  if (M > (1ull << 26) || N > (1ull << 26) || M * N > (1ull << 26)) return fail(FH_E_ARG, "fh_set_identity: at most 2^26 entries (got %llu x %llu)", (unsigned long long)M, (unsigned long long)N);
+  FH_TRY(use_device(c));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  free_operator(c);
+  if (!sp_prox_ok(c->prox_kind)) { c->prox_kind = FH_PROX_IDENTITY; c->mu = 0.0; }
+  c->loss_kind = LOSS_LSQ; c->lazy = false; c->last_accel = false; c->commits = 0;
+  c->id_M = M; c->id_N = N;
+  c->m = c->n = M * N;
+  c->mp = c->m; c->ld = c->n;
+  c->nv = round_up(c->n, 16); c->mv = round_up(c->m, 16);
+  c->op = OP_IDENTITY;
+  const int rc = alloc_vectors(c);
+  if (rc != 0) { free_operator(c); return rc; }
+  return finish(c);
+}
+
+// FH_PROX_NUCLEAR on the identity operator: the geometry (FH_TUNE_NUC_BLOCK_ROWS is read here) and the working buffers
+extern "C" int fh_set_prox_nuclear(fh_ctx* c, double mu, int objective) {
+  if (!c) return fail(FH_E_ARG, "null context");
+  if (c->op != OP_IDENTITY) return fail(FH_E_STATE, "FH_PROX_NUCLEAR (singular-value soft-threshold of a matrix unknown) is served by the identity operator only: call fh_set_identity first");
+  if (c->pending_step) return fail(FH_E_STATE, "a step issued by fh_step_begin is still in flight on this context: call fh_step_end first");
+  NucShape sh;
+  FH_TRY(nuc_shape_for(c->id_M, c->id_N, c->nuc_block_rows, &sh));
+  FH_TRY(use_device(c));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (c->nuc_w) { HIP_TRY(hipFree(c->nuc_w)); c->nuc_w = nullptr; }
+  if (c->nuc_phi) { HIP_TRY(hipFree(c->nuc_phi)); c->nuc_phi = nullptr; }
+  HIP_TRY(hipMalloc((void**)&c->nuc_w, sh.bytes));
+  HIP_TRY(hipMalloc((void**)&c->nuc_phi, (size_t)sh.g.P * sizeof(double)));
+  if (!c->nuc_scal) FH_TRY(alloc_zero(c, &c->nuc_scal, 8));
+  if (!c->nuc_cnt) { HIP_TRY(hipMalloc((void**)&c->nuc_cnt, 32 * sizeof(unsigned))); HIP_TRY(hipMemsetAsync(c->nuc_cnt, 0, 32 * sizeof(unsigned), c->stream)); }
+  if (!c->nuc_host) { HIP_TRY(hipHostMalloc((void**)&c->nuc_host, 64 * sizeof(unsigned), hipHostMallocDefault)); memset(c->nuc_host, 0, 64 * sizeof(unsigned)); }
+  c->nuc_sh = sh;
+  c->nuc_objective = objective ? 1 : 0;
+  c->nuc_info[0] = c->nuc_info[1] = c->nuc_info[2] = c->nuc_info[3] = 0;
+  c->prox_kind = FH_PROX_NUCLEAR; c->mu = mu; c->lo = 0.0; c->hi = 0.0;
+  return finish(c);
+}
+
+// the latest thresholding (fh_fwd / fh_fwd_adj / fh_iterate) of this context: sweeps, steps launched, rotations, rank kept
+extern "C" int fh_nuclear_info(fh_ctx* c, uint64_t* out) {
+  if (!c || !out) return fail(FH_E_ARG, "fh_nuclear_info: null argument");
+  if (c->op != OP_IDENTITY || c->prox_kind != FH_PROX_NUCLEAR) return fail(FH_E_STATE, "fh_nuclear_info: the context holds no identity operator with FH_PROX_NUCLEAR (fh_set_identity, fh_set_prox_nuclear)");
+  FH_TRY(use_device(c));
+  FH_TRY(finish(c));
+  double rank = 0.0;
+  memcpy(&rank, c->nuc_host + 32, sizeof(double));
+  out[0] = c->nuc_info[0]; out[1] = c->nuc_info[1]; out[2] = c->nuc_info[2]; out[3] = (uint64_t)rank;
+  return 0;
+}
+
 extern "C" int fh_shape(fh_ctx* c, uint64_t* m, uint64_t* n) {
   if (!c || !m || !n) return fail(FH_E_ARG, "null argument");
   if (c->op == OP_NONE) return fail(FH_E_STATE, "no operator set");
@@ -782,6 +847,7 @@ extern "C" int fh_set_rhs(fh_ctx* c, uint32_t L) {
   if (c->op == OP_SPARSE) return fail(FH_E_STATE, "fh_set_rhs: the sparse operator has no multi-column form through fh_set_rhs: its column count is fixed when it is set (fh_set_matrix_csr_rhs)");
   if (c->op == OP_STENCIL3D) return fail(FH_E_STATE, "fh_set_rhs: the 3-D stencil operator has no multi-column form");
   if (c->op == OP_DCT) return fail(FH_E_STATE, "fh_set_rhs: the DCT operator has no multi-column form");
+  if (c->op == OP_IDENTITY) return fail(FH_E_STATE, "fh_set_rhs: the identity operator has no multi-column form (its unknown is already an (M, N) matrix: fh_set_identity)");
   if (c->op == OP_QUAD) return fail(FH_E_STATE, "fh_set_rhs: the column count of a quadratic operator is fixed when it is set (fh_set_quadratic)");
   if (c->op == OP_BILINEAR) return fail(FH_E_STATE, "fh_set_rhs: the column count of a bilinear operator is fixed when it is set (fh_set_factorization)");
   if (c->op != OP_DENSE) return fail(FH_E_STATE, "fh_set_rhs: the stencil operator has no multi-column form");
@@ -919,7 +985,7 @@ static int set_loss(fh_ctx* c, int kind, const double* b, uint64_t len) {
   if (kind != LOSS_LSQ && c->LB) return fail(FH_E_STATE, "the logistic loss has no multi-column form (fh_set_rhs / fh_set_matrix_csr_rhs)");
   if (kind != LOSS_LSQ && c->op == OP_STENCIL3D) return fail(FH_E_STATE, "the 3-D stencil operator serves the least-squares loss only (the logistic loss is implemented for the dense and sparse operators)");
   if (kind != LOSS_LSQ && c->op == OP_DCT) return fail(FH_E_STATE, "the DCT operator serves the least-squares loss only (the logistic loss is implemented for the dense and sparse operators)");
-  if (kind != LOSS_LSQ && c->op != OP_DENSE && c->op != OP_SPARSE) return fail(FH_E_STATE, "the logistic loss is implemented for the dense operator");
+  if (kind != LOSS_LSQ && c->op != OP_DENSE && c->op != OP_SPARSE && c->op != OP_IDENTITY) return fail(FH_E_STATE, "the logistic loss is implemented for the dense operator");
   if (!c->shards.empty()) {          // shell: b is sharded like the rows
     for (int k = 0; k < nshards(c); ++k) FH_TRY(set_loss(c->shards[k], kind, b + c->shard_row0[k], shard_rows(c, k)));
     c->has_b = true; c->loss_kind = kind;
@@ -940,10 +1006,13 @@ extern "C" int fh_set_loss_logistic(fh_ctx* c, const double* labels, uint64_t le
   return set_loss(c, LOSS_LOGISTIC, labels, len);
 }
 
+extern "C" int fh_set_prox_nuclear(fh_ctx* c, double mu, int objective);
 extern "C" int fh_set_prox(fh_ctx* c, int kind, double mu, double lo, double hi) {
   if (!c) return fail(FH_E_ARG, "null context");
   if (kind == FH_PROX_ROWSPLIT) return fail(FH_E_ARG, "unknown prox kind %d for fh_set_prox: FH_PROX_ROWSPLIT takes two kinds and their parameters, set it with fh_set_prox_split (bilinear operator only)", kind);
+  if (kind == FH_PROX_NUCLEAR) return fh_set_prox_nuclear(c, mu, 1);
   if (kind < FH_PROX_IDENTITY || kind > FH_PROX_ROWBALL) return fail(FH_E_ARG, "unknown prox kind %d", kind);
+  if (c->op == OP_IDENTITY && !id_prox_ok(kind)) return fail(FH_E_ARG, "prox kind %d (LINF / L1BALL / TVBALL / GROUP / ROWBALL) is not implemented for the identity operator", kind);
   if (c->op == OP_BILINEAR && !bl_prox_ok(kind)) return fail(FH_E_ARG, "prox kind %d (LINF / L1BALL / TVBALL / GROUP / ROWBALL) has no bilinear form", kind);
   if (kind == FH_PROX_ROWBALL && c->op != OP_QUAD) return fail(FH_E_ARG, "FH_PROX_ROWBALL (row-wise projection onto the ball of radius mu) is served by the quadratic operator only: call fh_set_quadratic first");
   if (c->op == OP_QUAD && !qd_prox_ok(kind)) return fail(FH_E_ARG, "prox kind %d (LINF / L1BALL / TVBALL) has no quadratic form", kind);
@@ -1459,6 +1528,7 @@ static int step_body(fh_ctx* c, double tau, double* scalars, bool wait) {
   if (c->op == OP_SPARSE) return fail(FH_E_STATE, "fh_step: the sparse operator has no one-pass kernel: use fh_fwd / fh_adj / fh_fwd_adj / fh_iterate");
   if (c->op == OP_STENCIL3D) return fail(FH_E_STATE, "fh_step: the 3-D stencil operator has no one-pass kernel: use fh_fwd / fh_adj / fh_fwd_adj / fh_iterate");
   if (c->op == OP_DCT) return fail(FH_E_STATE, "fh_step: the DCT operator has no one-pass kernel: use fh_fwd / fh_adj / fh_fwd_adj / fh_iterate");
+  if (c->op == OP_IDENTITY) return fail(FH_E_STATE, "fh_step: the identity operator has no one-pass kernel: use fh_fwd / fh_adj / fh_fwd_adj / fh_iterate");
   if (c->op == OP_QUAD) return fail(FH_E_STATE, "fh_step: the quadratic operator has no one-pass kernel: use fh_fwd / fh_adj / fh_fwd_adj / fh_iterate");
   if (c->op == OP_BILINEAR) return fail(FH_E_STATE, "fh_step: the bilinear operator has no one-pass kernel: use fh_fwd / fh_adj / fh_fwd_adj / fh_iterate");
   if (c->LB) return fail(FH_E_STATE, "fh_step: the multi-column form (fh_set_rhs) has no one-pass kernel: use fh_fwd / fh_adj / fh_iterate");
@@ -1509,6 +1579,7 @@ extern "C" int fh_step_accel(fh_ctx* c, double tau, double coef, int restart, do
   if (c->op == OP_SPARSE) return fail(FH_E_STATE, "fh_step_accel: the sparse operator has no one-pass kernel: use fh_fwd / fh_adj / fh_iterate");
   if (c->op == OP_STENCIL3D) return fail(FH_E_STATE, "fh_step_accel: the 3-D stencil operator has no one-pass kernel: use fh_fwd / fh_adj / fh_iterate");
   if (c->op == OP_DCT) return fail(FH_E_STATE, "fh_step_accel: the DCT operator has no one-pass kernel: use fh_fwd / fh_adj / fh_iterate");
+  if (c->op == OP_IDENTITY) return fail(FH_E_STATE, "fh_step_accel: the identity operator has no one-pass kernel: use fh_fwd / fh_adj / fh_iterate");
   if (c->op == OP_QUAD) return fail(FH_E_STATE, "fh_step_accel: the quadratic operator has no one-pass kernel: use fh_fwd / fh_adj / fh_iterate");
   if (c->op == OP_BILINEAR) return fail(FH_E_STATE, "fh_step_accel: the bilinear operator has no one-pass kernel: use fh_fwd / fh_adj / fh_iterate");
   if (c->LB) return fail(FH_E_STATE, "fh_step_accel: the multi-column form (fh_set_rhs) has no one-pass kernel: use fh_fwd / fh_adj / fh_iterate");
@@ -1677,7 +1748,7 @@ static void run_opts_in(const fh_run_opts* o, RunOpts* r) {
   r->stepsize_shrink = o->stepsize_shrink; r->tolerance = o->tolerance;
 }
 // g(x) from the prox's reductions (proximal.py: g_from_sums)
-static int g_kind_of(const fh_ctx* c) { return (c->prox_kind == FH_PROX_SHRINK || c->prox_kind == FH_PROX_GROUP || (c->prox_kind == FH_PROX_ROWSPLIT && c->rs_kind_top == FH_PROX_SHRINK)) ? FC_G_SUM : (c->prox_kind == FH_PROX_LINF ? FC_G_MAX : FC_G_NONE); }
+static int g_kind_of(const fh_ctx* c) { return (c->prox_kind == FH_PROX_SHRINK || c->prox_kind == FH_PROX_GROUP || (c->prox_kind == FH_PROX_ROWSPLIT && c->rs_kind_top == FH_PROX_SHRINK)) ? FC_G_SUM : ((c->prox_kind == FH_PROX_LINF || c->prox_kind == FH_PROX_NUCLEAR) ? FC_G_MAX : FC_G_NONE); }      // (FH_PROX_NUCLEAR: the example's g is mu times the LARGEST singular value, proximal.py: NuclearShrink)
 static int run_adopt(fh_ctx* c, const fh_run_opts* o, const RunState* hs, double* const (&nb)[5], int max_steps, fh_run_state* state, double* history, int* steps_done, const char* what);
 static int run_chain(fh_ctx* c, int max_steps, const fh_run_opts* o, fh_run_state* state, double* history, int* steps_done);
 extern "C" int fh_run(fh_ctx* c, int max_steps, const fh_run_opts* o, fh_run_state* state, double* history, int* steps_done) {
@@ -1689,6 +1760,7 @@ extern "C" int fh_run(fh_ctx* c, int max_steps, const fh_run_opts* o, fh_run_sta
   if (c->op == OP_SPARSE) return fail(FH_E_STATE, "fh_run: the sparse operator has no device-side loop: use fh_iterate");
   if (c->op == OP_STENCIL3D) return fail(FH_E_STATE, "fh_run: the 3-D stencil operator has no device-side loop: use fh_iterate");
   if (c->op == OP_DCT) return fail(FH_E_STATE, "fh_run: the DCT operator has no device-side loop: use fh_iterate");
+  if (c->op == OP_IDENTITY) return fail(FH_E_STATE, "fh_run: the identity operator has no device-side loop: use fh_iterate");
   if (c->op == OP_QUAD) return fail(FH_E_STATE, "fh_run: the quadratic operator has no device-side loop: use fh_iterate");
   if (c->op == OP_BILINEAR) return fail(FH_E_STATE, "fh_run: the bilinear operator has no device-side loop: use fh_iterate");
   if (c->LB) return fail(FH_E_STATE, "fh_run: the multi-column form (fh_set_rhs) has no device-side loop: use fh_iterate");
@@ -1921,6 +1993,7 @@ extern "C" int fh_comm_init(fh_ctx* c, int nranks, int rank, const void* id128) 
   if (c->op == OP_SPARSE) return fail(FH_E_STATE, "fh_comm_init: a context with a sparse operator cannot be row-sharded");
   if (c->op == OP_STENCIL3D) return fail(FH_E_STATE, "fh_comm_init: a context with a 3-D stencil operator cannot be row-sharded");
   if (c->op == OP_DCT) return fail(FH_E_STATE, "fh_comm_init: a context with a DCT operator cannot be row-sharded");
+  if (c->op == OP_IDENTITY) return fail(FH_E_STATE, "fh_comm_init: a context with the identity operator cannot be row-sharded");
   if (c->op == OP_QUAD) return fail(FH_E_STATE, "fh_comm_init: a context with a quadratic operator cannot be row-sharded");
   if (c->op == OP_BILINEAR) return fail(FH_E_STATE, "fh_comm_init: a context with a bilinear operator cannot be row-sharded");
   if (c->LB) return fail(FH_E_STATE, "fh_comm_init: a context in multi-column form (fh_set_rhs) cannot be row-sharded");
@@ -2115,6 +2188,7 @@ extern "C" int fh_stream_read_ms(fh_ctx* c, int reps, double* ms_per_pass, uint6
   if (c->op == OP_SPARSE) return fail(FH_E_STATE, "fh_stream_read_ms: the stream-read ceiling is measured on a dense matrix, not on the sparse operator");
   if (c->op == OP_STENCIL3D) return fail(FH_E_STATE, "fh_stream_read_ms: the stream-read ceiling is measured on a dense matrix, not on the 3-D stencil operator");
   if (c->op == OP_DCT) return fail(FH_E_STATE, "fh_stream_read_ms: the stream-read ceiling is measured on a dense matrix, not on the DCT operator");
+  if (c->op == OP_IDENTITY) return fail(FH_E_STATE, "fh_stream_read_ms: the stream-read ceiling is measured on a dense matrix, not on the identity operator");
   if (c->op == OP_QUAD) return fail(FH_E_STATE, "fh_stream_read_ms: the stream-read ceiling is measured on a dense matrix, not on the quadratic operator");
   if (c->op == OP_BILINEAR) return fail(FH_E_STATE, "fh_stream_read_ms: the stream-read ceiling is measured on a dense matrix, not on the bilinear operator");
   if (c->op != OP_DENSE) return fail(FH_E_STATE, "stream-read ceiling needs a dense matrix");

@@ -97,10 +97,13 @@ static int rccl_load() {
 // geometry of the DCT operator's launches (csrc/fh_host_launch.h: dct_shape_for fills it)
 struct DctShape { uint32_t levels, N1, N2, cap; DctRad r1, r2; uint32_t ldsn1, rpw1, grid1, ldsn2, rpw2, grid2, tiles, launches, lds_bytes; };
 
+// geometry of the nuclear-norm prox's launches (csrc/fh_host_launch.h: nuc_shape_for fills it)
+struct NucShape { NucGeo g; uint32_t Bk, steps, wgs, chunks, lds_bytes; uint64_t bytes; };
+
 // ------------------------------------------------------------------------------------------------
 // context
 // ------------------------------------------------------------------------------------------------
-enum { OP_NONE = 0, OP_DENSE = 1, OP_STENCIL = 2, OP_SPARSE = 3, OP_STENCIL3D = 4, OP_QUAD = 5, OP_BILINEAR = 6, OP_DCT = 7 };
+enum { OP_NONE = 0, OP_DENSE = 1, OP_STENCIL = 2, OP_SPARSE = 3, OP_STENCIL3D = 4, OP_QUAD = 5, OP_BILINEAR = 6, OP_DCT = 7, OP_IDENTITY = 8 };
 
 struct fh_ctx {
   int device = 0;
@@ -131,6 +134,15 @@ struct fh_ctx {
   d2* dct_w0 = nullptr; d2* dct_w1 = nullptr;
   DctShape dct_sh = {};      // the geometry dct_shape_for gave when the operator was set (every launch reads it; fh_dct_shape reports it)
   double dct_sc0 = 0.0, dct_sck = 0.0;   // sqrt(1/N), sqrt(2/N)
+  // identity operator (fh_set_identity, csrc/fh_nuclear.h): the unknown is an (id_M, id_N) matrix in the vector form's buffers.  FH_PROX_NUCLEAR
+  // (fh_set_prox_nuclear): the geometry nuc_shape_for gave when the prox was set, the working buffer [ W | J^T ], phi, three device scalars
+  // (||xhat||_F^2, the nuclear norm of xprox, the rank kept), one rotation counter per sweep with its pinned host copy, and the latest run's record
+  uint64_t id_M = 0, id_N = 0;
+  NucShape nuc_sh = {};
+  int nuc_objective = 1;
+  double* nuc_w = nullptr; double* nuc_phi = nullptr; double* nuc_scal = nullptr;
+  unsigned* nuc_cnt = nullptr; unsigned* nuc_host = nullptr;
+  uint64_t nuc_info[4] = {0, 0, 0, 0};      // sweeps, steps launched, rotations, rank kept
   uint64_t D = 0;            // 3-D stencil (fh_set_stencil3d, csrc/fh_tv3d.h): the volume is (D, H, W), m = D*H*W, n = 3*m
   // sparse operator (fh_set_matrix_csr, csrc/fh_sparse.h): sp[0] = A by rows, sp[1] = A^T by rows, each with its non-zero-balanced row ranges,
   // its list of long rows and the lanes-per-row G chosen from its mean row length; sp_r = the adjoint's residual (m-side).  In multi-column form
@@ -205,6 +217,7 @@ struct fh_ctx {
   int tv_slots = 0;          // FH_TUNE_TV_SLOTS: persistent one-pass sweep, workgroups per CU (0 = one workgroup per chunk)
   int tv_ring = 0;           // FH_TUNE_TV_RING: LDS-DMA trip ring of the one-pass sweep (0 = auto, 1 = off, 2 / 3 = slots per wave)
   int tv3_planes = 0;        // FH_TUNE_TV3_PLANES: planes a workgroup of the 3-D stencil kernels marches over (0 = auto: tv3_shape_for)
+  int nuc_block_rows = 0;    // FH_TUNE_NUC_BLOCK_ROWS: rows per block of the nuclear-norm prox's steps (0 = 8); read when the prox is set
   int dct_row_cap = 0;       // FH_TUNE_DCT_ROW_CAP: longest row transform of the DCT operator (0 = DCT_ROW_CAP); read when fh_set_dct sets the operator
   int tv_pipe = 0;           // FH_TUNE_TV_PIPE: rotating trip buffers of the one-pass sweep (0 = auto, 1 = burst, 2, 3)
   bool fused_variant_auto = true;   // cleared by FH_TUNE_FUSED_VARIANT: the caller's word is taken as it is (fused_variant_for)
@@ -404,12 +417,17 @@ static void free_operator(fh_ctx* c) {
   fr(c->sp_r); c->nnz = 0;
   for (d2** q : {&c->dct_tw, &c->dct_pw, &c->dct_w0, &c->dct_w1}) if (*q) { (void)hipFree(*q); *q = nullptr; }
   fr(c->dct_diag);
+  fr(c->nuc_w); fr(c->nuc_phi); fr(c->nuc_scal);
+  if (c->nuc_cnt) { (void)hipFree(c->nuc_cnt); c->nuc_cnt = nullptr; }
+  if (c->nuc_host) { (void)hipHostFree(c->nuc_host); c->nuc_host = nullptr; }
+  c->id_M = c->id_N = 0;
   free_vectors(c);
   c->L = c->LB = 0;                  // a new operator starts in the vector form
   if (c->loss_kind == LOSS_QUAD) c->loss_kind = LOSS_LSQ;                                        // ... and leaves the quadratic form (fh_set_quadratic) behind:
   if (c->prox_kind == FH_PROX_ROWBALL) { c->prox_kind = FH_PROX_IDENTITY; c->mu = 0.0; }      // its loss and the prox only it serves
   if (c->loss_kind == LOSS_BILINEAR) c->loss_kind = LOSS_LSQ;                                    // ... and the bilinear form (fh_set_factorization) likewise
   if (c->prox_kind == FH_PROX_ROWSPLIT) { c->prox_kind = FH_PROX_IDENTITY; c->mu = 0.0; }
+  if (c->prox_kind == FH_PROX_NUCLEAR) { c->prox_kind = FH_PROX_IDENTITY; c->mu = 0.0; }         // ... and the identity form's (fh_set_identity)
   fr(c->bl_part); c->bl_part_bytes = 0; c->bl_have_grad = false; c->bl_m = c->bl_n = 0;
   fr(c->ws); c->ws_bytes = 0;
   fr(c->slotbuf); c->slotbuf_bytes = 0; c->slots_sig = 0;

@@ -1141,8 +1141,189 @@ static int launch_adj_dct(fh_ctx* c, const AdjIO& io) {
   return 0;
 }
 
+// ---- identity operator with an elementwise loss, and the nuclear-norm prox (fh_set_identity / fh_set_prox_nuclear; kernels in csrc/fh_nuclear.h) ----
+#ifndef FH_SINGLE_TU
+NUC_KERNELS(extern template)
+#endif
+static inline bool id_prox_ok(int kind) { return sp_prox_ok(kind) || kind == FH_PROX_NUCLEAR; }
+// THE geometry of the thresholding, a pure function of (M, N) and FH_TUNE_NUC_BLOCK_ROWS (0 = auto = NUC_AUTO_BLOCK_ROWS): p = min, q = max, P = p padded to a multiple of
+// Bk, nb = P / Bk blocks, a sweep of nb - 1 steps (nb even; nb for an odd nb, whose steps each give one block a bye; 1 for nb = 1: the self-pair) of
+// ceil(nb / 2) workgroups, rows of [ W | J^T ] of ld = (q padded to even) + (P padded to even) doubles.
+static int nuc_shape_for(uint64_t M, uint64_t N, int block_rows, NucShape* sh) {
+  memset(sh, 0, sizeof(*sh));
+  if (block_rows != 0 && block_rows != 1 && block_rows != 2 && block_rows != 4 && block_rows != 8) return fail(FH_E_ARG, "NUC_BLOCK_ROWS must be 0 (auto), 1, 2, 4 or 8 rows per block");
+  if (M == 0 || N == 0) return fail(FH_E_ARG, "the identity operator needs a non-empty matrix unknown (got %llu x %llu)", (unsigned long long)M, (unsigned long long)N);
+  if (M > (1ull << 26) || N > (1ull << 26) || M * N > (1ull << 26)) return fail(FH_E_ARG, "the identity operator serves at most 2^26 entries (got %llu x %llu)", (unsigned long long)M, (unsigned long long)N);
+  const uint64_t p = std::min(M, N), q = std::max(M, N);
+  if (p > NUC_MAX_P) return fail(FH_E_ARG, "FH_PROX_NUCLEAR serves min(M, N) <= %d (got %llu x %llu): the Jacobi sweeps are quadratic in it", NUC_MAX_P, (unsigned long long)M, (unsigned long long)N);
+  const uint32_t Bk = block_rows ? (uint32_t)block_rows : NUC_AUTO_BLOCK_ROWS;
+  NucGeo& g = sh->g;
+  g.M = (uint32_t)M; g.N = (uint32_t)N; g.p = (uint32_t)p; g.q = (uint32_t)q; g.transposed = M > N ? 1 : 0;
+  g.P = (uint32_t)round_up(p, Bk); g.nb = g.P / Bk;
+  g.qpad = (uint32_t)round_up(q, 2); g.ld = g.qpad + (uint32_t)round_up(g.P, 2);
+  const uint32_t nbe = g.nb + (g.nb & 1u);
+  sh->Bk = Bk;
+  sh->steps = g.nb == 1 ? 1u : nbe - 1u;
+  sh->wgs = g.nb == 1 ? 1u : nbe / 2u;
+  sh->chunks = (g.qpad + NUC_CC - 1) / NUC_CC;
+  sh->bytes = (uint64_t)g.P * g.ld * sizeof(double);
+  sh->lds_bytes = (uint32_t)((2 * Bk * NUC_LDT + 2 * (2 * Bk) * (2 * Bk) + FH_WG) * sizeof(double));
+  return 0;
+}
+static void nuc_shape_out(const NucShape& sh, uint64_t* out) {
+  const uint64_t v[FH_NUCLEAR_SHAPE_LEN] = {(uint64_t)sh.g.transposed, sh.g.p, sh.g.q, sh.Bk, sh.g.P, sh.g.nb, sh.steps, sh.wgs, NUC_CC, sh.chunks, sh.g.ld, sh.bytes, sh.lds_bytes};
+  memcpy(out, v, sizeof(v));
+}
+extern "C" int fh_nuclear_shape(fh_ctx* c, uint64_t* out) {
+  if (!c || !out) return fail(FH_E_ARG, "fh_nuclear_shape: null argument");
+  if (c->op != OP_IDENTITY || c->prox_kind != FH_PROX_NUCLEAR) return fail(FH_E_STATE, "fh_nuclear_shape: the context holds no identity operator with FH_PROX_NUCLEAR (fh_set_identity, fh_set_prox_nuclear)");
+  nuc_shape_out(c->nuc_sh, out);                          // (what nuc_shape_for gave when the prox was set: the launchers read the same copy)
+  return 0;
+}
+extern "C" int fh_nuclear_shape_for(uint64_t M, uint64_t N, int block_rows, int ncu, uint64_t* out) {
+  (void)ncu;                                              // (the schedule is the tournament's: it does not depend on the device's size)
+  if (!out) return fail(FH_E_ARG, "fh_nuclear_shape_for: null argument");
+  NucShape sh;
+  const int rc = nuc_shape_for(M, N, block_rows, &sh);
+  nuc_shape_out(sh, out);
+  return rc;
+}
+
+static void nuc_launch_step(fh_ctx* c, const NucStepP& q, uint32_t Bk, uint32_t wgs) {
+  switch (Bk) {
+    case 1: k_nuc_step<1><<<dim3(wgs), dim3(FH_WG), 0, c->stream>>>(q); break;
+    case 2: k_nuc_step<2><<<dim3(wgs), dim3(FH_WG), 0, c->stream>>>(q); break;
+    case 4: k_nuc_step<4><<<dim3(wgs), dim3(FH_WG), 0, c->stream>>>(q); break;
+    default: k_nuc_step<8><<<dim3(wgs), dim3(FH_WG), 0, c->stream>>>(q); break;
+  }
+}
+// W := the operand (x0 - tau*g0, kept in `xhat`, or x0 itself when g0 is null), then sweeps of steps until one rotates nothing.  ONE host
+// synchronisation per sweep (the sweep's integer counter), none per step.  FH_E_NOCONV after NUC_MAX_SWEEPS sweeps that all rotated.
+static int nuc_decompose(fh_ctx* c, const double* x0, const double* g0, double tau, double* xhat, int with_j, uint64_t* info) {
+  const NucShape& sh = c->nuc_sh;
+  const uint64_t total = (uint64_t)sh.g.P * sh.g.ld;
+  const unsigned lgrid = (unsigned)std::min<uint64_t>((total + FH_WG - 1) / FH_WG, 2048);
+  FH_TRY(ensure_ws(c, (size_t)lgrid * sizeof(double)));
+  NucLoadP lp;
+  lp.g = sh.g; lp.x0 = x0; lp.g0 = g0; lp.tau = tau; lp.xhat = xhat; lp.W = c->nuc_w; lp.with_j = with_j;
+  lp.red = c->ws; lp.counter = c->counters + CNT_AUX; lp.fro2 = c->nuc_scal;
+  HIP_TRY(hipMemsetAsync(c->nuc_cnt, 0, 32 * sizeof(unsigned), c->stream));
+  k_nuc_load<<<dim3(lgrid), dim3(FH_WG), 0, c->stream>>>(lp);
+  HIP_TRY(hipGetLastError());
+  NucStepP q;
+  q.g = sh.g; q.W = c->nuc_w; q.cols = with_j ? sh.g.ld : sh.g.qpad; q.fro2 = c->nuc_scal;
+  info[0] = info[1] = info[2] = 0;
+  for (int sweep = 0; sweep < NUC_MAX_SWEEPS; ++sweep) {
+    q.rotations = c->nuc_cnt + sweep;
+    for (uint32_t st = 0; st < sh.steps; ++st) { q.step = st; nuc_launch_step(c, q, sh.Bk, sh.wgs); }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(c->nuc_host + sweep, c->nuc_cnt + sweep, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    info[0] += 1; info[1] += sh.steps; info[2] += c->nuc_host[sweep];
+    if (c->nuc_host[sweep] == 0u) return 0;
+  }
+  return fail(FH_E_NOCONV, "FH_PROX_NUCLEAR: the block-Jacobi sweeps still rotated after %d sweeps (%llu rotations in the last one)", NUC_MAX_SWEEPS,
+              (unsigned long long)c->nuc_host[NUC_MAX_SWEEPS - 1]);
+}
+static int nuc_sigma(fh_ctx* c, double thr, double* phi, double* out_gsum, double* out_gmax, double* out_rank, int to_host) {
+  const NucShape& sh = c->nuc_sh;
+  FH_TRY(ensure_ws(c, (size_t)sh.g.P * 2 * sizeof(double)));
+  NucSigmaP sp;
+  sp.g = sh.g; sp.W = c->nuc_w; sp.thr = thr; sp.phi = phi; sp.red = c->ws; sp.counter = c->counters + CNT_AUX;
+  sp.out_gsum = out_gsum; sp.out_gmax = out_gmax; sp.out_rank = out_rank; sp.to_host = to_host;
+  k_nuc_sigma<<<dim3(sh.g.P), dim3(FH_WG), 0, c->stream>>>(sp);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+// xhat = x0 - tau*g0 and xp = its singular-value soft-threshold at tau*mu; nuc_scal[1] = the nuclear norm of xp, [2] = the rank kept, [3] = its largest singular value
+static int nuc_prox(fh_ctx* c, double tau, const double* x0, const double* g0, double* xhat, double* xp) {
+  const NucShape& sh = c->nuc_sh;
+  t_begin(c, FH_K_LEVEL);
+  const int rc = nuc_decompose(c, x0, g0, tau, xhat, 1, c->nuc_info);
+  if (rc != 0) {                                          // never a finite wrong prox
+    char keep[sizeof(g_err)];
+    memcpy(keep, g_err, sizeof(keep));
+    k_nuc_fill<<<dim3(256), dim3(FH_WG), 0, c->stream>>>(xp, c->n, __builtin_nan(""));
+    (void)hipStreamSynchronize(c->stream);
+    t_end(c, FH_K_LEVEL);
+    memcpy(g_err, keep, sizeof(keep));
+    return rc;
+  }
+  FH_TRY(nuc_sigma(c, tau * c->mu, c->nuc_phi, c->nuc_scal + 1, c->nuc_scal + 3, c->nuc_scal + 2, 0));
+  NucReconP rp;
+  rp.g = sh.g; rp.W = c->nuc_w; rp.phi = c->nuc_phi; rp.xp = xp;
+  k_nuc_recon<<<dim3((sh.g.q + FH_WG - 1) / FH_WG, (sh.g.p + NUC_TR - 1) / NUC_TR), dim3(FH_WG), 0, c->stream>>>(rp);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(c->nuc_host + 32, c->nuc_scal + 2, sizeof(double), hipMemcpyDeviceToHost, c->stream));      // the rank kept, for fh_nuclear_info
+  t_end(c, FH_K_LEVEL);
+  return 0;
+}
+// the nuclear and the spectral norm of x (a values-only decomposition: the same steps, no J block, no reconstruction) -> *out_gsum, *out_gmax;
+// objective = 0: NaN in *out_gsum instead, *out_gmax is left as it is
+static __global__ void k_nuc_set(double* p, double v) { scal_store(p, v); }
+static int nuc_norm(fh_ctx* c, const double* x, double* out_gsum, double* out_gmax) {
+  if (!c->nuc_objective) {
+    k_nuc_set<<<dim3(1), dim3(1), 0, c->stream>>>(out_gsum, __builtin_nan(""));
+    HIP_TRY(hipGetLastError());
+    return 0;
+  }
+  t_begin(c, FH_K_LEVEL);
+  uint64_t info[3];                                       // (fh_nuclear_info reports on the latest PROX, not on this run)
+  const int rc = nuc_decompose(c, x, nullptr, 0.0, nullptr, 0, info);
+  if (rc == 0) FH_TRY(nuc_sigma(c, 0.0, nullptr, out_gsum, out_gmax, nullptr, 1));
+  t_end(c, FH_K_LEVEL);
+  return rc;
+}
+
+// z := prox(x0 - tau g0) (mode 0) or x0 (mode 1), the loss sum and the n-side sums: one elementwise launch (behind the thresholding for FH_PROX_NUCLEAR)
+static int launch_fwd_identity(fh_ctx* c, int mode, double tau, const double* x0, const double* g0, const double* xacc0,
+                               double* xhat, double* xp, double* z, int sub_b) {
+  if (mode == 0 && !id_prox_ok(c->prox_kind)) return fail(FH_E_STATE, "prox kind %d (LINF / L1BALL / TVBALL / GROUP / ROWBALL / ROWSPLIT) is not implemented for the identity operator", c->prox_kind);
+  const bool nuc = mode == 0 && c->prox_kind == FH_PROX_NUCLEAR;
+  if (nuc) FH_TRY(nuc_prox(c, tau, x0, g0, xhat, xp));
+  IdFwdP p;
+  p.n = c->n; p.mode = mode; p.given = nuc ? 1 : 0; p.sub_b = sub_b; p.loss = c->loss_kind;
+  p.x0 = x0; p.g0 = g0; p.xacc0 = xacc0; p.xhat = xhat; p.xp = xp; p.z = z; p.b = c->b; p.tau = tau;
+  p.px = make_prox(c, tau);
+  p.nuc = c->nuc_scal ? c->nuc_scal + 1 : nullptr;
+  const unsigned grid = (unsigned)std::min<uint64_t>((c->n + FH_WG - 1) / FH_WG, 2048);
+  FH_TRY(ensure_ws(c, (size_t)grid * 8 * sizeof(double)));
+  p.red = c->ws; p.counter = c->counters + CNT_FWD; p.out = scalar_out(c);
+  t_begin(c, FH_K_FWD);
+  p.seq = seq_offer(c);
+  k_id_fwd<<<dim3(grid), dim3(FH_WG), 0, c->stream>>>(p);
+  t_end(c, FH_K_FWD);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// g1 := grad f(x1), x1 = xprox or its extrapolation, and the n-side epilogue; FH_PROX_NUCLEAR: the norms of x1 are the thresholding's when x1 is xprox,
+// a values-only decomposition of the extrapolated x1 otherwise
+static int launch_adj_identity(fh_ctx* c, const AdjIO& io) {
+  if (io.mode != 0 && io.mode != 1) return fail(FH_E_STATE, "the identity operator has no row-sharded adjoint");
+  const bool nuc = io.mode == 0 && c->prox_kind == FH_PROX_NUCLEAR;
+  IdAdjP p;
+  p.n = c->n; p.mode = io.mode; p.accel = io.accel; p.sub_b = io.sub_b; p.loss = c->loss_kind;
+  p.gsum_mode = !nuc ? 0 : (!io.accel ? 1 : (c->nuc_objective ? 3 : 2));
+  p.coef = io.coef; p.tau = io.tau; p.z = io.z; p.b = c->b;
+  p.x0 = io.x0; p.xp = io.xp; p.xacc0 = io.xacc0; p.xhat = io.xhat; p.x1 = io.x1; p.g1 = io.g1;
+  p.gsum_src = c->nuc_scal ? c->nuc_scal + 1 : nullptr;
+  const unsigned grid = (unsigned)std::min<uint64_t>((c->n + FH_WG - 1) / FH_WG, 2048);
+  FH_TRY(ensure_ws(c, (size_t)grid * 8 * sizeof(double)));
+  p.red = c->ws; p.counter = c->counters + CNT_ADJ_FIN; p.out = scalar_out(c);
+  t_begin(c, FH_K_ADJ);
+  p.seq = (io.mode == 0 && p.gsum_mode != 3) ? seq_offer(c) : 0u;
+  k_id_adj<<<dim3(grid), dim3(FH_WG), 0, c->stream>>>(p);
+  t_end(c, FH_K_ADJ);
+  HIP_TRY(hipGetLastError());
+  if (p.gsum_mode == 3) FH_TRY(nuc_norm(c, io.x1, scalar_out(c) + FH_S_GSUM_ADJ, scalar_out(c) + FH_S_GMAX_ADJ));
+  return 0;
+}
+
 // sum|x_i| and max|x_i| of an n-length device vector -> dscal[GSUM], dscal[GMAX]  (g(x0) for objective_hist[0], :143)
 static int launch_gterms(fh_ctx* c, const double* x) {
+  if (c->op == OP_IDENTITY && c->prox_kind == FH_PROX_NUCLEAR)      // the norms of x0 are not free here (the forward pass that precedes wrote FH_S_GMAX = 0)
+    return nuc_norm(c, x, scalar_out(c) + FH_S_GSUM, scalar_out(c) + FH_S_GMAX);
   if (c->LB) {              // (n, L) matrix: the same two terms, or the sum of row norms for FH_PROX_GROUP
     const unsigned mgrid = (unsigned)std::min<uint64_t>((c->n + FH_WG - 1) / FH_WG, 1024);
     FH_TRY(ensure_ws(c, (size_t)mgrid * 2 * sizeof(double)));
@@ -1572,6 +1753,7 @@ static int op_fwd(fh_ctx* c, int mode, double tau, const double* x0, const doubl
   if (c->op == OP_SPARSE) return c->LB ? launch_fwd_spmulti(c, mode, tau, x0, g0, xacc0, xhat, xp, z, sub_b) : launch_fwd_sparse(c, mode, tau, x0, g0, xacc0, xhat, xp, z, sub_b);
   if (c->op == OP_STENCIL3D) return launch_fwd_tv3(c, mode, tau, x0, g0, xacc0, xhat, xp, z, sub_b);
   if (c->op == OP_DCT) return launch_fwd_dct(c, mode, tau, x0, g0, xacc0, xhat, xp, z, sub_b);
+  if (c->op == OP_IDENTITY) return launch_fwd_identity(c, mode, tau, x0, g0, xacc0, xhat, xp, z, sub_b);
   if (c->op == OP_QUAD) return launch_fwd_quad(c, mode, tau, x0, g0, xacc0, xhat, xp, z, sub_b);
   if (c->op == OP_BILINEAR) return launch_fwd_bilinear(c, mode, tau, x0, g0, xacc0, xhat, xp, z, sub_b);
   return fail(FH_E_STATE, "no operator set");
@@ -1589,6 +1771,7 @@ static int adj_local(fh_ctx* c, const AdjIO& io_in) {
   if (c->op == OP_SPARSE) return c->LB ? launch_adj_spmulti(c, io) : launch_adj_sparse(c, io);
   if (c->op == OP_STENCIL3D) return launch_adj_tv3(c, io);
   if (c->op == OP_DCT) return launch_adj_dct(c, io);
+  if (c->op == OP_IDENTITY) return launch_adj_identity(c, io);
   if (c->op == OP_QUAD) return launch_adj_quad(c, io);
   if (c->op == OP_BILINEAR) return launch_adj_bilinear(c, io);
   return fail(FH_E_STATE, "no operator set");
@@ -1619,7 +1802,7 @@ static int reduce_fsq_over_ranks(fh_ctx* c) {
 static int check_ready(fh_ctx* c, bool need_b) {
   if (!c) return fail(FH_E_ARG, "null context");
   if (c->pending_step) return fail(FH_E_STATE, "a step issued by fh_step_begin is still in flight on this context: call fh_step_end first");
-  if (c->op == OP_NONE) return fail(FH_E_STATE, "no operator set (call fh_set_matrix / fh_set_matrix_csr / fh_generate_matrix / fh_set_stencil / fh_set_stencil3d / fh_set_dct / fh_set_quadratic / fh_set_factorization)");
+  if (c->op == OP_NONE) return fail(FH_E_STATE, "no operator set (call fh_set_matrix / fh_set_matrix_csr / fh_generate_matrix / fh_set_stencil / fh_set_stencil3d / fh_set_dct / fh_set_identity / fh_set_quadratic / fh_set_factorization)");
   if (need_b && !c->has_b) return fail(FH_E_STATE, "no loss set (call fh_set_loss_lsq)");
   return c->shards.empty() ? use_device(c) : 0;      // (a shell selects the device shard by shard)
 }

@@ -17,6 +17,7 @@ LIB_PATH = os.environ.get("FASTA_HIP_LIB") or os.path.join(_HERE, "libfasta_hip.
 
 # enums mirrored from include/fasta_hip.h ---------------------------------------------------------
 PROX_IDENTITY, PROX_SHRINK, PROX_NONNEG, PROX_LINF, PROX_L1BALL, PROX_TVBALL, PROX_BOX, PROX_GROUP, PROX_ROWBALL, PROX_ROWSPLIT = range(10)
+PROX_NUCLEAR = 10                  # singular-value soft-threshold, identity operator only (fh_set_identity, csrc/fh_nuclear.h)
 MAX_RHS = 16                       # columns of a matrix unknown (fh_set_rhs, fh_set_matrix_csr_rhs, fh_set_quadratic, fh_set_factorization)
 (VEC_X0, VEC_G0, VEC_XHAT, VEC_XPROX, VEC_X1, VEC_G1, VEC_BEST, VEC_B, VEC_Z,
  VEC_T0, VEC_T1, VEC_T2, VEC_T3) = range(13)
@@ -27,6 +28,7 @@ K_FWD, K_ADJ, K_AUX, K_COMM, K_FUSED, K_HOST_ISSUE, K_LEVEL = range(7)
 (TUNE_FWD_ROWS, TUNE_FWD_GRID_CAP, TUNE_ADJ_SLAB_ROWS, TUNE_ADJ_CPT, TUNE_LD_PAD, TUNE_NT_LOADS,
  TUNE_TV_U, TUNE_TV_ROWS, TUNE_TV_NT, TUNE_FUSED_VARIANT, TUNE_TV_ZFREE, TUNE_TV_PIPE, TUNE_TV_XCD, TUNE_TV_LDS_PAD,
  TUNE_TV_RING, TUNE_TV_SLOTS, TUNE_FUSED_CUS, TUNE_RUN_MAX_N, TUNE_SEQ_POLL, TUNE_RUN_CHAIN, TUNE_ADJ_CYCLIC, TUNE_TV3_PLANES, TUNE_DCT_ROW_CAP) = range(23)
+TUNE_NUC_BLOCK_ROWS = 23           # rows per block of the nuclear-norm prox's Jacobi steps: 0 (auto = 1), 1, 2, 4, 8; read when the prox is set
 # keys 10, 13, 14, 15 (TUNE_TV_ZFREE / _LDS_PAD / _RING / _SLOTS) are NOT in include/fasta_hip.h: experimental forms of the stencil sweep,
 # accepted only by libfasta_hip_experimental.so (csrc/fh_experimental.h); the shipped library answers FH_E_ARG
 EXPERIMENTAL_KEYS = (TUNE_TV_ZFREE, TUNE_TV_LDS_PAD, TUNE_TV_RING, TUNE_TV_SLOTS)
@@ -36,6 +38,7 @@ TUNE_TEST_HOOKS = 0x7E57             # tests only (csrc/fh_experimental.h): 1 = 
 HOOK_WITHHOLD_PARTIAL, HOOK_PROBE_SAYS_NO, HOOK_LEVEL_WITHHOLD, HOOK_LEVEL_NO_FALLBACK = 1, 2, 4, 8
 HOOK_RUN_ATTEMPT_SHIFT = 8
 E_ARG, E_STATE, E_RCCL, E_TIMEOUT = 10001, 10002, 10003, 10004
+E_NOCONV = 10005                   # FH_PROX_NUCLEAR: the Jacobi sweeps did not settle within 30 sweeps (xprox is NaN)
 LAUNCH_SEPARATE, LAUNCH_ONEPASS_ALWAYS, LAUNCH_ONEPASS_SPECULATIVE, LAUNCH_PAIR = range(4)     # fh_run_opts.launch_mode (fh_iterate)
 LAUNCH_MODES = {None: LAUNCH_SEPARATE, "always": LAUNCH_ONEPASS_ALWAYS, "speculative": LAUNCH_ONEPASS_SPECULATIVE, "pair": LAUNCH_PAIR}
 RECOVERED_LEVEL_FALLBACK, RECOVERED_LEVEL_FAILED, RECOVERED_RUN_TIMEOUT = range(3)
@@ -92,6 +95,11 @@ SIGNATURES = {
     "fh_dct_shape": (_i32, [_ctx, C.POINTER(C.c_uint32)]),
     "fh_dct_shape_for": (_i32, [_u64, _i32, _i32, C.POINTER(C.c_uint32)]),
     "fh_shape": (_i32, [_ctx, C.POINTER(_u64), C.POINTER(_u64)]),
+    "fh_set_identity": (_i32, [_ctx, _u64, _u64]),
+    "fh_set_prox_nuclear": (_i32, [_ctx, _dbl, _i32]),
+    "fh_nuclear_shape": (_i32, [_ctx, C.POINTER(_u64)]),
+    "fh_nuclear_shape_for": (_i32, [_u64, _u64, _i32, _i32, C.POINTER(_u64)]),
+    "fh_nuclear_info": (_i32, [_ctx, C.POINTER(_u64)]),
     "fh_set_quadratic": (_i32, [_ctx, _pd, _u64, _u64, _pd, C.c_uint32]),
     "fh_quad_shape": (_i32, [_ctx, C.POINTER(C.c_uint32)]),
     "fh_quad_shape_for": (_i32, [_u64, C.c_uint32, C.c_longlong, _i32, C.POINTER(C.c_uint32)]),
@@ -321,6 +329,20 @@ def dct_refusal(N, row_cap=0, ncu=256):
         return f"[{status}] " + lib.fh_last_error().decode(errors="replace")
     _check(lib, status)
     return None
+
+
+NUCLEAR_SHAPE_LEN = 13
+NuclearShape = collections.namedtuple("NuclearShape", "transposed p q Bk P nb steps_per_sweep wgs_per_step column_chunk chunks_per_row ld bytes lds_bytes")
+NuclearInfo = collections.namedtuple("NuclearInfo", "sweeps steps rotations rank")
+
+
+def nuclear_shape(M, N, block_rows=0, ncu=256):
+    """NuclearShape of the nuclear-norm prox's launches for an (M, N) unknown under FH_TUNE_NUC_BLOCK_ROWS = block_rows (0 = auto = 1):
+    fh_nuclear_shape_for, the rule the launchers call.  Host-only.  HipError with the library's sentence for a shape the device refuses."""
+    lib = load_library()
+    out = (_u64 * NUCLEAR_SHAPE_LEN)()
+    _check(lib, lib.fh_nuclear_shape_for(int(M), int(N), int(block_rows), int(ncu), out))
+    return NuclearShape(*(int(v) for v in out))
 
 
 def comm_library():
@@ -591,6 +613,28 @@ class HipContext:
         out = (C.c_uint32 * DCT_SHAPE_LEN)()
         self._call("fh_dct_shape", out)
         return _dct_shape(out)
+
+    def set_identity(self, M, N):
+        """The identity operator on an (M, N) matrix unknown with an elementwise loss (csrc/fh_nuclear.h): m = n = M * N; set the loss
+        afterwards (set_loss_lsq / set_loss_logistic with M * N entries)."""
+        self._call("fh_set_identity", int(M), int(N))
+
+    def set_prox_nuclear(self, mu, objective=True):
+        """FH_PROX_NUCLEAR on the identity operator; objective=False skips the values-only decompositions that g(x0) and g at an
+        extrapolated x1 cost (S_GSUM of init() and S_GSUM_ADJ of an accelerated adj() are then NaN)."""
+        self._call("fh_set_prox_nuclear", float(mu), 1 if objective else 0)
+
+    def nuclear_shape(self):
+        """NuclearShape the next thresholding of this context launches with (fh_nuclear_shape)."""
+        out = (_u64 * NUCLEAR_SHAPE_LEN)()
+        self._call("fh_nuclear_shape", out)
+        return NuclearShape(*(int(v) for v in out))
+
+    def nuclear_info(self):
+        """NuclearInfo of the latest thresholding: sweeps, steps launched, rotations, rank kept (fh_nuclear_info)."""
+        out = (_u64 * 4)()
+        self._call("fh_nuclear_info", out)
+        return NuclearInfo(*(int(v) for v in out))
 
     def shape(self):
         m, n = _u64(0), _u64(0)

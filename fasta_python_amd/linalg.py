@@ -17,7 +17,9 @@ subclasses are *recognised* by `fasta()` and run on the device:
   GradDivMap      -- the periodic div/grad stencil pair of examples/tv_denoising.py:26-63;
   DCTMap          -- the subsampled orthonormal DCT of examples/democratic_representation.py:80-82, an implicit fast transform (csrc/fh_dct.h);
   QuadraticMap    -- the identity operator of a quadratic smooth term (losses.Quadratic): what `fasta(None, None, q.f, q.gradf, ...)` runs on;
-  BilinearMap     -- the identity operator of a bilinear smooth term (losses.Factorization): what `fasta(None, None, fz.f, fz.gradf, ...)` runs on.
+  BilinearMap     -- the identity operator of a bilinear smooth term (losses.Factorization): what `fasta(None, None, fz.f, fz.gradf, ...)` runs on;
+  IdentityMap     -- the identity operator on an (M, N) matrix unknown with an elementwise loss (losses.LeastSquares / LogisticLoss): what
+                     `fasta(None, None, ll.f, ll.gradf, reg.g, reg.prox, X0)` runs on (examples/logistic_matrix_completion.py, csrc/fh_nuclear.h).
 
 A DenseMatrixMap built from a host ndarray uploads LAZILY: it keeps a reference to the array (as the
 closures of fasta/linalg.py:41 do) and copies it into HBM when the device loop first asks for its
@@ -38,7 +40,7 @@ from . import hip
 Matrix = np.ndarray
 Vector = np.ndarray
 
-__all__ = ["LinearMap", "LinearOperator", "DenseMatrixMap", "ShardedDenseMatrixMap", "SparseMatrixMap", "GradDivMap", "DCTMap", "QuadraticMap", "BilinearMap", "is_sparse_matrix", "Matrix", "Vector"]
+__all__ = ["LinearMap", "LinearOperator", "DenseMatrixMap", "ShardedDenseMatrixMap", "SparseMatrixMap", "GradDivMap", "DCTMap", "QuadraticMap", "BilinearMap", "IdentityMap", "is_sparse_matrix", "Matrix", "Vector"]
 
 
 class LinearMap:
@@ -495,6 +497,41 @@ class BilinearMap(_DeviceMap):
         for key, value in self._tuning.items():
             ctx.set_tuning(key, value)
         ctx.set_factorization(self.loss.S, self.rhs)
+
+    def _apply_fwd(self, v):
+        return v
+
+    def _apply_adj(self, w):
+        return w
+
+
+class IdentityMap(_DeviceMap):
+    """The operator of `fasta(None, None, loss.f, loss.gradf, g, prox, X0)` with loss = losses.LogisticLoss(B) or losses.LeastSquares(B) and a
+    2-D X0 of B's shape: the identity on (M, N) matrices.  Its device context keeps the unknown in the vector form's buffers (fh_set_identity,
+    csrc/fh_nuclear.h) and serves proximal.NuclearShrink, Shrink, NonNeg, Box or no prox.  Lazy like QuadraticMap; on host arrays it is the
+    identity, as `A = None` is in the reference (examples/logistic_matrix_completion.py:47).
+    tuning: {hip.TUNE_NUC_BLOCK_ROWS: 1 | 2 | 4 | 8} sets the rows per block of the nuclear-norm prox's Jacobi steps."""
+
+    MAX_ENTRIES = 1 << 26
+    MAX_NUCLEAR_RANK = 1024
+
+    def __init__(self, shape, device=0, tuning=None):
+        shape = tuple(int(k) for k in shape)
+        if len(shape) != 2 or min(shape) < 1:
+            raise ValueError(f"the identity operator takes a non-empty matrix unknown of shape (M, N) (got {shape})")
+        if shape[0] * shape[1] > self.MAX_ENTRIES:
+            raise ValueError(f"the identity operator serves at most 2^26 entries on the device (got {shape})")
+        self.shape = (shape[0] * shape[1], shape[0] * shape[1])
+        self.matrix_shape = shape
+        self.rhs = None
+        self.storage = "f64"
+        self._tuning = dict(tuning or {})
+        _DeviceMap.__init__(self, shape, shape, device, lazy=True)
+
+    def _on_context(self, ctx):
+        for key, value in self._tuning.items():
+            ctx.set_tuning(key, value)
+        ctx.set_identity(*self.matrix_shape)
 
     def _apply_fwd(self, v):
         return v

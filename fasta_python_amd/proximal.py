@@ -19,7 +19,7 @@ import numpy as np
 
 from . import hip
 
-__all__ = ["Shrink", "NonNeg", "LinfProx", "L1Ball", "Box", "TVDualBall", "GroupShrink", "RowBall", "RowSplit", "NoProx", "device_prox", "release_scratch",
+__all__ = ["Shrink", "NonNeg", "LinfProx", "L1Ball", "Box", "TVDualBall", "GroupShrink", "RowBall", "RowSplit", "NuclearShrink", "NoProx", "device_prox", "release_scratch",
            "shrink", "project_Linf_ball", "project_L1_ball", "project_Lnuc_ball"]
 
 
@@ -198,6 +198,40 @@ class RowSplit(ProxTag):
         return self.top.g(Z[:self.split, ...])
 
 
+class NuclearShrink(ProxTag):
+    """Low-rank regulariser of a matrix unknown X of shape (M, N) (examples/logistic_matrix_completion.py:44-45): proxg(X, t) soft-thresholds the
+    singular values by t*mu, the prox of mu * ||X||_*.  On host arrays `g` and `prox` are the example's closures in the example's own
+    arithmetic (a full SVD, the thresholded values on the diagonal of a zero (M, N) matrix, U @ S @ V), so the generic host loop reproduces a
+    reference run bit for bit.  NOTE what that arithmetic makes of g: `la.norm(np.diag(s), 1)` is the induced 1-norm of a diagonal MATRIX, its
+    largest entry -- the example's objective (and with it the iterate it returns as best) is f + mu * sigma_max(X), not f + mu * ||X||_*.  The
+    device reports both norms (FH_S_GSUM: nuclear, FH_S_GMAX: spectral) and `g_from_sums` takes the one the example's `g` evaluates, so that
+    device and reference runs agree; `nuclear_norm_from_sums` gives the other.  The device serves it on the identity operator only (FH_PROX_NUCLEAR, csrc/fh_nuclear.h: block
+    one-sided Jacobi, no LAPACK), for min(M, N) <= 1024."""
+    kind = hip.PROX_NUCLEAR
+
+    def __init__(self, mu):
+        self.mu = float(mu)
+
+    def bind_prox(self, ctx, evaluate_objective=True):
+        # g is not free at x0 nor at an extrapolated iterate: the values-only decompositions are skipped when nobody reads the objective
+        ctx.set_prox_nuclear(self.mu, bool(evaluate_objective))
+
+    def g_from_sums(self, gsum, gmax):
+        return self.mu * gmax                   # FH_S_GMAX carries the largest singular value for this kind: what `g` below evaluates
+
+    def nuclear_norm_from_sums(self, gsum, gmax):
+        return gsum                             # FH_S_GSUM: the sum of the singular values
+
+    def prox(self, X, t):
+        U, s, V = np.linalg.svd(X)
+        S = np.zeros(X.shape)
+        S[:len(s), :len(s)] = np.diag(shrink(s, t * self.mu))
+        return U @ S @ V
+
+    def g(self, X):
+        return self.mu * np.linalg.norm(np.diag(np.linalg.svd(X)[1]), 1)
+
+
 # ---- the device prox on host arrays -----------------------------------------------------------------
 _scratch = {}            # (device, "dense", n) or (device, "tv", H, W) -> operator holding a scratch HipContext
 
@@ -255,6 +289,8 @@ def device_prox(tag, x, t, device=0):
     tag on such an array (same bits as on the flattened array).  Every other call is flattened and takes the vector kernels."""
     x = np.asarray(x, dtype=np.float64)
     flat = x.ravel()
+    if tag.kind == hip.PROX_NUCLEAR:
+        return _device_prox_nuclear(tag, x, t, device)
     tv = tag.kind == hip.PROX_TVBALL
     if tv:
         assert x.ndim == 3 and x.shape[-1] == 2
@@ -267,6 +303,27 @@ def device_prox(tag, x, t, device=0):
         ctx.init()
     ctx.fwd(float(t))
     return ctx.get_vector(hip.VEC_XPROX, flat.size).reshape(x.shape)
+
+
+def _device_prox_nuclear(tag, x, t, device):
+    """NuclearShrink through a scratch identity context (csrc/fh_nuclear.h), cached per (device, M, N) like the others."""
+    from .linalg import IdentityMap
+    if x.ndim != 2:
+        raise ValueError(f"NuclearShrink needs a 2-D array (got shape {x.shape})")
+    key = (device, "identity") + tuple(x.shape)
+    op = _scratch.get(key)
+    if op is None:
+        if len(_scratch) >= 8:
+            _scratch.pop(next(iter(_scratch))).close()
+        op = IdentityMap(x.shape, device=device)
+        op.ctx.set_loss_lsq(np.zeros(x.size))
+        _scratch[key] = op
+    ctx = op.ctx
+    tag.bind_prox(ctx, False)
+    ctx.set_vector(hip.VEC_X0, x)
+    ctx.set_vector(hip.VEC_G0, np.zeros(x.size))
+    ctx.fwd(float(t))
+    return ctx.get_vector(hip.VEC_XPROX, x.size).reshape(x.shape)
 
 
 # ---- the reference's function names (host arrays, NumPy) ------------------------------------------------
@@ -293,7 +350,7 @@ def project_L1_ball(x, t):
 
 
 def project_Lnuc_ball(X, t):
-    """Soft-threshold the singular values of X by t (fasta/proximal.py:44-55).  Host only: a dense SVD is not on the
-    MI355X hot path."""
+    """Soft-threshold the singular values of X by t (fasta/proximal.py:44-55), by LAPACK's thin SVD on the host.  The device's form is
+    NuclearShrink on the identity operator (FH_PROX_NUCLEAR, csrc/fh_nuclear.h), which the -m gpu tests hold to this function."""
     U, s, Vh = np.linalg.svd(X, full_matrices=False)
     return (U * shrink(s, t)) @ Vh

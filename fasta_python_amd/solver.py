@@ -30,9 +30,9 @@ from time import time
 import numpy as np
 
 from . import hip, stopping
-from .linalg import BilinearMap, DCTMap, DenseMatrixMap, GradDivMap, LinearMap, QuadraticMap, SparseMatrixMap, _DeviceMap, is_sparse_matrix
+from .linalg import BilinearMap, DCTMap, DenseMatrixMap, GradDivMap, IdentityMap, LinearMap, QuadraticMap, SparseMatrixMap, _DeviceMap, is_sparse_matrix
 from .losses import Factorization, LeastSquares, LogisticLoss, Quadratic
-from .proximal import NoProx, ProxTag
+from .proximal import NoProx, NuclearShrink, ProxTag
 
 __all__ = ["fasta", "Convergence", "FBSolver", "EPSILON"]
 
@@ -199,6 +199,40 @@ def _factorization_form_refusal(A, At, loss_f, loss_g, g, proxg, x0):
     return None
 
 
+_NUCLEAR_ELSEWHERE = ("proximal.NuclearShrink is served on the device by the identity operator only: fasta(None, None, loss.f, loss.gradf, reg.g, reg.prox, X0) "
+                      "with loss = losses.LogisticLoss(B) or losses.LeastSquares(B) and a 2-D X0 of B's shape")
+
+
+def _identity_form_refusal(A, loss, g, proxg, x0):
+    """`fasta(None, None, loss.f, loss.gradf, g, prox, X0)` with loss = losses.LogisticLoss(B) or LeastSquares(B), or the same with an explicit
+    linalg.IdentityMap: the device serves it through fh_set_identity (csrc/fh_nuclear.h) for a 2-D X0 of B's shape with NuclearShrink, Shrink,
+    NonNeg, Box or no prox.  None, or the reason."""
+    from .proximal import Box, NonNeg, Shrink
+    shape = None if x0 is None else tuple(np.shape(x0))
+    if shape is not None and len(shape) != 2:
+        return (f"the identity operator takes a MATRIX unknown on the device: x0 must be 2-D of shape (M, N) (x0 has shape {shape}); "
+                "a vector unknown with A=None runs the host loop (backend='numpy')")
+    if shape is not None and loss.b.shape != shape:
+        return f"B must have x0's shape with the identity operator (B has {loss.b.shape}, x0 has {shape})"
+    if isinstance(A, IdentityMap) and shape is not None and A.Vshape != shape:
+        return f"x0 has shape {shape}, the IdentityMap was built for {A.Vshape}"
+    if shape is not None and (min(shape) < 1 or shape[0] * shape[1] > IdentityMap.MAX_ENTRIES):
+        return f"the identity operator serves 1 to 2^26 entries on the device (x0 has shape {shape})"
+    if g is None and proxg is None:
+        return None
+    prox, owner_g = _tag_of(proxg, ProxTag), _tag_of(g, ProxTag)
+    if prox is None or (owner_g is not None and owner_g is not prox) or (owner_g is None and g is not None):
+        return ("g and proxg must be the `.g` / `.prox` of one proximal.* tag object "
+                "(NuclearShrink, Shrink, NonNeg, Box)")
+    if not isinstance(prox, (NuclearShrink, Shrink, NonNeg, Box)) and type(prox) is not NoProx:
+        return (f"proximal.{type(prox).__name__} is not implemented for the identity operator on the device "
+                "(NuclearShrink, Shrink, NonNeg, Box or no prox are)")
+    if isinstance(prox, NuclearShrink) and shape is not None and min(shape) > IdentityMap.MAX_NUCLEAR_RANK:
+        return (f"proximal.NuclearShrink serves min(M, N) <= {IdentityMap.MAX_NUCLEAR_RANK} on the device (x0 has shape {shape}): "
+                "the Jacobi sweeps are quadratic in it")
+    return None
+
+
 def _unrecognised(A, At, f, gradf, g, proxg, x0=None):
     """None when the seven operands can run on the device, else the reason they cannot (a sentence)."""
     fz_f, fz_g = _tag_of(f, Factorization), _tag_of(gradf, Factorization)
@@ -208,7 +242,16 @@ def _unrecognised(A, At, f, gradf, g, proxg, x0=None):
     if quad_f is not None or quad_g is not None:
         if _tag_of(proxg, ProxTag) is not None and _tag_of(proxg, ProxTag).kind == hip.PROX_ROWSPLIT:
             return "proximal.RowSplit is served on the device with a factorization loss only: fasta(None, None, fz.f, fz.gradf, ...) with fz = losses.Factorization(S)"
+        if isinstance(_tag_of(proxg, ProxTag), NuclearShrink):
+            return _NUCLEAR_ELSEWHERE
         return _quadratic_form_refusal(A, At, quad_f, quad_g, g, proxg, x0)
+    # A = None with the `.f` / `.gradf` of ONE elementwise loss tag, or an explicit IdentityMap: the identity operator (csrc/fh_nuclear.h).
+    # Every other call with A = None keeps the answer below.
+    loss_f, loss_g = _tag_of(f, (LeastSquares, LogisticLoss)), _tag_of(gradf, (LeastSquares, LogisticLoss))
+    if isinstance(A, IdentityMap) or (A is None and At is None and loss_f is not None and loss_f is loss_g):
+        if loss_f is None or loss_f is not loss_g:
+            return "f and gradf must be the `.f` / `.gradf` of one losses.LeastSquares(B) or losses.LogisticLoss(B) object"
+        return _identity_form_refusal(A, loss_f, g, proxg, x0)
     if not isinstance(A, (np.ndarray, _DeviceMap)) and not is_sparse_matrix(A):
         return ("operator A is not device-resident (pass a 2-D float64 ndarray, a scipy.sparse matrix, a linalg.DenseMatrixMap / "
                 "LinearMap.from_matrix(A), a linalg.SparseMatrixMap, a linalg.GradDivMap or a linalg.DCTMap); arbitrary Python callables cannot run inside the fused HIP kernels")
@@ -221,6 +264,8 @@ def _unrecognised(A, At, f, gradf, g, proxg, x0=None):
     if prox is None or (owner_g is not None and owner_g is not prox) or (owner_g is None and g is not None):
         return ("g and proxg must be the `.g` / `.prox` of one proximal.* tag object "
                 "(Shrink, NonNeg, LinfProx, L1Ball, Box, TVDualBall, GroupShrink)")
+    if prox.kind == hip.PROX_NUCLEAR:
+        return _NUCLEAR_ELSEWHERE
     if prox.kind == hip.PROX_ROWBALL:
         return "proximal.RowBall is served on the device with a quadratic loss only: fasta(None, None, q.f, q.gradf, ...) with q = losses.Quadratic(Q, c)"
     if prox.kind == hip.PROX_ROWSPLIT:
@@ -238,6 +283,9 @@ def _recognise(A, At, f, gradf, g, proxg, x0):
     if quad is not None:                               # A = None: the identity; Q and c travel with the operator
         prox = NoProx() if (g is None and proxg is None) else _tag_of(proxg, ProxTag)
         return QuadraticMap(quad, x0.shape), quad, prox
+    if A is None or isinstance(A, IdentityMap):        # A = None: the identity on matrices; B travels with the loss
+        prox = NoProx() if (g is None and proxg is None) else _tag_of(proxg, ProxTag)
+        return (IdentityMap(x0.shape) if A is None else A), _tag_of(f, (LeastSquares, LogisticLoss)), prox
     if isinstance(A, np.ndarray):
         if A.ndim != 2:
             raise AssertionError("matrix operator must be 2-D")            # linalg.py:40
@@ -288,6 +336,10 @@ class FBSolver:
         self.A, self.loss, self.prox = A, loss, prox
         if isinstance(A, SparseMatrixMap) and fused is True:
             raise ValueError("fused=True: a sparse operator has no one-pass kernel (csrc/fh_sparse.h, csrc/fh_spmulti.h: K-fwd and K-adj)")
+        if isinstance(A, IdentityMap) and fused is True:
+            raise ValueError("fused=True: the identity operator has no one-pass kernel (csrc/fh_nuclear.h: K-fwd and K-adj are elementwise launches)")
+        if isinstance(A, IdentityMap) and (driver == "device" or (driver is None and device_iters not in (None, "auto") and int(device_iters) > 0)):
+            raise ValueError('driver="device": the identity operator has no device-side loop (fh_run); the library loop (driver="library") is the default')
         self.fused_opt = fused
         self.ctx = A.ctx
         self.x0 = np.asarray(x0, dtype=np.float64)
@@ -319,7 +371,9 @@ class FBSolver:
         self.loss.bind(c)
         fval = self.loss.f_from_device
         self._fval = fval
-        if hasattr(self.prox, "bind_prox"):                             # (proximal.RowSplit: two kinds, fh_set_prox_split)
+        if isinstance(self.prox, NuclearShrink):                        # (the objective decides whether g is evaluated where it is not free)
+            self.prox.bind_prox(c, self.evaluate_objective)
+        elif hasattr(self.prox, "bind_prox"):                           # (proximal.RowSplit: two kinds, fh_set_prox_split)
             self.prox.bind_prox(c)
         else:
             c.set_prox(self.prox.kind, self.prox.mu, self.prox.lo, self.prox.hi)

@@ -36,6 +36,8 @@ typedef struct fh_ctx fh_ctx;
                                  could finish the call: the clipping-level search of FH_PROX_LINF / FH_PROX_L1BALL (its outputs are NaN,
                                  never a finite wrong prox), or a grid barrier of fh_run's persistent launch (the state of the last
                                  completed iteration is adopted and the completed history returned: continue with fh_iterate / fh_step) */
+#define FH_E_NOCONV   10005   /* the block-Jacobi decomposition behind FH_PROX_NUCLEAR still rotated after 30 sweeps: xprox is filled with NaN,
+                                 never a finite wrong prox                                                                             */
 
 /* prox operators g(x) <-> proxg(x, t)                                                   */
 enum fh_prox_kind {
@@ -52,6 +54,11 @@ enum fh_prox_kind {
   FH_PROX_ROWBALL  = 8,  /* row-wise projection of an (n, L) matrix, examples/max_norm.py:53-59: with nu = ||xhat_j||_2 over the L entries of row j,
                             xprox_j = (mu * xhat_j) / (max(nu, mu) + (nu == 0)) -- independent of the step; g = 0, so the objective adds nothing for it.
                             Served by the quadratic operator only (fh_set_quadratic); every other operator refuses it with a sentence.        */
+  FH_PROX_NUCLEAR  = 10, /* singular-value soft-threshold of an (M, N) matrix, examples/logistic_matrix_completion.py: xprox = U max(S - t*mu, 0) V^T of
+                            xhat = U S V^T, by block one-sided Jacobi on the device (csrc/fh_nuclear.h).  FH_S_GSUM = sum max(sigma_i - t*mu, 0), the nuclear
+                            norm of xprox; FH_S_GMAX = max max(sigma_i - t*mu, 0), its spectral norm -- which is what the example's g evaluates
+                            (la.norm(np.diag(s), 1) is the induced 1-norm of a diagonal matrix: its largest entry); FH_S_ALPHA = the rank kept.  Served by the identity operator only (fh_set_identity); set by fh_set_prox (objective
+                            = 1) or fh_set_prox_nuclear.                                                                                          */
   FH_PROX_ROWSPLIT = 9   /* two elementwise kinds on one (n, L) matrix, examples/nn_factorization.py:60-61: rows [0, split) take one kind with its own
                             parameters (IDENTITY, SHRINK, NONNEG or BOX), rows [split, n) another (IDENTITY, NONNEG or BOX), each half bit for bit what
                             that kind gives alone.  Set by fh_set_prox_split, never by fh_set_prox.  FH_S_GSUM / FH_S_GSUM_ADJ sum |x| over the TOP rows
@@ -139,6 +146,9 @@ enum fh_tuning_key {
   FH_TUNE_DCT_ROW_CAP = 22,  /* DCT operator (fh_set_dct): longest row transform, 0 = default (2048) or 2..2048.  A small value gives a small N the
                                 two-level form (the tests: N = 60 at a cap of 16).  Read when fh_set_dct sets the operator: set it before; fh_dct_shape
                                 reports what the launches take                                                                                    */
+  FH_TUNE_NUC_BLOCK_ROWS = 23, /* FH_PROX_NUCLEAR: rows per block of the block-Jacobi steps: 1, 2, 4, 8 (1: the classical pairwise rotation) or 0 = auto, which is 1 -- the fastest at every
+                                shape measured with the present step kernel, profiles/nuclear_sizes.txt.
+                                Read when the prox is set: set it before.  It exists so that small shapes reach several blocks, byes and Bk = 1   */
   FH_TUNE_FUSED_CUS = 16     /* dense one-pass kernel: launch it on at most this many CUs (one workgroup each; 0 = every CU the device
                                 reports).  The co-residency probe then asks for that many.  Lets several one-pass grids run side by side
                                 on one device: two solves at once, partitioned devices, ranks of a row-sharded run that share a GPU
@@ -277,6 +287,36 @@ int fh_set_dct(fh_ctx* ctx, uint64_t N, const double* diag);
 int fh_dct_shape(fh_ctx* ctx, uint32_t* out);
 int fh_dct_shape_for(uint64_t N, int row_cap, int ncu, uint32_t* out);
 int fh_shape(fh_ctx* ctx, uint64_t* m, uint64_t* n);
+
+/* ---- the identity operator with an elementwise loss: the unknown is an (M, N) MATRIX, f(X) = sum of a loss over its entries (csrc/fh_nuclear.h) --
+ * examples/logistic_matrix_completion.py: min mu ||X||_* + sum log(1 + e^X) - (B == 1) X, fasta(None, None, f, gradf, g, proxg, X0).  The matrix lives
+ * in the vector form's buffers, M * N doubles in C order: m = n = M * N (fh_shape reports them), z = x, FH_VEC_B holds B.  The loss is set afterwards
+ * by fh_set_loss_lsq / fh_set_loss_logistic (length M * N).  Both directions are elementwise launches with fixed-order reductions: no float atomics,
+ * bitwise repeatable; with the prox kinds IDENTITY, SHRINK, NONNEG and BOX the prox is fused into K-fwd (one launch per direction).
+ * FH_PROX_NUCLEAR (fh_set_prox_nuclear, or fh_set_prox with objective = 1) is the singular-value soft-threshold by block one-sided Jacobi: with
+ * p = min(M, N), q = max(M, N), p rows of length q (xhat, transposed when M > N) in blocks of Bk rows (FH_TUNE_NUC_BLOCK_ROWS), a STEP = one launch
+ * whose workgroups each own a disjoint pair of blocks of a round-robin schedule, a SWEEP = all steps; the host reads one integer rotation count per
+ * sweep and stops after the first sweep without a rotation; more than 30 sweeps is FH_E_NOCONV and xprox is NaN.  The norms are not free at x0 (fh_init)
+ * nor at the extrapolated x1 of an accelerated fh_adj: a values-only decomposition computes them there, unless objective = 0, when FH_S_GSUM (fh_init) and
+ * FH_S_GSUM_ADJ (accelerated fh_adj) hold NaN and FH_S_GMAX / FH_S_GMAX_ADJ 0.  The thresholding's time is reported under FH_K_LEVEL.
+ * Served entry points: fh_init, fh_setup (its three-pass route), fh_gradient_at, fh_apply (a copy), fh_diff_norm, fh_commit, fh_fwd, fh_adj
+ * (accel / coef), fh_fwd_adj, fh_iterate, fh_timing_*.
+ * Refused, each with a sentence: M or N = 0, M * N > 2^26 (FH_E_ARG); min(M, N) > 1024 for FH_PROX_NUCLEAR (FH_E_ARG); fh_step* and fh_run
+ * (FH_E_STATE; fh_fused_supported, fh_fused_agree and fh_run_supported report 0); fh_set_rhs, float32 storage, multi-device contexts, communicators,
+ * fh_get_matrix_rows, fh_stream_read_ms (FH_E_STATE); the prox kinds LINF, L1BALL, TVBALL, GROUP, ROWBALL and ROWSPLIT (FH_E_ARG).  Every other
+ * operator refuses FH_PROX_NUCLEAR; a context holding it returns to IDENTITY when another operator is set.                                       */
+int fh_set_identity(fh_ctx* ctx, uint64_t M, uint64_t N);
+int fh_set_prox_nuclear(fh_ctx* ctx, double mu, int objective);
+/* read-only: the geometry of the thresholding's launches (csrc/fh_host_launch.h: nuc_shape_for, the ONE rule the launchers call).
+ * out[FH_NUCLEAR_SHAPE_LEN]: [0] transposed (M > N), [1] p, [2] q, [3] Bk, [4] P (p padded to a multiple of Bk), [5] nb = P / Bk, [6] steps per
+ * sweep, [7] workgroups per step (the bye's included), [8] column chunk of the Gram pass, [9] chunks per row, [10] leading dimension of the working
+ * buffer [ W | J^T ] in doubles, [11] its bytes, [12] static LDS bytes of the step kernel.  fh_nuclear_shape reads the context (FH_E_STATE unless it
+ * holds the identity operator with FH_PROX_NUCLEAR); fh_nuclear_shape_for is the same rule as a pure host function (block_rows: 0 = auto = 1).           */
+#define FH_NUCLEAR_SHAPE_LEN 13
+int fh_nuclear_shape(fh_ctx* ctx, uint64_t* out);
+int fh_nuclear_shape_for(uint64_t M, uint64_t N, int block_rows, int ncu, uint64_t* out);
+/* the latest thresholding of this context: out[4] = { sweeps, steps launched, rotations, rank kept }                                             */
+int fh_nuclear_info(fh_ctx* ctx, uint64_t* out);
 
 /* ---- quadratic smooth term on an explicit symmetric matrix: f(X) = .5 <X, Q X> + <C, X>, A = identity (csrc/fh_quad.h) -----------------------
  * examples/max_norm.py:49-50 (Q = S + S^T, C = 0, X of shape (N, K)) and the dual of examples/svm.py:68-69 (Q = (l l^T) o (D D^T), C = -1, the box
