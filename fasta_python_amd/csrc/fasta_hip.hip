@@ -21,6 +21,7 @@
 #include "fh_bilinear.h"
 #include "fh_sparse.h"
 #include "fh_spmulti.h"
+#include "fh_softmax.h"
 #include "fh_tv.h"
 #include "fh_tv3d.h"
 #include "fh_dct.h"
@@ -126,6 +127,9 @@ SPMC_FOR_EACH_LB(SPMC_INSTANTIATE_LB)
 #define SPMC_INSTANTIATE(G, LB) SPMC_KERNELS(template, G, LB)
 SPMC_FOR_EACH(SPMC_INSTANTIATE)
 #undef SPMC_INSTANTIATE
+#define SM_INSTANTIATE(LB) SM_KERNELS(template, LB)
+SM_FOR_EACH_LB(SM_INSTANTIATE)
+#undef SM_INSTANTIATE
 TV3_KERNELS(template)
 #define DCT_INSTANTIATE(LDSN) DCT_KERNELS(template, LDSN)
 DCT_FOR_EACH(DCT_INSTANTIATE)
@@ -852,7 +856,7 @@ extern "C" int fh_set_rhs(fh_ctx* c, uint32_t L) {
   if (c->op == OP_BILINEAR) return fail(FH_E_STATE, "fh_set_rhs: the column count of a bilinear operator is fixed when it is set (fh_set_factorization)");
   if (c->op != OP_DENSE) return fail(FH_E_STATE, "fh_set_rhs: the stencil operator has no multi-column form");
   if (c->f32) return fail(FH_E_STATE, "fh_set_rhs: float32 storage of A has no multi-column form");
-  if (L && c->has_b && c->loss_kind != LOSS_LSQ) return fail(FH_E_STATE, "fh_set_rhs: the logistic loss has no multi-column form");
+  if (L && c->has_b && c->loss_kind == LOSS_LOGISTIC) return fail(FH_E_STATE, "fh_set_rhs: the logistic loss has no multi-column form");
   if (L && !mc_prox_ok(c->prox_kind)) return fail(FH_E_STATE, "fh_set_rhs: prox kind %d (LINF / L1BALL / TVBALL) has no multi-column form", c->prox_kind);
   const uint32_t LB = L == 0 ? 0u : (L <= 2 ? 2u : (L <= 4 ? 4u : (L <= 8 ? 8u : 16u)));
   FH_TRY(use_device(c));
@@ -1004,6 +1008,36 @@ extern "C" int fh_set_loss_logistic(fh_ctx* c, const double* labels, uint64_t le
   if (labels) for (uint64_t i = 0; i < len; ++i)
     if (labels[i] != 1.0 && labels[i] != -1.0) return fail(FH_E_ARG, "logistic labels must be -1 or +1 (entry %llu is %g)", (unsigned long long)i, labels[i]);
   return set_loss(c, LOSS_LOGISTIC, labels, len);
+}
+
+// the softmax loss over the L columns of a matrix unknown (csrc/fh_softmax.h): B becomes the one-hot matrix of the labels
+extern "C" int fh_set_loss_softmax(fh_ctx* c, const int32_t* labels, uint64_t m) {
+  if (!c || !labels) return fail(FH_E_ARG, "fh_set_loss_softmax: null argument");
+  if (c->pending_step) return fail(FH_E_STATE, "a step issued by fh_step_begin is still in flight on this context: call fh_step_end first");
+  if (c->op == OP_NONE) return fail(FH_E_STATE, "set the operator before the loss");
+  if (!c->shards.empty() || c->owner || c->comm) return fail(FH_E_STATE, "fh_set_loss_softmax: a multi-device or row-sharded context has no multi-column form, which the softmax loss needs");
+  if (c->op != OP_DENSE && c->op != OP_SPARSE)
+    return fail(FH_E_STATE, "fh_set_loss_softmax: the softmax loss is implemented for the dense and the sparse operator in multi-column form only "
+                            "(fh_set_matrix + fh_set_rhs, or fh_set_matrix_csr_rhs), not for the stencil, DCT, identity, quadratic or bilinear operators");
+  if (!c->LB) return fail(FH_E_STATE, "fh_set_loss_softmax: the softmax loss needs the multi-column form, one column of the unknown per class: call fh_set_rhs (dense operator) "
+                                      "or fh_set_matrix_csr_rhs (sparse operator) with L >= 2 first (two classes on a vector unknown: fh_set_loss_logistic)");
+  if (c->L < 2) return fail(FH_E_STATE, "fh_set_loss_softmax: the softmax loss needs at least two columns (classes), the context has L = %u", c->L);
+  if (m != c->m) return fail(FH_E_ARG, "fh_set_loss_softmax: labels has %llu entries, operator has %llu rows", (unsigned long long)m, (unsigned long long)c->m);
+  for (uint64_t i = 0; i < m; ++i)
+    if (labels[i] < 0 || (uint32_t)labels[i] >= c->L)
+      return fail(FH_E_ARG, "fh_set_loss_softmax: labels must be in [0, %u) (entry %llu is %d)", c->L, (unsigned long long)i, (int)labels[i]);
+  std::vector<double> onehot((size_t)m * c->L, 0.0);
+  for (uint64_t i = 0; i < m; ++i) onehot[(size_t)i * c->L + (size_t)labels[i]] = 1.0;
+  FH_TRY(use_device(c));
+  if (c->op == OP_DENSE) {             // the residual the row kernel hands to K-adj: (mv, LB), padding rows zero for good (the sparse operator owns one already)
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (c->sp_r) { HIP_TRY(hipFree(c->sp_r)); c->sp_r = nullptr; }
+    FH_TRY(alloc_zero(c, &c->sp_r, c->mv * lb_of(c) + 16));
+  }
+  FH_TRY(copy_in(c, c->b, onehot.data(), c->m));
+  c->has_b = true;
+  c->loss_kind = LOSS_SOFTMAX;
+  return finish(c);
 }
 
 extern "C" int fh_set_prox_nuclear(fh_ctx* c, double mu, int objective);

@@ -239,23 +239,54 @@ extern "C" int fh_multi_shape_for(uint64_t m, uint64_t n, uint32_t L, int slab_r
   return 0;
 }
 
+// ---- softmax loss on a matrix unknown (fh_set_loss_softmax; row kernel in csrc/fh_softmax.h, instantiated by fh_softmax_part.hip) -----------
+#ifndef FH_SINGLE_TU
+#define SM_DECLARE(LB) SM_KERNELS(extern template, LB)
+SM_FOR_EACH_LB(SM_DECLARE)
+#undef SM_DECLARE
+#endif
+struct SmEntry { int lb; void (*rows)(const SmRowsP); };
+#define SM_ROW(LB) {LB, k_sm_rows<LB>},
+static const SmEntry kSmTable[] = { SM_FOR_EACH_LB(SM_ROW) };
+#undef SM_ROW
+// does this launch evaluate the softmax loss?  (sub_b = 0 is the plain operator: fh_apply)
+static inline bool sm_on(const fh_ctx* c, int sub_b) { return sub_b && c->loss_kind == LOSS_SOFTMAX; }
+static inline uint32_t sm_records(const fh_ctx* c) { return (uint32_t)((c->m * (uint64_t)(c->LB / 2) + FH_WG - 1) / FH_WG); }
+// the row pass over Z' (Z, or its extrapolation): residual into `r` (nullptr: value only), sm_records(c) loss records into `red_f`.
+// finalise: its last workgroup adds the records into out[slot] and publishes `seq`; otherwise the caller's next launch consumes them.
+static int launch_sm_rows(fh_ctx* c, const double* z, const double* zacc0, int accel, double coef, double* r, double* red_f,
+                          bool finalise, int slot, unsigned seq) {
+  const SmEntry* e = nullptr;
+  for (const SmEntry& k : kSmTable) if ((uint32_t)k.lb == c->LB) e = &k;
+  if (!e) return fail(FH_E_STATE, "softmax loss: no kernel for %u columns per row", c->LB);
+  SmRowsP q;
+  q.m = (uint32_t)c->m; q.L = c->L; q.z = z; q.zacc0 = zacc0; q.b = c->b; q.r = r;
+  q.accel = accel; q.coef = coef; q.red_f = red_f;
+  q.counter = finalise ? c->counters + CNT_AUX : nullptr;
+  q.out = scalar_out(c); q.slot = slot; q.seq = seq;
+  e->rows<<<dim3(sm_records(c)), dim3(FH_WG), 0, c->stream>>>(q);
+  return 0;
+}
+static inline bool loss_has_multi_form(int kind) { return kind == LOSS_LSQ || kind == LOSS_SOFTMAX; }
+
 // Z := A * (mode 0: prox(X0 - tau G0), by the prologue launch ; mode 1: X0) for LB columns from one read of A
 static int launch_fwd_multi(fh_ctx* c, int mode, double tau, const double* x0, const double* g0, const double* xacc0,
                             double* xhat, double* xp, double* z, int sub_b) {
   const McShape sh = mc_shape(c);
   const McEntry* e = sh.e;
   if (!e) return fail(FH_E_STATE, "multi-column form: no kernel for %u columns per row", c->LB);
-  if (c->loss_kind != LOSS_LSQ) return fail(FH_E_STATE, "the multi-column form serves the least-squares loss only");
+  if (!loss_has_multi_form(c->loss_kind)) return fail(FH_E_STATE, "the multi-column form serves the least-squares loss only");
   if (mode == 0 && !mc_prox_ok(c->prox_kind)) return fail(FH_E_STATE, "prox kind %d has no multi-column form", c->prox_kind);
+  const bool sm = sm_on(c, sub_b);                // K-fwd's sum of squares means nothing then: the row pass behind it writes FH_S_FSQ and publishes
   McFwdP p;
   p.A = c->A; p.ld2 = sh.ld2; p.m = (uint32_t)c->m; p.L = c->L;
   p.nrg = sh.nrg;
   const uint32_t npro = mode == 0 ? sh.npro : 0u;
   p.nred_n = npro;
   const unsigned grid = sh.fwd_grid;
-  FH_TRY(ensure_ws(c, ((size_t)npro * 8 + grid) * sizeof(double)));
+  FH_TRY(ensure_ws(c, ((size_t)npro * 8 + grid + (sm ? sm_records(c) : 0u)) * sizeof(double)));
   p.red_n = c->ws; p.red_m = c->ws + (size_t)npro * 8;
-  p.x = c->xs;                       // the operand in K-fwd's streaming layout: written by the prologue, or packed from a plain operand below
+  p.x = c->xs;                      // the operand in K-fwd's streaming layout: written by the prologue, or packed from a plain operand below
   p.b = c->b; p.z = z; p.sub_b = sub_b;
   p.counter = c->counters + CNT_FWD;
   p.out = scalar_out(c);
@@ -271,8 +302,9 @@ static int launch_fwd_multi(fh_ctx* c, int mode, double tau, const double* x0, c
   } else {
     e->pack<<<dim3(sh.npro), dim3(FH_WG), 0, c->stream>>>(x0, c->xs, (uint32_t)c->nv, p.ld2);
   }
-  p.seq = seq_offer(c);
+  p.seq = sm ? 0u : seq_offer(c);
   e->fwd[sh.nt]<<<dim3(grid), dim3(FH_WG), 0, c->stream>>>(p);
+  if (sm) FH_TRY(launch_sm_rows(c, z, nullptr, 0, 0.0, nullptr, p.red_m + grid, true, FH_S_FSQ, seq_offer(c)));
   t_end(c, FH_K_FWD);
   HIP_TRY(hipGetLastError());
   return 0;
@@ -355,8 +387,10 @@ static int launch_adj_multi(fh_ctx* c, const AdjIO& io) {
   const McShape sh = mc_shape(c);
   const McEntry* e = sh.e;
   if (!e) return fail(FH_E_STATE, "multi-column form: no kernel for %u columns per row", c->LB);
-  if (io.sub_b && c->loss_kind != LOSS_LSQ) return fail(FH_E_STATE, "the multi-column form serves the least-squares loss only");
+  if (io.sub_b && !loss_has_multi_form(c->loss_kind)) return fail(FH_E_STATE, "the multi-column form serves the least-squares loss only");
   if (io.mode != 0 && io.mode != 1) return fail(FH_E_STATE, "the multi-column form has no row-sharded adjoint");
+  const bool sm = sm_on(c, io.sub_b);
+  if (sm && !c->sp_r) return fail(FH_E_STATE, "softmax loss: the residual buffer is missing (call fh_set_loss_softmax after fh_set_rhs)");
   McAdjP p;
   p.A = c->A; p.ld2 = sh.ld2; p.n = (uint32_t)c->n; p.L = c->L; p.mp = (uint32_t)c->mp; p.m = (uint32_t)c->m;
   p.ncc = sh.ncc;
@@ -368,14 +402,27 @@ static int launch_adj_multi(fh_ctx* c, const AdjIO& io) {
   p.x0 = io.x0; p.xp = io.xp; p.xacc0 = io.xacc0; p.xhat = io.xhat; p.x1 = io.x1; p.g1 = io.g1;
   const size_t gpart_elems = (size_t)p.nslab * c->ld * c->LB;
   if ((uint64_t)c->ld * c->LB / 2 >= ((uint64_t)1 << 27)) return fail(FH_E_ARG, "multi-column K-adj: n * LB too large for one slab partial");
-  FH_TRY(ensure_ws(c, (gpart_elems + (size_t)p.ncc * 8 + p.nslab) * sizeof(double)));
+  FH_TRY(ensure_ws(c, (gpart_elems + (size_t)p.ncc * 8 + p.nslab + (sm ? sm_records(c) : 0u)) * sizeof(double)));
   p.gpart = c->ws; p.red_bb = c->ws + gpart_elems; p.red_f = p.red_bb + (size_t)p.ncc * 8;
+  double* sm_red = p.red_f + p.nslab;
   p.cc_counter = c->counters + CNT_ADJ_CC; p.fin_counter = c->counters + CNT_ADJ_FIN;
   p.out = scalar_out(c);
   const unsigned grid = p.ncc * p.nslab;
   t_begin(c, FH_K_ADJ);
-  p.seq = io.mode == 0 ? seq_offer(c) : 0u;
-  e->adj[sh.nt]<<<dim3(grid), dim3(FH_WG), 0, c->stream>>>(p);
+  if (sm) {
+    // The row pass forms the residual R = softmax(Z') - Y at the (extrapolated) Z' and the loss records; K-adj then takes R as a residual that is
+    // already formed: no right-hand side (sub_b = 0), and R as its own extrapolation partner -- extrapolate(R, R, coef) = R + coef * (R - R) is R
+    // exactly for finite R and coef -- so its code is the least-squares launch's, instruction for instruction.  Its sum of squares of R in
+    // FH_S_FSQ_ADJ means nothing: it publishes no sequence number, and the one-workgroup launch behind it writes the loss there and publishes.
+    FH_TRY(launch_sm_rows(c, io.z, io.zacc0, io.accel, io.coef, c->sp_r, sm_red, false, 0, 0u));
+    p.z = c->sp_r; p.zacc0 = c->sp_r; p.sub_b = 0;
+    p.seq = 0u;
+    e->adj[sh.nt]<<<dim3(grid), dim3(FH_WG), 0, c->stream>>>(p);
+    k_sm_finish<<<dim3(1), dim3(FH_WG), 0, c->stream>>>(sm_red, sm_records(c), p.out, FH_S_FSQ_ADJ, io.mode == 0 ? seq_offer(c) : 0u);
+  } else {
+    p.seq = io.mode == 0 ? seq_offer(c) : 0u;
+    e->adj[sh.nt]<<<dim3(grid), dim3(FH_WG), 0, c->stream>>>(p);
+  }
   t_end(c, FH_K_ADJ);
   HIP_TRY(hipGetLastError());
   return 0;
@@ -785,14 +832,15 @@ static int launch_fwd_spmulti(fh_ctx* c, int mode, double tau, const double* x0,
   const SpmcEntry* e = spmc_entry(c, 0);
   const SpmcLbEntry* lbe = spmc_lb_entry(c);
   if (!e || !lbe) return fail(FH_E_STATE, "sparse multi-column form: no kernel for %d lanes per row at %u columns per row", c->sp_G[0], c->LB);
-  if (c->loss_kind != LOSS_LSQ) return fail(FH_E_STATE, "the multi-column form serves the least-squares loss only");
+  if (!loss_has_multi_form(c->loss_kind)) return fail(FH_E_STATE, "the multi-column form serves the least-squares loss only");
   if (mode == 0 && !mc_prox_ok(c->prox_kind)) return fail(FH_E_STATE, "prox kind %d has no multi-column form", c->prox_kind);
+  const bool sm = sm_on(c, sub_b);                // as launch_fwd_multi: the row pass behind K-fwd writes FH_S_FSQ and publishes
   SpmcFwdP p;
   p.a = c->sp[0]; p.m = (uint32_t)c->m; p.L = c->L;
   const uint32_t npro = mode == 0 ? (uint32_t)((c->nv + FH_WG - 1) / FH_WG) : 0u;
   p.nred_n = npro;
   const unsigned grid = p.a.nwg + p.a.nlong;
-  FH_TRY(ensure_ws(c, ((size_t)npro * 8 + grid) * sizeof(double)));
+  FH_TRY(ensure_ws(c, ((size_t)npro * 8 + grid + (sm ? sm_records(c) : 0u)) * sizeof(double)));
   p.red_n = c->ws; p.red_m = c->ws + (size_t)npro * 8;
   p.x = mode == 0 ? xp : x0;
   p.b = c->b; p.z = z; p.sub_b = sub_b;
@@ -807,8 +855,9 @@ static int launch_fwd_spmulti(fh_ctx* c, int mode, double tau, const double* x0,
     q.red_n = c->ws;
     lbe->pro<<<dim3(npro), dim3(FH_WG), 0, c->stream>>>(q);
   }
-  p.seq = seq_offer(c);
+  p.seq = sm ? 0u : seq_offer(c);
   e->fwd[sp_nt_for(c) ? 1 : 0]<<<dim3(grid), dim3(FH_WG), 0, c->stream>>>(p);
+  if (sm) FH_TRY(launch_sm_rows(c, z, nullptr, 0, 0.0, nullptr, p.red_m + grid, true, FH_S_FSQ, seq_offer(c)));
   t_end(c, FH_K_FWD);
   HIP_TRY(hipGetLastError());
   return 0;
@@ -819,7 +868,7 @@ static int launch_adj_spmulti(fh_ctx* c, const AdjIO& io) {
   const SpmcEntry* e = spmc_entry(c, 1);
   const SpmcLbEntry* lbe = spmc_lb_entry(c);
   if (!e || !lbe) return fail(FH_E_STATE, "sparse multi-column form: no kernel for %d lanes per row at %u columns per row", c->sp_G[1], c->LB);
-  if (io.sub_b && c->loss_kind != LOSS_LSQ) return fail(FH_E_STATE, "the multi-column form serves the least-squares loss only");
+  if (io.sub_b && !loss_has_multi_form(c->loss_kind)) return fail(FH_E_STATE, "the multi-column form serves the least-squares loss only");
   if (io.mode != 0 && io.mode != 1) return fail(FH_E_STATE, "the sparse operator has no row-sharded adjoint");
   SpmcAdjP p;
   p.a = c->sp[1]; p.n = (uint32_t)c->n; p.L = c->L;
@@ -839,7 +888,8 @@ static int launch_adj_spmulti(fh_ctx* c, const AdjIO& io) {
   q.sub_b = io.sub_b; q.accel = io.accel; q.coef = io.coef;
   q.red_f = c->ws;
   t_begin(c, FH_K_ADJ);
-  lbe->resid<<<dim3(nres), dim3(FH_WG), 0, c->stream>>>(q);
+  if (sm_on(c, io.sub_b)) FH_TRY(launch_sm_rows(c, io.z, io.zacc0, io.accel, io.coef, c->sp_r, c->ws, false, 0, 0u));   // the same contract (sp_r, red_f; nres = sm_records)
+  else lbe->resid<<<dim3(nres), dim3(FH_WG), 0, c->stream>>>(q);
   p.seq = io.mode == 0 ? seq_offer(c) : 0u;
   e->adj[sp_nt_for(c) ? 1 : 0]<<<dim3(grid), dim3(FH_WG), 0, c->stream>>>(p);
   t_end(c, FH_K_ADJ);

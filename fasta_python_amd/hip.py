@@ -113,6 +113,7 @@ SIGNATURES = {
     "fh_multi_shape_for": (_i32, [_u64, _u64, C.c_uint32, _i32, C.c_longlong, _i32, C.POINTER(C.c_uint32)]),
     "fh_set_loss_lsq": (_i32, [_ctx, _pd, _u64]),
     "fh_set_loss_logistic": (_i32, [_ctx, _pd, _u64]),
+    "fh_set_loss_softmax": (_i32, [_ctx, C.POINTER(C.c_int32), _u64]),
     "fh_set_prox": (_i32, [_ctx, _i32, _dbl, _dbl, _dbl]),
     "fh_set_vector": (_i32, [_ctx, _i32, _pd, _u64]),
     "fh_get_vector": (_i32, [_ctx, _i32, _pd, _u64]),
@@ -667,6 +668,17 @@ class HipContext:
     def set_loss_logistic(self, labels):
         labels, p = _as_f64(np.ravel(labels))
         self._call("fh_set_loss_logistic", p, labels.size)
+
+    def set_loss_softmax(self, labels):
+        """Softmax loss over the L columns of a matrix unknown (csrc/fh_softmax.h): integer class labels in [0, L), one per row of the operator.
+        The context must be in multi-column form with L >= 2 (set_rhs on a dense operator, or a sparse operator set with rhs=L)."""
+        raw = np.asarray(labels)
+        if raw.dtype.kind not in "iu":
+            raise ValueError(f"softmax labels must be integers (got dtype {raw.dtype})")
+        if raw.size and (raw.min() < -2**31 or raw.max() >= 2**31):
+            raise ValueError("softmax labels do not fit 32 bits")
+        lab = np.ascontiguousarray(np.ravel(raw), dtype=np.int32)
+        self._call("fh_set_loss_softmax", lab.ctypes.data_as(C.POINTER(C.c_int32)), lab.size)
 
     def set_prox(self, kind, mu=0.0, lo=0.0, hi=0.0):
         self._call("fh_set_prox", int(kind), float(mu), float(lo), float(hi))

@@ -1,6 +1,6 @@
 """Smooth terms f(z) recognised by the device loop.
 
-LogisticLoss(b), Quadratic(Q, c), Factorization(S): see the classes.  LeastSquares(b):  f(z) = .5*||z - b||^2,  gradf(z) = z - b   (examples/sparse_least_squares.py:41-42,
+LogisticLoss(b), SoftmaxLoss(y), Quadratic(Q, c), Factorization(S): see the classes.  LeastSquares(b):  f(z) = .5*||z - b||^2,  gradf(z) = z - b   (examples/sparse_least_squares.py:41-42,
 same closures in lasso.py:42-43, nn_least_squares.py:39-40, tv_denoising.py:85-86 with b = M/mu).
 Pass `ls.f` and `ls.gradf` as the `f` / `gradf` arguments of `fasta()`.
 """
@@ -9,7 +9,7 @@ import math
 
 import numpy as np
 
-__all__ = ["LeastSquares", "LogisticLoss", "Quadratic", "Factorization"]
+__all__ = ["LeastSquares", "LogisticLoss", "SoftmaxLoss", "Quadratic", "Factorization"]
 
 
 class LeastSquares:
@@ -54,6 +54,71 @@ class LogisticLoss:
 
     def gradf(self, z):
         return -self.b / (1 + np.exp(self.b * z))
+
+    __call__ = f
+
+
+class SoftmaxLoss:
+    """Multinomial logistic loss over a MATRIX unknown: Z = A X is (m, L), one column per class, y integer labels in {0 .. L-1}^m,
+    f(Z) = sum_i [logsumexp(Z_i,:) - Z_i,y_i], gradf(Z) = softmax(Z) - Y with Y the one-hot matrix of y.  With proximal.Shrink: sparse
+    weights; with proximal.GroupShrink: a feature kept or dropped for all classes at once (the "grouped" multinomial of glmnet).
+    On the device a dense or sparse operator in its matrix form serves it (csrc/fh_softmax.h); 2 to 16 classes.
+
+    The arithmetic of a row z is fixed, the same here and in the kernel: mx = max_l z_l, e_l = exp(z_l - mx), s = e_0 + e_1 + ... + e_{L-1}
+    with the columns added in index order, term = (mx + log(s)) - z_y, grad_l = e_l / s - Y_l.  The maximum is always subtracted, so
+    z = (800, -800) gives (1, 0) and a finite loss.  (The row sums are formed column by column and not by `.sum(axis=1)`, whose
+    pairwise blocks add eight or more columns in another order.)"""
+
+    MAX_CLASSES = 16
+
+    def __init__(self, y, classes=None):
+        raw = np.asarray(y)
+        if raw.ndim != 1 or raw.size == 0:
+            raise ValueError(f"SoftmaxLoss needs a non-empty 1-D array of integer class labels (got shape {raw.shape})")
+        if raw.dtype.kind not in "iu":
+            raise ValueError(f"SoftmaxLoss needs integer class labels (got dtype {raw.dtype})")
+        if int(raw.min()) < 0:
+            raise ValueError(f"SoftmaxLoss labels must be >= 0 (entry {int(np.argmax(raw < 0))} is {int(raw.min())})")
+        top = int(raw.max())
+        if classes is None:
+            classes = top + 1
+        classes = int(classes)
+        if not 2 <= classes <= self.MAX_CLASSES:
+            raise ValueError(f"SoftmaxLoss serves 2 to {self.MAX_CLASSES} classes (got {classes})")
+        if top >= classes:
+            raise ValueError(f"SoftmaxLoss labels must be below classes = {classes} (entry {int(np.argmax(raw >= classes))} is {top})")
+        self.y = np.ascontiguousarray(raw, dtype=np.int64)
+        self.classes = classes
+        self._rows = np.arange(self.y.size)
+        self.Y = np.zeros((self.y.size, classes))
+        self.Y[self._rows, self.y] = 1.0
+        self.b = self.Y                         # what the device holds in FH_VEC_B: the shape the solver checks against the operator
+
+    def bind(self, ctx):
+        ctx.set_loss_softmax(self.y)
+
+    @staticmethod
+    def f_from_device(s):
+        return np.float64(s)                    # FH_S_FSQ carries f itself
+
+    def _rows_of(self, Z):
+        Z = np.asarray(Z, dtype=np.float64)
+        if Z.shape != self.Y.shape:
+            raise ValueError(f"SoftmaxLoss: Z has shape {Z.shape}, the labels need {self.Y.shape}")
+        mx = Z.max(axis=1)
+        E = np.exp(Z - mx[:, np.newaxis])
+        s = E[:, 0].copy()
+        for l in range(1, self.classes):        # columns in index order
+            s += E[:, l]
+        return Z, mx, E, s
+
+    def f(self, Z):
+        Z, mx, _, s = self._rows_of(Z)
+        return np.sum((mx + np.log(s)) - Z[self._rows, self.y])
+
+    def gradf(self, Z):
+        _, _, E, s = self._rows_of(Z)
+        return E / s[:, np.newaxis] - self.Y
 
     __call__ = f
 

@@ -31,7 +31,7 @@ import numpy as np
 
 from . import hip, stopping
 from .linalg import BilinearMap, DCTMap, DenseMatrixMap, GradDivMap, IdentityMap, LinearMap, QuadraticMap, SparseMatrixMap, _DeviceMap, is_sparse_matrix
-from .losses import Factorization, LeastSquares, LogisticLoss, Quadratic
+from .losses import Factorization, LeastSquares, LogisticLoss, Quadratic, SoftmaxLoss
 from .proximal import NoProx, NuclearShrink, ProxTag
 
 __all__ = ["fasta", "Convergence", "FBSolver", "EPSILON"]
@@ -199,6 +199,53 @@ def _factorization_form_refusal(A, At, loss_f, loss_g, g, proxg, x0):
     return None
 
 
+def _softmax_form_refusal(A, At, loss_f, loss_g, g, proxg, x0):
+    """`fasta(A, At, sm.f, sm.gradf, g, prox, X0)` with sm = losses.SoftmaxLoss(y): the device serves it over a matrix unknown (n, L), L = sm.classes,
+    on a dense operator (a 2-D ndarray, DenseMatrixMap(A, rhs=L)) or SparseMatrixMap(S, rhs=L), with Shrink, NonNeg, Box, GroupShrink or no prox
+    (csrc/fh_softmax.h).  None, or the reason -- every sentence names SoftmaxLoss, except the raw scipy.sparse matrix with a 2-D x0, which keeps its own."""
+    from .linalg import ShardedDenseMatrixMap
+    from .proximal import Box, GroupShrink, NonNeg, Shrink
+    if loss_f is None or loss_f is not loss_g:
+        return "f and gradf must be the `.f` / `.gradf` of one losses.SoftmaxLoss(y) object"
+    if A is None or isinstance(A, IdentityMap):
+        return ("losses.SoftmaxLoss is not implemented for the identity operator (A=None / linalg.IdentityMap) on the device: "
+                "it is served by a dense or a sparse matrix operator over a matrix unknown (n, L)")
+    if isinstance(A, DCTMap):
+        return "losses.SoftmaxLoss is not implemented for a DCT operator on the device: least squares only"
+    if isinstance(A, GradDivMap):
+        return "losses.SoftmaxLoss is not implemented for a stencil (GradDivMap) operator on the device: least squares only"
+    if not isinstance(A, (np.ndarray, DenseMatrixMap, SparseMatrixMap)) and not is_sparse_matrix(A):
+        return ("losses.SoftmaxLoss: operator A is not device-resident (pass a 2-D float64 ndarray, a linalg.DenseMatrixMap(A, rhs=L) or a "
+                "linalg.SparseMatrixMap(S, rhs=L)); arbitrary Python callables cannot run inside the fused HIP kernels")
+    prox = None
+    if not (g is None and proxg is None):
+        prox, owner_g = _tag_of(proxg, ProxTag), _tag_of(g, ProxTag)
+        if prox is None or (owner_g is not None and owner_g is not prox) or (owner_g is None and g is not None):
+            return ("losses.SoftmaxLoss: g and proxg must be the `.g` / `.prox` of one proximal.* tag object "
+                    "(Shrink, NonNeg, Box, GroupShrink)")
+        if not isinstance(prox, (Shrink, NonNeg, Box, GroupShrink)) and type(prox) is not NoProx:
+            return (f"proximal.{type(prox).__name__} is not served with losses.SoftmaxLoss on the device "
+                    "(Shrink, NonNeg, Box, GroupShrink or no prox are)")
+    if is_sparse_matrix(A) and x0 is not None and np.ndim(x0) == 2:
+        return _sparse_form_refusal(A, loss_f, prox, x0)          # (its existing sentence: pass linalg.SparseMatrixMap(S, rhs=L))
+    if isinstance(A, ShardedDenseMatrixMap):
+        return "losses.SoftmaxLoss needs the matrix (multi-column) form, which a row-sharded operator does not have on the device"
+    if isinstance(A, DenseMatrixMap) and A.storage != "f64":
+        return 'losses.SoftmaxLoss needs the matrix (multi-column) form, which storage="f32" does not have on the device'
+    L = loss_f.classes
+    if x0 is not None and np.ndim(x0) != 2:
+        return (f"losses.SoftmaxLoss needs a MATRIX unknown on the device: a 2-D x0 of shape (n, {L}), one column per class "
+                f"(x0 has shape {tuple(np.shape(x0))}); two classes over a vector unknown are losses.LogisticLoss")
+    cols = A.rhs if isinstance(A, (DenseMatrixMap, SparseMatrixMap)) else (None if x0 is None else np.shape(x0)[1])
+    if isinstance(A, (DenseMatrixMap, SparseMatrixMap)) and cols is None:
+        return (f"losses.SoftmaxLoss needs the operator in its matrix form: pass linalg.{type(A).__name__}(A, rhs={L}), "
+                "or the raw 2-D ndarray with a 2-D x0")
+    for what, have in (("the operator was built for", cols), ("x0 has", None if x0 is None else np.shape(x0)[1])):
+        if have is not None and int(have) != L:
+            return f"losses.SoftmaxLoss has {L} classes, {what} {int(have)} columns: the unknown has one column per class"
+    return None
+
+
 _NUCLEAR_ELSEWHERE = ("proximal.NuclearShrink is served on the device by the identity operator only: fasta(None, None, loss.f, loss.gradf, reg.g, reg.prox, X0) "
                       "with loss = losses.LogisticLoss(B) or losses.LeastSquares(B) and a 2-D X0 of B's shape")
 
@@ -245,6 +292,9 @@ def _unrecognised(A, At, f, gradf, g, proxg, x0=None):
         if isinstance(_tag_of(proxg, ProxTag), NuclearShrink):
             return _NUCLEAR_ELSEWHERE
         return _quadratic_form_refusal(A, At, quad_f, quad_g, g, proxg, x0)
+    sm_f, sm_g = _tag_of(f, SoftmaxLoss), _tag_of(gradf, SoftmaxLoss)
+    if sm_f is not None or sm_g is not None:
+        return _softmax_form_refusal(A, At, sm_f, sm_g, g, proxg, x0)
     # A = None with the `.f` / `.gradf` of ONE elementwise loss tag, or an explicit IdentityMap: the identity operator (csrc/fh_nuclear.h).
     # Every other call with A = None keeps the answer below.
     loss_f, loss_g = _tag_of(f, (LeastSquares, LogisticLoss)), _tag_of(gradf, (LeastSquares, LogisticLoss))
@@ -297,7 +347,7 @@ def _recognise(A, At, f, gradf, g, proxg, x0):
         if At is not None and hasattr(At, "shape") and tuple(At.shape) != tuple(A.shape)[::-1]:
             raise AssertionError("At must have the transposed shape of A")
         A = SparseMatrixMap(A)
-    loss_f = _tag_of(f, (LeastSquares, LogisticLoss))
+    loss_f = _tag_of(f, (LeastSquares, LogisticLoss, SoftmaxLoss))
     prox = NoProx() if (g is None and proxg is None) else _tag_of(proxg, ProxTag)      # :88-90
     if tuple(x0.shape) != A.Vshape:
         raise AssertionError(f"x0 has shape {x0.shape}, operator expects {A.Vshape}")   # linalg.py:58

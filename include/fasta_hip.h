@@ -416,6 +416,18 @@ int fh_set_loss_lsq(fh_ctx* ctx, const double* b, uint64_t len);
 /* ---- smooth term f(z) = sum log(1+exp(z)) - (b==1)*z, grad f(z) = -b/(1+exp(b*z)), labels b in {-1,+1}
  *      (examples/sparse_logistic.py:47-48); FH_S_FSQ / FH_S_FSQ_ADJ then carry f itself. Dense and sparse operators.   */
 int fh_set_loss_logistic(fh_ctx* ctx, const double* labels, uint64_t len);
+/* ---- smooth term f(Z) = sum_i [ logsumexp(Z_i,:) - Z_i,y_i ] over the L columns of a MATRIX unknown (multinomial logistic regression, one column of
+ *      X per class), grad f(Z)_i,l = exp(Z_i,l) / sum_k exp(Z_i,k) - [l == y_i]; labels y in {0 .. L-1}^m (csrc/fh_softmax.h).  The arithmetic of a row z:
+ *      mx = max_l z_l, e_l = exp(z_l - mx), s = e_0 + e_1 + ... + e_{L-1} in index order, term = (mx + log(s)) - z_y, grad_l = e_l / s - Y_l: the maximum
+ *      is always subtracted, so z = (800, -800) gives (1, 0) and a finite loss.  Needs the multi-column form with L >= 2: fh_set_rhs on a dense operator, or
+ *      fh_set_matrix_csr_rhs.  FH_VEC_B then holds the one-hot matrix Y (m, L); FH_S_FSQ / FH_S_FSQ_ADJ carry f itself.  Each direction is the
+ *      least-squares multi-column launch plus one short row pass over Z (the dense adjoint: plus a one-workgroup launch that writes FH_S_FSQ_ADJ).
+ *      Served: fh_init, fh_setup (its three-pass route), fh_gradient_at, fh_apply (the plain operator), fh_fwd, fh_adj (accel / coef), fh_fwd_adj,
+ *      fh_iterate, fh_commit; the prox kinds of the multi-column form (IDENTITY, SHRINK, NONNEG, BOX, GROUP).
+ *      Refused: a label outside [0, L) (FH_E_ARG, naming the first offender), m != rows of the operator (FH_E_ARG); the vector form, L = 1, every operator
+ *      other than dense and sparse in multi-column form, multi-device contexts and communicators (FH_E_STATE); fh_step* and fh_run as for every
+ *      multi-column context.  fh_set_rhs and setting an operator return the context to the least-squares loss.                          */
+int fh_set_loss_softmax(fh_ctx* ctx, const int32_t* labels, uint64_t m);
 /* ---- prox term (kinds above); mu as in the closures, lo/hi for FH_PROX_BOX only              */
 int fh_set_prox(fh_ctx* ctx, int kind, double mu, double lo, double hi);
 
