@@ -15,11 +15,11 @@ losses.LogisticLoss(B) / LeastSquares(B) and a 2-D x0 of B's shape (the identity
 """
 
 from . import generic, hip, linalg, losses, proximal, stopping
-from .linalg import BilinearMap, DCTMap, DenseMatrixMap, GradDivMap, IdentityMap, LinearMap, LinearOperator, QuadraticMap, ShardedDenseMatrixMap, SparseMatrixMap
+from .linalg import BilinearMap, ConvMap, DCTMap, DenseMatrixMap, GradDivMap, IdentityMap, LinearMap, LinearOperator, QuadraticMap, ShardedDenseMatrixMap, SparseMatrixMap
 from .losses import Factorization, LeastSquares, LogisticLoss, Quadratic, SoftmaxLoss
 from .proximal import Box, GroupShrink, L1Ball, LinfProx, NonNeg, NoProx, NuclearShrink, RowBall, RowSplit, Shrink, TVDualBall
 from .solver import EPSILON, Convergence, FBSolver, fasta
 
 __all__ = ["fasta", "Convergence", "FBSolver", "EPSILON", "linalg", "proximal", "stopping", "losses", "hip",
-           "LinearMap", "LinearOperator", "DenseMatrixMap", "ShardedDenseMatrixMap", "SparseMatrixMap", "GradDivMap", "DCTMap", "QuadraticMap", "BilinearMap", "IdentityMap", "LeastSquares", "LogisticLoss", "SoftmaxLoss", "Quadratic", "Factorization",
+           "LinearMap", "LinearOperator", "DenseMatrixMap", "ShardedDenseMatrixMap", "SparseMatrixMap", "GradDivMap", "DCTMap", "ConvMap", "QuadraticMap", "BilinearMap", "IdentityMap", "LeastSquares", "LogisticLoss", "SoftmaxLoss", "Quadratic", "Factorization",
            "Shrink", "NonNeg", "LinfProx", "L1Ball", "Box", "TVDualBall", "GroupShrink", "RowBall", "RowSplit", "NuclearShrink", "NoProx"]

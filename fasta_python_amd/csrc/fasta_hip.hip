@@ -25,6 +25,7 @@
 #include "fh_tv.h"
 #include "fh_tv3d.h"
 #include "fh_dct.h"
+#include "fh_conv.h"
 #include "fh_nuclear.h"
 #include "fh_prox.h"
 #include "fh_fused.h"
@@ -135,6 +136,7 @@ TV3_KERNELS(template)
 DCT_FOR_EACH(DCT_INSTANTIATE)
 #undef DCT_INSTANTIATE
 DCT_TILE_KERNELS(template)
+CONV_KERNELS(template)
 #endif
 
 #include "fh_host_ctx.h"
@@ -670,6 +672,7 @@ extern "C" int fh_get_matrix_rows(fh_ctx* c, uint64_t row0, uint64_t nrows, doub
   if (c->op == OP_SPARSE) return fail(FH_E_STATE, "fh_get_matrix_rows: the sparse operator keeps no dense rows");
   if (c->op == OP_STENCIL3D) return fail(FH_E_STATE, "fh_get_matrix_rows: the 3-D stencil operator keeps no dense rows");
   if (c->op == OP_DCT) return fail(FH_E_STATE, "fh_get_matrix_rows: the DCT operator keeps no dense rows");
+  if (c->op == OP_CONV) return fail(FH_E_STATE, "fh_get_matrix_rows: the convolution operator keeps no dense rows");
   if (c->op == OP_IDENTITY) return fail(FH_E_STATE, "fh_get_matrix_rows: the identity operator keeps no matrix");
   if (c->op == OP_QUAD) return fail(FH_E_STATE, "fh_get_matrix_rows: the quadratic operator is not read back (the caller holds Q)");
   if (c->op == OP_BILINEAR) return fail(FH_E_STATE, "fh_get_matrix_rows: the bilinear operator is not read back (the caller holds S)");
@@ -773,6 +776,38 @@ extern "C" int fh_set_dct(fh_ctx* c, uint64_t N, const double* diag) {
   return finish(c);
 }
 
+// the periodic convolution (csrc/fh_conv.h): A x = d * (K conv x), m = n = H * W; vectors in the vector form's padded layout, no matrix stored: the
+// taps stay on the host (they travel in every launch's argument block), d is copied to the device
+extern "C" int fh_set_conv2d(fh_ctx* c, uint64_t H, uint64_t W, uint32_t kh, uint32_t kw, uint32_t oh, uint32_t ow, const double* taps, const double* diag) {
+  if (!c) return fail(FH_E_ARG, "null context");
+  if (!c->shards.empty() || c->owner) return fail(FH_E_STATE, "fh_set_conv2d: a multi-device context has no convolution operator (row sharding is implemented for the dense operator only)");
+  if (c->comm) return fail(FH_E_STATE, "fh_set_conv2d: a context with a communicator (row-sharded run) has no convolution operator");
+  if (c->f32) return fail(FH_E_STATE, "fh_set_conv2d: float32 storage is a storage mode of a dense matrix; the convolution operator stores no matrix and computes in float64");
+  if (c->pending_step) return fail(FH_E_STATE, "a step issued by fh_step_begin is still in flight on this context: call fh_step_end first");
+  if (!taps) return fail(FH_E_ARG, "fh_set_conv2d: null taps");
+  ConvShape sh;
+  FH_TRY(conv_shape_for(H, W, kh, kw, c->ncu, &sh));      // (dimensions >= 1, 1 <= kh, kw <= 16, H * W < 2^31: FH_E_ARG with the sentence)
+  if (oh >= kh || ow >= kw) return fail(FH_E_ARG, "fh_set_conv2d: the origin (%u, %u) lies outside the %u x %u kernel", oh, ow, kh, kw);
+  FH_TRY(use_device(c));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  free_operator(c);
+  if (!conv_prox_ok(c->prox_kind)) { c->prox_kind = FH_PROX_IDENTITY; c->mu = 0.0; }
+  c->loss_kind = LOSS_LSQ; c->lazy = false; c->last_accel = false; c->commits = 0;
+  c->H = H; c->W = W;
+  c->m = c->n = H * W;
+  c->mp = c->m; c->ld = c->n;
+  c->nv = round_up(c->n, 16); c->mv = round_up(c->m, 16);
+  c->conv_kh = kh; c->conv_kw = kw; c->conv_oh = oh; c->conv_ow = ow;
+  memset(c->conv_taps, 0, sizeof(c->conv_taps));
+  memcpy(c->conv_taps, taps, (size_t)kh * kw * sizeof(double));
+  c->conv_sh = sh;
+  c->op = OP_CONV;                                        // (from here on free_operator gives the diagonal back)
+  int rc = alloc_vectors(c);
+  if (rc == 0 && diag) rc = conv_alloc_diag(c, diag);
+  if (rc != 0) { free_operator(c); return rc; }
+  return finish(c);
+}
+
 // the identity operator with an elementwise loss (csrc/fh_nuclear.h): the unknown is an (M, N) matrix in the vector form's buffers, m = n = M * N;
 // nothing is stored for the operator itself
 extern "C" int fh_set_identity(fh_ctx* c, uint64_t M, uint64_t N) {
@@ -851,6 +886,7 @@ extern "C" int fh_set_rhs(fh_ctx* c, uint32_t L) {
   if (c->op == OP_SPARSE) return fail(FH_E_STATE, "fh_set_rhs: the sparse operator has no multi-column form through fh_set_rhs: its column count is fixed when it is set (fh_set_matrix_csr_rhs)");
   if (c->op == OP_STENCIL3D) return fail(FH_E_STATE, "fh_set_rhs: the 3-D stencil operator has no multi-column form");
   if (c->op == OP_DCT) return fail(FH_E_STATE, "fh_set_rhs: the DCT operator has no multi-column form");
+  if (c->op == OP_CONV) return fail(FH_E_STATE, "fh_set_rhs: the convolution operator has no multi-column form");
   if (c->op == OP_IDENTITY) return fail(FH_E_STATE, "fh_set_rhs: the identity operator has no multi-column form (its unknown is already an (M, N) matrix: fh_set_identity)");
   if (c->op == OP_QUAD) return fail(FH_E_STATE, "fh_set_rhs: the column count of a quadratic operator is fixed when it is set (fh_set_quadratic)");
   if (c->op == OP_BILINEAR) return fail(FH_E_STATE, "fh_set_rhs: the column count of a bilinear operator is fixed when it is set (fh_set_factorization)");
@@ -989,6 +1025,7 @@ static int set_loss(fh_ctx* c, int kind, const double* b, uint64_t len) {
   if (kind != LOSS_LSQ && c->LB) return fail(FH_E_STATE, "the logistic loss has no multi-column form (fh_set_rhs / fh_set_matrix_csr_rhs)");
   if (kind != LOSS_LSQ && c->op == OP_STENCIL3D) return fail(FH_E_STATE, "the 3-D stencil operator serves the least-squares loss only (the logistic loss is implemented for the dense and sparse operators)");
   if (kind != LOSS_LSQ && c->op == OP_DCT) return fail(FH_E_STATE, "the DCT operator serves the least-squares loss only (the logistic loss is implemented for the dense and sparse operators)");
+  if (kind != LOSS_LSQ && c->op == OP_CONV) return fail(FH_E_STATE, "the convolution operator serves the least-squares loss only (the logistic loss is implemented for the dense and sparse operators)");
   if (kind != LOSS_LSQ && c->op != OP_DENSE && c->op != OP_SPARSE && c->op != OP_IDENTITY) return fail(FH_E_STATE, "the logistic loss is implemented for the dense operator");
   if (!c->shards.empty()) {          // shell: b is sharded like the rows
     for (int k = 0; k < nshards(c); ++k) FH_TRY(set_loss(c->shards[k], kind, b + c->shard_row0[k], shard_rows(c, k)));
@@ -1018,7 +1055,7 @@ extern "C" int fh_set_loss_softmax(fh_ctx* c, const int32_t* labels, uint64_t m)
   if (!c->shards.empty() || c->owner || c->comm) return fail(FH_E_STATE, "fh_set_loss_softmax: a multi-device or row-sharded context has no multi-column form, which the softmax loss needs");
   if (c->op != OP_DENSE && c->op != OP_SPARSE)
     return fail(FH_E_STATE, "fh_set_loss_softmax: the softmax loss is implemented for the dense and the sparse operator in multi-column form only "
-                            "(fh_set_matrix + fh_set_rhs, or fh_set_matrix_csr_rhs), not for the stencil, DCT, identity, quadratic or bilinear operators");
+                            "(fh_set_matrix + fh_set_rhs, or fh_set_matrix_csr_rhs), not for the stencil, DCT, convolution, identity, quadratic or bilinear operators");
   if (!c->LB) return fail(FH_E_STATE, "fh_set_loss_softmax: the softmax loss needs the multi-column form, one column of the unknown per class: call fh_set_rhs (dense operator) "
                                       "or fh_set_matrix_csr_rhs (sparse operator) with L >= 2 first (two classes on a vector unknown: fh_set_loss_logistic)");
   if (c->L < 2) return fail(FH_E_STATE, "fh_set_loss_softmax: the softmax loss needs at least two columns (classes), the context has L = %u", c->L);
@@ -1044,6 +1081,7 @@ extern "C" int fh_set_prox_nuclear(fh_ctx* c, double mu, int objective);
 extern "C" int fh_set_prox(fh_ctx* c, int kind, double mu, double lo, double hi) {
   if (!c) return fail(FH_E_ARG, "null context");
   if (kind == FH_PROX_ROWSPLIT) return fail(FH_E_ARG, "unknown prox kind %d for fh_set_prox: FH_PROX_ROWSPLIT takes two kinds and their parameters, set it with fh_set_prox_split (bilinear operator only)", kind);
+  if (kind == FH_PROX_NUCLEAR && c->op == OP_CONV) return fail(FH_E_ARG, "prox kind %d (NUCLEAR) is not implemented for the convolution operator: it is served by the identity operator only", kind);
   if (kind == FH_PROX_NUCLEAR) return fh_set_prox_nuclear(c, mu, 1);
   if (kind < FH_PROX_IDENTITY || kind > FH_PROX_ROWBALL) return fail(FH_E_ARG, "unknown prox kind %d", kind);
   if (c->op == OP_IDENTITY && !id_prox_ok(kind)) return fail(FH_E_ARG, "prox kind %d (LINF / L1BALL / TVBALL / GROUP / ROWBALL) is not implemented for the identity operator", kind);
@@ -1055,6 +1093,7 @@ extern "C" int fh_set_prox(fh_ctx* c, int kind, double mu, double lo, double hi)
   if (c->op == OP_SPARSE && !c->LB && !sp_prox_ok(kind)) return fail(FH_E_ARG, "prox kind %d (LINF / L1BALL / TVBALL / GROUP) is not implemented for the sparse operator", kind);
   if (c->op == OP_STENCIL3D && !tv3_prox_ok(kind)) return fail(FH_E_ARG, "prox kind %d (LINF / L1BALL / GROUP) is not implemented for the 3-D stencil operator", kind);
   if (c->op == OP_DCT && !dct_prox_ok(kind)) return fail(FH_E_ARG, "prox kind %d (TVBALL / GROUP) is not implemented for the DCT operator", kind);
+  if (c->op == OP_CONV && !conv_prox_ok(kind)) return fail(FH_E_ARG, "prox kind %d (TVBALL / GROUP) is not implemented for the convolution operator", kind);
   if (kind == FH_PROX_BOX && !(lo <= hi)) return fail(FH_E_ARG, "box prox needs lo <= hi");
   for (fh_ctx* s : c->shards) { s->prox_kind = kind; s->mu = mu; s->lo = lo; s->hi = hi; }      // the prox is replicated work
   c->prox_kind = kind; c->mu = mu; c->lo = lo; c->hi = hi;
@@ -1562,6 +1601,7 @@ static int step_body(fh_ctx* c, double tau, double* scalars, bool wait) {
   if (c->op == OP_SPARSE) return fail(FH_E_STATE, "fh_step: the sparse operator has no one-pass kernel: use fh_fwd / fh_adj / fh_fwd_adj / fh_iterate");
   if (c->op == OP_STENCIL3D) return fail(FH_E_STATE, "fh_step: the 3-D stencil operator has no one-pass kernel: use fh_fwd / fh_adj / fh_fwd_adj / fh_iterate");
   if (c->op == OP_DCT) return fail(FH_E_STATE, "fh_step: the DCT operator has no one-pass kernel: use fh_fwd / fh_adj / fh_fwd_adj / fh_iterate");
+  if (c->op == OP_CONV) return fail(FH_E_STATE, "fh_step: the convolution operator has no one-pass kernel: use fh_fwd / fh_adj / fh_fwd_adj / fh_iterate");
   if (c->op == OP_IDENTITY) return fail(FH_E_STATE, "fh_step: the identity operator has no one-pass kernel: use fh_fwd / fh_adj / fh_fwd_adj / fh_iterate");
   if (c->op == OP_QUAD) return fail(FH_E_STATE, "fh_step: the quadratic operator has no one-pass kernel: use fh_fwd / fh_adj / fh_fwd_adj / fh_iterate");
   if (c->op == OP_BILINEAR) return fail(FH_E_STATE, "fh_step: the bilinear operator has no one-pass kernel: use fh_fwd / fh_adj / fh_fwd_adj / fh_iterate");
@@ -1613,6 +1653,7 @@ extern "C" int fh_step_accel(fh_ctx* c, double tau, double coef, int restart, do
   if (c->op == OP_SPARSE) return fail(FH_E_STATE, "fh_step_accel: the sparse operator has no one-pass kernel: use fh_fwd / fh_adj / fh_iterate");
   if (c->op == OP_STENCIL3D) return fail(FH_E_STATE, "fh_step_accel: the 3-D stencil operator has no one-pass kernel: use fh_fwd / fh_adj / fh_iterate");
   if (c->op == OP_DCT) return fail(FH_E_STATE, "fh_step_accel: the DCT operator has no one-pass kernel: use fh_fwd / fh_adj / fh_iterate");
+  if (c->op == OP_CONV) return fail(FH_E_STATE, "fh_step_accel: the convolution operator has no one-pass kernel: use fh_fwd / fh_adj / fh_iterate");
   if (c->op == OP_IDENTITY) return fail(FH_E_STATE, "fh_step_accel: the identity operator has no one-pass kernel: use fh_fwd / fh_adj / fh_iterate");
   if (c->op == OP_QUAD) return fail(FH_E_STATE, "fh_step_accel: the quadratic operator has no one-pass kernel: use fh_fwd / fh_adj / fh_iterate");
   if (c->op == OP_BILINEAR) return fail(FH_E_STATE, "fh_step_accel: the bilinear operator has no one-pass kernel: use fh_fwd / fh_adj / fh_iterate");
@@ -1794,6 +1835,7 @@ extern "C" int fh_run(fh_ctx* c, int max_steps, const fh_run_opts* o, fh_run_sta
   if (c->op == OP_SPARSE) return fail(FH_E_STATE, "fh_run: the sparse operator has no device-side loop: use fh_iterate");
   if (c->op == OP_STENCIL3D) return fail(FH_E_STATE, "fh_run: the 3-D stencil operator has no device-side loop: use fh_iterate");
   if (c->op == OP_DCT) return fail(FH_E_STATE, "fh_run: the DCT operator has no device-side loop: use fh_iterate");
+  if (c->op == OP_CONV) return fail(FH_E_STATE, "fh_run: the convolution operator has no device-side loop: use fh_iterate");
   if (c->op == OP_IDENTITY) return fail(FH_E_STATE, "fh_run: the identity operator has no device-side loop: use fh_iterate");
   if (c->op == OP_QUAD) return fail(FH_E_STATE, "fh_run: the quadratic operator has no device-side loop: use fh_iterate");
   if (c->op == OP_BILINEAR) return fail(FH_E_STATE, "fh_run: the bilinear operator has no device-side loop: use fh_iterate");
@@ -2027,6 +2069,7 @@ extern "C" int fh_comm_init(fh_ctx* c, int nranks, int rank, const void* id128) 
   if (c->op == OP_SPARSE) return fail(FH_E_STATE, "fh_comm_init: a context with a sparse operator cannot be row-sharded");
   if (c->op == OP_STENCIL3D) return fail(FH_E_STATE, "fh_comm_init: a context with a 3-D stencil operator cannot be row-sharded");
   if (c->op == OP_DCT) return fail(FH_E_STATE, "fh_comm_init: a context with a DCT operator cannot be row-sharded");
+  if (c->op == OP_CONV) return fail(FH_E_STATE, "fh_comm_init: a context with a convolution operator cannot be row-sharded");
   if (c->op == OP_IDENTITY) return fail(FH_E_STATE, "fh_comm_init: a context with the identity operator cannot be row-sharded");
   if (c->op == OP_QUAD) return fail(FH_E_STATE, "fh_comm_init: a context with a quadratic operator cannot be row-sharded");
   if (c->op == OP_BILINEAR) return fail(FH_E_STATE, "fh_comm_init: a context with a bilinear operator cannot be row-sharded");
@@ -2222,6 +2265,7 @@ extern "C" int fh_stream_read_ms(fh_ctx* c, int reps, double* ms_per_pass, uint6
   if (c->op == OP_SPARSE) return fail(FH_E_STATE, "fh_stream_read_ms: the stream-read ceiling is measured on a dense matrix, not on the sparse operator");
   if (c->op == OP_STENCIL3D) return fail(FH_E_STATE, "fh_stream_read_ms: the stream-read ceiling is measured on a dense matrix, not on the 3-D stencil operator");
   if (c->op == OP_DCT) return fail(FH_E_STATE, "fh_stream_read_ms: the stream-read ceiling is measured on a dense matrix, not on the DCT operator");
+  if (c->op == OP_CONV) return fail(FH_E_STATE, "fh_stream_read_ms: the stream-read ceiling is measured on a dense matrix, not on the convolution operator");
   if (c->op == OP_IDENTITY) return fail(FH_E_STATE, "fh_stream_read_ms: the stream-read ceiling is measured on a dense matrix, not on the identity operator");
   if (c->op == OP_QUAD) return fail(FH_E_STATE, "fh_stream_read_ms: the stream-read ceiling is measured on a dense matrix, not on the quadratic operator");
   if (c->op == OP_BILINEAR) return fail(FH_E_STATE, "fh_stream_read_ms: the stream-read ceiling is measured on a dense matrix, not on the bilinear operator");

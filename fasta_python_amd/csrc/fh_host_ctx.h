@@ -100,10 +100,13 @@ struct DctShape { uint32_t levels, N1, N2, cap; DctRad r1, r2; uint32_t ldsn1, r
 // geometry of the nuclear-norm prox's launches (csrc/fh_host_launch.h: nuc_shape_for fills it)
 struct NucShape { NucGeo g; uint32_t Bk, steps, wgs, chunks, lds_bytes; uint64_t bytes; };
 
+// geometry of the convolution operator's launches (csrc/fh_host_launch.h: conv_shape_for fills it)
+struct ConvShape { uint32_t th, tw, tw_log2, pitch, tiles_h, tiles_w, grid, lds_bytes; };
+
 // ------------------------------------------------------------------------------------------------
 // context
 // ------------------------------------------------------------------------------------------------
-enum { OP_NONE = 0, OP_DENSE = 1, OP_STENCIL = 2, OP_SPARSE = 3, OP_STENCIL3D = 4, OP_QUAD = 5, OP_BILINEAR = 6, OP_DCT = 7, OP_IDENTITY = 8 };
+enum { OP_NONE = 0, OP_DENSE = 1, OP_STENCIL = 2, OP_SPARSE = 3, OP_STENCIL3D = 4, OP_QUAD = 5, OP_BILINEAR = 6, OP_DCT = 7, OP_IDENTITY = 8, OP_CONV = 9 };
 
 struct fh_ctx {
   int device = 0;
@@ -134,6 +137,12 @@ struct fh_ctx {
   d2* dct_w0 = nullptr; d2* dct_w1 = nullptr;
   DctShape dct_sh = {};      // the geometry dct_shape_for gave when the operator was set (every launch reads it; fh_dct_shape reports it)
   double dct_sc0 = 0.0, dct_sck = 0.0;   // sqrt(1/N), sqrt(2/N)
+  // periodic convolution (fh_set_conv2d, csrc/fh_conv.h): the image is (H, W), m = n = H * W; the taps (kh * kw, C order: they travel in the
+  // kernels' argument block), the origin, the diagonal d (nullptr: all ones) and the geometry conv_shape_for gave when the operator was set
+  uint32_t conv_kh = 0, conv_kw = 0, conv_oh = 0, conv_ow = 0;
+  double conv_taps[256] = {};
+  double* conv_diag = nullptr;
+  ConvShape conv_sh = {};
   // identity operator (fh_set_identity, csrc/fh_nuclear.h): the unknown is an (id_M, id_N) matrix in the vector form's buffers.  FH_PROX_NUCLEAR
   // (fh_set_prox_nuclear): the geometry nuc_shape_for gave when the prox was set, the working buffer [ W | J^T ], phi, three device scalars
   // (||xhat||_F^2, the nuclear norm of xprox, the rank kept), one rotation counter per sweep with its pinned host copy, and the latest run's record
@@ -417,6 +426,7 @@ static void free_operator(fh_ctx* c) {
   fr(c->sp_r); c->nnz = 0;
   for (d2** q : {&c->dct_tw, &c->dct_pw, &c->dct_w0, &c->dct_w1}) if (*q) { (void)hipFree(*q); *q = nullptr; }
   fr(c->dct_diag);
+  fr(c->conv_diag);
   fr(c->nuc_w); fr(c->nuc_phi); fr(c->nuc_scal);
   if (c->nuc_cnt) { (void)hipFree(c->nuc_cnt); c->nuc_cnt = nullptr; }
   if (c->nuc_host) { (void)hipHostFree(c->nuc_host); c->nuc_host = nullptr; }

@@ -1,4 +1,4 @@
-// fh_host_launch.h -- kernel launchers of libfasta_hip.so: shapes, grids and workspace of every kernel in fh_dense.h / fh_quad.h / fh_bilinear.h / fh_tv.h / fh_tv3d.h / fh_dct.h /
+// fh_host_launch.h -- kernel launchers of libfasta_hip.so: shapes, grids and workspace of every kernel in fh_dense.h / fh_quad.h / fh_bilinear.h / fh_tv.h / fh_tv3d.h / fh_dct.h / fh_conv.h /
 // fh_prox.h / fh_fused.h, the one-pass kernel's shape rule and dispatch table, the co-residency probe, and the three-stage form
 // (local launch / sum over row blocks / n-side epilogue) the C ABI in fasta_hip.hip builds its entry points from.
 #pragma once
@@ -993,6 +993,107 @@ static int launch_adj_tv3(fh_ctx* c, const AdjIO& io) {
   return 0;
 }
 
+// ---- periodic convolution operator (fh_set_conv2d; kernels in csrc/fh_conv.h, instantiated by fh_conv_part.hip) ---------------------------
+#ifndef FH_SINGLE_TU
+CONV_KERNELS(extern template)
+#endif
+// THE launch geometry of both kernels, a pure function of the image, the kernel and the device's CU count: a workgroup owns a tile of
+// th x tw = 2048 output pixels, 8 consecutive ones along w per lane.  32 x 64 in general (LDS: 47 rows at a pitch of 104 doubles hold the
+// tile and a halo of up to 15 rows and 15 skewed columns); a signal -- H == 1 with kh == 1 -- takes 1 x 2048 (one row at a pitch of 2344),
+// where the square tile would leave 31 of 32 lanes idle.  grid = tiles_h x tiles_w.  The CU count does not enter the rule today: an image
+// of fewer tiles than CUs runs on fewer CUs, a smaller tile would only add halo (it is a parameter so that the rule may use it later
+// without a change of the interface).
+static int conv_shape_for(uint64_t H, uint64_t W, uint32_t kh, uint32_t kw, int ncu, ConvShape* sh) {
+  (void)ncu;
+  memset(sh, 0, sizeof(*sh));
+  if (H < 1 || W < 1) return fail(FH_E_ARG, "the convolution operator needs H >= 1 and W >= 1 (got %llu x %llu)", (unsigned long long)H, (unsigned long long)W);
+  if (kh < 1 || kh > CONV_MAXK || kw < 1 || kw > CONV_MAXK)
+    return fail(FH_E_ARG, "the convolution operator serves kernels of 1 to %d taps along each axis (got %u x %u): a larger point-spread function is a job for an FFT", CONV_MAXK, kh, kw);
+  if (H >= (1ull << 31) || W >= (1ull << 31) || H * W >= (1ull << 31))
+    return fail(FH_E_ARG, "the convolution operator needs H * W < 2^31: pixel offsets and vector lengths count in 32 bits (got %llu x %llu)", (unsigned long long)H, (unsigned long long)W);
+  const bool flat = H == 1 && kh == 1;
+  sh->th = flat ? 1u : 32u; sh->tw = flat ? 2048u : 64u; sh->tw_log2 = flat ? 11u : 6u;
+  sh->pitch = flat ? 2344u : 104u;                        // >= CONV_SKEW(tw + 15 - 1) + 1 and 8 mod 32 (csrc/fh_conv.h)
+  sh->tiles_h = (uint32_t)((H + sh->th - 1) / sh->th); sh->tiles_w = (uint32_t)((W + sh->tw - 1) / sh->tw);
+  sh->grid = sh->tiles_h * sh->tiles_w;                   // (< 2^31 / 2048)
+  sh->lds_bytes = CONV_LDS_DOUBLES * (uint32_t)sizeof(double);
+  return 0;
+}
+static inline bool conv_prox_ok(int kind) { return sp_prox_ok(kind) || kind == FH_PROX_LINF || kind == FH_PROX_L1BALL; }
+static void conv_shape_out(const ConvShape& sh, uint32_t* out) {
+  out[0] = sh.th; out[1] = sh.tw; out[2] = sh.tiles_h; out[3] = sh.tiles_w; out[4] = sh.grid; out[5] = CONV_RUN; out[6] = FH_WG; out[7] = sh.lds_bytes;
+}
+extern "C" int fh_conv_shape(fh_ctx* c, uint32_t* out) {
+  if (!c || !out) return fail(FH_E_ARG, "fh_conv_shape: null argument");
+  if (c->op != OP_CONV) return fail(FH_E_STATE, "fh_conv_shape: the context holds no convolution operator (fh_set_conv2d)");
+  conv_shape_out(c->conv_sh, out);                        // (what conv_shape_for gave when fh_set_conv2d set the operator: the launchers read the same copy)
+  return 0;
+}
+extern "C" int fh_conv_shape_for(uint64_t H, uint64_t W, uint32_t kh, uint32_t kw, int ncu, uint32_t* out) {
+  if (!out) return fail(FH_E_ARG, "fh_conv_shape_for: null argument");
+  ConvShape sh;
+  const int rc = conv_shape_for(H, W, kh, kw, ncu, &sh);
+  conv_shape_out(sh, out);                                // (a refusal: all zeros beside the error and its sentence)
+  return rc;
+}
+static int conv_alloc_diag(fh_ctx* c, const double* diag) {
+  HIP_TRY(hipMalloc((void**)&c->conv_diag, c->m * sizeof(double)));
+  HIP_TRY(hipMemcpy(c->conv_diag, diag, c->m * sizeof(double), hipMemcpyHostToDevice));
+  return 0;
+}
+static ConvGeo conv_geo(const fh_ctx* c) {
+  const ConvShape& sh = c->conv_sh;
+  ConvGeo g;
+  g.H = (uint32_t)c->H; g.W = (uint32_t)c->W; g.kh = c->conv_kh; g.kw = c->conv_kw; g.oh = c->conv_oh; g.ow = c->conv_ow;
+  g.th = sh.th; g.tw = sh.tw; g.tw_log2 = sh.tw_log2; g.pitch = sh.pitch; g.tiles_w = sh.tiles_w;
+  return g;
+}
+
+// z := d * (K conv (mode 0: prox(x0 - tau g0) ; mode 1: x0)), ONE launch
+static int launch_fwd_conv(fh_ctx* c, int mode, double tau, const double* x0, const double* g0, const double* xacc0,
+                           double* xhat, double* xp, double* z, int sub_b) {
+  if (c->loss_kind != LOSS_LSQ) return fail(FH_E_STATE, "the convolution operator serves the least-squares loss only (the logistic loss is implemented for the dense and sparse operators)");
+  if (mode == 0 && !conv_prox_ok(c->prox_kind))
+    return fail(FH_E_STATE, "prox kind %d (TVBALL / GROUP) is not implemented for the convolution operator", c->prox_kind);
+  const ConvShape& sh = c->conv_sh;
+  ConvFwdP p;
+  p.g = conv_geo(c);
+  p.sub_b = sub_b;
+  p.x0 = x0; p.g0 = g0; p.xacc0 = xacc0; p.xhat = xhat; p.xp = xp; p.b = c->b; p.z = z; p.diag = c->conv_diag; p.tau = tau;
+  p.px = make_prox(c, tau);
+  memcpy(p.taps, c->conv_taps, sizeof(p.taps));
+  FH_TRY(ensure_ws(c, (size_t)sh.grid * 8 * sizeof(double)));
+  p.red = c->ws; p.counter = c->counters + CNT_FWD; p.out = scalar_out(c);
+  t_begin(c, FH_K_FWD);
+  p.seq = seq_offer(c);
+  if (mode == 0) k_conv_fwd<0><<<dim3(sh.grid), dim3(FH_WG), 0, c->stream>>>(p);
+  else k_conv_fwd<1><<<dim3(sh.grid), dim3(FH_WG), 0, c->stream>>>(p);
+  t_end(c, FH_K_FWD);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// g1 := K corr (d * (z' - b)) with the residual, the loss at z' and the n-side epilogue in the same launch
+static int launch_adj_conv(fh_ctx* c, const AdjIO& io) {
+  if (c->loss_kind != LOSS_LSQ) return fail(FH_E_STATE, "the convolution operator serves the least-squares loss only (the logistic loss is implemented for the dense and sparse operators)");
+  if (io.mode != 0 && io.mode != 1) return fail(FH_E_STATE, "the convolution operator has no row-sharded adjoint");
+  const ConvShape& sh = c->conv_sh;
+  ConvAdjP p;
+  p.g = conv_geo(c);
+  p.z = io.z; p.zacc0 = io.zacc0; p.b = c->b; p.diag = c->conv_diag; p.sub_b = io.sub_b; p.accel = io.accel; p.coef = io.coef; p.tau = io.tau;
+  p.x0 = io.x0; p.xp = io.xp; p.xacc0 = io.xacc0; p.xhat = io.xhat; p.x1 = io.x1; p.g1 = io.g1;
+  memcpy(p.taps, c->conv_taps, sizeof(p.taps));
+  FH_TRY(ensure_ws(c, (size_t)sh.grid * 8 * sizeof(double)));
+  p.red = c->ws; p.counter = c->counters + CNT_ADJ_FIN; p.out = scalar_out(c);
+  t_begin(c, FH_K_ADJ);
+  p.seq = io.mode == 0 ? seq_offer(c) : 0u;
+  if (io.mode == 0) k_conv_adj<0><<<dim3(sh.grid), dim3(FH_WG), 0, c->stream>>>(p);
+  else k_conv_adj<1><<<dim3(sh.grid), dim3(FH_WG), 0, c->stream>>>(p);
+  t_end(c, FH_K_ADJ);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
 // ---- subsampled DCT operator (fh_set_dct; kernels in csrc/fh_dct.h, instantiated by fh_dct_part.hip) -------------------------------------
 #ifndef FH_SINGLE_TU
 #define DCT_DECLARE(LDSN) DCT_KERNELS(extern template, LDSN)
@@ -1395,7 +1496,7 @@ static int launch_gterms(fh_ctx* c, const double* x) {
 
 // clipping level alpha for FH_PROX_LINF (radius tau*mu) / FH_PROX_L1BALL (radius mu) -> dscal[FH_NSCALARS]
 static int launch_level_search(fh_ctx* c, double tau) {
-  if (c->op != OP_DENSE && c->op != OP_DCT) return fail(FH_E_STATE, "LINF / L1BALL prox need the dense operator");      // (the search reads x0, g0 and n only)
+  if (c->op != OP_DENSE && c->op != OP_DCT && c->op != OP_CONV) return fail(FH_E_STATE, "LINF / L1BALL prox need the dense operator");      // (the search reads x0, g0 and n only)
   const double radius = c->prox_kind == FH_PROX_L1BALL ? c->mu : tau * c->mu;
   const double* x0 = c->X[c->xi];
   const double* g0 = c->G[c->gc];
@@ -1803,6 +1904,7 @@ static int op_fwd(fh_ctx* c, int mode, double tau, const double* x0, const doubl
   if (c->op == OP_SPARSE) return c->LB ? launch_fwd_spmulti(c, mode, tau, x0, g0, xacc0, xhat, xp, z, sub_b) : launch_fwd_sparse(c, mode, tau, x0, g0, xacc0, xhat, xp, z, sub_b);
   if (c->op == OP_STENCIL3D) return launch_fwd_tv3(c, mode, tau, x0, g0, xacc0, xhat, xp, z, sub_b);
   if (c->op == OP_DCT) return launch_fwd_dct(c, mode, tau, x0, g0, xacc0, xhat, xp, z, sub_b);
+  if (c->op == OP_CONV) return launch_fwd_conv(c, mode, tau, x0, g0, xacc0, xhat, xp, z, sub_b);
   if (c->op == OP_IDENTITY) return launch_fwd_identity(c, mode, tau, x0, g0, xacc0, xhat, xp, z, sub_b);
   if (c->op == OP_QUAD) return launch_fwd_quad(c, mode, tau, x0, g0, xacc0, xhat, xp, z, sub_b);
   if (c->op == OP_BILINEAR) return launch_fwd_bilinear(c, mode, tau, x0, g0, xacc0, xhat, xp, z, sub_b);
@@ -1821,6 +1923,7 @@ static int adj_local(fh_ctx* c, const AdjIO& io_in) {
   if (c->op == OP_SPARSE) return c->LB ? launch_adj_spmulti(c, io) : launch_adj_sparse(c, io);
   if (c->op == OP_STENCIL3D) return launch_adj_tv3(c, io);
   if (c->op == OP_DCT) return launch_adj_dct(c, io);
+  if (c->op == OP_CONV) return launch_adj_conv(c, io);
   if (c->op == OP_IDENTITY) return launch_adj_identity(c, io);
   if (c->op == OP_QUAD) return launch_adj_quad(c, io);
   if (c->op == OP_BILINEAR) return launch_adj_bilinear(c, io);
@@ -1852,7 +1955,7 @@ static int reduce_fsq_over_ranks(fh_ctx* c) {
 static int check_ready(fh_ctx* c, bool need_b) {
   if (!c) return fail(FH_E_ARG, "null context");
   if (c->pending_step) return fail(FH_E_STATE, "a step issued by fh_step_begin is still in flight on this context: call fh_step_end first");
-  if (c->op == OP_NONE) return fail(FH_E_STATE, "no operator set (call fh_set_matrix / fh_set_matrix_csr / fh_generate_matrix / fh_set_stencil / fh_set_stencil3d / fh_set_dct / fh_set_identity / fh_set_quadratic / fh_set_factorization)");
+  if (c->op == OP_NONE) return fail(FH_E_STATE, "no operator set (call fh_set_matrix / fh_set_matrix_csr / fh_generate_matrix / fh_set_stencil / fh_set_stencil3d / fh_set_dct / fh_set_conv2d / fh_set_identity / fh_set_quadratic / fh_set_factorization)");
   if (need_b && !c->has_b) return fail(FH_E_STATE, "no loss set (call fh_set_loss_lsq)");
   return c->shards.empty() ? use_device(c) : 0;      // (a shell selects the device shard by shard)
 }

@@ -94,6 +94,9 @@ SIGNATURES = {
     "fh_set_dct": (_i32, [_ctx, _u64, _pd]),
     "fh_dct_shape": (_i32, [_ctx, C.POINTER(C.c_uint32)]),
     "fh_dct_shape_for": (_i32, [_u64, _i32, _i32, C.POINTER(C.c_uint32)]),
+    "fh_set_conv2d": (_i32, [_ctx, _u64, _u64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _pd, _pd]),
+    "fh_conv_shape": (_i32, [_ctx, C.POINTER(C.c_uint32)]),
+    "fh_conv_shape_for": (_i32, [_u64, _u64, C.c_uint32, C.c_uint32, _i32, C.POINTER(C.c_uint32)]),
     "fh_shape": (_i32, [_ctx, C.POINTER(_u64), C.POINTER(_u64)]),
     "fh_set_identity": (_i32, [_ctx, _u64, _u64]),
     "fh_set_prox_nuclear": (_i32, [_ctx, _dbl, _i32]),
@@ -344,6 +347,32 @@ def nuclear_shape(M, N, block_rows=0, ncu=256):
     out = (_u64 * NUCLEAR_SHAPE_LEN)()
     _check(lib, lib.fh_nuclear_shape_for(int(M), int(N), int(block_rows), int(ncu), out))
     return NuclearShape(*(int(v) for v in out))
+
+
+CONV_SHAPE_LEN = 8
+CONV_MAX_TAPS = 16
+ConvShape = collections.namedtuple("ConvShape", "tile_h tile_w tiles_h tiles_w grid run threads lds_bytes")
+
+
+def conv_shape(H, W, kh, kw, ncu=256):
+    """ConvShape of the convolution operator's launches for an (H, W) image and a (kh, kw) kernel on a device of ncu compute units:
+    fh_conv_shape_for, the rule both launchers call.  Host-only.  HipError with the library's sentence for what the device refuses."""
+    lib = load_library()
+    out = (C.c_uint32 * CONV_SHAPE_LEN)()
+    _check(lib, lib.fh_conv_shape_for(int(H), int(W), int(kh), int(kw), int(ncu), out))
+    return ConvShape(*(int(v) for v in out))
+
+
+def conv_refusal(H, W, kh, kw, ncu=256):
+    """None when the device serves an (H, W) image under a (kh, kw) kernel, else the library's sentence (a zero dimension, more than 16 taps
+    along an axis, H * W >= 2^31).  A library that is missing or does not load, or any other status, raises."""
+    lib = load_library()
+    out = (C.c_uint32 * CONV_SHAPE_LEN)()
+    status = lib.fh_conv_shape_for(int(H), int(W), int(kh), int(kw), int(ncu), out)
+    if status == E_ARG:
+        return f"[{status}] " + lib.fh_last_error().decode(errors="replace")
+    _check(lib, status)
+    return None
 
 
 def comm_library():
@@ -636,6 +665,31 @@ class HipContext:
         out = (_u64 * 4)()
         self._call("fh_nuclear_info", out)
         return NuclearInfo(*(int(v) for v in out))
+
+    def set_conv2d(self, shape, kernel, origin=None, diag=None):
+        """A x = d * (K conv x), A^H w = K corr (d * w), periodic, on an (H, W) image (csrc/fh_conv.h); origin=None: (kh // 2, kw // 2);
+        diag=None: all ones."""
+        H, W = (int(k) for k in shape)
+        k, pk = _as_f64(kernel)
+        if k.ndim != 2:
+            raise ValueError(f"the kernel of a convolution operator is 2-D (got {k.ndim} dimensions)")
+        kh, kw = k.shape
+        oh, ow = (kh // 2, kw // 2) if origin is None else (int(origin[0]), int(origin[1]))
+        if oh < 0 or ow < 0:
+            raise ValueError(f"the origin ({oh}, {ow}) lies outside the {kh} x {kw} kernel")
+        if diag is None:
+            self._call("fh_set_conv2d", H, W, kh, kw, oh, ow, pk, None)
+            return
+        d, pd = _as_f64(diag)
+        if d.shape != (H, W):
+            raise ValueError(f"diag has shape {d.shape}, the convolution operator on an ({H}, {W}) image takes ({H}, {W})")
+        self._call("fh_set_conv2d", H, W, kh, kw, oh, ow, pk, pd)
+
+    def conv_shape(self):
+        """ConvShape the next fwd / adj of this context launches with (fh_conv_shape).  E_STATE without a convolution operator."""
+        out = (C.c_uint32 * CONV_SHAPE_LEN)()
+        self._call("fh_conv_shape", out)
+        return ConvShape(*(int(v) for v in out))
 
     def shape(self):
         m, n = _u64(0), _u64(0)

@@ -16,6 +16,7 @@ subclasses are *recognised* by `fasta()` and run on the device:
                      the unknown is an (n, L) matrix and every entry gathers a whole row of it, csrc/fh_spmulti.h);
   GradDivMap      -- the periodic div/grad stencil pair of examples/tv_denoising.py:26-63;
   DCTMap          -- the subsampled orthonormal DCT of examples/democratic_representation.py:80-82, an implicit fast transform (csrc/fh_dct.h);
+  ConvMap         -- periodic convolution with a small kernel (a point-spread function) and its correlation adjoint, an implicit operator (csrc/fh_conv.h);
   QuadraticMap    -- the identity operator of a quadratic smooth term (losses.Quadratic): what `fasta(None, None, q.f, q.gradf, ...)` runs on;
   BilinearMap     -- the identity operator of a bilinear smooth term (losses.Factorization): what `fasta(None, None, fz.f, fz.gradf, ...)` runs on;
   IdentityMap     -- the identity operator on an (M, N) matrix unknown with an elementwise loss (losses.LeastSquares / LogisticLoss): what
@@ -40,7 +41,7 @@ from . import hip
 Matrix = np.ndarray
 Vector = np.ndarray
 
-__all__ = ["LinearMap", "LinearOperator", "DenseMatrixMap", "ShardedDenseMatrixMap", "SparseMatrixMap", "GradDivMap", "DCTMap", "QuadraticMap", "BilinearMap", "IdentityMap", "is_sparse_matrix", "Matrix", "Vector"]
+__all__ = ["LinearMap", "LinearOperator", "DenseMatrixMap", "ShardedDenseMatrixMap", "SparseMatrixMap", "GradDivMap", "DCTMap", "ConvMap", "QuadraticMap", "BilinearMap", "IdentityMap", "is_sparse_matrix", "Matrix", "Vector"]
 
 
 class LinearMap:
@@ -628,3 +629,65 @@ class DCTMap(_DeviceMap):
     def _apply_adj(self, w):
         from scipy.fftpack import idct
         return idct(w if self.mask is None else self.mask * w, norm='ortho')
+
+
+class ConvMap(_DeviceMap):
+    """Periodic convolution of an image (H, W) or a signal (N,) with a small kernel K -- a point-spread function -- and its adjoint, the
+    correlation: deblurring, spike deconvolution, inpainting under a blur, compressed sensing by random convolution.
+        (A x)[i,j]   = mask[i,j] * sum_{a,b} K[a,b] * x[i-(a-oh), j-(b-ow)]
+        (A^H w)[i,j] =             sum_{a,b} K[a,b] * (mask * w)[i+(a-oh), j+(b-ow)]          indices modulo the dimension
+    `kernel`: 2-D, or 1-D for a 1-D shape; `origin`: (oh, ow) inside the kernel (an int for a signal), None = (kh // 2, kw // 2);
+    `mask`: float64 of the image's shape (a 0/1 mask gives inpainting or subsampled convolution), None = all ones.
+    An implicit operator: no matrix is stored, the device convolves directly (fh_set_conv2d, csrc/fh_conv.h: an LDS tile with its halo, a
+    sliding register window).  Lazy like the 3-D GradDivMap: the device context is created when the device loop first asks for it, and on
+    host arrays the map is exactly `out = zeros; for a: for b: out += K[a,b] * np.roll(x, (a-oh, b-ow), axis=(0,1))` (the adjoint: the
+    negated shifts of mask * w) -- the arithmetic the device kernels keep term by term, so `backend="numpy"`, the generic host loop and the
+    device agree bit for bit on A x and A^H w.  A kernel the device refuses (more than 16 taps along an axis: `refusal` holds the
+    library's sentence) stays a host map: `fasta()` runs it on the generic host loop, and `backend="hip"` raises with that sentence."""
+
+    def __init__(self, shape, kernel, origin=None, mask=None, device=0):
+        shape = (int(shape),) if np.ndim(shape) == 0 else tuple(int(k) for k in shape)
+        kernel = np.ascontiguousarray(kernel, dtype=np.float64)
+        if len(shape) not in (1, 2):
+            raise ValueError(f"ConvMap takes an image shape (H, W) or a signal shape (N,); got {len(shape)} dimensions")
+        if kernel.ndim != len(shape):
+            raise ValueError(f"ConvMap: a {len(shape)}-D shape takes a {len(shape)}-D kernel (got {kernel.ndim} dimensions)")
+        if min(shape) < 1 or kernel.size == 0:
+            raise ValueError(f"ConvMap takes a non-empty shape and a non-empty kernel (got {shape} and {kernel.shape})")
+        self.image_shape = shape
+        self.shape2d = shape if len(shape) == 2 else (1, shape[0])
+        self.kernel = kernel.reshape((1, -1)) if kernel.ndim == 1 else kernel
+        kh, kw = self.kernel.shape
+        if origin is None:
+            origin = (kh // 2, kw // 2)
+        elif len(shape) == 1:
+            origin = (0, int(origin if np.ndim(origin) == 0 else origin[0]))
+        self.origin = (int(origin[0]), int(origin[1]))
+        if not (0 <= self.origin[0] < kh and 0 <= self.origin[1] < kw):
+            raise ValueError(f"ConvMap: the origin {self.origin} lies outside the {kh} x {kw} kernel")
+        self.mask = None if mask is None else np.ascontiguousarray(mask, dtype=np.float64)
+        if self.mask is not None and self.mask.shape != shape:
+            raise ValueError(f"mask has shape {self.mask.shape}, a ConvMap on {shape} takes {shape}")
+        self.refusal = hip.conv_refusal(self.shape2d[0], self.shape2d[1], kh, kw)      # (a library that does not load raises: only a sentence about the shape is a refusal)
+        self.geometry = None if self.refusal is not None else hip.conv_shape(self.shape2d[0], self.shape2d[1], kh, kw)
+        _DeviceMap.__init__(self, shape, shape, device, lazy=True)
+
+    def _on_context(self, ctx):
+        ctx.set_conv2d(self.shape2d, self.kernel, self.origin, None if self.mask is None else self.mask.reshape(self.shape2d))
+
+    def _rolls(self, v, sign):
+        x = np.asarray(v, dtype=np.float64).reshape(self.shape2d)
+        out = np.zeros(self.shape2d)
+        oh, ow = self.origin
+        for a in range(self.kernel.shape[0]):
+            for b in range(self.kernel.shape[1]):
+                out += self.kernel[a, b] * np.roll(x, (sign * (a - oh), sign * (b - ow)), axis=(0, 1))
+        return out
+
+    def _apply_fwd(self, v):
+        y = self._rolls(v, 1).reshape(self.image_shape)
+        return y if self.mask is None else self.mask * y
+
+    def _apply_adj(self, w):
+        w = np.asarray(w, dtype=np.float64).reshape(self.image_shape)
+        return self._rolls(w if self.mask is None else self.mask * w, -1).reshape(self.image_shape)

@@ -334,7 +334,10 @@ def shrink(x, t):
 
 def project_Linf_ball(x, t):
     """The prox of t*||.||_inf, as the reference implements it (fasta/proximal.py:12-31): clip |x| at the level
-    alpha = max_k (sum of the k largest |x_i| - t)/k, or return float64 zeros when that level is not positive."""
+    alpha = max_k (sum of the k largest |x_i| - t)/k, or return float64 zeros when that level is not positive.  An image (linalg.ConvMap) is
+    projected as the vector of its entries and comes back in its shape."""
+    if np.ndim(x) > 1:
+        return project_Linf_ball(np.ravel(x), t).reshape(np.shape(x))
     mags = np.abs(x)
     ranked = mags.copy()
     ranked[::-1].sort()                                          # descending, in place through the reversed view

@@ -30,7 +30,7 @@ from time import time
 import numpy as np
 
 from . import hip, stopping
-from .linalg import BilinearMap, DCTMap, DenseMatrixMap, GradDivMap, IdentityMap, LinearMap, QuadraticMap, SparseMatrixMap, _DeviceMap, is_sparse_matrix
+from .linalg import BilinearMap, ConvMap, DCTMap, DenseMatrixMap, GradDivMap, IdentityMap, LinearMap, QuadraticMap, SparseMatrixMap, _DeviceMap, is_sparse_matrix
 from .losses import Factorization, LeastSquares, LogisticLoss, Quadratic, SoftmaxLoss
 from .proximal import NoProx, NuclearShrink, ProxTag
 
@@ -139,6 +139,24 @@ def _dct_form_refusal(A, loss, prox, x0):
     return None
 
 
+def _conv_form_refusal(A, loss, prox, x0):
+    """A ConvMap serves an unknown of the image's shape with least squares and Shrink, NonNeg, Box, LinfProx, L1Ball or no prox (csrc/fh_conv.h); a
+    kernel the device refuses (ConvMap.refusal: the library's sentence) stays on the host.  None, or the reason."""
+    from .proximal import GroupShrink, TVDualBall
+    if not isinstance(A, ConvMap):
+        return None
+    if A.refusal is not None:
+        return A.refusal
+    if isinstance(loss, LogisticLoss):
+        return "losses.LogisticLoss is not implemented for a convolution operator on the device: least squares only"
+    if isinstance(prox, (TVDualBall, GroupShrink)):
+        return (f"proximal.{type(prox).__name__} is not implemented for a convolution operator on the device "
+                "(Shrink, NonNeg, Box, LinfProx, L1Ball or no prox are)")
+    if x0 is not None and tuple(np.shape(x0)) != A.Vshape:
+        return f"a convolution operator on {A.Vshape} takes an unknown of that shape on the device (x0 has shape {tuple(np.shape(x0))})"
+    return None
+
+
 def _quadratic_form_refusal(A, At, loss_f, loss_g, g, proxg, x0):
     """`fasta(None, None, q.f, q.gradf, g, prox, x0)` with q = losses.Quadratic(Q, c): the device serves it through fh_set_quadratic
     (csrc/fh_quad.h) for a vector or a matrix unknown of at most 16 columns, with the elementwise prox kinds, GroupShrink and RowBall.
@@ -212,6 +230,8 @@ def _softmax_form_refusal(A, At, loss_f, loss_g, g, proxg, x0):
                 "it is served by a dense or a sparse matrix operator over a matrix unknown (n, L)")
     if isinstance(A, DCTMap):
         return "losses.SoftmaxLoss is not implemented for a DCT operator on the device: least squares only"
+    if isinstance(A, ConvMap):
+        return "losses.SoftmaxLoss is not implemented for a convolution operator on the device: least squares only"
     if isinstance(A, GradDivMap):
         return "losses.SoftmaxLoss is not implemented for a stencil (GradDivMap) operator on the device: least squares only"
     if not isinstance(A, (np.ndarray, DenseMatrixMap, SparseMatrixMap)) and not is_sparse_matrix(A):
@@ -304,12 +324,12 @@ def _unrecognised(A, At, f, gradf, g, proxg, x0=None):
         return _identity_form_refusal(A, loss_f, g, proxg, x0)
     if not isinstance(A, (np.ndarray, _DeviceMap)) and not is_sparse_matrix(A):
         return ("operator A is not device-resident (pass a 2-D float64 ndarray, a scipy.sparse matrix, a linalg.DenseMatrixMap / "
-                "LinearMap.from_matrix(A), a linalg.SparseMatrixMap, a linalg.GradDivMap or a linalg.DCTMap); arbitrary Python callables cannot run inside the fused HIP kernels")
+                "LinearMap.from_matrix(A), a linalg.SparseMatrixMap, a linalg.GradDivMap, a linalg.DCTMap or a linalg.ConvMap); arbitrary Python callables cannot run inside the fused HIP kernels")
     loss_f, loss_g = _tag_of(f, (LeastSquares, LogisticLoss)), _tag_of(gradf, (LeastSquares, LogisticLoss))
     if loss_f is None or loss_f is not loss_g:
         return "f and gradf must be the `.f` / `.gradf` of one losses.LeastSquares(b) or losses.LogisticLoss(b) object"
     if g is None and proxg is None:
-        return _dct_form_refusal(A, loss_f, None, x0) or _sparse_form_refusal(A, loss_f, None, x0) or _matrix_form_refusal(A, loss_f, None, x0)
+        return _dct_form_refusal(A, loss_f, None, x0) or _conv_form_refusal(A, loss_f, None, x0) or _sparse_form_refusal(A, loss_f, None, x0) or _matrix_form_refusal(A, loss_f, None, x0)
     prox, owner_g = _tag_of(proxg, ProxTag), _tag_of(g, ProxTag)
     if prox is None or (owner_g is not None and owner_g is not prox) or (owner_g is None and g is not None):
         return ("g and proxg must be the `.g` / `.prox` of one proximal.* tag object "
@@ -320,7 +340,7 @@ def _unrecognised(A, At, f, gradf, g, proxg, x0=None):
         return "proximal.RowBall is served on the device with a quadratic loss only: fasta(None, None, q.f, q.gradf, ...) with q = losses.Quadratic(Q, c)"
     if prox.kind == hip.PROX_ROWSPLIT:
         return "proximal.RowSplit is served on the device with a factorization loss only: fasta(None, None, fz.f, fz.gradf, ...) with fz = losses.Factorization(S)"
-    return _dct_form_refusal(A, loss_f, prox, x0) or _sparse_form_refusal(A, loss_f, prox, x0) or _matrix_form_refusal(A, loss_f, prox, x0)
+    return _dct_form_refusal(A, loss_f, prox, x0) or _conv_form_refusal(A, loss_f, prox, x0) or _sparse_form_refusal(A, loss_f, prox, x0) or _matrix_form_refusal(A, loss_f, prox, x0)
 
 
 def _recognise(A, At, f, gradf, g, proxg, x0):

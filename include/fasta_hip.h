@@ -286,6 +286,36 @@ int fh_set_dct(fh_ctx* ctx, uint64_t N, const double* diag);
 #define FH_DCT_SHAPE_LEN 40
 int fh_dct_shape(fh_ctx* ctx, uint32_t* out);
 int fh_dct_shape_for(uint64_t N, int row_cap, int ncu, uint32_t* out);
+/* ---- periodic convolution with a small kernel: A x = d * (K conv x), A^T w = K corr (d * w) (csrc/fh_conv.h) --------------------------------------
+ * Image x of shape (H, W) in C order (a signal: H = 1), taps K of shape (kh, kw) in C order with 1 <= kh, kw <= 16, origin (oh, ow) inside the
+ * kernel, all indices modulo the dimension:
+ *   (A x)[i,j]   = d[i,j] * sum_{a,b} K[a,b] * x[i-(a-oh), j-(b-ow)]        (A^T w)[i,j] = sum_{a,b} K[a,b] * (d*w)[i+(a-oh), j+(b-ow)]
+ * m = n = H * W (fh_shape reports them).  d: H * W float64 values copied to the device, NULL = all ones (a 0/1 mask: inpainting, subsampled
+ * convolution); d[i,j] == 0.0 gives z[i,j] == 0.0 exactly.  The arithmetic is fixed: the accumulator starts at +0.0, taps are visited a outer,
+ * b inner, both ascending, each term is a rounded product followed by a rounded sum (no FMA), no tap is skipped, d is applied last in A and
+ * first in A^T -- NumPy's `out += K[a,b] * np.roll(x, (a-oh, b-ow), axis=(0,1))`, bit for bit.  Any H, W >= 1 is served, images smaller than
+ * the kernel included (taps then wrap more than once); H * W < 2^31.  No matrix is stored.  Vectors live in the vector form's padded buffers,
+ * so fh_set_vector / fh_get_vector, fh_diff_norm, fh_commit, fh_set_loss_lsq, fh_set_prox and fh_shape work unchanged.  One launch per
+ * direction, no atomics on floats, fixed summation order, bitwise repeatable.  Prox kinds served: IDENTITY, SHRINK, NONNEG, BOX, LINF and
+ * L1BALL (the level search of the dense operator reads x0, g0 and n only); least squares only.
+ * Served entry points, the FH_S_* scalars meaning what they mean for the sparse operator: fh_init, fh_setup (its three-pass route),
+ * fh_gradient_at, fh_apply (both ways), fh_fwd, fh_adj (accel / coef), fh_fwd_adj, fh_iterate, fh_commit, fh_timing_* (FH_K_FWD / FH_K_ADJ /
+ * FH_K_LEVEL).
+ * Refused (FH_E_ARG with a sentence): a zero dimension, kh or kw outside 1..16, an origin outside the kernel, H * W >= 2^31; FH_PROX_TVBALL /
+ * GROUP / ROWBALL / ROWSPLIT / NUCLEAR (a context holding one returns to IDENTITY when the operator is set).  Refused (FH_E_STATE):
+ * fh_step*, fh_run, fh_set_rhs, multi-device contexts, a context with a communicator and fh_comm_init, float32 storage, the logistic and
+ * softmax losses, fh_get_matrix_rows, fh_stream_read_ms.  fh_fused_supported, fh_fused_agree and fh_run_supported report 0.  Setting any
+ * other operator leaves this form and frees its tables.                                                                                       */
+int fh_set_conv2d(fh_ctx* ctx, uint64_t H, uint64_t W, uint32_t kh, uint32_t kw, uint32_t oh, uint32_t ow, const double* taps, const double* diag);
+/* read-only: the geometry the convolution launches take (csrc/fh_host_launch.h: conv_shape_for, the ONE rule both launchers call), so that a
+ * test can assert the path it meant to reach.  out[FH_CONV_SHAPE_LEN]: [0] tile rows, [1] tile columns (32 x 64; 1 x 2048 for a signal with
+ * H == 1 and kh == 1), [2] tiles along h, [3] tiles along w, [4] grid (= [2] * [3]), [5] consecutive outputs along w per lane, [6] threads
+ * per workgroup, [7] static LDS bytes of the tile.  fh_conv_shape is FH_E_STATE without this operator; fh_conv_shape_for is the same rule as
+ * a pure host function (no device needed; ncu: the device's compute units) and answers FH_E_ARG, with out all zeros, for what fh_set_conv2d
+ * refuses by shape.                                                                                                                          */
+#define FH_CONV_SHAPE_LEN 8
+int fh_conv_shape(fh_ctx* ctx, uint32_t* out);
+int fh_conv_shape_for(uint64_t H, uint64_t W, uint32_t kh, uint32_t kw, int ncu, uint32_t* out);
 int fh_shape(fh_ctx* ctx, uint64_t* m, uint64_t* n);
 
 /* ---- the identity operator with an elementwise loss: the unknown is an (M, N) MATRIX, f(X) = sum of a loss over its entries (csrc/fh_nuclear.h) --
