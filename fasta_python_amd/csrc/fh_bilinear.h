@@ -19,7 +19,7 @@
 //   k_bl_extrap    x1 = xprox + coef (xprox - xacc0): the point of the second pass of an accelerated step (the form is not linear: the
 //                  gradient at the extrapolated point is not the extrapolation of two gradients).
 //   k_bl_grad      the n-side epilogue, elementwise, one lane per row of Z: g1 = the sum of that row's partials in index order (column tiles
-//                  for a row of X, row panels for a row of Y), k_mc_adj's n-side sums, FH_S_FSQ_ADJ = f of the pass that produced the partials.
+//                  for a row of X, row panels for a row of Y), the n-side sums (fh_nside.h), FH_S_FSQ_ADJ = f of the pass that produced the partials.
 // Finalisers are arrive_last only: no spin waits, no co-residency assumption.  Bitwise repeatable run to run.
 #pragma once
 #include "fh_quad.h"
@@ -64,28 +64,15 @@ __global__ __launch_bounds__(FH_WG) void k_bl_prologue(const BlProP p) {
       double q = prox_scalar_rt(px.kind, xh[l], px, 0.0);
       if (!valid) q = 0.0;
       xq[l] = q;
-      if (valid) {
-        const double dx = q - x0v[l];
-        const double dh = q - xh[l];
-        v[0] = fma(dx, g0v[l], v[0]);
-        v[1] = fma(dx, dx, v[1]);
-        v[2] = fma(dh, dh, v[2]);
-        v[3] = fma(g0v[l], g0v[l], v[3]);
-        if (top) v[4] += fabs(q);
-        v[5] = fmax(v[5], fabs(q));
-      }
     }
-    if (p.a.xacc0) {
+    // the n-side sums, a column pair at a time next to its 16 bytes of x_accel0
 #pragma unroll
-      for (int l = 0; l < LB; l += 2) {
-        const d2 a = *reinterpret_cast<const d2*>(p.a.xacc0 + o + l);
-        if (rowok && (uint32_t)l < p.a.L) v[6] = fma(x0v[l] - xq[l], xq[l] - a.x, v[6]);
-        if (rowok && (uint32_t)(l + 1) < p.a.L) v[6] = fma(x0v[l + 1] - xq[l + 1], xq[l + 1] - a.y, v[6]);
-      }
-    } else {
+    for (int l = 0; l < LB; l += 2) {
+      d2 a = {0.0, 0.0};
+      if (p.a.xacc0) a = *reinterpret_cast<const d2*>(p.a.xacc0 + o + l);
 #pragma unroll
-      for (int l = 0; l < LB; ++l)
-        if (rowok && (uint32_t)l < p.a.L) v[6] = fma(x0v[l] - xq[l], xq[l], v[6]);
+      for (int h = 0; h < 2; ++h)
+        if (rowok && (uint32_t)(l + h) < p.a.L) nside_fwd_sums<0>(x0v[l + h], g0v[l + h], xh[l + h], xq[l + h], a[h], v, top);
     }
 #pragma unroll
     for (int l = 0; l < LB; l += 2) {
@@ -93,11 +80,7 @@ __global__ __launch_bounds__(FH_WG) void k_bl_prologue(const BlProP p) {
       *reinterpret_cast<d2*>(p.a.xp + o + l) = (d2){xq[l], xq[l + 1]};
     }
   }
-  block_reduce<7>(v, s_scr, 5);
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int k = 0; k < 7; ++k) store_partial(p.a.red_n + (uint64_t)blockIdx.x * 8 + 1 + k, v[k]);
-  }
+  publish_record<7, 5>(v, p.a.red_n + 1, blockIdx.x, s_scr);
 }
 
 // ---- the pass over S ----------------------------------------------------------------------------------------------------------------------------
@@ -199,35 +182,14 @@ __global__ __launch_bounds__(FH_WG) __attribute__((amdgpu_waves_per_eu(1, 2))) v
       }
     }
   }
-  {
-    double v[1] = {fpart};
-    block_reduce<1>(v, s_scr, -1);
-    if (tid == 0) store_partial(p.red_m + blockIdx.x, v[0]);
-  }
-  if (arrive_last(p.counter, gridDim.x, s_flag)) {
-    double v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    for (uint32_t i = tid; i < gridDim.x; i += FH_WG) v[0] += load_partial(p.red_m + i);
-    for (uint32_t i = tid; i < p.nred_n; i += FH_WG) {
-#pragma unroll
-      for (int k = 1; k < 8; ++k) {
-        const double t = load_partial(p.red_n + (uint64_t)i * 8 + k);
-        if (k == S_GMAX) v[k] = fmax(v[k], t); else v[k] += t;
-      }
-    }
-    block_reduce<8>(v, s_scr, S_GMAX);
-    if (tid == 0) {
-      const double f = 0.5 * v[0];
-      *p.fout = f;
-      if (p.publish) {
-        scal_store(p.out + S_FSQ, f);
-#pragma unroll
-        for (int k = 1; k < 8; ++k) scal_store(p.out + k, v[k]);
-        scal_store(p.out + S_ALPHA, 0.0);
-        publish_seq(p.out, p.seq);
-      }
-      __hip_atomic_store(p.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
+  double v[1] = {fpart};
+  finish_records<1, S_GMAX, 8>(v, p.red_m, blockIdx.x, gridDim.x, p.counter, p.out, p.publish ? p.seq : 0u, s_scr, s_flag,
+                               [&](double (&w)[8]) { add_records<1, 8, S_GMAX>(w, p.red_n, p.nred_n); },      // the prologue's n-side sums
+                               [&](double (&w)[8]) {
+                                 w[S_FSQ] = 0.5 * w[S_FSQ];
+                                 *p.fout = w[S_FSQ];
+                                 if (p.publish) store_fwd_scalars(p.out, w, 0.0);
+                               });
 }
 
 // ---- the point of an accelerated step's second pass ------------------------------------------------------------------------------------------
@@ -239,7 +201,7 @@ static __global__ __launch_bounds__(FH_WG) void k_bl_extrap(const double* xp, co
   x1[i] = valid ? extrapolate(xp[i], xacc0[i], coef) : 0.0;
 }
 
-// ---- the n-side epilogue: partial reduction and k_mc_adj's sums ------------------------------------------------------------------------------
+// ---- the n-side epilogue: partial reduction and the n-side sums ---------------------------------------------------------------------------------
 struct BlGradP {
   uint32_t m, n, L;     // rows of X / of Y, columns
   uint32_t rows;        // device rows of Z (every lane of the grid owns one)
@@ -289,43 +251,16 @@ __global__ __launch_bounds__(FH_WG) void k_bl_grad(const BlGradP p) {
         const bool valid = (isx || isy) && (uint32_t)(2 * l + h) < p.L;
         const double g = valid ? gv[h] : 0.0;
         gv[h] = g;
-        if (valid && p.mode == 0) {
-          double x1 = xpv[h];
-          if (p.accel) x1 = extrapolate(xpv[h], xav[h], p.coef);      // (the bits k_bl_extrap wrote)
-          const double dx = sub_nofma(xpv[h], x0v[h]);
-          const double dg = bb_dgrad(g, xhv[h], x0v[h], p.tau);
-          const double dh = sub_nofma(x1, xhv[h]);
-          v[0] = fma(dx, dg, v[0]);
-          v[1] = fma(dg, dg, v[1]);
-          v[2] = fma(dh, dh, v[2]);
-          if (row < p.gtop) v[3] += fabs(x1);
-          v[4] = fmax(v[4], fabs(x1));
-        }
+        // (x1, which is not kept: the bits k_bl_extrap wrote)
+        if (valid && p.mode == 0) nside_adj_sums(g, x0v[h], xpv[h], xav[h], xhv[h], p.accel, p.coef, p.tau, v, row < p.gtop);
       }
       *reinterpret_cast<d2*>(p.g1 + o + 2 * l) = gv;
     }
   }
-  block_reduce<5>(v, s_scr, 4);
-  if (tid == 0) {
-#pragma unroll
-    for (int k = 0; k < 5; ++k) store_partial(p.red + (uint64_t)blockIdx.x * 8 + k, v[k]);
-  }
-  if (!arrive_last(p.counter, gridDim.x, s_flag)) return;
-  double w[5] = {0, 0, 0, 0, 0};
-  for (uint32_t i = tid; i < gridDim.x; i += FH_WG) {
-#pragma unroll
-    for (int k = 0; k < 5; ++k) {
-      const double t = load_partial(p.red + (uint64_t)i * 8 + k);
-      if (k == 4) w[k] = fmax(w[k], t); else w[k] += t;
-    }
-  }
-  block_reduce<5>(w, s_scr, 4);
-  if (tid == 0) {
+  finish_records<5, 4>(v, p.red, blockIdx.x, gridDim.x, p.counter, p.out, p.seq, s_scr, s_flag, NoRecords(), [&](double (&w)[5]) {
     scal_store(p.out + S_DXDG, w[0]); scal_store(p.out + S_DG2, w[1]); scal_store(p.out + S_XH2_ADJ, w[2]);
     scal_store(p.out + S_GSUM_ADJ, w[3]); scal_store(p.out + S_GMAX_ADJ, w[4]); scal_store(p.out + S_FSQ_ADJ, *p.fsrc);
-    publish_seq(p.out, p.seq);
-    __hip_atomic_store(p.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+  });
 }
 
 // ---- the instantiations (ONE table for fh_bilinear_part.hip, the extern declarations and the dispatch) ----

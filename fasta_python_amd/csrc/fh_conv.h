@@ -19,7 +19,7 @@
 //               x0 / g0, never read back from a stored xprox; the sums count a pixel in its owner only.  Prox kinds: IDENTITY, SHRINK,
 //               NONNEG, BOX, and LINF / L1BALL with the level the search in front of the launch left at *px.level.
 //   k_conv_adj<MODE>  r = z' - b (z' = z or its FISTA extrapolation; the loss at z' is FH_S_FSQ_ADJ), d * r staged with its halo,
-//               g1 = correlation written, and k_sp_adj's n-side epilogue in the owner's lane (every g1 entry has one owner); modes 0, 1.
+//               g1 = correlation written, and the n-side epilogue (fh_nside.h) in the owner's lane (every g1 entry has one owner); modes 0, 1.
 // The tap loop: a lane computes CONV_RUN = 8 consecutive outputs along w.  Per kernel row it reads the CONV_RUN + kw - 1 operands of that
 // row from LDS ONCE into registers and slides over them for the kw taps: (8 + kw - 1) / (8 kw) LDS reads per tap instead of 1.  kh is a
 // run-time trip count; kw selects one of 16 unrolled bodies (conv_taps<KW>) by a grid-uniform switch, so the window is indexed by constants
@@ -29,7 +29,7 @@
 // After the tap loop the outputs go back through LDS so that z / g1 and everything the epilogues read and write are wave-contiguous.
 // Wraps are a conditional correction where the kernel is no larger than the image along that axis, a true modulo otherwise.
 #pragma once
-#include "fh_device.h"
+#include "fh_records.h"
 
 #define CONV_RUN 8                                 // consecutive outputs along w per lane
 #define CONV_MAXK 16                               // taps per axis, at most
@@ -154,15 +154,7 @@ __global__ __launch_bounds__(FH_WG) void k_conv_fwd(const ConvFwdP p) {
         y = prox_scalar_rt(p.px.kind, xhe, p.px, level);
         if (lr >= top && lr < top + t.the && lc >= left && lc < left + t.twe) {        // the owner's copy (not a halo copy)
           const double xav = p.xacc0 ? p.xacc0[gi] : 0.0;
-          const double dx = sub_nofma(y, x0e);
-          const double dh = sub_nofma(y, xhe);
-          v[1] = fma(dx, g0e, v[1]);
-          v[2] = fma(dx, dx, v[2]);
-          v[3] = fma(dh, dh, v[3]);
-          v[4] = fma(g0e, g0e, v[4]);
-          v[5] += fabs(y);
-          v[6] = fmax(v[6], fabs(y));
-          v[7] = fma(sub_nofma(x0e, y), sub_nofma(y, xav), v[7]);
+          nside_fwd_sums<1>(x0e, g0e, xhe, y, xav, v);
           p.xhat[gi] = xhe;
           p.xp[gi] = y;
         }
@@ -184,28 +176,8 @@ __global__ __launch_bounds__(FH_WG) void k_conv_fwd(const ConvFwdP p) {
       v[0] += p.sub_b ? loss_term(zv, p.b[zi], LOSS_LSQ) : zv * zv;
     }
   }
-  block_reduce<8>(v, s_scr, S_GMAX);
-  if (tid == 0) {
-#pragma unroll
-    for (int k = 0; k < 8; ++k) store_partial(p.red + (uint64_t)blockIdx.x * 8 + k, v[k]);
-  }
-  if (!arrive_last(p.counter, gridDim.x, s_flag)) return;
-  double w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  for (uint32_t i = tid; i < gridDim.x; i += FH_WG) {                   // records in index order: lane l adds l, l + 256, ...
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const double r = load_partial(p.red + (uint64_t)i * 8 + k);
-      if (k == S_GMAX) w[k] = fmax(w[k], r); else w[k] += r;
-    }
-  }
-  block_reduce<8>(w, s_scr, S_GMAX);
-  if (tid == 0) {
-#pragma unroll
-    for (int k = 0; k < 8; ++k) scal_store(p.out + k, w[k]);
-    scal_store(p.out + S_ALPHA, 0.0);
-    publish_seq(p.out, p.seq);
-    __hip_atomic_store(p.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+  finish_records<8, S_GMAX>(v, p.red, blockIdx.x, gridDim.x, p.counter, p.out, p.seq, s_scr, s_flag, NoRecords(),
+                            [&](double (&w)[8]) { store_fwd_scalars(p.out, w, 0.0); });
 }
 
 // ---- K-adj --------------------------------------------------------------------------------------------------------------------------------
@@ -263,43 +235,14 @@ __global__ __launch_bounds__(FH_WG) void k_conv_adj(const ConvAdjP p) {
       const uint32_t gi = (t.h0 + r) * g.W + (t.w0 + c);
       const double gv = s_t[r * g.pitch + CONV_SKEW(c)];
       p.g1[gi] = gv;
-      if (MODE == 0) {                                                  // the n-side epilogue of this element (k_sp_adj's sp_adj_element)
-        const double x0e = p.x0[gi], xpe = p.xp[gi], xhe = p.xhat[gi];
-        double x1 = xpe;
-        if (p.accel) x1 = extrapolate(xpe, p.xacc0[gi], p.coef);
-        const double dx = sub_nofma(xpe, x0e);
-        const double dg = bb_dgrad(gv, xhe, x0e, p.tau);
-        const double dh = sub_nofma(x1, xhe);
-        v[0] = fma(dx, dg, v[0]);
-        v[1] = fma(dg, dg, v[1]);
-        v[2] = fma(dh, dh, v[2]);
-        v[3] += fabs(x1);
-        v[4] = fmax(v[4], fabs(x1));
+      if (MODE == 0) {
+        const double x1 = nside_adj_sums(gv, p.x0[gi], p.xp[gi], p.accel ? p.xacc0[gi] : 0.0, p.xhat[gi], p.accel, p.coef, p.tau, v);
         if (p.accel) p.x1[gi] = x1;
       }
     }
   }
-  block_reduce<6>(v, s_scr, 4);
-  if (tid == 0) {
-#pragma unroll
-    for (int k = 0; k < 6; ++k) store_partial(p.red + (uint64_t)blockIdx.x * 8 + k, v[k]);
-  }
-  if (!arrive_last(p.counter, gridDim.x, s_flag)) return;
-  double w[6] = {0, 0, 0, 0, 0, 0};
-  for (uint32_t i = tid; i < gridDim.x; i += FH_WG) {
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-      const double r = load_partial(p.red + (uint64_t)i * 8 + k);
-      if (k == 4) w[k] = fmax(w[k], r); else w[k] += r;
-    }
-  }
-  block_reduce<6>(w, s_scr, 4);
-  if (tid == 0) {
-    scal_store(p.out + S_DXDG, w[0]); scal_store(p.out + S_DG2, w[1]); scal_store(p.out + S_XH2_ADJ, w[2]);
-    scal_store(p.out + S_GSUM_ADJ, w[3]); scal_store(p.out + S_GMAX_ADJ, w[4]); scal_store(p.out + S_FSQ_ADJ, w[5]);
-    publish_seq(p.out, p.seq);
-    __hip_atomic_store(p.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+  finish_records<6, 4>(v, p.red, blockIdx.x, gridDim.x, p.counter, p.out, p.seq, s_scr, s_flag, NoRecords(),
+                       [&](double (&w)[6]) { store_adj_scalars(p.out, w); });
 }
 
 // ---- the instantiations (ONE table for fh_conv_part.hip, the extern declarations and the dispatch) ----

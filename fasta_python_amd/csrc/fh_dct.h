@@ -20,14 +20,14 @@
 //     k_dct_tr                         transpose (a2, b1) -> rows b1 of length N2
 //     k_dct_rows<LDSN, CONJ>           N1 row transforms of length N2
 //     k_dct_post_fwd / k_dct_post_adj  transpose (b1, b2) -> k = b1 + N1 b2, the post-twiddle and z = d y with the loss sum (the Makhoul scatter
-//                                      and k_sp_adj's n-side epilogue in g1's one owner), the finaliser
+//                                      and the n-side epilogue (fh_nside.h) in g1's one owner), the finaliser
 // LDSN in {128, 512, 2048} is the row-length class: two buffers of LDSN double2 (4 / 16 / 64 KiB), so that short rows do not pay 64 KiB of
 // occupancy; a workgroup takes LDSN / L rows (at most DCT_MAX_ROWS).  The geometry is ONE rule on the host (csrc/fh_host_launch.h:dct_shape_for).
 // No kernel reads or writes beyond N: every tile access is guarded by the matrix extent, ragged tiles included.  N <= 2^22, so every index
 // fits 32 bits; byte offsets are formed by pointer arithmetic in 64 bits.  Elementwise solver arithmetic runs with FMA contraction off
 // (fwd_point, prox_scalar, sub_nofma, bb_dgrad: fh_device.h); the transform's own arithmetic may contract.
 #pragma once
-#include "fh_device.h"
+#include "fh_records.h"
 
 #define DCT_ROW_CAP 2048                           // longest row transform: two ping-pong buffers of 2048 double2 = 64 KiB of LDS
 #define DCT_MAXRAD 12                              // radices of a row (2048 = 4^5 * 2: 6; all twos would be 11)
@@ -175,15 +175,7 @@ __device__ __forceinline__ double dct_fwd_element(const DctFwdP& p, uint32_t i, 
   const double xav = p.xacc0 ? p.xacc0[i] : 0.0;
   const double xhe = fwd_point(x0e, g0e, p.tau);
   const double xpe = prox_scalar_rt(p.px.kind, xhe, p.px, level);
-  const double dx = sub_nofma(xpe, x0e);
-  const double dh = sub_nofma(xpe, xhe);
-  v[1] = fma(dx, g0e, v[1]);
-  v[2] = fma(dx, dx, v[2]);
-  v[3] = fma(dh, dh, v[3]);
-  v[4] = fma(g0e, g0e, v[4]);
-  v[5] += fabs(xpe);
-  v[6] = fmax(v[6], fabs(xpe));
-  v[7] = fma(sub_nofma(x0e, xpe), sub_nofma(xpe, xav), v[7]);
+  nside_fwd_sums<1>(x0e, g0e, xhe, xpe, xav, v);
   p.xhat[i] = xhe;
   p.xp[i] = xpe;
   return xpe;
@@ -204,36 +196,9 @@ __device__ __forceinline__ void dct_fwd_out(const DctFwdP& p, uint32_t k, d2 V, 
 
 // records in index order, the scalar block and the sequence number: the last workgroup of the launch that ends K-fwd
 __device__ __forceinline__ void dct_fwd_finish(const DctFwdP& p, double (&v)[8], double* s_scr, unsigned* s_flag) {
-  const uint32_t tid = threadIdx.x;
-  block_reduce<8>(v, s_scr, S_GMAX);
-  if (tid == 0) {
-#pragma unroll
-    for (int k = 0; k < 8; ++k) store_partial(p.red + (uint64_t)blockIdx.x * 8 + k, v[k]);
-  }
-  if (!arrive_last(p.counter, gridDim.x, s_flag)) return;
-  double w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  for (uint32_t i = tid; i < gridDim.x; i += FH_WG) {
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const double r = load_partial(p.red + (uint64_t)i * 8 + k);
-      if (k == S_GMAX) w[k] = fmax(w[k], r); else w[k] += r;
-    }
-  }
-  for (uint32_t i = tid; i < p.nred_n; i += FH_WG) {
-#pragma unroll
-    for (int k = 1; k < 8; ++k) {
-      const double r = load_partial(p.red_n + (uint64_t)i * 8 + k);
-      if (k == S_GMAX) w[k] = fmax(w[k], r); else w[k] += r;
-    }
-  }
-  block_reduce<8>(w, s_scr, S_GMAX);
-  if (tid == 0) {
-#pragma unroll
-    for (int k = 0; k < 8; ++k) scal_store(p.out + k, w[k]);
-    scal_store(p.out + S_ALPHA, 0.0);
-    publish_seq(p.out, p.seq);
-    __hip_atomic_store(p.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+  finish_records<8, S_GMAX>(v, p.red, blockIdx.x, gridDim.x, p.counter, p.out, p.seq, s_scr, s_flag,
+                            [&](double (&w)[8]) { add_records<1, 8, S_GMAX>(w, p.red_n, p.nred_n); },      // two-level: k_dct_pre_fwd's n-side sums
+                            [&](double (&w)[8]) { store_fwd_scalars(p.out, w, 0.0); });
 }
 
 // the m-side residual of row k: r = z' - b (z' = z or its FISTA extrapolation) and the loss term at z'
@@ -261,49 +226,18 @@ __device__ __forceinline__ d2 dct_adj_in(const DctAdjP& p, uint32_t k, double* f
   return V;
 }
 
-// g1[i] = g and k_sp_adj's n-side epilogue of element i, in its one owner; v = dxdg, dg2, xh2, gsum, gmax
+// g1[i] = g and the n-side epilogue of element i, in its one owner; v = dxdg, dg2, xh2, gsum, gmax, fsq
 __device__ __forceinline__ void dct_adj_element(const DctAdjP& p, uint32_t i, double g, double (&v)[6]) {
-#pragma clang fp contract(off)
   p.g1[i] = g;
   if (p.mode != 0) return;
-  const double x0e = p.x0[i], xpe = p.xp[i], xhe = p.xhat[i];
-  double x1 = xpe;
-  if (p.accel) x1 = extrapolate(xpe, p.xacc0[i], p.coef);
-  const double dx = sub_nofma(xpe, x0e);
-  const double dg = bb_dgrad(g, xhe, x0e, p.tau);
-  const double dh = sub_nofma(x1, xhe);
-  v[0] = fma(dx, dg, v[0]);
-  v[1] = fma(dg, dg, v[1]);
-  v[2] = fma(dh, dh, v[2]);
-  v[3] += fabs(x1);
-  v[4] = fmax(v[4], fabs(x1));
+  const double x1 = nside_adj_sums(g, p.x0[i], p.xp[i], p.accel ? p.xacc0[i] : 0.0, p.xhat[i], p.accel, p.coef, p.tau, v);
   if (p.accel) p.x1[i] = x1;
 }
 
 __device__ __forceinline__ void dct_adj_finish(const DctAdjP& p, double (&v)[6], double* s_scr, unsigned* s_flag) {
-  const uint32_t tid = threadIdx.x;
-  block_reduce<6>(v, s_scr, 4);
-  if (tid == 0) {
-#pragma unroll
-    for (int k = 0; k < 6; ++k) store_partial(p.red + (uint64_t)blockIdx.x * 8 + k, v[k]);
-  }
-  if (!arrive_last(p.counter, gridDim.x, s_flag)) return;
-  double w[6] = {0, 0, 0, 0, 0, 0};
-  for (uint32_t i = tid; i < gridDim.x; i += FH_WG) {
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-      const double r = load_partial(p.red + (uint64_t)i * 8 + k);
-      if (k == 4) w[k] = fmax(w[k], r); else w[k] += r;
-    }
-  }
-  for (uint32_t i = tid; i < p.nred_f; i += FH_WG) w[5] += load_partial(p.red_f + i);
-  block_reduce<6>(w, s_scr, 4);
-  if (tid == 0) {
-    scal_store(p.out + S_DXDG, w[0]); scal_store(p.out + S_DG2, w[1]); scal_store(p.out + S_XH2_ADJ, w[2]);
-    scal_store(p.out + S_GSUM_ADJ, w[3]); scal_store(p.out + S_GMAX_ADJ, w[4]); scal_store(p.out + S_FSQ_ADJ, w[5]);
-    publish_seq(p.out, p.seq);
-    __hip_atomic_store(p.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+  finish_records<6, 4>(v, p.red, blockIdx.x, gridDim.x, p.counter, p.out, p.seq, s_scr, s_flag,
+                       [&](double (&w)[6]) { add_column(w[5], p.red_f, p.nred_f); },                      // two-level: k_dct_pre_adj's loss sums
+                       [&](double (&w)[6]) { store_adj_scalars(p.out, w); });
 }
 
 // ---- N <= row cap: one launch per direction, one workgroup -----------------------------------------------------------------------------------
@@ -412,11 +346,7 @@ __global__ __launch_bounds__(FH_WG) void k_dct_pre_fwd(const DctFwdP p) {
     if (a1 < N1 && a2 < N2) out[a2 * N1 + a1] = s_t[t.tx][cc];
   }
   if (p.mode != 0) return;                          // a plain operand has no n-side sums
-  block_reduce<8>(v, s_scr, S_GMAX);
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int k = 0; k < 8; ++k) store_partial(const_cast<double*>(p.red_n) + (uint64_t)blockIdx.x * 8 + k, v[k]);
-  }
+  publish_record<8, S_GMAX>(v, const_cast<double*>(p.red_n), blockIdx.x, s_scr);
 }
 
 // out (cols x rows) = in (rows x cols) transposed, complex
@@ -473,8 +403,7 @@ __global__ __launch_bounds__(FH_WG) void k_dct_pre_adj(const DctAdjP p) {
     const uint32_t a2 = t.c0 + cc, a1 = t.r0 + t.tx;
     if (a1 < N1 && a2 < N2) p.op.w0[a2 * N1 + a1] = s_t[t.tx][cc];
   }
-  block_reduce<1>(v, s_scr, -1);
-  if (threadIdx.x == 0) store_partial(const_cast<double*>(p.red_f) + blockIdx.x, v[0]);
+  publish_record<1, -1>(v, const_cast<double*>(p.red_f), blockIdx.x, s_scr);
 }
 
 // last launch of K-adj: v[n], n = b1 + N1 b2, from the N1 x N2 matrix (b1, b2) in w0; g1[dct_src(n)] = Re v[n] and the n-side epilogue, the finaliser

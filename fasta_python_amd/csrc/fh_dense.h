@@ -21,6 +21,7 @@
 //       Algorithmic HBM bytes: m*n*8 (A) + (2m [+m]) + 4n reads + n [+n] writes (+ partials, <0.2 %).
 #pragma once
 #include "fh_device.h"
+#include "fh_records.h"
 
 struct FwdP {
   const double* A;
@@ -56,6 +57,9 @@ __device__ __forceinline__ d2 xprox_pair(const FwdP& p, uint32_t c, double level
   return xv;
 }
 
+// (k_fwd_dense keeps its own text of the n-side sums and of the finaliser: routed through fh_nside.h / fh_records.h it computes the same values but is not
+// byte-identical to its measured form -- instruction order and register numbers move -- and this kernel is held to byte identity,
+// profiles/nside_refactor.txt section 2.  The same goes for k_diff_sq below.)
 template <int R, int NT, int KIND, int F32 = 0>
 __global__ __launch_bounds__(FH_WG) void k_fwd_dense(const FwdP p) {
   typedef typename PieceOf<F32>::type PT;
@@ -218,25 +222,11 @@ struct AdjP {
 
 #define ADJ_MAX_SLAB 2048
 
-// n-side epilogue for one element: BB terms and (optionally) FISTA extrapolation.
+// n-side epilogue for one element (nside_adj_sums); a padding element has no share in the sums and its x1 is zero.
 // v: dxdg, dg2, xh2, gsum, gmax
 __device__ __forceinline__ double bb_element(const AdjP& p, double g1, double x0, double xp, double xacc0,
                                              double xhat, bool valid, double (&v)[5]) {
-  double x1 = xp;
-  if (p.accel) x1 = extrapolate(xp, xacc0, p.coef);
-  if (valid) {
-    const double dx = sub_nofma(xp, x0);
-    const double dg = bb_dgrad(g1, xhat, x0, p.tau);
-    const double dh = sub_nofma(x1, xhat);
-    v[0] = fma(dx, dg, v[0]);
-    v[1] = fma(dg, dg, v[1]);
-    v[2] = fma(dh, dh, v[2]);
-    v[3] += fabs(x1);
-    v[4] = fmax(v[4], fabs(x1));
-  } else {
-    x1 = 0.0;
-  }
-  return x1;
+  return valid ? nside_adj_sums(g1, x0, xp, xacc0, xhat, p.accel, p.coef, p.tau, v) : 0.0;
 }
 
 template <int CPT, int NT, int F32 = 0>
@@ -324,30 +314,10 @@ __global__ __launch_bounds__(FH_WG) void k_adj_dense(const AdjP p) {
       if (p.accel) reinterpret_cast<d2*>(p.x1)[c] = x1v;
     }
   }
-  block_reduce<5>(v, s_scr, 4);
-  if (tid == 0) {
-#pragma unroll
-    for (int k = 0; k < 5; ++k) store_partial(p.red_bb + (uint64_t)cc * 8 + k, v[k]);
-  }
-
-  // ---- last column-chunk finaliser: ordered scalar sums ------------------------------------------
-  if (!arrive_last(p.fin_counter, p.ncc, s_flag)) return;
-  double w[6] = {0, 0, 0, 0, 0, 0};   // dxdg, dg2, xh2, gsum, gmax, fsq
-  for (uint32_t i = tid; i < p.ncc; i += FH_WG) {
-#pragma unroll
-    for (int k = 0; k < 5; ++k) {
-      const double t = load_partial(p.red_bb + (uint64_t)i * 8 + k);
-      if (k == 4) w[k] = fmax(w[k], t); else w[k] += t;
-    }
-  }
-  for (uint32_t i = tid; i < p.nslab; i += FH_WG) w[5] += load_partial(p.red_f + i);
-  block_reduce<6>(w, s_scr, 4);
-  if (tid == 0) {
-    scal_store(p.out + S_DXDG, w[0]); scal_store(p.out + S_DG2, w[1]); scal_store(p.out + S_XH2_ADJ, w[2]);
-    scal_store(p.out + S_GSUM_ADJ, w[3]); scal_store(p.out + S_GMAX_ADJ, w[4]); scal_store(p.out + S_FSQ_ADJ, w[5]);
-    publish_seq(p.out, p.seq);
-    __hip_atomic_store(p.fin_counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+  // ---- one record per column chunk; the last chunk finaliser: ordered scalar sums -------------------
+  finish_records<5, 4, 6>(v, p.red_bb, cc, p.ncc, p.fin_counter, p.out, p.seq, s_scr, s_flag,
+                          [&](double (&w)[6]) { add_column(w[5], p.red_f, p.nslab); },      // fsq: one loss sum per slab
+                          [&](double (&w)[6]) { store_adj_scalars(p.out, w); });
 }
 
 // n-side epilogue as its own launch: used after the RCCL all-reduce when A is row-sharded
@@ -376,22 +346,8 @@ static __global__ __launch_bounds__(FH_WG) void k_bb_epilogue(const AdjP p_in, u
     x1v.y = bb_element(p, g.y, x0v.y, xpv.y, xav.y, xhv.y, 2u * c + 1u < p.n, v);
     if (p.accel) reinterpret_cast<d2*>(p.x1)[c] = x1v;
   }
-  block_reduce<5>(v, s_scr, 4);
-  if (tid == 0) {
-#pragma unroll
-    for (int k = 0; k < 5; ++k) store_partial(p.red_bb + (uint64_t)blockIdx.x * 8 + k, v[k]);
-  }
-  if (!arrive_last(p.fin_counter, nchunks, s_flag)) return;
-  double w[5] = {0, 0, 0, 0, 0};
-  for (uint32_t i = tid; i < nchunks; i += FH_WG) {
-#pragma unroll
-    for (int k = 0; k < 5; ++k) {
-      const double t = load_partial(p.red_bb + (uint64_t)i * 8 + k);
-      if (k == 4) w[k] = fmax(w[k], t); else w[k] += t;
-    }
-  }
-  block_reduce<5>(w, s_scr, 4);
-  if (tid == 0) {
+  // (seq = 0: the caller learns of the block from the end of the launch, no sequence number)
+  finish_records<5, 4>(v, p.red_bb, blockIdx.x, nchunks, p.fin_counter, p.out, 0u, s_scr, s_flag, NoRecords(), [&](double (&w)[5]) {
     p.out[S_DXDG] = w[0]; p.out[S_DG2] = w[1]; p.out[S_XH2_ADJ] = w[2];
     p.out[S_GSUM_ADJ] = w[3]; p.out[S_GMAX_ADJ] = w[4];
     p.out[S_FSQ_ADJ] = *fsq_src;
@@ -400,8 +356,7 @@ static __global__ __launch_bounds__(FH_WG) void k_bb_epilogue(const AdjP p_in, u
 #pragma unroll
       for (int k = 0; k < 16; ++k) mirror[k] = p.out[k];
     }
-    __hip_atomic_store(p.fin_counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+  });
 }
 
 // ---- utility kernels (non-template kernels are `static`: this header is included by several translation units) ------------

@@ -11,6 +11,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "fh_nside.h"        // fwd_point, extrapolate, bb_dgrad, sub_nofma and the n-side sums of one element: host and device
 
 typedef double d2 __attribute__((ext_vector_type(2)));   // one 16-byte global access
 typedef float f4 __attribute__((ext_vector_type(4)));    // one 16-byte piece of a float32-storage matrix: four columns
@@ -112,29 +113,6 @@ __device__ __forceinline__ double prox_scalar_rt(int kind, double x, const ProxP
   }
 }
 
-// forward (gradient) step x0 - tau*g0, two roundings as in fasta/__init__.py:181
-__device__ __forceinline__ double fwd_point(double x0, double g0, double tau) {
-#pragma clang fp contract(off)
-  double s = tau * g0;
-  return x0 - s;
-}
-
-// z + coef*(z - zprev), fasta/__init__.py:242-243 evaluation order
-__device__ __forceinline__ double extrapolate(double v, double vprev, double coef) {
-#pragma clang fp contract(off)
-  double d = v - vprev;
-  double s = coef * d;
-  return v + s;
-}
-
-// Dg = g1 + (xhat - x0)/tau, fasta/__init__.py:254
-__device__ __forceinline__ double bb_dgrad(double g1, double xhat, double x0, double tau) {
-#pragma clang fp contract(off)
-  double d = xhat - x0;
-  double q = d / tau;
-  return g1 + q;
-}
-
 // The same with the quotient by a launch-uniform tau formed from its reciprocal (rtau = 1/tau, correctly rounded, computed once
 // per thread): q = d*rtau, one exact-remainder correction (Markstein).  The result is the correctly rounded quotient except in
 // rare corner cases (tau's significand all ones, subnormal quotients), where it is off by one ulp -- used ONLY where Dg feeds the
@@ -149,10 +127,6 @@ __device__ __forceinline__ double bb_dgrad_rcp(double g1, double xhat, double x0
   return g1 + q;
 }
 
-__device__ __forceinline__ double sub_nofma(double a, double b) {
-#pragma clang fp contract(off)
-  return a - b;
-}
 __device__ __forceinline__ double add_nofma(double a, double b) {
 #pragma clang fp contract(off)
   return a + b;

@@ -145,30 +145,17 @@ __global__ __launch_bounds__(FH_WG) void k_mc_prologue(const McProP p) {
       if (!valid) q = 0.0;
       xq[l] = q;
       pn2 += q * q;
-      if (valid) {
-        const double dx = q - x0v[l];
-        const double dh = q - xh[l];
-        v[0] = fma(dx, g0v[l], v[0]);
-        v[1] = fma(dx, dx, v[1]);
-        v[2] = fma(dh, dh, v[2]);
-        v[3] = fma(g0v[l], g0v[l], v[3]);
-        if (p.px.kind != PX_GROUP) v[4] += fabs(q);
-        v[5] = fmax(v[5], fabs(q));
-      }
+    }
+    // the n-side sums, a column pair at a time next to its 16 bytes of x_accel0
+#pragma unroll
+    for (int l = 0; l < LB; l += 2) {
+      d2 a = {0.0, 0.0};
+      if (p.xacc0) a = *reinterpret_cast<const d2*>(p.xacc0 + o + l);
+#pragma unroll
+      for (int h = 0; h < 2; ++h)
+        if (rowok && (uint32_t)(l + h) < p.L) nside_fwd_sums<0>(x0v[l + h], g0v[l + h], xh[l + h], xq[l + h], a[h], v, p.px.kind != PX_GROUP);
     }
     if (p.px.kind == PX_GROUP) v[4] = sqrt(pn2);
-    if (p.xacc0) {
-#pragma unroll
-      for (int l = 0; l < LB; l += 2) {
-        const d2 a = *reinterpret_cast<const d2*>(p.xacc0 + o + l);
-        if (rowok && (uint32_t)l < p.L) v[6] = fma(x0v[l] - xq[l], xq[l] - a.x, v[6]);
-        if (rowok && (uint32_t)(l + 1) < p.L) v[6] = fma(x0v[l + 1] - xq[l + 1], xq[l + 1] - a.y, v[6]);
-      }
-    } else {
-#pragma unroll
-      for (int l = 0; l < LB; ++l)
-        if (rowok && (uint32_t)l < p.L) v[6] = fma(x0v[l] - xq[l], xq[l], v[6]);
-    }
 #pragma unroll
     for (int l = 0; l < LB; l += 2) {
       *reinterpret_cast<d2*>(p.xhat + o + l) = (d2){xh[l], xh[l + 1]};
@@ -176,11 +163,7 @@ __global__ __launch_bounds__(FH_WG) void k_mc_prologue(const McProP p) {
     }
     mc_pack_row<LB>(p.xs, p.ld2, row, xq);
   }
-  block_reduce<7>(v, s_scr, 5);
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int k = 0; k < 7; ++k) store_partial(p.red_n + (uint64_t)blockIdx.x * 8 + 1 + k, v[k]);
-  }
+  publish_record<7, 5>(v, p.red_n + 1, blockIdx.x, s_scr);
 }
 
 // sum of the g terms of an (n, L) matrix held as (nv, LB): out[S_GSUM] = sum |x| (group = 0) or sum of row norms (group = 1), out[S_GMAX] = max |x|
@@ -299,30 +282,10 @@ __global__ __launch_bounds__(FH_WG) __attribute__((amdgpu_waves_per_eu(1, 2))) v
     }
     __syncthreads();
   }
-  {
-    double v[1] = {fpart};
-    block_reduce<1>(v, s_scr, -1);
-    if (tid == 0) store_partial(p.red_m + blockIdx.x, v[0]);
-  }
-  if (arrive_last(p.counter, gridDim.x, s_flag)) {
-    double v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    for (uint32_t i = tid; i < gridDim.x; i += FH_WG) v[0] += load_partial(p.red_m + i);
-    for (uint32_t i = tid; i < p.nred_n; i += FH_WG) {
-#pragma unroll
-      for (int k = 1; k < 8; ++k) {
-        const double t = load_partial(p.red_n + (uint64_t)i * 8 + k);
-        if (k == S_GMAX) v[k] = fmax(v[k], t); else v[k] += t;
-      }
-    }
-    block_reduce<8>(v, s_scr, S_GMAX);
-    if (tid == 0) {
-#pragma unroll
-      for (int k = 0; k < 8; ++k) scal_store(p.out + k, v[k]);
-      scal_store(p.out + S_ALPHA, 0.0);
-      publish_seq(p.out, p.seq);
-      __hip_atomic_store(p.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
+  double v[1] = {fpart};
+  finish_records<1, S_GMAX, 8>(v, p.red_m, blockIdx.x, gridDim.x, p.counter, p.out, p.seq, s_scr, s_flag,
+                               [&](double (&w)[8]) { add_records<1, 8, S_GMAX>(w, p.red_n, p.nred_n); },      // the prologue's n-side sums
+                               [&](double (&w)[8]) { store_fwd_scalars(p.out, w, 0.0); });
 }
 
 // ---- K-adj, LB columns --------------------------------------------------------------------------------------------------------------------
@@ -464,20 +427,10 @@ __global__ __launch_bounds__(FH_WG) __attribute__((amdgpu_waves_per_eu(1, 4))) v
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
           const bool valid = grow < p.n && (uint32_t)(2 * l + h) < p.L;
-          double x1 = xpv[h];
-          if (p.accel) x1 = extrapolate(xpv[h], xav[h], p.coef);
+          double x1 = 0.0;
           if (valid) {
-            const double dx = sub_nofma(xpv[h], x0v[h]);
-            const double dg = bb_dgrad(g[l][h], xhv[h], x0v[h], p.tau);
-            const double dh = sub_nofma(x1, xhv[h]);
-            v[0] = fma(dx, dg, v[0]);
-            v[1] = fma(dg, dg, v[1]);
-            v[2] = fma(dh, dh, v[2]);
-            if (!p.group) v[3] += fabs(x1);
-            v[4] = fmax(v[4], fabs(x1));
+            x1 = nside_adj_sums(g[l][h], x0v[h], xpv[h], xav[h], xhv[h], p.accel, p.coef, p.tau, v, !p.group);
             n2 = add_nofma(n2, x1 * x1);
-          } else {
-            x1 = 0.0;
           }
           x1v[h] = x1;
         }
@@ -486,30 +439,10 @@ __global__ __launch_bounds__(FH_WG) __attribute__((amdgpu_waves_per_eu(1, 4))) v
       if (p.group) v[3] += sqrt(n2);
     }
   }
-  block_reduce<5>(v, s_scr, 4);
-  if (tid == 0) {
-#pragma unroll
-    for (int k = 0; k < 5; ++k) store_partial(p.red_bb + (uint64_t)cc * 8 + k, v[k]);
-  }
-
-  // ---- last column-chunk finaliser: ordered scalar sums ------------------------------------------
-  if (!arrive_last(p.fin_counter, p.ncc, s_flag)) return;
-  double w[6] = {0, 0, 0, 0, 0, 0};   // dxdg, dg2, xh2, gsum, gmax, fsq
-  for (uint32_t i = tid; i < p.ncc; i += FH_WG) {
-#pragma unroll
-    for (int k = 0; k < 5; ++k) {
-      const double t = load_partial(p.red_bb + (uint64_t)i * 8 + k);
-      if (k == 4) w[k] = fmax(w[k], t); else w[k] += t;
-    }
-  }
-  for (uint32_t i = tid; i < p.nslab; i += FH_WG) w[5] += load_partial(p.red_f + i);
-  block_reduce<6>(w, s_scr, 4);
-  if (tid == 0) {
-    scal_store(p.out + S_DXDG, w[0]); scal_store(p.out + S_DG2, w[1]); scal_store(p.out + S_XH2_ADJ, w[2]);
-    scal_store(p.out + S_GSUM_ADJ, w[3]); scal_store(p.out + S_GMAX_ADJ, w[4]); scal_store(p.out + S_FSQ_ADJ, w[5]);
-    publish_seq(p.out, p.seq);
-    __hip_atomic_store(p.fin_counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+  // ---- one record per column chunk; the last chunk finaliser: ordered scalar sums -------------------
+  finish_records<5, 4, 6>(v, p.red_bb, cc, p.ncc, p.fin_counter, p.out, p.seq, s_scr, s_flag,
+                          [&](double (&w)[6]) { add_column(w[5], p.red_f, p.nslab); },      // fsq: one loss sum per slab
+                          [&](double (&w)[6]) { store_adj_scalars(p.out, w); });
 }
 
 // ---- the instantiations (ONE table for the explicit instantiations of fh_multi_part.hip, their extern declarations and the dispatch) ----

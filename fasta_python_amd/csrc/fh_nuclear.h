@@ -6,8 +6,8 @@
 //   k_id_fwd       K-fwd, elementwise: xhat = x0 - tau*g0, xprox = prox(xhat) for the kinds IDENTITY / SHRINK / NONNEG / BOX (the same device
 //                  functions, FMA contraction off, as every vector kernel: bit-exact outputs) -- or, for FH_PROX_NUCLEAR, xhat and xprox as the
 //                  thresholding below left them --, z1 = xprox, the loss sum and the seven n-side sums.  Mode 1: z = x0 and the loss sum alone.
-//   k_id_adj       K-adj, elementwise: x1 = xprox + coef*(xprox - x_accel0), g1 = loss_grad(x1), the loss at x1 and the n-side epilogue of
-//                  k_sp_adj.  Mode 1: g1 = loss_grad(z) (or z itself, fh_apply).
+//   k_id_adj       K-adj, elementwise: x1 = xprox + coef*(xprox - x_accel0), g1 = loss_grad(x1), the loss at x1 and the n-side epilogue
+//                  (its own text of nside_adj_sums, see below).  Mode 1: g1 = loss_grad(z) (or z itself, fh_apply).
 //   Both are grid-stride launches, a lane's elements in index order, workgroup records summed in index order by the last workgroup to arrive:
 //   no float atomics, bitwise repeatable.
 //
@@ -87,40 +87,13 @@ static __global__ __launch_bounds__(FH_WG) void k_id_fwd(const IdFwdP p) {
     }
     p.z[j] = xpe;
     v[0] += loss_term(xpe, p.b[j], p.loss);
-    const double dx = sub_nofma(xpe, x0e);
-    const double dh = sub_nofma(xpe, xhe);
-    v[1] = fma(dx, g0e, v[1]);
-    v[2] = fma(dx, dx, v[2]);
-    v[3] = fma(dh, dh, v[3]);
-    v[4] = fma(g0e, g0e, v[4]);
-    v[5] += fabs(xpe);
-    v[6] = fmax(v[6], fabs(xpe));
-    v[7] = fma(sub_nofma(x0e, xpe), sub_nofma(xpe, xav), v[7]);
+    nside_fwd_sums<1>(x0e, g0e, xhe, xpe, xav, v);
   }
-  block_reduce<8>(v, s_scr, S_GMAX);
-  if (tid == 0) {
-#pragma unroll
-    for (int k = 0; k < 8; ++k) store_partial(p.red + (uint64_t)blockIdx.x * 8 + k, v[k]);
-  }
-  if (!arrive_last(p.counter, gridDim.x, s_flag)) return;
-  double w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  for (uint32_t i = tid; i < gridDim.x; i += FH_WG) {
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const double t = load_partial(p.red + (uint64_t)i * 8 + k);
-      if (k == S_GMAX) w[k] = fmax(w[k], t); else w[k] += t;
-    }
-  }
-  block_reduce<8>(w, s_scr, S_GMAX);
-  if (tid == 0) {
-    double alpha = 0.0;
+  finish_records<8, S_GMAX>(v, p.red, blockIdx.x, gridDim.x, p.counter, p.out, p.seq, s_scr, s_flag, NoRecords(), [&](double (&w)[8]) {
+    double alpha = 0.0;                      // the thresholding's g terms and the rank it kept stand in for the elementwise ones
     if (p.mode == 0 && p.given) { w[S_GSUM] = p.nuc[0]; alpha = p.nuc[1]; w[S_GMAX] = p.nuc[2]; }
-#pragma unroll
-    for (int k = 0; k < 8; ++k) scal_store(p.out + k, w[k]);
-    scal_store(p.out + S_ALPHA, alpha);
-    publish_seq(p.out, p.seq);
-    __hip_atomic_store(p.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+    store_fwd_scalars(p.out, w, alpha);
+  });
 }
 
 struct IdAdjP {
@@ -139,6 +112,8 @@ struct IdAdjP {
   double* out;
 };
 
+// (k_id_adj keeps its own text of the n-side epilogue and of the finaliser: the gradient is taken AT x1, so the extrapolation has to be formed before
+// nside_adj_sums would form it, and through the shared code the small launch (64 x 64) measured 0.27 us slower; profiles/nside_refactor.txt section 6.)
 static __global__ __launch_bounds__(FH_WG) void k_id_adj(const IdAdjP p) {
 #pragma clang fp contract(off)
   __shared__ __attribute__((aligned(16))) double s_scr[4 * 8];
@@ -238,16 +213,8 @@ static __global__ __launch_bounds__(FH_WG) void k_nuc_load(const NucLoadP p) {
     }
     p.W[e] = val;
   }
-  block_reduce<1>(v, s_scr, -1);
-  if (tid == 0) store_partial(p.red + blockIdx.x, v[0]);
-  if (!arrive_last(p.counter, gridDim.x, s_flag)) return;
-  double w[1] = {0.0};
-  for (uint32_t i = tid; i < gridDim.x; i += FH_WG) w[0] += load_partial(p.red + i);
-  block_reduce<1>(w, s_scr, -1);
-  if (tid == 0) {
-    store_partial(p.fro2, w[0]);
-    __hip_atomic_store(p.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+  finish_records<1, -1>(v, p.red, blockIdx.x, gridDim.x, p.counter, nullptr, 0u, s_scr, s_flag, NoRecords(),      // (no scalar block, no sequence number)
+                        [&](double (&w)[1]) { store_partial(p.fro2, w[0]); });
 }
 
 // Pair k of step r of a sweep over nb blocks: the round-robin tournament by the circle method over nbe = nb rounded up to even (the last

@@ -15,7 +15,7 @@
 //                  xprox[i,l] * (.5 * w[i,l] + c[i,l]) over the valid entries, xprox read from the row-major copy.  Last workgroup: the
 //                  m-side records, then the prologue's records, in index order.
 //   k_qd_grad      the adjoint direction, elementwise, one lane per row: w' = w or its FISTA extrapolation (Q is linear: that IS Q applied to
-//                  the extrapolated iterate), g1 = w' + c, k_mc_adj's n-side epilogue, and FH_S_FSQ_ADJ = sum x1' * (.5 * w' + c).  Never reads Q.
+//                  the extrapolated iterate), g1 = w' + c, the n-side epilogue (fh_nside.h), and FH_S_FSQ_ADJ = sum x1' * (.5 * w' + c).  Never reads Q.
 // Finalisers are arrive_last only: no spin waits, no co-residency assumption.  No float atomics: bitwise repeatable.
 #pragma once
 #include "fh_multi.h"
@@ -67,30 +67,17 @@ __global__ __launch_bounds__(FH_WG) void k_qd_prologue(const McProP p) {
       if (!valid) q = 0.0;
       xq[l] = q;
       pn2 += q * q;
-      if (valid) {
-        const double dx = q - x0v[l];
-        const double dh = q - xh[l];
-        v[0] = fma(dx, g0v[l], v[0]);
-        v[1] = fma(dx, dx, v[1]);
-        v[2] = fma(dh, dh, v[2]);
-        v[3] = fma(g0v[l], g0v[l], v[3]);
-        if (p.px.kind != PX_GROUP) v[4] += fabs(q);
-        v[5] = fmax(v[5], fabs(q));
-      }
+    }
+    // the n-side sums, a column pair at a time next to its 16 bytes of x_accel0
+#pragma unroll
+    for (int l = 0; l < LB; l += 2) {
+      d2 a = {0.0, 0.0};
+      if (p.xacc0) a = *reinterpret_cast<const d2*>(p.xacc0 + o + l);
+#pragma unroll
+      for (int h = 0; h < 2; ++h)
+        if (rowok && (uint32_t)(l + h) < p.L) nside_fwd_sums<0>(x0v[l + h], g0v[l + h], xh[l + h], xq[l + h], a[h], v, p.px.kind != PX_GROUP);
     }
     if (p.px.kind == PX_GROUP) v[4] = sqrt(pn2);
-    if (p.xacc0) {
-#pragma unroll
-      for (int l = 0; l < LB; l += 2) {
-        const d2 a = *reinterpret_cast<const d2*>(p.xacc0 + o + l);
-        if (rowok && (uint32_t)l < p.L) v[6] = fma(x0v[l] - xq[l], xq[l] - a.x, v[6]);
-        if (rowok && (uint32_t)(l + 1) < p.L) v[6] = fma(x0v[l + 1] - xq[l + 1], xq[l + 1] - a.y, v[6]);
-      }
-    } else {
-#pragma unroll
-      for (int l = 0; l < LB; ++l)
-        if (rowok && (uint32_t)l < p.L) v[6] = fma(x0v[l] - xq[l], xq[l], v[6]);
-    }
 #pragma unroll
     for (int l = 0; l < LB; l += 2) {
       *reinterpret_cast<d2*>(p.xhat + o + l) = (d2){xh[l], xh[l + 1]};
@@ -98,11 +85,7 @@ __global__ __launch_bounds__(FH_WG) void k_qd_prologue(const McProP p) {
     }
     mc_pack_row<LB>(p.xs, p.ld2, row, xq);
   }
-  block_reduce<7>(v, s_scr, 5);
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int k = 0; k < 7; ++k) store_partial(p.red_n + (uint64_t)blockIdx.x * 8 + 1 + k, v[k]);
-  }
+  publish_record<7, 5>(v, p.red_n + 1, blockIdx.x, s_scr);
 }
 
 // one entry's share of f: x * (.5 * w + c), three roundings
@@ -197,6 +180,8 @@ __global__ __launch_bounds__(FH_WG) __attribute__((amdgpu_waves_per_eu(1, 2))) v
     }
     __syncthreads();
   }
+  // (This kernel keeps its own text of the finaliser -- what finish_records<1, S_GMAX, 8> does, fh_records.h: routed through it, a small K-fwd
+  // (n = 512 .. 1024, L = 4) measured 0.25 us slower on the MI355X, below the parent's band; profiles/nside_refactor.txt section 6.)
   {
     double v[1] = {fpart};
     block_reduce<1>(v, s_scr, -1);
@@ -269,21 +254,11 @@ __global__ __launch_bounds__(FH_WG) void k_qd_grad(const QdGradP p) {
         if (p.accel) we = extrapolate(wv[h], wa[h], p.coef);
         const double g = valid ? add_nofma(we, cv[h]) : 0.0;
         gv[h] = g;
-        double x1 = xpv[h];
-        if (p.accel) x1 = extrapolate(xpv[h], xav[h], p.coef);
+        double x1 = 0.0;
         if (valid && p.mode == 0) {
-          const double dx = sub_nofma(xpv[h], x0v[h]);
-          const double dg = bb_dgrad(g, xhv[h], x0v[h], p.tau);
-          const double dh = sub_nofma(x1, xhv[h]);
-          v[0] = fma(dx, dg, v[0]);
-          v[1] = fma(dg, dg, v[1]);
-          v[2] = fma(dh, dh, v[2]);
-          if (!p.group) v[3] += fabs(x1);
-          v[4] = fmax(v[4], fabs(x1));
+          x1 = nside_adj_sums(g, x0v[h], xpv[h], xav[h], xhv[h], p.accel, p.coef, p.tau, v, !p.group);
           n2 = add_nofma(n2, x1 * x1);
           v[5] = add_nofma(v[5], qd_term(x1, we, cv[h]));
-        } else {
-          x1 = 0.0;
         }
         x1v[h] = x1;
       }
@@ -292,27 +267,8 @@ __global__ __launch_bounds__(FH_WG) void k_qd_grad(const QdGradP p) {
     }
     if (p.mode == 0 && p.group) v[3] += sqrt(n2);
   }
-  block_reduce<6>(v, s_scr, 4);
-  if (tid == 0) {
-#pragma unroll
-    for (int k = 0; k < 6; ++k) store_partial(p.red + (uint64_t)blockIdx.x * 8 + k, v[k]);
-  }
-  if (!arrive_last(p.counter, gridDim.x, s_flag)) return;
-  double w[6] = {0, 0, 0, 0, 0, 0};
-  for (uint32_t i = tid; i < gridDim.x; i += FH_WG) {
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-      const double t = load_partial(p.red + (uint64_t)i * 8 + k);
-      if (k == 4) w[k] = fmax(w[k], t); else w[k] += t;
-    }
-  }
-  block_reduce<6>(w, s_scr, 4);
-  if (tid == 0) {
-    scal_store(p.out + S_DXDG, w[0]); scal_store(p.out + S_DG2, w[1]); scal_store(p.out + S_XH2_ADJ, w[2]);
-    scal_store(p.out + S_GSUM_ADJ, w[3]); scal_store(p.out + S_GMAX_ADJ, w[4]); scal_store(p.out + S_FSQ_ADJ, w[5]);
-    publish_seq(p.out, p.seq);
-    __hip_atomic_store(p.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+  finish_records<6, 4>(v, p.red, blockIdx.x, gridDim.x, p.counter, p.out, p.seq, s_scr, s_flag, NoRecords(),
+                       [&](double (&w)[6]) { store_adj_scalars(p.out, w); });
 }
 
 // ---- the instantiations: MC_FOR_EACH's shapes (ONE table for fh_quad_part.hip, the extern declarations and the dispatch) ----

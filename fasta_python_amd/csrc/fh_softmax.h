@@ -18,9 +18,9 @@
 //                   Outputs: the residual R (mv, LB) unless p.r is null (VALUE-ONLY mode); one loss record per workgroup (store_partial; inside the
 //                   workgroup: block_reduce's fixed order over the rows' terms, held by the lanes with c = 0).  Padding columns of R are written
 //                   as +0.0, padding rows are never touched (they are zero from the allocation).
-//                   With p.counter set the last-arriving workgroup (arrive_last) adds the records -- sm_sum_records: lane t takes records t, t + 256,
-//                   ... in order, then block_reduce -- writes out[p.slot] and publishes p.seq: how a forward launch gets its FH_S_FSQ.
-//   k_sm_finish     the same ordered sum as ONE workgroup of its own: how the dense adjoint gets its FH_S_FSQ_ADJ after k_mc_adj has run.
+//                   With p.counter set the last-arriving workgroup adds the records (fh_records.h: finish_records -- lane t takes records t, t + 256,
+//                   ... in order, then block_reduce), writes out[p.slot] and publishes p.seq: how a forward launch gets its FH_S_FSQ.
+//   k_sm_finish     the same ordered sum as ONE workgroup of its own (sm_sum_records): how the dense adjoint gets its FH_S_FSQ_ADJ after k_mc_adj has run.
 // No float atomics, no spin waits: bitwise repeatable.
 #pragma once
 #include "fh_spmulti.h"
@@ -126,12 +126,9 @@ __global__ __launch_bounds__(FH_WG) void k_sm_rows(const SmRowsP p) {
   }
   double v[1] = {0.0};
   if (live && c == 0u) v[0] = (mx + log(s)) - zy;
-  block_reduce<1>(v, s_scr, -1);
-  if (threadIdx.x == 0) store_partial(p.red_f + blockIdx.x, v[0]);
-  if (!p.counter) return;
-  if (!arrive_last(p.counter, gridDim.x, s_flag)) return;
-  sm_sum_records(p.red_f, gridDim.x, p.out, p.slot, p.seq, s_scr);
-  if (threadIdx.x == 0) __hip_atomic_store(p.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (!p.counter) { publish_record<1, -1>(v, p.red_f, blockIdx.x, s_scr); return; }
+  finish_records<1, -1>(v, p.red_f, blockIdx.x, gridDim.x, p.counter, p.out, p.seq, s_scr, s_flag, NoRecords(),
+                        [&](double (&w)[1]) { scal_store(p.out + p.slot, w[0]); });
 }
 
 static __global__ __launch_bounds__(FH_WG) void k_sm_finish(const double* red, uint32_t n, double* out, int slot, unsigned seq) {

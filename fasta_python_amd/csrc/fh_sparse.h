@@ -85,23 +85,11 @@ static __global__ __launch_bounds__(FH_WG) void k_sp_prologue(const SpProP p) {
     const double xav = p.xacc0 ? p.xacc0[j] : 0.0;
     const double xhe = fwd_point(x0e, g0e, p.tau);
     const double xpe = prox_scalar_rt(p.px.kind, xhe, p.px, 0.0);
-    const double dx = sub_nofma(xpe, x0e);
-    const double dh = sub_nofma(xpe, xhe);
-    v[0] = fma(dx, g0e, v[0]);
-    v[1] = fma(dx, dx, v[1]);
-    v[2] = fma(dh, dh, v[2]);
-    v[3] = fma(g0e, g0e, v[3]);
-    v[4] += fabs(xpe);
-    v[5] = fmax(v[5], fabs(xpe));
-    v[6] = fma(sub_nofma(x0e, xpe), sub_nofma(xpe, xav), v[6]);
+    nside_fwd_sums<0>(x0e, g0e, xhe, xpe, xav, v);
     p.xhat[j] = xhe;
     p.xp[j] = xpe;
   }
-  block_reduce<7>(v, s_scr, 5);
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int k = 0; k < 7; ++k) store_partial(p.red_n + (uint64_t)blockIdx.x * 8 + 1 + k, v[k]);
-  }
+  publish_record<7, 5>(v, p.red_n + 1, blockIdx.x, s_scr);
 }
 
 // ---- K-fwd --------------------------------------------------------------------------------------------------------------------------------
@@ -150,30 +138,10 @@ __global__ __launch_bounds__(FH_WG) void k_sp_fwd(const SpFwdP p) {
       fpart += p.sub_b ? loss_term(v[0], p.b[row], p.loss) : v[0] * v[0];
     }
   }
-  {
-    double v[1] = {fpart};
-    block_reduce<1>(v, s_scr, -1);
-    if (tid == 0) store_partial(p.red_m + blockIdx.x, v[0]);
-  }
-  if (arrive_last(p.counter, gridDim.x, s_flag)) {
-    double v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    for (uint32_t i = tid; i < gridDim.x; i += FH_WG) v[0] += load_partial(p.red_m + i);
-    for (uint32_t i = tid; i < p.nred_n; i += FH_WG) {
-#pragma unroll
-      for (int k = 1; k < 8; ++k) {
-        const double t = load_partial(p.red_n + (uint64_t)i * 8 + k);
-        if (k == S_GMAX) v[k] = fmax(v[k], t); else v[k] += t;
-      }
-    }
-    block_reduce<8>(v, s_scr, S_GMAX);
-    if (tid == 0) {
-#pragma unroll
-      for (int k = 0; k < 8; ++k) scal_store(p.out + k, v[k]);
-      scal_store(p.out + S_ALPHA, 0.0);
-      publish_seq(p.out, p.seq);
-      __hip_atomic_store(p.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
+  double v[1] = {fpart};
+  finish_records<1, S_GMAX, 8>(v, p.red_m, blockIdx.x, gridDim.x, p.counter, p.out, p.seq, s_scr, s_flag,
+                               [&](double (&w)[8]) { add_records<1, 8, S_GMAX>(w, p.red_n, p.nred_n); },
+                               [&](double (&w)[8]) { store_fwd_scalars(p.out, w, 0.0); });
 }
 
 // ---- m-side prologue of the adjoint -------------------------------------------------------------------------------------------------------
@@ -218,21 +186,11 @@ struct SpAdjP {
   double* out;
 };
 
-// the n-side epilogue of one element, in its owner's lane (k_adj_dense's bb_element)
+// g1 and the n-side epilogue of one element, in its owner's lane
 __device__ __forceinline__ void sp_adj_element(const SpAdjP& p, uint32_t j, double g, double (&v)[5]) {
   p.g1[j] = g;
   if (p.mode != 0) return;
-  const double x0e = p.x0[j], xpe = p.xp[j], xhe = p.xhat[j];
-  double x1 = xpe;
-  if (p.accel) x1 = extrapolate(xpe, p.xacc0[j], p.coef);
-  const double dx = sub_nofma(xpe, x0e);
-  const double dg = bb_dgrad(g, xhe, x0e, p.tau);
-  const double dh = sub_nofma(x1, xhe);
-  v[0] = fma(dx, dg, v[0]);
-  v[1] = fma(dg, dg, v[1]);
-  v[2] = fma(dh, dh, v[2]);
-  v[3] += fabs(x1);
-  v[4] = fmax(v[4], fabs(x1));
+  const double x1 = nside_adj_sums(g, p.x0[j], p.xp[j], p.accel ? p.xacc0[j] : 0.0, p.xhat[j], p.accel, p.coef, p.tau, v);
   if (p.accel) p.x1[j] = x1;
 }
 
@@ -261,28 +219,9 @@ __global__ __launch_bounds__(FH_WG) void k_sp_adj(const SpAdjP p) {
     block_reduce<1>(w, s_scr, -1);
     if (tid == 0) sp_adj_element(p, row, w[0], v);
   }
-  block_reduce<5>(v, s_scr, 4);
-  if (tid == 0) {
-#pragma unroll
-    for (int k = 0; k < 5; ++k) store_partial(p.red_bb + (uint64_t)blockIdx.x * 8 + k, v[k]);
-  }
-  if (!arrive_last(p.counter, gridDim.x, s_flag)) return;
-  double w[6] = {0, 0, 0, 0, 0, 0};   // dxdg, dg2, xh2, gsum, gmax, fsq
-  for (uint32_t i = tid; i < gridDim.x; i += FH_WG) {
-#pragma unroll
-    for (int k = 0; k < 5; ++k) {
-      const double t = load_partial(p.red_bb + (uint64_t)i * 8 + k);
-      if (k == 4) w[k] = fmax(w[k], t); else w[k] += t;
-    }
-  }
-  for (uint32_t i = tid; i < p.nred_f; i += FH_WG) w[5] += load_partial(p.red_f + i);
-  block_reduce<6>(w, s_scr, 4);
-  if (tid == 0) {
-    scal_store(p.out + S_DXDG, w[0]); scal_store(p.out + S_DG2, w[1]); scal_store(p.out + S_XH2_ADJ, w[2]);
-    scal_store(p.out + S_GSUM_ADJ, w[3]); scal_store(p.out + S_GMAX_ADJ, w[4]); scal_store(p.out + S_FSQ_ADJ, w[5]);
-    publish_seq(p.out, p.seq);
-    __hip_atomic_store(p.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+  finish_records<5, 4, 6>(v, p.red_bb, blockIdx.x, gridDim.x, p.counter, p.out, p.seq, s_scr, s_flag,
+                          [&](double (&w)[6]) { add_column(w[5], p.red_f, p.nred_f); },      // fsq: k_sp_resid's records
+                          [&](double (&w)[6]) { store_adj_scalars(p.out, w); });
 }
 
 // ---- the instantiations (ONE table for fh_sparse_part.hip, the extern declarations and the dispatch) ----

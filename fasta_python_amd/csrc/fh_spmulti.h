@@ -129,36 +129,24 @@ __global__ __launch_bounds__(FH_WG) void k_spmc_prologue(const SpmcProP p) {
       if (!valid) q = 0.0;
       xq[l] = q;
       pn2 += q * q;
-      if (valid) {
-        const double dx = q - x0v[l];
-        const double dh = q - xh[l];
-        v[0] = fma(dx, g0v[l], v[0]);
-        v[1] = fma(dx, dx, v[1]);
-        v[2] = fma(dh, dh, v[2]);
-        v[3] = fma(g0v[l], g0v[l], v[3]);
-        if (p.px.kind != PX_GROUP) v[4] += fabs(q);
-        v[5] = fmax(v[5], fabs(q));
-      }
     }
-    if (p.px.kind == PX_GROUP) v[4] = sqrt(pn2);
+    // the n-side sums, a column pair at a time next to its 16 bytes of x_accel0
 #pragma unroll
     for (int l = 0; l < LB; l += 2) {
       d2 a = {0.0, 0.0};
       if (p.xacc0) a = *reinterpret_cast<const d2*>(p.xacc0 + o + l);
-      if (rowok && (uint32_t)l < p.L) v[6] = fma(x0v[l] - xq[l], xq[l] - a.x, v[6]);
-      if (rowok && (uint32_t)(l + 1) < p.L) v[6] = fma(x0v[l + 1] - xq[l + 1], xq[l + 1] - a.y, v[6]);
+#pragma unroll
+      for (int h = 0; h < 2; ++h)
+        if (rowok && (uint32_t)(l + h) < p.L) nside_fwd_sums<0>(x0v[l + h], g0v[l + h], xh[l + h], xq[l + h], a[h], v, p.px.kind != PX_GROUP);
     }
+    if (p.px.kind == PX_GROUP) v[4] = sqrt(pn2);
 #pragma unroll
     for (int l = 0; l < LB; l += 2) {
       *reinterpret_cast<d2*>(p.xhat + o + l) = (d2){xh[l], xh[l + 1]};
       *reinterpret_cast<d2*>(p.xp + o + l) = (d2){xq[l], xq[l + 1]};
     }
   }
-  block_reduce<7>(v, s_scr, 5);
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int k = 0; k < 7; ++k) store_partial(p.red_n + (uint64_t)blockIdx.x * 8 + 1 + k, v[k]);
-  }
+  publish_record<7, 5>(v, p.red_n + 1, blockIdx.x, s_scr);
 }
 
 // ---- K-fwd --------------------------------------------------------------------------------------------------------------------------------
@@ -217,6 +205,8 @@ __global__ __launch_bounds__(FH_WG) void k_spmc_fwd(const SpmcFwdP p) {
     const d2 zv = spmc_long_row<LB, NT>(p.a, p.x, row, s_col);
     if (tid < (uint32_t)C) spmc_fwd_row<LB>(p, row, tid, zv, fpart);
   }
+  // (This kernel keeps its own text of the finaliser -- what finish_records<1, S_GMAX, 8> does, fh_records.h: routed through it, k_spmc_fwd<64, 16, *>
+  // takes 66 VGPRs instead of 64 and loses an occupancy step, 8 -> 7 waves per SIMD; profiles/nside_refactor.txt section 3.)
   {
     double v[1] = {fpart};
     block_reduce<1>(v, s_scr, -1);
@@ -275,8 +265,7 @@ __global__ __launch_bounds__(FH_WG) void k_spmc_resid(const SpmcResP p) {
     if (2u * c < p.L) v[0] += p.sub_b ? loss_term(zv.x, bv.x, LOSS_LSQ) : zv.x * zv.x;
     if (2u * c + 1u < p.L) v[0] += p.sub_b ? loss_term(zv.y, bv.y, LOSS_LSQ) : zv.y * zv.y;
   }
-  block_reduce<1>(v, s_scr, -1);
-  if (threadIdx.x == 0) store_partial(p.red_f + blockIdx.x, v[0]);
+  publish_record<1, -1>(v, p.red_f, blockIdx.x, s_scr);
 }
 
 // ---- K-adj --------------------------------------------------------------------------------------------------------------------------------
@@ -296,7 +285,7 @@ struct SpmcAdjP {
   double* out;
 };
 
-// the n-side epilogue of columns 2c, 2c + 1 of row j of G1, in their owner's lane (k_mc_adj's, per column pair).  Returns the pair's share of
+// the n-side epilogue of columns 2c, 2c + 1 of row j of G1, in their owner's lane (nside_adj_sums per column).  Returns the pair's share of
 // the squared row norm of x1 (valid columns only), which FH_PROX_GROUP sums over the row's column lanes.
 template <int LB>
 __device__ __forceinline__ double spmc_adj_pair(const SpmcAdjP& p, uint32_t j, uint32_t c, d2 g, double (&v)[5]) {
@@ -313,20 +302,10 @@ __device__ __forceinline__ double spmc_adj_pair(const SpmcAdjP& p, uint32_t j, u
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
     const bool valid = 2u * c + (uint32_t)h < p.L;
-    double x1 = xpv[h];
-    if (p.accel) x1 = extrapolate(xpv[h], xav[h], p.coef);
+    double x1 = 0.0;
     if (valid) {
-      const double dx = sub_nofma(xpv[h], x0v[h]);
-      const double dg = bb_dgrad(g[h], xhv[h], x0v[h], p.tau);
-      const double dh = sub_nofma(x1, xhv[h]);
-      v[0] = fma(dx, dg, v[0]);
-      v[1] = fma(dg, dg, v[1]);
-      v[2] = fma(dh, dh, v[2]);
-      if (!p.group) v[3] += fabs(x1);
-      v[4] = fmax(v[4], fabs(x1));
+      x1 = nside_adj_sums(g[h], x0v[h], xpv[h], xav[h], xhv[h], p.accel, p.coef, p.tau, v, !p.group);
       n2 = add_nofma(n2, x1 * x1);
-    } else {
-      x1 = 0.0;
     }
     x1v[h] = x1;
   }
@@ -374,28 +353,9 @@ __global__ __launch_bounds__(FH_WG) void k_spmc_adj(const SpmcAdjP p) {
       if (tid == 0) v[3] += sqrt(n2);
     }
   }
-  block_reduce<5>(v, s_scr, 4);
-  if (tid == 0) {
-#pragma unroll
-    for (int k = 0; k < 5; ++k) store_partial(p.red_bb + (uint64_t)blockIdx.x * 8 + k, v[k]);
-  }
-  if (!arrive_last(p.counter, gridDim.x, s_flag)) return;
-  double w[6] = {0, 0, 0, 0, 0, 0};   // dxdg, dg2, xh2, gsum, gmax, fsq
-  for (uint32_t i = tid; i < gridDim.x; i += FH_WG) {
-#pragma unroll
-    for (int k = 0; k < 5; ++k) {
-      const double t = load_partial(p.red_bb + (uint64_t)i * 8 + k);
-      if (k == 4) w[k] = fmax(w[k], t); else w[k] += t;
-    }
-  }
-  for (uint32_t i = tid; i < p.nred_f; i += FH_WG) w[5] += load_partial(p.red_f + i);
-  block_reduce<6>(w, s_scr, 4);
-  if (tid == 0) {
-    scal_store(p.out + S_DXDG, w[0]); scal_store(p.out + S_DG2, w[1]); scal_store(p.out + S_XH2_ADJ, w[2]);
-    scal_store(p.out + S_GSUM_ADJ, w[3]); scal_store(p.out + S_GMAX_ADJ, w[4]); scal_store(p.out + S_FSQ_ADJ, w[5]);
-    publish_seq(p.out, p.seq);
-    __hip_atomic_store(p.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+  finish_records<5, 4, 6>(v, p.red_bb, blockIdx.x, gridDim.x, p.counter, p.out, p.seq, s_scr, s_flag,
+                          [&](double (&w)[6]) { add_column(w[5], p.red_f, p.nred_f); },      // fsq: k_spmc_resid's records
+                          [&](double (&w)[6]) { store_adj_scalars(p.out, w); });
 }
 
 // ---- the instantiations (ONE table for fh_spmulti_part.hip, the extern declarations and the dispatch) ----

@@ -21,14 +21,14 @@
 //                         prox (IDENTITY / SHRINK / NONNEG / BOX through prox_scalar) or the plain operand; IDENT = 0: FH_PROX_TVBALL, the
 //                         projection of each voxel's 3-vector, nr = sqrt((y0*y0 + y1*y1) + y2*y2), y / fmax(nr, 1) -- la.norm(Y, axis=-1) and
 //                         np.maximum.  n-side sums count a voxel in its owner only (not in a halo copy, not in the halo plane).
-//   k_tv3_adj<NT>         r = z' - b (z' = z or its FISTA extrapolation; the loss at z' is FH_S_FSQ_ADJ), g1 = grad(r) written, and k_sp_adj's
-//                         n-side epilogue in the owner's lane (every g1 entry has one owner: no partials); modes 0 and 1.  The r tile with its
+//   k_tv3_adj<NT>         r = z' - b (z' = z or its FISTA extrapolation; the loss at z' is FH_S_FSQ_ADJ), g1 = grad(r) written, and the
+//                         n-side epilogue (fh_nside.h) in the owner's lane (every g1 entry has one owner: no partials); modes 0 and 1.  The r tile with its
 //                         h-1 row and w-1 column sits in LDS two planes deep; the march starts one plane early (d0 - 1).
 // Wraps are conditional corrections (as tv_wrap_row), flat offsets 64-bit, elementwise arithmetic under fp contract(off).
 // NT = 1 (FH_TUNE_NT_LOADS): non-temporal stores of xhat / xprox / g1; measured within 1.4 % of plain stores from 256^3 on
 // (profiles/tv3d_sizes.txt), so plain stores are the default.
 #pragma once
-#include "fh_device.h"
+#include "fh_records.h"
 
 #define TV3_TH 8                                   // tile: rows (h) ...
 #define TV3_TW 64                                  // ... and columns (w); TV3_TH * TV3_TW voxels = 2 per lane
@@ -106,15 +106,7 @@ __global__ __launch_bounds__(FH_WG) void k_tv3_fwd(const Tv3FwdP p) {
   // the forward point's outputs and sums of one element, in its owner
   auto account = [&](uint64_t gi, double x0e, double g0e, double xhe, double xpe) {
     const double xav = p.xacc0 ? p.xacc0[gi] : 0.0;
-    const double dx = sub_nofma(xpe, x0e);
-    const double dh = sub_nofma(xpe, xhe);
-    v[1] = fma(dx, g0e, v[1]);
-    v[2] = fma(dx, dx, v[2]);
-    v[3] = fma(dh, dh, v[3]);
-    v[4] = fma(g0e, g0e, v[4]);
-    v[5] += fabs(xpe);
-    v[6] = fmax(v[6], fabs(xpe));
-    v[7] = fma(sub_nofma(x0e, xpe), sub_nofma(xpe, xav), v[7]);
+    nside_fwd_sums<1>(x0e, g0e, xhe, xpe, xav, v);
     tv3_store<NT>(p.xhat + gi, xhe);
     tv3_store<NT>(p.xp + gi, xpe);
   };
@@ -188,28 +180,8 @@ __global__ __launch_bounds__(FH_WG) void k_tv3_fwd(const Tv3FwdP p) {
     }
     __syncthreads();                                                    // `prev` is the next plane's target
   }
-  block_reduce<8>(v, s_scr, S_GMAX);
-  if (tid == 0) {
-#pragma unroll
-    for (int k = 0; k < 8; ++k) store_partial(p.red + (uint64_t)blockIdx.x * 8 + k, v[k]);
-  }
-  if (!arrive_last(p.counter, gridDim.x, s_flag)) return;
-  double w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  for (uint32_t i = tid; i < gridDim.x; i += FH_WG) {                   // records in index order: lane l adds l, l + 256, ...
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const double r = load_partial(p.red + (uint64_t)i * 8 + k);
-      if (k == S_GMAX) w[k] = fmax(w[k], r); else w[k] += r;
-    }
-  }
-  block_reduce<8>(w, s_scr, S_GMAX);
-  if (tid == 0) {
-#pragma unroll
-    for (int k = 0; k < 8; ++k) scal_store(p.out + k, w[k]);
-    scal_store(p.out + S_ALPHA, 0.0);
-    publish_seq(p.out, p.seq);
-    __hip_atomic_store(p.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+  finish_records<8, S_GMAX>(v, p.red, blockIdx.x, gridDim.x, p.counter, p.out, p.seq, s_scr, s_flag, NoRecords(),
+                            [&](double (&w)[8]) { store_fwd_scalars(p.out, w, 0.0); });
 }
 
 // ---- K-adj --------------------------------------------------------------------------------------------------------------------------------
@@ -297,18 +269,8 @@ __global__ __launch_bounds__(FH_WG) void k_tv3_adj(const Tv3AdjP p) {
           const double g = nb - rp;
           const uint64_t gi = base_n + g_off[j];
           tv3_store<NT>(p.g1 + gi, g);
-          if (p.mode == 0) {                                            // the n-side epilogue of this element (k_sp_adj's sp_adj_element)
-            const double x0e = p.x0[gi], xpe = p.xp[gi], xhe = p.xhat[gi];
-            double x1 = xpe;
-            if (p.accel) x1 = extrapolate(xpe, p.xacc0[gi], p.coef);
-            const double dx = sub_nofma(xpe, x0e);
-            const double dg = bb_dgrad(g, xhe, x0e, p.tau);
-            const double dh = sub_nofma(x1, xhe);
-            v[0] = fma(dx, dg, v[0]);
-            v[1] = fma(dg, dg, v[1]);
-            v[2] = fma(dh, dh, v[2]);
-            v[3] += fabs(x1);
-            v[4] = fmax(v[4], fabs(x1));
+          if (p.mode == 0) {
+            const double x1 = nside_adj_sums(g, p.x0[gi], p.xp[gi], p.accel ? p.xacc0[gi] : 0.0, p.xhat[gi], p.accel, p.coef, p.tau, v);
             if (p.accel) p.x1[gi] = x1;
           }
         }
@@ -316,27 +278,8 @@ __global__ __launch_bounds__(FH_WG) void k_tv3_adj(const Tv3AdjP p) {
     }
     __syncthreads();                                                    // `prev` is the next plane's target
   }
-  block_reduce<6>(v, s_scr, 4);
-  if (tid == 0) {
-#pragma unroll
-    for (int k = 0; k < 6; ++k) store_partial(p.red + (uint64_t)blockIdx.x * 8 + k, v[k]);
-  }
-  if (!arrive_last(p.counter, gridDim.x, s_flag)) return;
-  double w[6] = {0, 0, 0, 0, 0, 0};
-  for (uint32_t i = tid; i < gridDim.x; i += FH_WG) {
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-      const double r = load_partial(p.red + (uint64_t)i * 8 + k);
-      if (k == 4) w[k] = fmax(w[k], r); else w[k] += r;
-    }
-  }
-  block_reduce<6>(w, s_scr, 4);
-  if (tid == 0) {
-    scal_store(p.out + S_DXDG, w[0]); scal_store(p.out + S_DG2, w[1]); scal_store(p.out + S_XH2_ADJ, w[2]);
-    scal_store(p.out + S_GSUM_ADJ, w[3]); scal_store(p.out + S_GMAX_ADJ, w[4]); scal_store(p.out + S_FSQ_ADJ, w[5]);
-    publish_seq(p.out, p.seq);
-    __hip_atomic_store(p.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+  finish_records<6, 4>(v, p.red, blockIdx.x, gridDim.x, p.counter, p.out, p.seq, s_scr, s_flag, NoRecords(),
+                       [&](double (&w)[6]) { store_adj_scalars(p.out, w); });
 }
 
 // ---- the instantiations (ONE table for fh_tv3d_part.hip, the extern declarations and the dispatch) ----
