@@ -25,6 +25,7 @@
 #include "fh_tv.h"
 #include "fh_tv3d.h"
 #include "fh_dct.h"
+#include "fh_dct2.h"
 #include "fh_conv.h"
 #include "fh_nuclear.h"
 #include "fh_prox.h"
@@ -136,6 +137,10 @@ TV3_KERNELS(template)
 DCT_FOR_EACH(DCT_INSTANTIATE)
 #undef DCT_INSTANTIATE
 DCT_TILE_KERNELS(template)
+#define DCT2_INSTANTIATE(LDSN) DCT2_KERNELS(template, LDSN)
+DCT_FOR_EACH(DCT2_INSTANTIATE)
+#undef DCT2_INSTANTIATE
+DCT2_TILE_KERNELS(template)
 CONV_KERNELS(template)
 #endif
 
@@ -772,6 +777,35 @@ extern "C" int fh_set_dct(fh_ctx* c, uint64_t N, const double* diag) {
   c->op = OP_DCT;                                         // (from here on free_operator gives the tables back)
   int rc = alloc_vectors(c);
   if (rc == 0) rc = dct_alloc_tables(c, sh, diag);
+  if (rc != 0) { free_operator(c); return rc; }
+  return finish(c);
+}
+
+// the subsampled 2-D DCT (csrc/fh_dct2.h): A x = d * (C_H X C_W^T), m = n = H * W; the DCT operator in its 2-D geometry (op == OP_DCT, dct2): vectors in
+// the vector form's padded layout, no matrix stored: a pair of twiddle tables per axis built here in long double, a copy of d, two work images
+extern "C" int fh_set_dct2(fh_ctx* c, uint64_t H, uint64_t W, const double* diag) {
+  if (!c) return fail(FH_E_ARG, "null context");
+  if (!c->shards.empty() || c->owner) return fail(FH_E_STATE, "fh_set_dct2: a multi-device context has no 2-D DCT operator (row sharding is implemented for the dense operator only)");
+  if (c->comm) return fail(FH_E_STATE, "fh_set_dct2: a context with a communicator (row-sharded run) has no 2-D DCT operator");
+  if (c->f32) return fail(FH_E_STATE, "fh_set_dct2: float32 storage is a storage mode of a dense matrix; the 2-D DCT operator stores no matrix and computes in float64");
+  if (c->pending_step) return fail(FH_E_STATE, "a step issued by fh_step_begin is still in flight on this context: call fh_step_end first");
+  Dct2Shape sh;
+  FH_TRY(dct2_shape_for(H, W, c->dct_row_cap, c->ncu, &sh));   // (each axis >= 1, at most the row cap, prime factors in {2, 3, 5}: FH_E_ARG with the sentence)
+  FH_TRY(use_device(c));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  free_operator(c);
+  if (!dct_prox_ok(c->prox_kind)) { c->prox_kind = FH_PROX_IDENTITY; c->mu = 0.0; }
+  c->loss_kind = LOSS_LSQ; c->lazy = false; c->last_accel = false; c->commits = 0;
+  c->H = H; c->W = W;
+  c->m = c->n = H * W;
+  c->mp = c->m; c->ld = c->n;
+  c->nv = round_up(c->n, 16); c->mv = round_up(c->m, 16);
+  c->dct2_sh = sh;
+  c->dct_sc0 = (double)sqrtl(1.0L / (long double)H); c->dct_sck = (double)sqrtl(2.0L / (long double)H);
+  c->dct2_sc0 = (double)sqrtl(1.0L / (long double)W); c->dct2_sck = (double)sqrtl(2.0L / (long double)W);
+  c->op = OP_DCT; c->dct2 = true;                          // (from here on free_operator gives the tables back)
+  int rc = alloc_vectors(c);
+  if (rc == 0) rc = dct2_alloc_tables(c, sh, diag);
   if (rc != 0) { free_operator(c); return rc; }
   return finish(c);
 }

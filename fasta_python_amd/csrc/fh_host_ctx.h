@@ -96,6 +96,8 @@ static int rccl_load() {
 
 // geometry of the DCT operator's launches (csrc/fh_host_launch.h: dct_shape_for fills it)
 struct DctShape { uint32_t levels, N1, N2, cap; DctRad r1, r2; uint32_t ldsn1, rpw1, grid1, ldsn2, rpw2, grid2, tiles, launches, lds_bytes; };
+// geometry of the 2-D DCT operator's launches (csrc/fh_host_launch.h: dct2_shape_for fills it); suffix h: the W rows of length H, w: the H rows of length W
+struct Dct2Shape { uint32_t served, H, W, cap; DctRad rh, rw; uint32_t ldsn_h, rpw_h, grid_h, ldsn_w, rpw_w, grid_w, tiles, launches, lds_bytes; };
 
 // geometry of the nuclear-norm prox's launches (csrc/fh_host_launch.h: nuc_shape_for fills it)
 struct NucShape { NucGeo g; uint32_t Bk, steps, wgs, chunks, lds_bytes; uint64_t bytes; };
@@ -137,6 +139,13 @@ struct fh_ctx {
   d2* dct_w0 = nullptr; d2* dct_w1 = nullptr;
   DctShape dct_sh = {};      // the geometry dct_shape_for gave when the operator was set (every launch reads it; fh_dct_shape reports it)
   double dct_sc0 = 0.0, dct_sck = 0.0;   // sqrt(1/N), sqrt(2/N)
+  // the DCT operator in its 2-D geometry (fh_set_dct2, csrc/fh_dct2.h): op == OP_DCT and dct2; m = n = H * W; dct_tw / dct_pw / dct_sc0 / dct_sck serve
+  // the H axis, the four below the W axis; dct_diag holds H * W values; two work buffers of H * W doubles
+  bool dct2 = false;
+  d2* dct2_tw = nullptr; d2* dct2_pw = nullptr;
+  double* dct2_w0 = nullptr; double* dct2_w1 = nullptr;
+  Dct2Shape dct2_sh = {};    // the geometry dct2_shape_for gave when the operator was set (every launch reads it; fh_dct2_shape reports it)
+  double dct2_sc0 = 0.0, dct2_sck = 0.0;
   // periodic convolution (fh_set_conv2d, csrc/fh_conv.h): the image is (H, W), m = n = H * W; the taps (kh * kw, C order: they travel in the
   // kernels' argument block), the origin, the diagonal d (nullptr: all ones) and the geometry conv_shape_for gave when the operator was set
   uint32_t conv_kh = 0, conv_kw = 0, conv_oh = 0, conv_ow = 0;
@@ -425,7 +434,8 @@ static void free_operator(fh_ctx* c) {
   }
   fr(c->sp_r); c->nnz = 0;
   for (d2** q : {&c->dct_tw, &c->dct_pw, &c->dct_w0, &c->dct_w1}) if (*q) { (void)hipFree(*q); *q = nullptr; }
-  fr(c->dct_diag);
+  for (d2** q : {&c->dct2_tw, &c->dct2_pw}) if (*q) { (void)hipFree(*q); *q = nullptr; }
+  fr(c->dct_diag); fr(c->dct2_w0); fr(c->dct2_w1); c->dct2 = false;
   fr(c->conv_diag);
   fr(c->nuc_w); fr(c->nuc_phi); fr(c->nuc_scal);
   if (c->nuc_cnt) { (void)hipFree(c->nuc_cnt); c->nuc_cnt = nullptr; }

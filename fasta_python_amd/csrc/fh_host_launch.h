@@ -1,4 +1,4 @@
-// fh_host_launch.h -- kernel launchers of libfasta_hip.so: shapes, grids and workspace of every kernel in fh_dense.h / fh_quad.h / fh_bilinear.h / fh_tv.h / fh_tv3d.h / fh_dct.h / fh_conv.h /
+// fh_host_launch.h -- kernel launchers of libfasta_hip.so: shapes, grids and workspace of every kernel in fh_dense.h / fh_quad.h / fh_bilinear.h / fh_tv.h / fh_tv3d.h / fh_dct.h / fh_dct2.h / fh_conv.h /
 // fh_prox.h / fh_fused.h, the one-pass kernel's shape rule and dispatch table, the co-residency probe, and the three-stage form
 // (local launch / sum over row blocks / n-side epilogue) the C ABI in fasta_hip.hip builds its entry points from.
 #pragma once
@@ -1163,6 +1163,7 @@ static void dct_shape_out(const DctShape& sh, uint32_t* out) {
 extern "C" int fh_dct_shape(fh_ctx* c, uint32_t* out) {
   if (!c || !out) return fail(FH_E_ARG, "fh_dct_shape: null argument");
   if (c->op != OP_DCT) return fail(FH_E_STATE, "fh_dct_shape: the context holds no DCT operator (fh_set_dct)");
+  if (c->dct2) return fail(FH_E_STATE, "fh_dct_shape: the context holds the DCT operator in its 2-D geometry (fh_set_dct2): fh_dct2_shape reports it");
   dct_shape_out(c->dct_sh, out);                          // (what dct_shape_for gave when fh_set_dct set the operator: the launchers read the same copy)
   return 0;
 }
@@ -1174,18 +1175,23 @@ extern "C" int fh_dct_shape_for(uint64_t N, int row_cap, int ncu, uint32_t* out)
   return rc;
 }
 
-// the two twiddle tables (long double on the host, rounded once), the diagonal and, for two levels, the work buffers.  A set-up cost, paid once
+// one pair of twiddle tables for a row length L (long double on the host, rounded once): tw[j] = e^{-2 pi i j / L}, pw[k] = e^{-i pi k / 2L}
+static int dct_axis_tables(uint64_t L, d2** tw, d2** pw) {
+  const long double pi = 3.14159265358979323846264338327950288L;
+  std::vector<double> t(2 * L);
+  HIP_TRY(hipMalloc((void**)tw, L * sizeof(d2)));
+  HIP_TRY(hipMalloc((void**)pw, L * sizeof(d2)));
+  for (uint64_t j = 0; j < L; ++j) { const long double a = 2.0L * pi * (long double)j / (long double)L; t[2 * j] = (double)cosl(a); t[2 * j + 1] = (double)-sinl(a); }
+  HIP_TRY(hipMemcpy(*tw, t.data(), L * sizeof(d2), hipMemcpyHostToDevice));
+  for (uint64_t k = 0; k < L; ++k) { const long double a = pi * (long double)k / (2.0L * (long double)L); t[2 * k] = (double)cosl(a); t[2 * k + 1] = (double)-sinl(a); }
+  HIP_TRY(hipMemcpy(*pw, t.data(), L * sizeof(d2), hipMemcpyHostToDevice));
+  return 0;
+}
+// the two twiddle tables, the diagonal and, for two levels, the work buffers.  A set-up cost, paid once
 // per fh_set_dct: 4 N cosl / sinl calls and a host vector of 16 N bytes (N = 2^22: about 17 M long-double calls, of the order of a second)
 static int dct_alloc_tables(fh_ctx* c, const DctShape& sh, const double* diag) {
   const uint64_t N = c->n;
-  const long double pi = 3.14159265358979323846264338327950288L;
-  std::vector<double> t(2 * N);
-  HIP_TRY(hipMalloc((void**)&c->dct_tw, N * sizeof(d2)));
-  HIP_TRY(hipMalloc((void**)&c->dct_pw, N * sizeof(d2)));
-  for (uint64_t j = 0; j < N; ++j) { const long double a = 2.0L * pi * (long double)j / (long double)N; t[2 * j] = (double)cosl(a); t[2 * j + 1] = (double)-sinl(a); }
-  HIP_TRY(hipMemcpy(c->dct_tw, t.data(), N * sizeof(d2), hipMemcpyHostToDevice));
-  for (uint64_t k = 0; k < N; ++k) { const long double a = pi * (long double)k / (2.0L * (long double)N); t[2 * k] = (double)cosl(a); t[2 * k + 1] = (double)-sinl(a); }
-  HIP_TRY(hipMemcpy(c->dct_pw, t.data(), N * sizeof(d2), hipMemcpyHostToDevice));
+  FH_TRY(dct_axis_tables(N, &c->dct_tw, &c->dct_pw));
   if (diag) {
     HIP_TRY(hipMalloc((void**)&c->dct_diag, N * sizeof(double)));
     HIP_TRY(hipMemcpy(c->dct_diag, diag, N * sizeof(double), hipMemcpyHostToDevice));
@@ -1224,12 +1230,165 @@ static void dct_launch_middle(fh_ctx* c, const DctShape& sh, int conj) {
   if (conj) dct_launch_rows_c<1>(c, sh.ldsn2, sh.grid2, q); else dct_launch_rows_c<0>(c, sh.ldsn2, sh.grid2, q);
 }
 
+// ---- the DCT operator on an H x W image (fh_set_dct2; kernels in csrc/fh_dct2.h, instantiated by fh_dct2_part.hip) ---------------------------
+#ifndef FH_SINGLE_TU
+#define DCT2_DECLARE(LDSN) DCT2_KERNELS(extern template, LDSN)
+DCT_FOR_EACH(DCT2_DECLARE)
+#undef DCT2_DECLARE
+DCT2_TILE_KERNELS(extern template)
+#endif
+// THE geometry of every launch of both directions, a pure function of (H, W), the row cap (FH_TUNE_DCT_ROW_CAP; 0 = DCT_ROW_CAP) and the device's CU
+// count.  Each axis is ONE row transform: its length is at least 1, at most the cap and has the prime factors 2, 3 and 5 only (there is no two-level
+// form per axis).  An axis takes the 1-D rule's radices and LDS class (dct_radices, dct_ldsn): along H there are W rows of length H, along W there
+// are H rows of length W.  A workgroup takes as many rows as the class holds, at most DCT_MAX_ROWS, and fewer where that would leave fewer workgroups
+// than CUs -- but never fewer than fill its 256 threads with one element each (short rows of a small image: lanes that would idle in every load and
+// store loop otherwise).  Four launches per direction: two row launches and two tile launches of ceil(H / 32) * ceil(W / 32) workgroups.
+static void dct2_rows_geometry(uint64_t L, uint64_t nrows, int ncu, uint32_t* ldsn, uint32_t* rpw, uint32_t* grid) {
+  *ldsn = dct_ldsn(L);
+  const uint64_t fit = std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>(*ldsn / L, DCT_MAX_ROWS), nrows));
+  const uint64_t fill = std::min<uint64_t>(fit, (FH_WG + L - 1) / L);
+  const uint64_t r = std::max<uint64_t>(fill, std::min<uint64_t>(fit, nrows / (uint64_t)std::max(1, ncu)));
+  *rpw = (uint32_t)r; *grid = (uint32_t)((nrows + r - 1) / r);
+}
+static int dct2_shape_for(uint64_t H, uint64_t W, int row_cap, int ncu, Dct2Shape* sh) {
+  memset(sh, 0, sizeof(*sh));
+  if (row_cap != 0 && (row_cap < 2 || row_cap > DCT_ROW_CAP)) return fail(FH_E_ARG, "DCT_ROW_CAP must be 0 (default: %d) or in [2, %d] elements per row transform", DCT_ROW_CAP, DCT_ROW_CAP);
+  const uint64_t cap = row_cap ? (uint64_t)row_cap : DCT_ROW_CAP;
+  sh->cap = (uint32_t)cap;                                // (set from here on: a refusal below is about the shape, not about the cap)
+  const uint64_t len[2] = {H, W};
+  const char* name[2] = {"H", "W"};
+  for (int a = 0; a < 2; ++a) {
+    const uint64_t L = len[a];
+    if (L == 0) return fail(FH_E_ARG, "the 2-D DCT operator needs H, W >= 1: axis %d (%s) of the shape (%llu, %llu) is empty", a, name[a], (unsigned long long)H, (unsigned long long)W);
+    uint64_t rest = L;
+    for (uint64_t r : {2u, 3u, 5u}) while (rest % r == 0) rest /= r;
+    if (rest != 1) return fail(FH_E_ARG, "the 2-D DCT operator serves axis lengths whose prime factors are 2, 3 and 5 only: axis %d (%s = %llu) of the shape (%llu, %llu) has a prime factor above 5",
+                               a, name[a], (unsigned long long)L, (unsigned long long)H, (unsigned long long)W);
+    if (L > cap) return fail(FH_E_ARG, "the 2-D DCT operator takes each axis as one row transform of at most the row cap (%llu): axis %d (%s = %llu) of the shape (%llu, %llu) is longer, and there is no two-level form per axis",
+                             (unsigned long long)cap, a, name[a], (unsigned long long)L, (unsigned long long)H, (unsigned long long)W);
+  }
+  if (!dct_radices(H, &sh->rh) || !dct_radices(W, &sh->rw)) return fail(FH_E_ARG, "the 2-D DCT operator: the shape (%llu, %llu) needs more than %d radix passes per row", (unsigned long long)H, (unsigned long long)W, DCT_MAXRAD);
+  sh->H = (uint32_t)H; sh->W = (uint32_t)W;
+  dct2_rows_geometry(H, W, ncu, &sh->ldsn_h, &sh->rpw_h, &sh->grid_h);
+  dct2_rows_geometry(W, H, ncu, &sh->ldsn_w, &sh->rpw_w, &sh->grid_w);
+  sh->tiles = (uint32_t)(((H + DCT_TT - 1) / DCT_TT) * ((W + DCT_TT - 1) / DCT_TT));
+  sh->launches = 4;
+  sh->lds_bytes = std::max(sh->ldsn_h, sh->ldsn_w) * 2u * (uint32_t)sizeof(d2);
+  sh->served = 1;
+  return 0;
+}
+static void dct2_shape_out(const Dct2Shape& sh, uint32_t* out) {
+  memset(out, 0, FH_DCT_SHAPE_LEN * sizeof(uint32_t));
+  out[0] = sh.served; out[1] = sh.H; out[2] = sh.W; out[3] = sh.cap;
+  out[4] = sh.rh.n; for (uint32_t i = 0; i < sh.rh.n; ++i) out[5 + i] = sh.rh.r[i];
+  out[17] = sh.rw.n; for (uint32_t i = 0; i < sh.rw.n; ++i) out[18 + i] = sh.rw.r[i];
+  out[30] = sh.ldsn_h; out[31] = sh.rpw_h; out[32] = sh.grid_h; out[33] = sh.ldsn_w; out[34] = sh.rpw_w; out[35] = sh.grid_w;
+  out[36] = FH_WG; out[37] = sh.lds_bytes; out[38] = sh.tiles; out[39] = sh.launches;
+}
+extern "C" int fh_dct2_shape(fh_ctx* c, uint32_t* out) {
+  if (!c || !out) return fail(FH_E_ARG, "fh_dct2_shape: null argument");
+  if (c->op != OP_DCT || !c->dct2) return fail(FH_E_STATE, "fh_dct2_shape: the context holds no 2-D DCT operator (fh_set_dct2)");
+  dct2_shape_out(c->dct2_sh, out);                        // (what dct2_shape_for gave when fh_set_dct2 set the operator: the launchers read the same copy)
+  return 0;
+}
+extern "C" int fh_dct2_shape_for(uint64_t H, uint64_t W, int row_cap, int ncu, uint32_t* out) {
+  if (!out) return fail(FH_E_ARG, "fh_dct2_shape_for: null argument");
+  Dct2Shape sh;
+  const int rc = dct2_shape_for(H, W, row_cap, ncu, &sh);
+  dct2_shape_out(sh, out);                                // (a refused shape: [0] = 0, "not served", beside the error and its sentence)
+  return rc;
+}
+
+// the tables of both axes, the diagonal and the two work images
+static int dct2_alloc_tables(fh_ctx* c, const Dct2Shape& sh, const double* diag) {
+  const uint64_t N = c->n;
+  FH_TRY(dct_axis_tables(sh.H, &c->dct_tw, &c->dct_pw));
+  FH_TRY(dct_axis_tables(sh.W, &c->dct2_tw, &c->dct2_pw));
+  if (diag) {
+    HIP_TRY(hipMalloc((void**)&c->dct_diag, N * sizeof(double)));
+    HIP_TRY(hipMemcpy(c->dct_diag, diag, N * sizeof(double), hipMemcpyHostToDevice));
+  }
+  HIP_TRY(hipMalloc((void**)&c->dct2_w0, N * sizeof(double)));
+  HIP_TRY(hipMalloc((void**)&c->dct2_w1, N * sizeof(double)));
+  return 0;
+}
+static Dct2OpP dct2_op_params(fh_ctx* c, const Dct2Shape& sh) {
+  Dct2OpP o;
+  o.H = sh.H; o.W = sh.W;
+  o.ah.L = sh.H; o.ah.rd = sh.rh; o.ah.tw = c->dct_tw; o.ah.pw = c->dct_pw; o.ah.sc0 = c->dct_sc0; o.ah.sck = c->dct_sck;
+  o.aw.L = sh.W; o.aw.rd = sh.rw; o.aw.tw = c->dct2_tw; o.aw.pw = c->dct2_pw; o.aw.sc0 = c->dct2_sc0; o.aw.sck = c->dct2_sck;
+  o.rpw_h = sh.rpw_h; o.rpw_w = sh.rpw_w;
+  o.diag = c->dct_diag; o.w0 = c->dct2_w0; o.w1 = c->dct2_w1;
+  return o;
+}
+template <int WHICH>
+static void dct2_launch_fwd_rows(fh_ctx* c, uint32_t ldsn, uint32_t grid, const Dct2FwdP& p) {
+  if (ldsn == 128u) k_dct2_fwd_rows<128, WHICH><<<dim3(grid), dim3(FH_WG), 0, c->stream>>>(p);
+  else if (ldsn == 512u) k_dct2_fwd_rows<512, WHICH><<<dim3(grid), dim3(FH_WG), 0, c->stream>>>(p);
+  else k_dct2_fwd_rows<2048, WHICH><<<dim3(grid), dim3(FH_WG), 0, c->stream>>>(p);
+}
+template <int WHICH>
+static void dct2_launch_adj_rows(fh_ctx* c, uint32_t ldsn, uint32_t grid, const Dct2AdjP& p) {
+  if (ldsn == 128u) k_dct2_adj_rows<128, WHICH><<<dim3(grid), dim3(FH_WG), 0, c->stream>>>(p);
+  else if (ldsn == 512u) k_dct2_adj_rows<512, WHICH><<<dim3(grid), dim3(FH_WG), 0, c->stream>>>(p);
+  else k_dct2_adj_rows<2048, WHICH><<<dim3(grid), dim3(FH_WG), 0, c->stream>>>(p);
+}
+
+// z := d * (C_H X C_W^T), X = prox(x0 - tau g0) (mode 0) or x0 (mode 1): four launches; the checks are launch_fwd_dct's
+static int launch_fwd_dct2(fh_ctx* c, int mode, double tau, const double* x0, const double* g0, const double* xacc0,
+                           double* xhat, double* xp, double* z, int sub_b) {
+  const Dct2Shape& sh = c->dct2_sh;
+  Dct2FwdP p;
+  memset(&p.f.op, 0, sizeof(p.f.op));                     // (the 1-D operator's block: the 2-D kernels do not read it)
+  p.o = dct2_op_params(c, sh);
+  p.f.mode = mode; p.f.sub_b = sub_b;
+  p.f.x0 = x0; p.f.g0 = g0; p.f.xacc0 = xacc0; p.f.xhat = xhat; p.f.xp = xp; p.f.b = c->b; p.f.z = z; p.f.tau = tau;
+  p.f.px = make_prox(c, tau);
+  p.f.seq = 0u; p.f.nred_n = 0u;
+  FH_TRY(ensure_ws(c, ((size_t)sh.tiles + sh.grid_w) * 8 * sizeof(double)));
+  p.f.red = c->ws; p.f.red_n = c->ws + (size_t)sh.tiles * 8; p.f.counter = c->counters + CNT_FWD; p.f.out = scalar_out(c);
+  t_begin(c, FH_K_FWD);
+  dct2_launch_fwd_rows<1>(c, sh.ldsn_w, sh.grid_w, p);
+  k_dct2_tr<DCT_TT><<<dim3(sh.tiles), dim3(FH_WG), 0, c->stream>>>(c->dct2_w0, c->dct2_w1, sh.H, sh.W);
+  dct2_launch_fwd_rows<0>(c, sh.ldsn_h, sh.grid_h, p);
+  p.f.nred_n = mode == 0 ? sh.grid_w : 0u;
+  p.f.seq = seq_offer(c);
+  k_dct2_post_fwd<DCT_TT><<<dim3(sh.tiles), dim3(FH_WG), 0, c->stream>>>(p);
+  t_end(c, FH_K_FWD);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// g1 := C_H^T (d * (z' - b)) C_W with the residual, the loss at z' and the n-side epilogue: four launches; the checks are launch_adj_dct's
+static int launch_adj_dct2(fh_ctx* c, const AdjIO& io) {
+  const Dct2Shape& sh = c->dct2_sh;
+  Dct2AdjP p;
+  memset(&p.a.op, 0, sizeof(p.a.op));
+  p.o = dct2_op_params(c, sh);
+  p.a.z = io.z; p.a.zacc0 = io.zacc0; p.a.b = c->b; p.a.sub_b = io.sub_b; p.a.accel = io.accel; p.a.mode = io.mode; p.a.coef = io.coef; p.a.tau = io.tau;
+  p.a.x0 = io.x0; p.a.xp = io.xp; p.a.xacc0 = io.xacc0; p.a.xhat = io.xhat; p.a.x1 = io.x1; p.a.g1 = io.g1;
+  p.a.seq = 0u; p.a.nred_f = 0u;
+  FH_TRY(ensure_ws(c, ((size_t)sh.tiles + sh.grid_w) * 8 * sizeof(double)));
+  p.a.red = c->ws; p.a.red_f = c->ws + (size_t)sh.grid_w * 8; p.a.counter = c->counters + CNT_ADJ_FIN; p.a.out = scalar_out(c);
+  t_begin(c, FH_K_ADJ);
+  k_dct2_pre_adj<DCT_TT><<<dim3(sh.tiles), dim3(FH_WG), 0, c->stream>>>(p);
+  dct2_launch_adj_rows<0>(c, sh.ldsn_h, sh.grid_h, p);
+  k_dct2_tr<DCT_TT><<<dim3(sh.tiles), dim3(FH_WG), 0, c->stream>>>(c->dct2_w0, c->dct2_w1, sh.W, sh.H);
+  p.a.nred_f = sh.tiles;
+  p.a.seq = io.mode == 0 ? seq_offer(c) : 0u;
+  dct2_launch_adj_rows<1>(c, sh.ldsn_w, sh.grid_w, p);
+  t_end(c, FH_K_ADJ);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
 // z := d * C (mode 0: prox(x0 - tau g0) ; mode 1: x0): one launch (N <= row cap) or five
 static int launch_fwd_dct(fh_ctx* c, int mode, double tau, const double* x0, const double* g0, const double* xacc0,
                           double* xhat, double* xp, double* z, int sub_b) {
   if (c->loss_kind != LOSS_LSQ) return fail(FH_E_STATE, "the DCT operator serves the least-squares loss only (the logistic loss is implemented for the dense and sparse operators)");
   if (mode == 0 && !dct_prox_ok(c->prox_kind))
     return fail(FH_E_STATE, "prox kind %d (TVBALL / GROUP) is not implemented for the DCT operator", c->prox_kind);
+  if (c->dct2) return launch_fwd_dct2(c, mode, tau, x0, g0, xacc0, xhat, xp, z, sub_b);
   const DctShape& sh = c->dct_sh;
   DctFwdP p;
   p.op = dct_op_params(c, sh);
@@ -1263,6 +1422,7 @@ static int launch_fwd_dct(fh_ctx* c, int mode, double tau, const double* x0, con
 static int launch_adj_dct(fh_ctx* c, const AdjIO& io) {
   if (c->loss_kind != LOSS_LSQ) return fail(FH_E_STATE, "the DCT operator serves the least-squares loss only (the logistic loss is implemented for the dense and sparse operators)");
   if (io.mode != 0 && io.mode != 1) return fail(FH_E_STATE, "the DCT operator has no row-sharded adjoint");
+  if (c->dct2) return launch_adj_dct2(c, io);
   const DctShape& sh = c->dct_sh;
   DctAdjP p;
   p.op = dct_op_params(c, sh);
@@ -1955,7 +2115,7 @@ static int reduce_fsq_over_ranks(fh_ctx* c) {
 static int check_ready(fh_ctx* c, bool need_b) {
   if (!c) return fail(FH_E_ARG, "null context");
   if (c->pending_step) return fail(FH_E_STATE, "a step issued by fh_step_begin is still in flight on this context: call fh_step_end first");
-  if (c->op == OP_NONE) return fail(FH_E_STATE, "no operator set (call fh_set_matrix / fh_set_matrix_csr / fh_generate_matrix / fh_set_stencil / fh_set_stencil3d / fh_set_dct / fh_set_conv2d / fh_set_identity / fh_set_quadratic / fh_set_factorization)");
+  if (c->op == OP_NONE) return fail(FH_E_STATE, "no operator set (call fh_set_matrix / fh_set_matrix_csr / fh_generate_matrix / fh_set_stencil / fh_set_stencil3d / fh_set_dct / fh_set_dct2 / fh_set_conv2d / fh_set_identity / fh_set_quadratic / fh_set_factorization)");
   if (need_b && !c->has_b) return fail(FH_E_STATE, "no loss set (call fh_set_loss_lsq)");
   return c->shards.empty() ? use_device(c) : 0;      // (a shell selects the device shard by shard)
 }

@@ -94,6 +94,9 @@ SIGNATURES = {
     "fh_set_dct": (_i32, [_ctx, _u64, _pd]),
     "fh_dct_shape": (_i32, [_ctx, C.POINTER(C.c_uint32)]),
     "fh_dct_shape_for": (_i32, [_u64, _i32, _i32, C.POINTER(C.c_uint32)]),
+    "fh_set_dct2": (_i32, [_ctx, _u64, _u64, _pd]),
+    "fh_dct2_shape": (_i32, [_ctx, C.POINTER(C.c_uint32)]),
+    "fh_dct2_shape_for": (_i32, [_u64, _u64, _i32, _i32, C.POINTER(C.c_uint32)]),
     "fh_set_conv2d": (_i32, [_ctx, _u64, _u64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _pd, _pd]),
     "fh_conv_shape": (_i32, [_ctx, C.POINTER(C.c_uint32)]),
     "fh_conv_shape_for": (_i32, [_u64, _u64, C.c_uint32, C.c_uint32, _i32, C.POINTER(C.c_uint32)]),
@@ -330,6 +333,37 @@ def dct_refusal(N, row_cap=0, ncu=256):
     out = (C.c_uint32 * DCT_SHAPE_LEN)()
     status = lib.fh_dct_shape_for(int(N), int(row_cap), int(ncu), out)
     if status == E_ARG and out[3] != 0:                  # (the cap was accepted -- the rule reports it -- so the sentence is about N)
+        return f"[{status}] " + lib.fh_last_error().decode(errors="replace")
+    _check(lib, status)
+    return None
+
+
+Dct2Shape = collections.namedtuple("Dct2Shape", "served H W cap radices_h radices_w lds_h rows_h grid_h lds_w rows_w grid_w threads lds_bytes tiles launches")
+
+
+def _dct2_shape(out):
+    v = [int(k) for k in out]
+    return Dct2Shape(v[0], v[1], v[2], v[3], tuple(v[5:5 + v[4]]), tuple(v[18:18 + v[17]]), *v[30:40])
+
+
+def dct2_shape(H, W, row_cap=0, ncu=256):
+    """Dct2Shape of the 2-D DCT operator's launches for an (H, W) image under FH_TUNE_DCT_ROW_CAP = row_cap (0 = 2048) on a device of ncu compute
+    units: fh_dct2_shape_for, the rule the launchers call.  Suffix _h: the W rows of length H, _w: the H rows of length W.  Host-only.  HipError
+    with the library's sentence for a shape the device refuses."""
+    lib = load_library()
+    out = (C.c_uint32 * DCT_SHAPE_LEN)()
+    _check(lib, lib.fh_dct2_shape_for(int(H), int(W), int(row_cap), int(ncu), out))
+    return _dct2_shape(out)
+
+
+def dct2_refusal(H, W, row_cap=0, ncu=256):
+    """None when the device serves the shape (H, W) under that row cap, else the library's sentence about the shape (an empty axis, a prime factor
+    above 5, an axis beyond the cap).  Only those are refusals: a row cap out of range, a library that is missing or does not load, or any other
+    status raises."""
+    lib = load_library()
+    out = (C.c_uint32 * DCT_SHAPE_LEN)()
+    status = lib.fh_dct2_shape_for(int(H), int(W), int(row_cap), int(ncu), out)
+    if status == E_ARG and out[3] != 0:                  # (the cap was accepted -- the rule reports it -- so the sentence is about the shape)
         return f"[{status}] " + lib.fh_last_error().decode(errors="replace")
     _check(lib, status)
     return None
@@ -643,6 +677,23 @@ class HipContext:
         out = (C.c_uint32 * DCT_SHAPE_LEN)()
         self._call("fh_dct_shape", out)
         return _dct_shape(out)
+
+    def set_dct2(self, H, W, diag=None):
+        """A x = d * (C_H X C_W^T), A^H w = C_H^T (d * w) C_W on an (H, W) image, C_L the orthonormal DCT-II of length L (csrc/fh_dct2.h);
+        diag=None: all ones."""
+        if diag is None:
+            self._call("fh_set_dct2", int(H), int(W), None)
+            return
+        d, pd = _as_f64(diag)
+        if d.shape != (int(H), int(W)):
+            raise ValueError(f"diag has shape {d.shape}, the DCT operator on an image of shape ({int(H)}, {int(W)}) takes ({int(H)}, {int(W)})")
+        self._call("fh_set_dct2", int(H), int(W), pd)
+
+    def dct2_shape(self):
+        """Dct2Shape the next fwd / adj of this context launches with (fh_dct2_shape).  E_STATE without a 2-D DCT operator."""
+        out = (C.c_uint32 * DCT_SHAPE_LEN)()
+        self._call("fh_dct2_shape", out)
+        return _dct2_shape(out)
 
     def set_identity(self, M, N):
         """The identity operator on an (M, N) matrix unknown with an elementwise loss (csrc/fh_nuclear.h): m = n = M * N; set the loss

@@ -15,7 +15,8 @@ subclasses are *recognised* by `fasta()` and run on the device:
                      device by rows and by columns; both directions are gathers (csrc/fh_sparse.h; with `rhs=L`
                      the unknown is an (n, L) matrix and every entry gathers a whole row of it, csrc/fh_spmulti.h);
   GradDivMap      -- the periodic div/grad stencil pair of examples/tv_denoising.py:26-63;
-  DCTMap          -- the subsampled orthonormal DCT of examples/democratic_representation.py:80-82, an implicit fast transform (csrc/fh_dct.h);
+  DCTMap          -- the subsampled orthonormal DCT of examples/democratic_representation.py:80-82, an implicit fast transform (csrc/fh_dct.h); on an image shape (H, W) the separable
+                     2-D transform `mask * dctn(x)` / `idctn(mask * w)` (csrc/fh_dct2.h);
   ConvMap         -- periodic convolution with a small kernel (a point-spread function) and its correlation adjoint, an implicit operator (csrc/fh_conv.h);
   QuadraticMap    -- the identity operator of a quadratic smooth term (losses.Quadratic): what `fasta(None, None, q.f, q.gradf, ...)` runs on;
   BilinearMap     -- the identity operator of a bilinear smooth term (losses.Factorization): what `fasta(None, None, fz.f, fz.gradf, ...)` runs on;
@@ -602,10 +603,21 @@ class DCTMap(_DeviceMap):
     lazy=True: the device context is created when the device loop first asks for it.  An N the device refuses (a prime factor above 5, no
     split within the row cap: `refusal` holds the library's sentence) stays a host map: `fasta()` runs it on the generic host loop, and
     `backend="hip"` raises with that sentence.  tuning (a keyword of this build, as DenseMatrixMap has one): {hip.TUNE_DCT_ROW_CAP: cap} lowers
-    the row cap (set before the operator); a cap out of range raises."""
+    the row cap (set before the operator); a cap out of range raises.
+    A 2-tuple (H, W) in place of N is the separable transform of an image, A x = mask * (C_H X C_W^T) and A^H w = C_H^T (mask * w) C_W
+    (fh_set_dct2, csrc/fh_dct2.h): on host arrays exactly `mask * scipy.fftpack.dctn(x, norm='ortho')` and
+    `scipy.fftpack.idctn(mask * w, norm='ortho')`, `mask` of shape (H, W), each axis at most the row cap with prime factors 2, 3 and 5 only
+    (an axis of length 1 is the identity).  An int or a 1-tuple is the 1-D operator; any other rank is a ValueError."""
 
     def __init__(self, N, mask=None, device=0, lazy=False, tuning=None):
-        N = int(N)
+        shape = (int(N),) if np.ndim(N) == 0 else tuple(int(k) for k in N)
+        if len(shape) not in (1, 2):
+            raise ValueError(f"DCTMap takes a length N, a shape (N,) or an image shape (H, W); got {len(shape)} dimensions")
+        self.image_shape = shape
+        if len(shape) == 2:
+            self._init_2d(shape, mask, device, lazy, tuning)
+            return
+        N = shape[0]
         self.N = N
         self.mask = None if mask is None else np.ascontiguousarray(mask, dtype=np.float64)
         if self.mask is not None and self.mask.shape != (N,):
@@ -616,17 +628,39 @@ class DCTMap(_DeviceMap):
         self.geometry = None if self.refusal is not None else hip.dct_shape(N, cap)
         _DeviceMap.__init__(self, (N,), (N,), device, lazy=lazy or self.refusal is not None)
 
+    def _init_2d(self, shape, mask, device, lazy, tuning):
+        H, W = shape
+        self.N = H * W
+        self.mask = None if mask is None else np.ascontiguousarray(mask, dtype=np.float64)
+        if self.mask is not None and self.mask.shape != shape:
+            raise ValueError(f"mask has shape {self.mask.shape}, a DCT on an image of shape {shape} takes {shape}")
+        self._tuning = dict(tuning or {})
+        cap = self._tuning.get(hip.TUNE_DCT_ROW_CAP, 0)
+        self.refusal = hip.dct2_refusal(H, W, cap)       # (a row cap out of range or a library that does not load raises: only a sentence about the shape is a refusal)
+        self.geometry = None if self.refusal is not None else hip.dct2_shape(H, W, cap)
+        _DeviceMap.__init__(self, shape, shape, device, lazy=lazy or self.refusal is not None)
+
     def _on_context(self, ctx):
         for key, value in self._tuning.items():
             ctx.set_tuning(key, value)
-        ctx.set_dct(self.N, self.mask)
+        if len(self.image_shape) == 2:
+            ctx.set_dct2(self.image_shape[0], self.image_shape[1], self.mask)
+        else:
+            ctx.set_dct(self.N, self.mask)
 
     def _apply_fwd(self, v):
+        if len(self.image_shape) == 2:
+            from scipy.fftpack import dctn
+            y = dctn(v, norm='ortho')
+            return y if self.mask is None else self.mask * y
         from scipy.fftpack import dct
         y = dct(v, norm='ortho')
         return y if self.mask is None else self.mask * y
 
     def _apply_adj(self, w):
+        if len(self.image_shape) == 2:
+            from scipy.fftpack import idctn
+            return idctn(w if self.mask is None else self.mask * w, norm='ortho')
         from scipy.fftpack import idct
         return idct(w if self.mask is None else self.mask * w, norm='ortho')
 

@@ -134,6 +134,10 @@ def _dct_form_refusal(A, loss, prox, x0):
     if isinstance(prox, (TVDualBall, GroupShrink)):
         return (f"proximal.{type(prox).__name__} is not implemented for a DCT operator on the device "
                 "(Shrink, NonNeg, Box, LinfProx, L1Ball or no prox are)")
+    if len(A.Vshape) == 2:                                 # the 2-D operator (csrc/fh_dct2.h): an unknown of the image's shape
+        if x0 is not None and tuple(np.shape(x0)) != A.Vshape:
+            return f"a DCT operator on an image of shape {A.Vshape} takes an unknown of that shape on the device (x0 has shape {tuple(np.shape(x0))})"
+        return None
     if x0 is not None and np.ndim(x0) != 1:
         return f"a DCT operator takes a vector unknown of shape ({A.N},) on the device (x0 has {np.ndim(x0)} dimensions)"
     return None

@@ -286,6 +286,29 @@ int fh_set_dct(fh_ctx* ctx, uint64_t N, const double* diag);
 #define FH_DCT_SHAPE_LEN 40
 int fh_dct_shape(fh_ctx* ctx, uint32_t* out);
 int fh_dct_shape_for(uint64_t N, int row_cap, int ncu, uint32_t* out);
+/* ---- subsampled 2-D DCT on an image: A x = d * (C_H X C_W^T), A^H w = C_H^T (d * w) C_W (csrc/fh_dct2.h) ------------------------------------------
+ * X is the unknown as an (H, W) image in C order, C_L the orthonormal DCT-II of length L documented at fh_set_dct: the pair is
+ * d * scipy.fftpack.dctn(x, norm='ortho') and scipy.fftpack.idctn(d * w, norm='ortho').  m = n = H * W (fh_shape reports them).  d: H * W float64
+ * values in C order copied to the device, NULL = all ones; d[k] == 0.0 gives z[k] == 0.0 exactly.  No matrix is stored: each direction is the 1-D
+ * operator's row transform (Makhoul, one complex Stockham FFT of the row's length in LDS, radices 2, 3, 4, 5) along W and along H with real H * W
+ * images between them, four launches per direction, from one pair of twiddle tables per axis built on the host in long double when the operator
+ * is set, and two work buffers of H * W doubles.  An axis of length 1 is the identity transform.  The context holds the DCT operator in its 2-D
+ * geometry: vectors, prox kinds (IDENTITY, SHRINK, NONNEG, BOX, LINF, L1BALL), the least-squares loss, the served entry points and the FH_S_*
+ * scalars are those of fh_set_dct, and so is everything fh_set_dct lists as refused (FH_E_STATE): multi-device contexts, a communicator,
+ * fh_set_rhs, float32 storage, the logistic loss, fh_step*, fh_run, fh_get_matrix_rows, fh_stream_read_ms; fh_dct_shape is FH_E_STATE too (the
+ * geometry is fh_dct2_shape's).  No atomics on floats, fixed summation order, bitwise repeatable.
+ * Refused (FH_E_ARG with a sentence naming the axis): an axis of length 0, an axis with a prime factor above 5, an axis longer than the row cap
+ * (2048; FH_TUNE_DCT_ROW_CAP lowers it) -- there is no two-level transform per axis.  Setting any other operator leaves this form.              */
+int fh_set_dct2(fh_ctx* ctx, uint64_t H, uint64_t W, const double* diag);
+/* read-only: the geometry the 2-D DCT launches take (csrc/fh_host_launch.h: dct2_shape_for, the ONE rule the launchers call).
+ * out[FH_DCT_SHAPE_LEN]: [0] 1 (0: the shape is not served -- the call then returns FH_E_ARG and the sentence), [1] H, [2] W, [3] the row cap,
+ * [4] number of radix passes of a row of length H, [5..16] its radices in pass order, [17] and [18..29] the same for W, [30] LDS class (double2 per
+ * ping-pong buffer: 128 / 512 / 2048), [31] rows per workgroup and [32] grid of the row launches along H (W rows of length H), [33..35] the same
+ * along W (H rows of length W), [36] threads per workgroup, [37] static LDS bytes of the largest row kernel, [38] grid of each tile launch (32 x 32
+ * tiles of the H x W image), [39] launches per direction.  fh_dct2_shape reports what the context was set with and is FH_E_STATE without a 2-D DCT
+ * operator; fh_dct2_shape_for is the same rule as a pure host function (no device needed; row_cap: 0 = 2048; ncu: the device's compute units). */
+int fh_dct2_shape(fh_ctx* ctx, uint32_t* out);
+int fh_dct2_shape_for(uint64_t H, uint64_t W, int row_cap, int ncu, uint32_t* out);
 /* ---- periodic convolution with a small kernel: A x = d * (K conv x), A^T w = K corr (d * w) (csrc/fh_conv.h) --------------------------------------
  * Image x of shape (H, W) in C order (a signal: H = 1), taps K of shape (kh, kw) in C order with 1 <= kh, kw <= 16, origin (oh, ow) inside the
  * kernel, all indices modulo the dimension:
