@@ -10,16 +10,16 @@ package in this repository re-exports these names so `import fasta` keeps workin
 Which loop runs is decided by the operand types: device-recognisable operands (matrix / sparse matrix / DenseMatrixMap / SparseMatrixMap / GradDivMap + tagged
 loss + tagged prox) run the HIP loop and raise when the built `libfasta_hip.so` or a gfx950 GPU is missing -- no CPU fallback;
 `A=None` with a tagged losses.Quadratic or losses.Factorization runs the HIP loop too (csrc/fh_quad.h, csrc/fh_bilinear.h), and so does `A=None` with one tagged
-losses.LogisticLoss(B) / LeastSquares(B) and a 2-D x0 of B's shape (the identity operator, csrc/fh_nuclear.h: proximal.NuclearShrink); closures, callable pairs, any other `A=None` and host LinearMaps cannot execute inside a kernel and run the generic host loop
+losses.LogisticLoss(B) / LeastSquares(B) and a 2-D x0 of B's shape (the identity operator, csrc/fh_nuclear.h: proximal.NuclearShrink / NuclearBall, observation weights); closures, callable pairs, any other `A=None` and host LinearMaps cannot execute inside a kernel and run the generic host loop
 (`generic.py`, the reference's semantics).  `backend="hip"` / `backend="numpy"` force either.
 """
 
 from . import generic, hip, linalg, losses, proximal, stopping
 from .linalg import BilinearMap, ConvMap, DCTMap, DenseMatrixMap, GradDivMap, IdentityMap, LinearMap, LinearOperator, QuadraticMap, ShardedDenseMatrixMap, SparseMatrixMap
 from .losses import Factorization, LeastSquares, LogisticLoss, Quadratic, SoftmaxLoss
-from .proximal import Box, GroupShrink, L1Ball, LinfProx, NonNeg, NoProx, NuclearShrink, RowBall, RowSplit, Shrink, TVDualBall
+from .proximal import Box, GroupShrink, L1Ball, LinfProx, NonNeg, NoProx, NuclearBall, NuclearShrink, RowBall, RowSplit, Shrink, TVDualBall
 from .solver import EPSILON, Convergence, FBSolver, fasta
 
 __all__ = ["fasta", "Convergence", "FBSolver", "EPSILON", "linalg", "proximal", "stopping", "losses", "hip",
            "LinearMap", "LinearOperator", "DenseMatrixMap", "ShardedDenseMatrixMap", "SparseMatrixMap", "GradDivMap", "DCTMap", "ConvMap", "QuadraticMap", "BilinearMap", "IdentityMap", "LeastSquares", "LogisticLoss", "SoftmaxLoss", "Quadratic", "Factorization",
-           "Shrink", "NonNeg", "LinfProx", "L1Ball", "Box", "TVDualBall", "GroupShrink", "RowBall", "RowSplit", "NuclearShrink", "NoProx"]
+           "Shrink", "NonNeg", "LinfProx", "L1Ball", "Box", "TVDualBall", "GroupShrink", "RowBall", "RowSplit", "NuclearShrink", "NuclearBall", "NoProx"]

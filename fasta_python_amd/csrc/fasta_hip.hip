@@ -434,6 +434,7 @@ static int setup_dense(fh_ctx* c, uint64_t m, uint64_t n) {
   if (m >= (1ull << 31) || n >= (1ull << 31)) return fail(FH_E_ARG, "matrix dimension exceeds 2^31-1");
   FH_TRY(use_device(c));
   HIP_TRY(hipStreamSynchronize(c->stream));
+  FH_TRY(refuse_weighted(c));
   free_operator(c);
   c->m = m; c->n = n;
   c->mp = round_up(m, 16);
@@ -619,6 +620,7 @@ static int set_matrix_csr(fh_ctx* c, const char* who, uint64_t m, uint64_t n, ui
   const int C = LB ? (int)(LB / 2) : 1;                  // lanes per gathered row of the operand
   FH_TRY(use_device(c));
   HIP_TRY(hipStreamSynchronize(c->stream));
+  FH_TRY(refuse_weighted(c));
   free_operator(c);                                      // (back to the vector form: L = LB = 0)
   if (L ? !mc_prox_ok(c->prox_kind) : !sp_prox_ok(c->prox_kind)) { c->prox_kind = FH_PROX_IDENTITY; c->mu = 0.0; }
   if (L) { c->loss_kind = LOSS_LSQ; c->lazy = false; c->last_accel = false; c->commits = 0; }
@@ -719,6 +721,7 @@ extern "C" int fh_set_stencil(fh_ctx* c, uint64_t H, uint64_t W) {
   if (!c->shards.empty() || c->owner) return fail(FH_E_STATE, "row sharding is implemented for the dense operator only");
   FH_TRY(use_device(c));
   HIP_TRY(hipStreamSynchronize(c->stream));
+  FH_TRY(refuse_weighted(c));
   free_operator(c);
   c->H = H; c->W = W;
   c->m = H * W; c->n = 2 * H * W;
@@ -741,6 +744,7 @@ extern "C" int fh_set_stencil3d(fh_ctx* c, uint64_t D, uint64_t H, uint64_t W) {
   FH_TRY(tv3_shape_for(D, H, W, 0, 1, &sh));             // (dimensions >= 1, 3 * D * H * W < 2^31: FH_E_ARG with the sentence)
   FH_TRY(use_device(c));
   HIP_TRY(hipStreamSynchronize(c->stream));
+  FH_TRY(refuse_weighted(c));
   free_operator(c);
   if (!tv3_prox_ok(c->prox_kind)) { c->prox_kind = FH_PROX_IDENTITY; c->mu = 0.0; }
   c->loss_kind = LOSS_LSQ; c->lazy = false; c->last_accel = false; c->commits = 0;
@@ -766,6 +770,7 @@ extern "C" int fh_set_dct(fh_ctx* c, uint64_t N, const double* diag) {
   FH_TRY(dct_shape_for(N, c->dct_row_cap, c->ncu, &sh));   // (N >= 1, prime factors in {2, 3, 5}, a split within the row cap: FH_E_ARG with the sentence)
   FH_TRY(use_device(c));
   HIP_TRY(hipStreamSynchronize(c->stream));
+  FH_TRY(refuse_weighted(c));
   free_operator(c);
   if (!dct_prox_ok(c->prox_kind)) { c->prox_kind = FH_PROX_IDENTITY; c->mu = 0.0; }
   c->loss_kind = LOSS_LSQ; c->lazy = false; c->last_accel = false; c->commits = 0;
@@ -793,6 +798,7 @@ extern "C" int fh_set_dct2(fh_ctx* c, uint64_t H, uint64_t W, const double* diag
   FH_TRY(dct2_shape_for(H, W, c->dct_row_cap, c->ncu, &sh));   // (each axis >= 1, at most the row cap, prime factors in {2, 3, 5}: FH_E_ARG with the sentence)
   FH_TRY(use_device(c));
   HIP_TRY(hipStreamSynchronize(c->stream));
+  FH_TRY(refuse_weighted(c));
   free_operator(c);
   if (!dct_prox_ok(c->prox_kind)) { c->prox_kind = FH_PROX_IDENTITY; c->mu = 0.0; }
   c->loss_kind = LOSS_LSQ; c->lazy = false; c->last_accel = false; c->commits = 0;
@@ -824,6 +830,7 @@ extern "C" int fh_set_conv2d(fh_ctx* c, uint64_t H, uint64_t W, uint32_t kh, uin
   if (oh >= kh || ow >= kw) return fail(FH_E_ARG, "fh_set_conv2d: the origin (%u, %u) lies outside the %u x %u kernel", oh, ow, kh, kw);
   FH_TRY(use_device(c));
   HIP_TRY(hipStreamSynchronize(c->stream));
+  FH_TRY(refuse_weighted(c));
   free_operator(c);
   if (!conv_prox_ok(c->prox_kind)) { c->prox_kind = FH_PROX_IDENTITY; c->mu = 0.0; }
   c->loss_kind = LOSS_LSQ; c->lazy = false; c->last_accel = false; c->commits = 0;
@@ -867,10 +874,12 @@ extern "C" int fh_set_identity(fh_ctx* c, uint64_t M, uint64_t N) {
   return finish(c);
 }
 
-// FH_PROX_NUCLEAR on the identity operator: the geometry (FH_TUNE_NUC_BLOCK_ROWS is read here) and the working buffers
-extern "C" int fh_set_prox_nuclear(fh_ctx* c, double mu, int objective) {
+// FH_PROX_NUCLEAR / FH_PROX_NUCBALL on the identity operator: the geometry (FH_TUNE_NUC_BLOCK_ROWS is read here) and the working buffers
+static int set_prox_jacobi(fh_ctx* c, int kind, double mu, int objective) {
   if (!c) return fail(FH_E_ARG, "null context");
+  if (c->op != OP_IDENTITY && kind == FH_PROX_NUCBALL) return fail(FH_E_STATE, "FH_PROX_NUCBALL (projection of a matrix unknown onto the nuclear-norm ball) is served by the identity operator only: call fh_set_identity first");
   if (c->op != OP_IDENTITY) return fail(FH_E_STATE, "FH_PROX_NUCLEAR (singular-value soft-threshold of a matrix unknown) is served by the identity operator only: call fh_set_identity first");
+  if (kind == FH_PROX_NUCBALL && !(mu >= 0.0 && mu <= 1.7976931348623157e308)) return fail(FH_E_ARG, "FH_PROX_NUCBALL: the radius (mu) must be finite and >= 0 (got %g)", mu);
   if (c->pending_step) return fail(FH_E_STATE, "a step issued by fh_step_begin is still in flight on this context: call fh_step_end first");
   NucShape sh;
   FH_TRY(nuc_shape_for(c->id_M, c->id_N, c->nuc_block_rows, &sh));
@@ -886,14 +895,15 @@ extern "C" int fh_set_prox_nuclear(fh_ctx* c, double mu, int objective) {
   c->nuc_sh = sh;
   c->nuc_objective = objective ? 1 : 0;
   c->nuc_info[0] = c->nuc_info[1] = c->nuc_info[2] = c->nuc_info[3] = 0;
-  c->prox_kind = FH_PROX_NUCLEAR; c->mu = mu; c->lo = 0.0; c->hi = 0.0;
+  c->prox_kind = kind; c->mu = mu; c->lo = 0.0; c->hi = 0.0;
   return finish(c);
 }
+extern "C" int fh_set_prox_nuclear(fh_ctx* c, double mu, int objective) { return set_prox_jacobi(c, FH_PROX_NUCLEAR, mu, objective); }
 
 // the latest thresholding (fh_fwd / fh_fwd_adj / fh_iterate) of this context: sweeps, steps launched, rotations, rank kept
 extern "C" int fh_nuclear_info(fh_ctx* c, uint64_t* out) {
   if (!c || !out) return fail(FH_E_ARG, "fh_nuclear_info: null argument");
-  if (c->op != OP_IDENTITY || c->prox_kind != FH_PROX_NUCLEAR) return fail(FH_E_STATE, "fh_nuclear_info: the context holds no identity operator with FH_PROX_NUCLEAR (fh_set_identity, fh_set_prox_nuclear)");
+  if (c->op != OP_IDENTITY || !nuc_kind(c->prox_kind)) return fail(FH_E_STATE, "fh_nuclear_info: the context holds no identity operator with FH_PROX_NUCLEAR or FH_PROX_NUCBALL (fh_set_identity, then fh_set_prox_nuclear / fh_set_prox)");
   FH_TRY(use_device(c));
   FH_TRY(finish(c));
   double rank = 0.0;
@@ -974,6 +984,7 @@ extern "C" int fh_set_quadratic(fh_ctx* c, const double* Q, uint64_t n, uint64_t
                 (unsigned long long)bi, (unsigned long long)bj, Q[bi * ld_host + bj], (unsigned long long)bj, (unsigned long long)bi, Q[bj * ld_host + bi]);
   FH_TRY(use_device(c));
   HIP_TRY(hipStreamSynchronize(c->stream));
+  FH_TRY(refuse_weighted(c));
   free_operator(c);
   if (!qd_prox_ok(c->prox_kind)) { c->prox_kind = FH_PROX_IDENTITY; c->mu = 0.0; }
   c->lazy = false; c->last_accel = false; c->commits = 0;
@@ -1012,6 +1023,7 @@ extern "C" int fh_set_factorization(fh_ctx* c, const double* S, uint64_t m, uint
   if (const char* why = bl_too_large(m, n, bl_shape_for(m, n, ld, LB, c->fwd_cap, c->nt_loads))) return fail(FH_E_ARG, "fh_set_factorization: %s", why);
   FH_TRY(use_device(c));
   HIP_TRY(hipStreamSynchronize(c->stream));
+  FH_TRY(refuse_weighted(c));
   free_operator(c);
   if (!bl_prox_ok(c->prox_kind)) { c->prox_kind = FH_PROX_IDENTITY; c->mu = 0.0; }
   c->lazy = false; c->last_accel = false; c->commits = 0;
@@ -1067,9 +1079,32 @@ static int set_loss(fh_ctx* c, int kind, const double* b, uint64_t len) {
     return 0;
   }
   FH_TRY(use_device(c));
+  FH_TRY(drop_loss_weights(c));                          // the weights belong to the loss
   FH_TRY(copy_in(c, c->b, b, c->m));
   c->has_b = true;
   c->loss_kind = kind;
+  return finish(c);
+}
+
+// observation weights of the elementwise loss on the identity operator (csrc/fh_nuclear.h): f(X) = sum_j w_j loss(x_j, b_j); NULL removes them
+extern "C" int fh_set_loss_weights(fh_ctx* c, const double* w) {
+  if (!c) return fail(FH_E_ARG, "null context");
+  if (c->pending_step) return fail(FH_E_STATE, "a step issued by fh_step_begin is still in flight on this context: call fh_step_end first");
+  if (c->op != OP_IDENTITY) {
+    if (!w && !c->loss_w) return 0;                      // (nothing held, nothing to remove)
+    return fail(FH_E_STATE, "fh_set_loss_weights: observation weights are served by the identity operator only (fh_set_identity, then fh_set_loss_lsq / "
+                            "fh_set_loss_logistic, then the weights)");
+  }
+  if (w && !c->has_b) return fail(FH_E_STATE, "fh_set_loss_weights: set the loss first (fh_set_loss_lsq / fh_set_loss_logistic): the weights belong to it");
+  if (w) for (uint64_t i = 0; i < c->n; ++i)
+    if (!(w[i] >= 0.0) || std::isinf(w[i]))
+      return fail(FH_E_ARG, "fh_set_loss_weights: weights must be finite and >= 0 (entry %llu is %g)", (unsigned long long)i, w[i]);
+  FH_TRY(use_device(c));
+  FH_TRY(drop_loss_weights(c));
+  if (!w) return 0;
+  HIP_TRY(hipMalloc((void**)&c->loss_w, (size_t)c->n * sizeof(double)));
+  const int rc = copy_in(c, c->loss_w, w, c->n);
+  if (rc != 0) { (void)hipFree(c->loss_w); c->loss_w = nullptr; return rc; }
   return finish(c);
 }
 
@@ -1116,7 +1151,9 @@ extern "C" int fh_set_prox(fh_ctx* c, int kind, double mu, double lo, double hi)
   if (!c) return fail(FH_E_ARG, "null context");
   if (kind == FH_PROX_ROWSPLIT) return fail(FH_E_ARG, "unknown prox kind %d for fh_set_prox: FH_PROX_ROWSPLIT takes two kinds and their parameters, set it with fh_set_prox_split (bilinear operator only)", kind);
   if (kind == FH_PROX_NUCLEAR && c->op == OP_CONV) return fail(FH_E_ARG, "prox kind %d (NUCLEAR) is not implemented for the convolution operator: it is served by the identity operator only", kind);
+  if (kind == FH_PROX_NUCBALL && c->op == OP_CONV) return fail(FH_E_ARG, "prox kind %d (NUCBALL) is not implemented for the convolution operator: it is served by the identity operator only", kind);
   if (kind == FH_PROX_NUCLEAR) return fh_set_prox_nuclear(c, mu, 1);
+  if (kind == FH_PROX_NUCBALL) return set_prox_jacobi(c, FH_PROX_NUCBALL, mu, 0);      // g = 0: the norms are never evaluated where they are not free
   if (kind < FH_PROX_IDENTITY || kind > FH_PROX_ROWBALL) return fail(FH_E_ARG, "unknown prox kind %d", kind);
   if (c->op == OP_IDENTITY && !id_prox_ok(kind)) return fail(FH_E_ARG, "prox kind %d (LINF / L1BALL / TVBALL / GROUP / ROWBALL) is not implemented for the identity operator", kind);
   if (c->op == OP_BILINEAR && !bl_prox_ok(kind)) return fail(FH_E_ARG, "prox kind %d (LINF / L1BALL / TVBALL / GROUP / ROWBALL) has no bilinear form", kind);

@@ -161,6 +161,8 @@ struct fh_ctx {
   double* nuc_w = nullptr; double* nuc_phi = nullptr; double* nuc_scal = nullptr;
   unsigned* nuc_cnt = nullptr; unsigned* nuc_host = nullptr;
   uint64_t nuc_info[4] = {0, 0, 0, 0};      // sweeps, steps launched, rotations, rank kept
+  // observation weights of the elementwise loss (fh_set_loss_weights): n doubles, or nullptr = unweighted.  They belong to the loss: fh_set_loss_* drops them.
+  double* loss_w = nullptr;
   uint64_t D = 0;            // 3-D stencil (fh_set_stencil3d, csrc/fh_tv3d.h): the volume is (D, H, W), m = D*H*W, n = 3*m
   // sparse operator (fh_set_matrix_csr, csrc/fh_sparse.h): sp[0] = A by rows, sp[1] = A^T by rows, each with its non-zero-balanced row ranges,
   // its list of long rows and the lanes-per-row G chosen from its mean row length; sp_r = the adjoint's residual (m-side).  In multi-column form
@@ -419,6 +421,21 @@ static void free_vectors(fh_ctx* c) {
   for (int i = 0; i < 4; ++i) fr(c->T[i]);
 }
 
+// every operator setter but fh_set_identity calls this before it frees anything: a weighted problem never silently runs unweighted
+static int refuse_weighted(const fh_ctx* c) {
+  if (c->loss_w) return fail(FH_E_STATE, "the context holds observation weights (fh_set_loss_weights), which the identity operator alone serves: remove them "
+                                         "(fh_set_loss_weights(ctx, NULL), or set the loss again) before another operator is set");
+  return 0;
+}
+
+static int drop_loss_weights(fh_ctx* c) {
+  if (!c->loss_w) return 0;
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  HIP_TRY(hipFree(c->loss_w));
+  c->loss_w = nullptr;
+  return 0;
+}
+
 static void free_operator(fh_ctx* c) {
   for (fh_ctx* s : c->shards) { (void)hipSetDevice(s->device); free_operator(s); }
   auto fr = [](double*& p) { if (p) { (void)hipFree(p); p = nullptr; } };
@@ -441,13 +458,14 @@ static void free_operator(fh_ctx* c) {
   if (c->nuc_cnt) { (void)hipFree(c->nuc_cnt); c->nuc_cnt = nullptr; }
   if (c->nuc_host) { (void)hipHostFree(c->nuc_host); c->nuc_host = nullptr; }
   c->id_M = c->id_N = 0;
+  fr(c->loss_w);
   free_vectors(c);
   c->L = c->LB = 0;                  // a new operator starts in the vector form
   if (c->loss_kind == LOSS_QUAD) c->loss_kind = LOSS_LSQ;                                        // ... and leaves the quadratic form (fh_set_quadratic) behind:
   if (c->prox_kind == FH_PROX_ROWBALL) { c->prox_kind = FH_PROX_IDENTITY; c->mu = 0.0; }      // its loss and the prox only it serves
   if (c->loss_kind == LOSS_BILINEAR) c->loss_kind = LOSS_LSQ;                                    // ... and the bilinear form (fh_set_factorization) likewise
   if (c->prox_kind == FH_PROX_ROWSPLIT) { c->prox_kind = FH_PROX_IDENTITY; c->mu = 0.0; }
-  if (c->prox_kind == FH_PROX_NUCLEAR) { c->prox_kind = FH_PROX_IDENTITY; c->mu = 0.0; }         // ... and the identity form's (fh_set_identity)
+  if (c->prox_kind == FH_PROX_NUCLEAR || c->prox_kind == FH_PROX_NUCBALL) { c->prox_kind = FH_PROX_IDENTITY; c->mu = 0.0; }         // ... and the identity form's (fh_set_identity)
   fr(c->bl_part); c->bl_part_bytes = 0; c->bl_have_grad = false; c->bl_m = c->bl_n = 0;
   fr(c->ws); c->ws_bytes = 0;
   fr(c->slotbuf); c->slotbuf_bytes = 0; c->slots_sig = 0;

@@ -1456,7 +1456,8 @@ static int launch_adj_dct(fh_ctx* c, const AdjIO& io) {
 #ifndef FH_SINGLE_TU
 NUC_KERNELS(extern template)
 #endif
-static inline bool id_prox_ok(int kind) { return sp_prox_ok(kind) || kind == FH_PROX_NUCLEAR; }
+static inline bool nuc_kind(int kind) { return kind == FH_PROX_NUCLEAR || kind == FH_PROX_NUCBALL; }      // the two kinds behind the Jacobi decomposition
+static inline bool id_prox_ok(int kind) { return sp_prox_ok(kind) || nuc_kind(kind); }
 // THE geometry of the thresholding, a pure function of (M, N) and FH_TUNE_NUC_BLOCK_ROWS (0 = auto = NUC_AUTO_BLOCK_ROWS): p = min, q = max, P = p padded to a multiple of
 // Bk, nb = P / Bk blocks, a sweep of nb - 1 steps (nb even; nb for an odd nb, whose steps each give one block a bye; 1 for nb = 1: the self-pair) of
 // ceil(nb / 2) workgroups, rows of [ W | J^T ] of ld = (q padded to even) + (P padded to even) doubles.
@@ -1466,7 +1467,7 @@ static int nuc_shape_for(uint64_t M, uint64_t N, int block_rows, NucShape* sh) {
   if (M == 0 || N == 0) return fail(FH_E_ARG, "the identity operator needs a non-empty matrix unknown (got %llu x %llu)", (unsigned long long)M, (unsigned long long)N);
   if (M > (1ull << 26) || N > (1ull << 26) || M * N > (1ull << 26)) return fail(FH_E_ARG, "the identity operator serves at most 2^26 entries (got %llu x %llu)", (unsigned long long)M, (unsigned long long)N);
   const uint64_t p = std::min(M, N), q = std::max(M, N);
-  if (p > NUC_MAX_P) return fail(FH_E_ARG, "FH_PROX_NUCLEAR serves min(M, N) <= %d (got %llu x %llu): the Jacobi sweeps are quadratic in it", NUC_MAX_P, (unsigned long long)M, (unsigned long long)N);
+  if (p > NUC_MAX_P) return fail(FH_E_ARG, "FH_PROX_NUCLEAR / FH_PROX_NUCBALL serve min(M, N) <= %d (got %llu x %llu): the Jacobi sweeps are quadratic in it", NUC_MAX_P, (unsigned long long)M, (unsigned long long)N);
   const uint32_t Bk = block_rows ? (uint32_t)block_rows : NUC_AUTO_BLOCK_ROWS;
   NucGeo& g = sh->g;
   g.M = (uint32_t)M; g.N = (uint32_t)N; g.p = (uint32_t)p; g.q = (uint32_t)q; g.transposed = M > N ? 1 : 0;
@@ -1487,7 +1488,7 @@ static void nuc_shape_out(const NucShape& sh, uint64_t* out) {
 }
 extern "C" int fh_nuclear_shape(fh_ctx* c, uint64_t* out) {
   if (!c || !out) return fail(FH_E_ARG, "fh_nuclear_shape: null argument");
-  if (c->op != OP_IDENTITY || c->prox_kind != FH_PROX_NUCLEAR) return fail(FH_E_STATE, "fh_nuclear_shape: the context holds no identity operator with FH_PROX_NUCLEAR (fh_set_identity, fh_set_prox_nuclear)");
+  if (c->op != OP_IDENTITY || !nuc_kind(c->prox_kind)) return fail(FH_E_STATE, "fh_nuclear_shape: the context holds no identity operator with FH_PROX_NUCLEAR or FH_PROX_NUCBALL (fh_set_identity, then fh_set_prox_nuclear / fh_set_prox)");
   nuc_shape_out(c->nuc_sh, out);                          // (what nuc_shape_for gave when the prox was set: the launchers read the same copy)
   return 0;
 }
@@ -1533,7 +1534,7 @@ static int nuc_decompose(fh_ctx* c, const double* x0, const double* g0, double t
     info[0] += 1; info[1] += sh.steps; info[2] += c->nuc_host[sweep];
     if (c->nuc_host[sweep] == 0u) return 0;
   }
-  return fail(FH_E_NOCONV, "FH_PROX_NUCLEAR: the block-Jacobi sweeps still rotated after %d sweeps (%llu rotations in the last one)", NUC_MAX_SWEEPS,
+  return fail(FH_E_NOCONV, "FH_PROX_NUCLEAR / FH_PROX_NUCBALL: the block-Jacobi sweeps still rotated after %d sweeps (%llu rotations in the last one)", NUC_MAX_SWEEPS,
               (unsigned long long)c->nuc_host[NUC_MAX_SWEEPS - 1]);
 }
 static int nuc_sigma(fh_ctx* c, double thr, double* phi, double* out_gsum, double* out_gmax, double* out_rank, int to_host) {
@@ -1546,7 +1547,8 @@ static int nuc_sigma(fh_ctx* c, double thr, double* phi, double* out_gsum, doubl
   HIP_TRY(hipGetLastError());
   return 0;
 }
-// xhat = x0 - tau*g0 and xp = its singular-value soft-threshold at tau*mu; nuc_scal[1] = the nuclear norm of xp, [2] = the rank kept, [3] = its largest singular value
+// xhat = x0 - tau*g0 and xp = its singular-value soft-threshold at tau*mu (FH_PROX_NUCBALL: its projection onto the nuclear-norm ball of radius mu, whose level
+// k_nuc_ball finds from the sigma that k_nuc_sigma left in its per-row records at thr = 0, a launch that forms no sums); nuc_scal[1] = the nuclear norm of xp, [2] = the rank kept, [3] = its largest singular value
 static int nuc_prox(fh_ctx* c, double tau, const double* x0, const double* g0, double* xhat, double* xp) {
   const NucShape& sh = c->nuc_sh;
   t_begin(c, FH_K_LEVEL);
@@ -1560,7 +1562,15 @@ static int nuc_prox(fh_ctx* c, double tau, const double* x0, const double* g0, d
     memcpy(g_err, keep, sizeof(keep));
     return rc;
   }
-  FH_TRY(nuc_sigma(c, tau * c->mu, c->nuc_phi, c->nuc_scal + 1, c->nuc_scal + 3, c->nuc_scal + 2, 0));
+  if (c->prox_kind == FH_PROX_NUCBALL) {
+    FH_TRY(nuc_sigma(c, 0.0, nullptr, nullptr, nullptr, nullptr, 0));
+    NucBallP bp;
+    bp.p = sh.g.p; bp.P = sh.g.P; bp.radius = c->mu; bp.red = c->ws; bp.phi = c->nuc_phi;
+    bp.out_gsum = c->nuc_scal + 1; bp.out_gmax = c->nuc_scal + 3; bp.out_rank = c->nuc_scal + 2;
+    k_nuc_ball<<<dim3(1), dim3(FH_WG), 0, c->stream>>>(bp);
+    HIP_TRY(hipGetLastError());
+  }
+  else FH_TRY(nuc_sigma(c, tau * c->mu, c->nuc_phi, c->nuc_scal + 1, c->nuc_scal + 3, c->nuc_scal + 2, 0));
   NucReconP rp;
   rp.g = sh.g; rp.W = c->nuc_w; rp.phi = c->nuc_phi; rp.xp = xp;
   k_nuc_recon<<<dim3((sh.g.q + FH_WG - 1) / FH_WG, (sh.g.p + NUC_TR - 1) / NUC_TR), dim3(FH_WG), 0, c->stream>>>(rp);
@@ -1590,7 +1600,7 @@ static int nuc_norm(fh_ctx* c, const double* x, double* out_gsum, double* out_gm
 static int launch_fwd_identity(fh_ctx* c, int mode, double tau, const double* x0, const double* g0, const double* xacc0,
                                double* xhat, double* xp, double* z, int sub_b) {
   if (mode == 0 && !id_prox_ok(c->prox_kind)) return fail(FH_E_STATE, "prox kind %d (LINF / L1BALL / TVBALL / GROUP / ROWBALL / ROWSPLIT) is not implemented for the identity operator", c->prox_kind);
-  const bool nuc = mode == 0 && c->prox_kind == FH_PROX_NUCLEAR;
+  const bool nuc = mode == 0 && nuc_kind(c->prox_kind);
   if (nuc) FH_TRY(nuc_prox(c, tau, x0, g0, xhat, xp));
   IdFwdP p;
   p.n = c->n; p.mode = mode; p.given = nuc ? 1 : 0; p.sub_b = sub_b; p.loss = c->loss_kind;
@@ -1602,7 +1612,8 @@ static int launch_fwd_identity(fh_ctx* c, int mode, double tau, const double* x0
   p.red = c->ws; p.counter = c->counters + CNT_FWD; p.out = scalar_out(c);
   t_begin(c, FH_K_FWD);
   p.seq = seq_offer(c);
-  k_id_fwd<<<dim3(grid), dim3(FH_WG), 0, c->stream>>>(p);
+  if (c->loss_w) { IdFwdWP q; q.p = p; q.w = c->loss_w; k_id_fwd<true><<<dim3(grid), dim3(FH_WG), 0, c->stream>>>(q); }
+  else k_id_fwd<false><<<dim3(grid), dim3(FH_WG), 0, c->stream>>>(p);
   t_end(c, FH_K_FWD);
   HIP_TRY(hipGetLastError());
   return 0;
@@ -1612,7 +1623,7 @@ static int launch_fwd_identity(fh_ctx* c, int mode, double tau, const double* x0
 // a values-only decomposition of the extrapolated x1 otherwise
 static int launch_adj_identity(fh_ctx* c, const AdjIO& io) {
   if (io.mode != 0 && io.mode != 1) return fail(FH_E_STATE, "the identity operator has no row-sharded adjoint");
-  const bool nuc = io.mode == 0 && c->prox_kind == FH_PROX_NUCLEAR;
+  const bool nuc = io.mode == 0 && nuc_kind(c->prox_kind);
   IdAdjP p;
   p.n = c->n; p.mode = io.mode; p.accel = io.accel; p.sub_b = io.sub_b; p.loss = c->loss_kind;
   p.gsum_mode = !nuc ? 0 : (!io.accel ? 1 : (c->nuc_objective ? 3 : 2));
@@ -1624,7 +1635,8 @@ static int launch_adj_identity(fh_ctx* c, const AdjIO& io) {
   p.red = c->ws; p.counter = c->counters + CNT_ADJ_FIN; p.out = scalar_out(c);
   t_begin(c, FH_K_ADJ);
   p.seq = (io.mode == 0 && p.gsum_mode != 3) ? seq_offer(c) : 0u;
-  k_id_adj<<<dim3(grid), dim3(FH_WG), 0, c->stream>>>(p);
+  if (c->loss_w) { IdAdjWP q; q.p = p; q.w = c->loss_w; k_id_adj<true><<<dim3(grid), dim3(FH_WG), 0, c->stream>>>(q); }
+  else k_id_adj<false><<<dim3(grid), dim3(FH_WG), 0, c->stream>>>(p);
   t_end(c, FH_K_ADJ);
   HIP_TRY(hipGetLastError());
   if (p.gsum_mode == 3) FH_TRY(nuc_norm(c, io.x1, scalar_out(c) + FH_S_GSUM_ADJ, scalar_out(c) + FH_S_GMAX_ADJ));
@@ -1633,7 +1645,7 @@ static int launch_adj_identity(fh_ctx* c, const AdjIO& io) {
 
 // sum|x_i| and max|x_i| of an n-length device vector -> dscal[GSUM], dscal[GMAX]  (g(x0) for objective_hist[0], :143)
 static int launch_gterms(fh_ctx* c, const double* x) {
-  if (c->op == OP_IDENTITY && c->prox_kind == FH_PROX_NUCLEAR)      // the norms of x0 are not free here (the forward pass that precedes wrote FH_S_GMAX = 0)
+  if (c->op == OP_IDENTITY && nuc_kind(c->prox_kind))      // the norms of x0 are not free here (the forward pass that precedes wrote FH_S_GMAX = 0)
     return nuc_norm(c, x, scalar_out(c) + FH_S_GSUM, scalar_out(c) + FH_S_GMAX);
   if (c->LB) {              // (n, L) matrix: the same two terms, or the sum of row norms for FH_PROX_GROUP
     const unsigned mgrid = (unsigned)std::min<uint64_t>((c->n + FH_WG - 1) / FH_WG, 1024);

@@ -10,6 +10,10 @@
 //                  (its own text of nside_adj_sums, see below).  Mode 1: g1 = loss_grad(z) (or z itself, fh_apply).
 //   Both are grid-stride launches, a lane's elements in index order, workgroup records summed in index order by the last workgroup to arrive:
 //   no float atomics, bitwise repeatable.
+//   OBSERVATION WEIGHTS (fh_set_loss_weights): f(X) = sum_j w_j loss(x_j, b_j).  Both kernels are templates on WEIGHTED; the weighted form takes
+//   the unweighted argument block followed by the pointer to w (IdFwdWP / IdAdjWP), so the unweighted instantiation is the code it always was.
+//   A term is w == 0 ? 0 : w * loss_term, a gradient entry w == 0 ? 0 : w * loss_grad: the SELECT keeps an unobserved entry at exactly 0.0
+//   whatever x is (log(1 + exp(800)) is inf, and 0 * inf is NaN); w == 1 gives the unweighted bits.
 //
 // FH_PROX_NUCLEAR: singular-value thresholding by BLOCK ONE-SIDED JACOBI (Hestenes).  With p = min(M, N), q = max(M, N): the working buffer
 // holds P rows (p padded with zero rows to a multiple of the block size Bk) of ld doubles, [ W | J^T ]: W = xhat, transposed when M > N, in
@@ -29,9 +33,17 @@
 //                  (FH_S_GMAX) and the rank kept (FH_S_ALPHA) come for free.
 //   k_nuc_recon    xprox = J diag(phi) W, plain FMA in index order, rows with phi_i = 0 skipped; written back transposed when M > N.
 //
+// FH_PROX_NUCBALL: the Euclidean projection onto { ||X||_* <= radius }, the same decomposition with another map of the singular values:
+//   k_nuc_ball     ONE workgroup, behind k_nuc_sigma at thr = 0 (whose per-row records hold sigma_i): the sigma are ordered descending by
+//                  counting (rank_i = #{j : sigma_j > sigma_i, or equal and j < i}: deterministic, no padding), ONE lane forms the running
+//                  sums c_k in that order (np.cumsum's order), alpha = max_k (c_k - radius) / k over the lanes (max is exact in any order),
+//                  theta = max(alpha, 0): proximal.project_L1_ball of the singular values.  Then phi_i = max(sigma_i - theta, 0) /
+//                  (sigma_i + (sigma_i == 0)) and the three scalars exactly as k_nuc_sigma forms them at thr = theta.
+//
 // A SWEEP is all steps of the schedule; the host reads the sweep's counter once (csrc/fh_host_launch.h: nuc_decompose) and stops after the first
 // sweep that rotated nothing.  No spin wait, no grid barrier, no persistent launch: steps are dependent launches on the context's stream.
 #pragma once
+#include <type_traits>
 #include "fh_dense.h"
 
 #define PX_NUCLEAR 10
@@ -62,8 +74,22 @@ struct IdFwdP {
   double* out;
 };
 
-static __global__ __launch_bounds__(FH_WG) void k_id_fwd(const IdFwdP p) {
+struct IdFwdWP { IdFwdP p; const double* w; };      // the weighted form's argument block: the unweighted one, then the weights (length n)
+__device__ __forceinline__ const IdFwdP& id_args(const IdFwdP& a) { return a; }
+__device__ __forceinline__ const IdFwdP& id_args(const IdFwdWP& a) { return a.p; }
+__device__ __forceinline__ const double* id_weights(const IdFwdP&) { return nullptr; }
+__device__ __forceinline__ const double* id_weights(const IdFwdWP& a) { return a.w; }
+// w == 0 ? 0 : w * t -- the select, not the product: an unobserved entry contributes exactly 0.0 even where t is inf
+__device__ __forceinline__ double id_weighted(double w, double t) {
 #pragma clang fp contract(off)
+  return w == 0.0 ? 0.0 : w * t;
+}
+
+template <bool WEIGHTED>
+static __global__ __launch_bounds__(FH_WG) void k_id_fwd(const typename std::conditional<WEIGHTED, IdFwdWP, IdFwdP>::type args) {
+#pragma clang fp contract(off)
+  const IdFwdP& p = id_args(args);
+  const double* wt = id_weights(args);
   __shared__ __attribute__((aligned(16))) double s_scr[4 * 8];
   __shared__ __attribute__((aligned(16))) unsigned s_flag[4];
   const uint32_t tid = threadIdx.x;
@@ -72,7 +98,8 @@ static __global__ __launch_bounds__(FH_WG) void k_id_fwd(const IdFwdP p) {
     if (p.mode != 0) {
       const double zv = p.x0[j];
       p.z[j] = zv;
-      v[0] += p.sub_b ? loss_term(zv, p.b[j], p.loss) : zv * zv;
+      if (WEIGHTED) v[0] += p.sub_b ? id_weighted(wt[j], loss_term(zv, p.b[j], p.loss)) : zv * zv;
+      else v[0] += p.sub_b ? loss_term(zv, p.b[j], p.loss) : zv * zv;
       continue;
     }
     const double x0e = p.x0[j], g0e = p.g0[j];
@@ -86,7 +113,8 @@ static __global__ __launch_bounds__(FH_WG) void k_id_fwd(const IdFwdP p) {
       p.xp[j] = xpe;
     }
     p.z[j] = xpe;
-    v[0] += loss_term(xpe, p.b[j], p.loss);
+    if (WEIGHTED) v[0] += id_weighted(wt[j], loss_term(xpe, p.b[j], p.loss));
+    else v[0] += loss_term(xpe, p.b[j], p.loss);
     nside_fwd_sums<1>(x0e, g0e, xhe, xpe, xav, v);
   }
   finish_records<8, S_GMAX>(v, p.red, blockIdx.x, gridDim.x, p.counter, p.out, p.seq, s_scr, s_flag, NoRecords(), [&](double (&w)[8]) {
@@ -114,8 +142,17 @@ struct IdAdjP {
 
 // (k_id_adj keeps its own text of the n-side epilogue and of the finaliser: the gradient is taken AT x1, so the extrapolation has to be formed before
 // nside_adj_sums would form it, and through the shared code the small launch (64 x 64) measured 0.27 us slower; profiles/nside_refactor.txt section 6.)
-static __global__ __launch_bounds__(FH_WG) void k_id_adj(const IdAdjP p) {
+struct IdAdjWP { IdAdjP p; const double* w; };
+__device__ __forceinline__ const IdAdjP& id_args(const IdAdjP& a) { return a; }
+__device__ __forceinline__ const IdAdjP& id_args(const IdAdjWP& a) { return a.p; }
+__device__ __forceinline__ const double* id_weights(const IdAdjP&) { return nullptr; }
+__device__ __forceinline__ const double* id_weights(const IdAdjWP& a) { return a.w; }
+
+template <bool WEIGHTED>
+static __global__ __launch_bounds__(FH_WG) void k_id_adj(const typename std::conditional<WEIGHTED, IdAdjWP, IdAdjP>::type args) {
 #pragma clang fp contract(off)
+  const IdAdjP& p = id_args(args);
+  const double* wt = id_weights(args);
   __shared__ __attribute__((aligned(16))) double s_scr[4 * 8];
   __shared__ __attribute__((aligned(16))) unsigned s_flag[4];
   const uint32_t tid = threadIdx.x;
@@ -124,6 +161,12 @@ static __global__ __launch_bounds__(FH_WG) void k_id_adj(const IdAdjP p) {
     if (p.mode != 0) {
       const double zv = p.z[j];
       const double bv = p.sub_b ? p.b[j] : 0.0;
+      if (WEIGHTED && p.sub_b) {
+        const double wv = wt[j];
+        p.g1[j] = id_weighted(wv, loss_grad(zv, bv, p.loss));
+        v[5] += id_weighted(wv, loss_term(zv, bv, p.loss));
+        continue;
+      }
       p.g1[j] = p.sub_b ? loss_grad(zv, bv, p.loss) : zv;
       v[5] += p.sub_b ? loss_term(zv, bv, p.loss) : zv * zv;
       continue;
@@ -131,9 +174,10 @@ static __global__ __launch_bounds__(FH_WG) void k_id_adj(const IdAdjP p) {
     const double x0e = p.x0[j], xpe = p.xp[j], xhe = p.xhat[j], bv = p.b[j];
     double x1 = xpe;
     if (p.accel) x1 = extrapolate(xpe, p.xacc0[j], p.coef);
-    const double g = loss_grad(x1, bv, p.loss);
+    double g = loss_grad(x1, bv, p.loss), ft = loss_term(x1, bv, p.loss);
+    if (WEIGHTED) { const double wv = wt[j]; g = id_weighted(wv, g); ft = id_weighted(wv, ft); }
     p.g1[j] = g;
-    v[5] += loss_term(x1, bv, p.loss);
+    v[5] += ft;
     const double dx = sub_nofma(xpe, x0e);
     const double dg = bb_dgrad(g, xhe, x0e, p.tau);
     const double dh = sub_nofma(x1, xhe);
@@ -394,7 +438,7 @@ struct NucSigmaP {
   double* phi;          // [P] (nullptr: values only)
   double* red;          // [P][2]
   unsigned* counter;
-  double* out_gsum;     // sum max(sigma_i - thr, 0)
+  double* out_gsum;     // sum max(sigma_i - thr, 0) (nullptr: no sums at all -- the per-row records are what the caller wants, k_nuc_ball reads them)
   double* out_gmax;     // max max(sigma_i - thr, 0)
   double* out_rank;     // #{sigma_i > thr} (nullptr: not wanted)
   int to_host;          // out_* lie in the mapped scalar block: system-scope stores
@@ -419,6 +463,10 @@ static __global__ __launch_bounds__(FH_WG) void k_nuc_sigma(const NucSigmaP p) {
     store_partial(p.red + 2 * (uint64_t)row + 1, (live && sigma > p.thr) ? 1.0 : 0.0);
   }
   if (!arrive_last(p.counter, gridDim.x, s_flag)) return;
+  if (!p.out_gsum) {                                                                 // (uniform: a kernel argument)
+    if (tid == 0) __hip_atomic_store(p.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return;
+  }
   double s[3] = {0.0, 0.0, 0.0};
   for (uint32_t i = tid; i < gridDim.x; i += FH_WG) {
     const double kept = load_partial(p.red + 2 * (uint64_t)i);
@@ -430,6 +478,58 @@ static __global__ __launch_bounds__(FH_WG) void k_nuc_sigma(const NucSigmaP p) {
     else { store_partial(p.out_gsum, s[0]); store_partial(p.out_gmax, s[2]); if (p.out_rank) store_partial(p.out_rank, s[1]); }
     __hip_atomic_store(p.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
+}
+
+struct NucBallP {
+  uint32_t p, P;        // singular values; rows of the working buffer (phi has P entries, the padded rows' are 0)
+  double radius;
+  const double* red;    // [P][2] as k_nuc_sigma left it at thr = 0: [2 i] = sigma_i
+  double* phi;          // [P]
+  double* out_gsum;     // sum max(sigma_i - theta, 0)
+  double* out_gmax;     // max max(sigma_i - theta, 0)
+  double* out_rank;     // #{sigma_i > theta}
+};
+
+// ONE workgroup; p <= NUC_MAX_P.  Padded rows (row >= p) never enter the ordering.
+static __global__ __launch_bounds__(FH_WG) void k_nuc_ball(const NucBallP p) {
+#pragma clang fp contract(off)
+  __shared__ __attribute__((aligned(16))) double s_sig[NUC_MAX_P];
+  __shared__ __attribute__((aligned(16))) double s_ord[NUC_MAX_P];      // the sigma in descending order, then their running sums
+  __shared__ __attribute__((aligned(16))) double s_scr[4 * 3];
+  __shared__ double s_theta;
+  const uint32_t tid = threadIdx.x;
+  const uint32_t n = p.p < NUC_MAX_P ? p.p : NUC_MAX_P;
+  for (uint32_t i = tid; i < n; i += FH_WG) { s_sig[i] = load_partial(p.red + 2 * (uint64_t)i); s_ord[i] = 0.0; }
+  __syncthreads();
+  // 1. rank by counting, the index as tie-break (every lane reads the same word of s_sig: a broadcast, no bank conflict)
+  for (uint32_t i = tid; i < n; i += FH_WG) {
+    const double si = s_sig[i];
+    uint32_t rank = 0;
+    for (uint32_t j = 0; j < n; ++j) { const double sj = s_sig[j]; rank += (sj > si || (sj == si && j < i)) ? 1u : 0u; }
+    s_ord[rank] = si;                                                    // (rank < n: a lane counts at most the n - 1 others)
+  }
+  __syncthreads();
+  // 2. the running sums, serially, in index order
+  if (tid == 0) { double c = 0.0; for (uint32_t k = 0; k < n; ++k) { c += s_ord[k]; s_ord[k] = c; } }
+  __syncthreads();
+  // 3. alpha = max_k (c_k - radius) / k, k = 1 .. n
+  double a[1] = {-__builtin_inf()};
+  for (uint32_t k = tid; k < n; k += FH_WG) a[0] = fmax(a[0], (s_ord[k] - p.radius) / (double)(k + 1u));
+  block_reduce<1>(a, s_scr, 0);
+  if (tid == 0) s_theta = fmax(a[0], 0.0);
+  __syncthreads();
+  const double theta = s_theta;
+  // 4. phi and the three scalars, as k_nuc_sigma's last workgroup forms them
+  double s[3] = {0.0, 0.0, 0.0};
+  for (uint32_t i = tid; i < p.P; i += FH_WG) {
+    const bool live = i < n;
+    const double sigma = live ? s_sig[i] : 0.0;
+    const double kept = live ? fmax(sigma - theta, 0.0) : 0.0;
+    p.phi[i] = kept / (sigma + (sigma == 0.0 ? 1.0 : 0.0));
+    s[0] += kept; s[1] += (live && sigma > theta) ? 1.0 : 0.0; s[2] = fmax(s[2], kept);
+  }
+  block_reduce<3>(s, s_scr, 2);
+  if (tid == 0) { store_partial(p.out_gsum, s[0]); store_partial(p.out_gmax, s[2]); store_partial(p.out_rank, s[1]); }
 }
 
 struct NucReconP {

@@ -18,6 +18,7 @@ LIB_PATH = os.environ.get("FASTA_HIP_LIB") or os.path.join(_HERE, "libfasta_hip.
 # enums mirrored from include/fasta_hip.h ---------------------------------------------------------
 PROX_IDENTITY, PROX_SHRINK, PROX_NONNEG, PROX_LINF, PROX_L1BALL, PROX_TVBALL, PROX_BOX, PROX_GROUP, PROX_ROWBALL, PROX_ROWSPLIT = range(10)
 PROX_NUCLEAR = 10                  # singular-value soft-threshold, identity operator only (fh_set_identity, csrc/fh_nuclear.h)
+PROX_NUCBALL = 11                  # projection onto the nuclear-norm ball of radius mu, identity operator only (csrc/fh_nuclear.h: k_nuc_ball)
 MAX_RHS = 16                       # columns of a matrix unknown (fh_set_rhs, fh_set_matrix_csr_rhs, fh_set_quadratic, fh_set_factorization)
 (VEC_X0, VEC_G0, VEC_XHAT, VEC_XPROX, VEC_X1, VEC_G1, VEC_BEST, VEC_B, VEC_Z,
  VEC_T0, VEC_T1, VEC_T2, VEC_T3) = range(13)
@@ -119,6 +120,7 @@ SIGNATURES = {
     "fh_multi_shape_for": (_i32, [_u64, _u64, C.c_uint32, _i32, C.c_longlong, _i32, C.POINTER(C.c_uint32)]),
     "fh_set_loss_lsq": (_i32, [_ctx, _pd, _u64]),
     "fh_set_loss_logistic": (_i32, [_ctx, _pd, _u64]),
+    "fh_set_loss_weights": (_i32, [_ctx, _pd]),
     "fh_set_loss_softmax": (_i32, [_ctx, C.POINTER(C.c_int32), _u64]),
     "fh_set_prox": (_i32, [_ctx, _i32, _dbl, _dbl, _dbl]),
     "fh_set_vector": (_i32, [_ctx, _i32, _pd, _u64]),
@@ -773,6 +775,17 @@ class HipContext:
     def set_loss_logistic(self, labels):
         labels, p = _as_f64(np.ravel(labels))
         self._call("fh_set_loss_logistic", p, labels.size)
+
+    def set_loss_weights(self, w):
+        """Observation weights of the elementwise loss on the identity operator (fh_set_loss_weights): f(X) = sum_j w_j * loss(x_j, b_j); an array of
+        B's size, every entry finite and >= 0, set AFTER the loss; None removes them."""
+        if w is None:
+            self._call("fh_set_loss_weights", None)
+            return
+        w, p = _as_f64(np.ravel(w))
+        if w.size != self.shape()[1]:
+            raise ValueError(f"weights have {w.size} entries, the unknown has {self.shape()[1]}")
+        self._call("fh_set_loss_weights", p)
 
     def set_loss_softmax(self, labels):
         """Softmax loss over the L columns of a matrix unknown (csrc/fh_softmax.h): integer class labels in [0, L), one per row of the operator.

@@ -510,7 +510,8 @@ class BilinearMap(_DeviceMap):
 class IdentityMap(_DeviceMap):
     """The operator of `fasta(None, None, loss.f, loss.gradf, g, prox, X0)` with loss = losses.LogisticLoss(B) or losses.LeastSquares(B) and a
     2-D X0 of B's shape: the identity on (M, N) matrices.  Its device context keeps the unknown in the vector form's buffers (fh_set_identity,
-    csrc/fh_nuclear.h) and serves proximal.NuclearShrink, Shrink, NonNeg, Box or no prox.  Lazy like QuadraticMap; on host arrays it is the
+    csrc/fh_nuclear.h) and serves proximal.NuclearShrink, NuclearBall, Shrink, NonNeg, Box or no prox, with or without observation weights on the loss
+    (losses.LeastSquares / LogisticLoss(B, weights=W): fh_set_loss_weights).  Lazy like QuadraticMap; on host arrays it is the
     identity, as `A = None` is in the reference (examples/logistic_matrix_completion.py:47).
     tuning: {hip.TUNE_NUC_BLOCK_ROWS: 1 | 2 | 4 | 8} sets the rows per block of the nuclear-norm prox's Jacobi steps."""
 

@@ -12,12 +12,39 @@ import numpy as np
 __all__ = ["LeastSquares", "LogisticLoss", "SoftmaxLoss", "Quadratic", "Factorization"]
 
 
+def _checked_weights(name, b, weights):
+    """The observation weights of an elementwise loss as a float64 array of b's shape (a boolean mask becomes 0.0 / 1.0), or ValueError with a
+    sentence that names the first offending entry."""
+    W = np.asarray(weights)
+    if W.shape != b.shape:
+        raise ValueError(f"{name}: weights must have B's shape {b.shape} (got {W.shape})")
+    if W.dtype.kind not in "biuf":
+        raise ValueError(f"{name}: weights must be real numbers or a boolean mask (got dtype {W.dtype})")
+    W = np.ascontiguousarray(W, dtype=np.float64)
+    bad = ~(np.isfinite(W) & (W >= 0))
+    if bad.any():
+        at = tuple(int(k) for k in np.argwhere(bad)[0])
+        raise ValueError(f"{name}: weights must be finite and >= 0 (entry {at if len(at) != 1 else at[0]} is {float(W[at])!r})")
+    return W
+
+
 class LeastSquares:
-    def __init__(self, b):
+    """f(z) = .5*||z - b||^2; with `weights` W (an array of b's shape, finite and >= 0, or a boolean mask): f(z) = .5 * sum W * (z - b)^2,
+    gradf(z) = W * (z - b) -- matrix completion from a subset of the entries.  The device serves weights on the identity operator only
+    (fasta(None, None, ls.f, ls.gradf, ...), fh_set_loss_weights)."""
+
+    def __init__(self, b, weights=None):
         self.b = np.ascontiguousarray(b, dtype=np.float64)
+        self.weights = None
+        if weights is not None:
+            self.weights = _checked_weights("LeastSquares", self.b, weights)
+            self._sqrtW = np.sqrt(self.weights)
+            self.f, self.gradf = self._f_weighted, self._gradf_weighted      # (instance attributes: `ls.f.__self__` is still the tag)
 
     def bind(self, ctx):
         ctx.set_loss_lsq(self.b)
+        if self.weights is not None:
+            ctx.set_loss_weights(self.weights)
 
     @staticmethod
     def f_from_device(s):
@@ -32,18 +59,32 @@ class LeastSquares:
     def gradf(self, z):
         return z - self.b
 
-    __call__ = f
+    def _f_weighted(self, z):
+        return .5 * np.linalg.norm((self._sqrtW * (z - self.b)).ravel()) ** 2
+
+    def _gradf_weighted(self, z):
+        return self.weights * (z - self.b)
+
+    def __call__(self, z):
+        return self.f(z)
 
 
 class LogisticLoss:
     """f(z) = sum log(1+exp(z)) - (b==1)*z, gradf(z) = -b/(1+exp(b*z)) with labels b in {-1,+1}
-    (examples/sparse_logistic.py:47-48).  Dense operators only."""
+    (examples/sparse_logistic.py:47-48).  Dense operators only.  With `weights` W (as for LeastSquares): f(z) = sum W * (log(1+exp(z)) - (b==1)*z),
+    gradf(z) = W * (-b/(1+exp(b*z))), on the identity operator only."""
 
-    def __init__(self, b):
+    def __init__(self, b, weights=None):
         self.b = np.ascontiguousarray(b, dtype=np.float64)
+        self.weights = None
+        if weights is not None:
+            self.weights = _checked_weights("LogisticLoss", self.b, weights)
+            self.f, self.gradf = self._f_weighted, self._gradf_weighted
 
     def bind(self, ctx):
         ctx.set_loss_logistic(self.b)
+        if self.weights is not None:
+            ctx.set_loss_weights(self.weights)
 
     @staticmethod
     def f_from_device(s):
@@ -55,7 +96,20 @@ class LogisticLoss:
     def gradf(self, z):
         return -self.b / (1 + np.exp(self.b * z))
 
-    __call__ = f
+    # (the select, as in the kernels: log(1 + exp(z)) is inf above z = 709.8 and 0 * inf is NaN -- an unobserved entry contributes exactly 0.0
+    # whatever z is; where W != 0 these are W * term and W * grad, bit for bit)
+    def _f_weighted(self, z):
+        W = self.weights
+        with np.errstate(over="ignore", invalid="ignore"):
+            return np.sum(np.where(W == 0, 0.0, W * (np.log(1 + np.exp(z)) - (self.b == 1) * z)))
+
+    def _gradf_weighted(self, z):
+        W = self.weights
+        with np.errstate(over="ignore", invalid="ignore"):
+            return np.where(W == 0, 0.0, W * (-self.b / (1 + np.exp(self.b * z))))
+
+    def __call__(self, z):
+        return self.f(z)
 
 
 class SoftmaxLoss:

@@ -19,8 +19,8 @@ import numpy as np
 
 from . import hip
 
-__all__ = ["Shrink", "NonNeg", "LinfProx", "L1Ball", "Box", "TVDualBall", "GroupShrink", "RowBall", "RowSplit", "NuclearShrink", "NoProx", "device_prox", "release_scratch",
-           "shrink", "project_Linf_ball", "project_L1_ball", "project_Lnuc_ball"]
+__all__ = ["Shrink", "NonNeg", "LinfProx", "L1Ball", "Box", "TVDualBall", "GroupShrink", "RowBall", "RowSplit", "NuclearShrink", "NuclearBall", "NoProx", "device_prox", "release_scratch",
+           "shrink", "project_Linf_ball", "project_L1_ball", "project_Lnuc_ball", "project_nuclear_ball"]
 
 
 class ProxTag:
@@ -232,8 +232,30 @@ class NuclearShrink(ProxTag):
         return self.mu * np.linalg.norm(np.diag(np.linalg.svd(X)[1]), 1)
 
 
+class NuclearBall(ProxTag):
+    """Low-rank CONSTRAINT on a matrix unknown X of shape (M, N): g = 0 on { ||X||_* <= radius }, and proxg(X, t) is the Euclidean projection onto that
+    ball, independent of t -- the singular values are projected onto the l1 ball of that radius (project_L1_ball), the singular vectors kept.  On host
+    arrays `prox` is LAPACK's thin SVD; the device serves it on the identity operator only (FH_PROX_NUCBALL, csrc/fh_nuclear.h: the Jacobi
+    decomposition of NuclearShrink and a one-workgroup launch that finds the level), for min(M, N) <= 1024.  (The reference's `project_Lnuc_ball`
+    is, despite its name, the soft-threshold: NuclearShrink.)"""
+    kind = hip.PROX_NUCBALL
+    step_scaled = False
+
+    def __init__(self, radius):
+        radius = float(radius)
+        if not (radius >= 0 and np.isfinite(radius)):
+            raise ValueError(f"NuclearBall needs a finite radius >= 0 (got {radius!r})")
+        self.radius = self.mu = radius
+
+    def nuclear_norm_from_sums(self, gsum, gmax):
+        return gsum                             # FH_S_GSUM after a forward launch: the sum of the singular values of xprox
+
+    def prox(self, X, t):
+        return project_nuclear_ball(X, self.radius)
+
+
 # ---- the device prox on host arrays -----------------------------------------------------------------
-_scratch = {}            # (device, "dense", n) or (device, "tv", H, W) -> operator holding a scratch HipContext
+_scratch = {}           # (device, "dense", n) or (device, "tv", H, W) -> operator holding a scratch HipContext
 
 
 _ELEMENTWISE = (hip.PROX_IDENTITY, hip.PROX_SHRINK, hip.PROX_NONNEG, hip.PROX_BOX)
@@ -289,7 +311,7 @@ def device_prox(tag, x, t, device=0):
     tag on such an array (same bits as on the flattened array).  Every other call is flattened and takes the vector kernels."""
     x = np.asarray(x, dtype=np.float64)
     flat = x.ravel()
-    if tag.kind == hip.PROX_NUCLEAR:
+    if tag.kind in (hip.PROX_NUCLEAR, hip.PROX_NUCBALL):
         return _device_prox_nuclear(tag, x, t, device)
     tv = tag.kind == hip.PROX_TVBALL
     if tv:
@@ -306,10 +328,10 @@ def device_prox(tag, x, t, device=0):
 
 
 def _device_prox_nuclear(tag, x, t, device):
-    """NuclearShrink through a scratch identity context (csrc/fh_nuclear.h), cached per (device, M, N) like the others."""
+    """NuclearShrink / NuclearBall through a scratch identity context (csrc/fh_nuclear.h), cached per (device, M, N) like the others."""
     from .linalg import IdentityMap
     if x.ndim != 2:
-        raise ValueError(f"NuclearShrink needs a 2-D array (got shape {x.shape})")
+        raise ValueError(f"{type(tag).__name__} needs a 2-D array (got shape {x.shape})")
     key = (device, "identity") + tuple(x.shape)
     op = _scratch.get(key)
     if op is None:
@@ -319,7 +341,10 @@ def _device_prox_nuclear(tag, x, t, device):
         op.ctx.set_loss_lsq(np.zeros(x.size))
         _scratch[key] = op
     ctx = op.ctx
-    tag.bind_prox(ctx, False)
+    if tag.kind == hip.PROX_NUCBALL:
+        ctx.set_prox(tag.kind, tag.mu)
+    else:
+        tag.bind_prox(ctx, False)
     ctx.set_vector(hip.VEC_X0, x)
     ctx.set_vector(hip.VEC_G0, np.zeros(x.size))
     ctx.fwd(float(t))
@@ -357,3 +382,11 @@ def project_Lnuc_ball(X, t):
     NuclearShrink on the identity operator (FH_PROX_NUCLEAR, csrc/fh_nuclear.h), which the -m gpu tests hold to this function."""
     U, s, Vh = np.linalg.svd(X, full_matrices=False)
     return (U * shrink(s, t)) @ Vh
+
+
+def project_nuclear_ball(X, radius):
+    """Euclidean projection onto {||X||_* <= radius}: LAPACK's thin SVD on the host, the singular values projected onto the l1 ball of that radius.
+    The device's form is NuclearBall on the identity operator (FH_PROX_NUCBALL, csrc/fh_nuclear.h), which the -m gpu tests hold to this function."""
+    U, s, Vh = np.linalg.svd(X, full_matrices=False)
+    s = project_L1_ball(s, radius)
+    return (U * s) @ Vh

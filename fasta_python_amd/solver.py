@@ -32,7 +32,7 @@ import numpy as np
 from . import hip, stopping
 from .linalg import BilinearMap, ConvMap, DCTMap, DenseMatrixMap, GradDivMap, IdentityMap, LinearMap, QuadraticMap, SparseMatrixMap, _DeviceMap, is_sparse_matrix
 from .losses import Factorization, LeastSquares, LogisticLoss, Quadratic, SoftmaxLoss
-from .proximal import NoProx, NuclearShrink, ProxTag
+from .proximal import NoProx, NuclearBall, NuclearShrink, ProxTag
 
 __all__ = ["fasta", "Convergence", "FBSolver", "EPSILON"]
 
@@ -270,14 +270,18 @@ def _softmax_form_refusal(A, At, loss_f, loss_g, g, proxg, x0):
     return None
 
 
+_WEIGHTS_ELSEWHERE = ("observation weights (losses.LeastSquares(B, weights=W) / losses.LogisticLoss(B, weights=W)) are served on the device by the identity operator "
+                      "only: fasta(None, None, loss.f, loss.gradf, g, prox, X0) with a 2-D X0 of B's shape and NuclearShrink, NuclearBall, Shrink, NonNeg, Box or no prox")
+_NUCBALL_ELSEWHERE = ("proximal.NuclearBall is served on the device by the identity operator only: fasta(None, None, loss.f, loss.gradf, reg.g, reg.prox, X0) "
+                      "with loss = losses.LogisticLoss(B) or losses.LeastSquares(B) and a 2-D X0 of B's shape")
 _NUCLEAR_ELSEWHERE = ("proximal.NuclearShrink is served on the device by the identity operator only: fasta(None, None, loss.f, loss.gradf, reg.g, reg.prox, X0) "
                       "with loss = losses.LogisticLoss(B) or losses.LeastSquares(B) and a 2-D X0 of B's shape")
 
 
 def _identity_form_refusal(A, loss, g, proxg, x0):
     """`fasta(None, None, loss.f, loss.gradf, g, prox, X0)` with loss = losses.LogisticLoss(B) or LeastSquares(B), or the same with an explicit
-    linalg.IdentityMap: the device serves it through fh_set_identity (csrc/fh_nuclear.h) for a 2-D X0 of B's shape with NuclearShrink, Shrink,
-    NonNeg, Box or no prox.  None, or the reason."""
+    linalg.IdentityMap: the device serves it through fh_set_identity (csrc/fh_nuclear.h) for a 2-D X0 of B's shape with NuclearShrink, NuclearBall,
+    Shrink, NonNeg, Box or no prox, with or without observation weights on the loss.  None, or the reason."""
     from .proximal import Box, NonNeg, Shrink
     shape = None if x0 is None else tuple(np.shape(x0))
     if shape is not None and len(shape) != 2:
@@ -294,12 +298,12 @@ def _identity_form_refusal(A, loss, g, proxg, x0):
     prox, owner_g = _tag_of(proxg, ProxTag), _tag_of(g, ProxTag)
     if prox is None or (owner_g is not None and owner_g is not prox) or (owner_g is None and g is not None):
         return ("g and proxg must be the `.g` / `.prox` of one proximal.* tag object "
-                "(NuclearShrink, Shrink, NonNeg, Box)")
-    if not isinstance(prox, (NuclearShrink, Shrink, NonNeg, Box)) and type(prox) is not NoProx:
+                "(NuclearShrink, NuclearBall, Shrink, NonNeg, Box)")
+    if not isinstance(prox, (NuclearShrink, NuclearBall, Shrink, NonNeg, Box)) and type(prox) is not NoProx:
         return (f"proximal.{type(prox).__name__} is not implemented for the identity operator on the device "
-                "(NuclearShrink, Shrink, NonNeg, Box or no prox are)")
-    if isinstance(prox, NuclearShrink) and shape is not None and min(shape) > IdentityMap.MAX_NUCLEAR_RANK:
-        return (f"proximal.NuclearShrink serves min(M, N) <= {IdentityMap.MAX_NUCLEAR_RANK} on the device (x0 has shape {shape}): "
+                "(NuclearShrink, NuclearBall, Shrink, NonNeg, Box or no prox are)")
+    if isinstance(prox, (NuclearShrink, NuclearBall)) and shape is not None and min(shape) > IdentityMap.MAX_NUCLEAR_RANK:
+        return (f"proximal.{type(prox).__name__} serves min(M, N) <= {IdentityMap.MAX_NUCLEAR_RANK} on the device (x0 has shape {shape}): "
                 "the Jacobi sweeps are quadratic in it")
     return None
 
@@ -315,6 +319,8 @@ def _unrecognised(A, At, f, gradf, g, proxg, x0=None):
             return "proximal.RowSplit is served on the device with a factorization loss only: fasta(None, None, fz.f, fz.gradf, ...) with fz = losses.Factorization(S)"
         if isinstance(_tag_of(proxg, ProxTag), NuclearShrink):
             return _NUCLEAR_ELSEWHERE
+        if isinstance(_tag_of(proxg, ProxTag), NuclearBall):
+            return _NUCBALL_ELSEWHERE
         return _quadratic_form_refusal(A, At, quad_f, quad_g, g, proxg, x0)
     sm_f, sm_g = _tag_of(f, SoftmaxLoss), _tag_of(gradf, SoftmaxLoss)
     if sm_f is not None or sm_g is not None:
@@ -332,6 +338,8 @@ def _unrecognised(A, At, f, gradf, g, proxg, x0=None):
     loss_f, loss_g = _tag_of(f, (LeastSquares, LogisticLoss)), _tag_of(gradf, (LeastSquares, LogisticLoss))
     if loss_f is None or loss_f is not loss_g:
         return "f and gradf must be the `.f` / `.gradf` of one losses.LeastSquares(b) or losses.LogisticLoss(b) object"
+    if loss_f.weights is not None:
+        return _WEIGHTS_ELSEWHERE
     if g is None and proxg is None:
         return _dct_form_refusal(A, loss_f, None, x0) or _conv_form_refusal(A, loss_f, None, x0) or _sparse_form_refusal(A, loss_f, None, x0) or _matrix_form_refusal(A, loss_f, None, x0)
     prox, owner_g = _tag_of(proxg, ProxTag), _tag_of(g, ProxTag)
@@ -340,6 +348,8 @@ def _unrecognised(A, At, f, gradf, g, proxg, x0=None):
                 "(Shrink, NonNeg, LinfProx, L1Ball, Box, TVDualBall, GroupShrink)")
     if prox.kind == hip.PROX_NUCLEAR:
         return _NUCLEAR_ELSEWHERE
+    if prox.kind == hip.PROX_NUCBALL:
+        return _NUCBALL_ELSEWHERE
     if prox.kind == hip.PROX_ROWBALL:
         return "proximal.RowBall is served on the device with a quadratic loss only: fasta(None, None, q.f, q.gradf, ...) with q = losses.Quadratic(Q, c)"
     if prox.kind == hip.PROX_ROWSPLIT:

@@ -36,7 +36,7 @@ typedef struct fh_ctx fh_ctx;
                                  could finish the call: the clipping-level search of FH_PROX_LINF / FH_PROX_L1BALL (its outputs are NaN,
                                  never a finite wrong prox), or a grid barrier of fh_run's persistent launch (the state of the last
                                  completed iteration is adopted and the completed history returned: continue with fh_iterate / fh_step) */
-#define FH_E_NOCONV   10005   /* the block-Jacobi decomposition behind FH_PROX_NUCLEAR still rotated after 30 sweeps: xprox is filled with NaN,
+#define FH_E_NOCONV   10005   /* the block-Jacobi decomposition behind FH_PROX_NUCLEAR / FH_PROX_NUCBALL still rotated after 30 sweeps: xprox is filled with NaN,
                                  never a finite wrong prox                                                                             */
 
 /* prox operators g(x) <-> proxg(x, t)                                                   */
@@ -59,7 +59,14 @@ enum fh_prox_kind {
                             norm of xprox; FH_S_GMAX = max max(sigma_i - t*mu, 0), its spectral norm -- which is what the example's g evaluates
                             (la.norm(np.diag(s), 1) is the induced 1-norm of a diagonal matrix: its largest entry); FH_S_ALPHA = the rank kept.  Served by the identity operator only (fh_set_identity); set by fh_set_prox (objective
                             = 1) or fh_set_prox_nuclear.                                                                                          */
-  FH_PROX_ROWSPLIT = 9   /* two elementwise kinds on one (n, L) matrix, examples/nn_factorization.py:60-61: rows [0, split) take one kind with its own
+  FH_PROX_NUCBALL  = 11, /* Euclidean projection of an (M, N) matrix onto the nuclear-norm ball { ||X||_* <= mu }: xprox = U max(S - theta, 0) V^T with
+                            max(S - theta, 0) = proximal.project_L1_ball(S, mu) -- theta = max(0, max_k (c_k - mu) / k) over the running sums c_k of the
+                            singular values in descending order.  Independent of the step; g = 0, so no values-only decomposition ever runs for it
+                            (FH_S_GSUM of fh_init and FH_S_GSUM_ADJ of an accelerated fh_adj hold NaN: not evaluated).  After a forward launch FH_S_GSUM =
+                            the nuclear norm of xprox (<= mu), FH_S_GMAX its spectral norm, FH_S_ALPHA the rank kept.  The decomposition, its bounds
+                            (min(M, N) <= 1024), FH_E_NOCONV, fh_nuclear_info and fh_nuclear_shape* are FH_PROX_NUCLEAR's; one more one-workgroup launch
+                            finds theta (csrc/fh_nuclear.h: k_nuc_ball).  Served by the identity operator only; set by fh_set_prox, mu = radius >= 0.     */
+  FH_PROX_ROWSPLIT = 9  /* two elementwise kinds on one (n, L) matrix, examples/nn_factorization.py:60-61: rows [0, split) take one kind with its own
                             parameters (IDENTITY, SHRINK, NONNEG or BOX), rows [split, n) another (IDENTITY, NONNEG or BOX), each half bit for bit what
                             that kind gives alone.  Set by fh_set_prox_split, never by fh_set_prox.  FH_S_GSUM / FH_S_GSUM_ADJ sum |x| over the TOP rows
                             only, so that g = mu_top * gsum (fh_init takes FH_S_GMAX over the same rows; no kind served here uses it).  Served by the bilinear operator only (fh_set_factorization); every other operator
@@ -364,7 +371,7 @@ int fh_set_prox_nuclear(fh_ctx* ctx, double mu, int objective);
  * out[FH_NUCLEAR_SHAPE_LEN]: [0] transposed (M > N), [1] p, [2] q, [3] Bk, [4] P (p padded to a multiple of Bk), [5] nb = P / Bk, [6] steps per
  * sweep, [7] workgroups per step (the bye's included), [8] column chunk of the Gram pass, [9] chunks per row, [10] leading dimension of the working
  * buffer [ W | J^T ] in doubles, [11] its bytes, [12] static LDS bytes of the step kernel.  fh_nuclear_shape reads the context (FH_E_STATE unless it
- * holds the identity operator with FH_PROX_NUCLEAR); fh_nuclear_shape_for is the same rule as a pure host function (block_rows: 0 = auto = 1).           */
+ * holds the identity operator with FH_PROX_NUCLEAR or FH_PROX_NUCBALL); fh_nuclear_shape_for is the same rule as a pure host function (block_rows: 0 = auto = 1).           */
 #define FH_NUCLEAR_SHAPE_LEN 13
 int fh_nuclear_shape(fh_ctx* ctx, uint64_t* out);
 int fh_nuclear_shape_for(uint64_t M, uint64_t N, int block_rows, int ncu, uint64_t* out);
@@ -469,6 +476,14 @@ int fh_set_loss_lsq(fh_ctx* ctx, const double* b, uint64_t len);
 /* ---- smooth term f(z) = sum log(1+exp(z)) - (b==1)*z, grad f(z) = -b/(1+exp(b*z)), labels b in {-1,+1}
  *      (examples/sparse_logistic.py:47-48); FH_S_FSQ / FH_S_FSQ_ADJ then carry f itself. Dense and sparse operators.   */
 int fh_set_loss_logistic(fh_ctx* ctx, const double* labels, uint64_t len);
+/* ---- observation weights on the identity operator: f(X) = sum_j w_j * loss(x_j, b_j) for either elementwise loss -- matrix completion from a subset
+ *      of the entries (w a 0 / 1 mask), or weighted data.  w has B's length (M * N); every entry finite and >= 0 (FH_E_ARG names the first offender);
+ *      NULL removes the weights.  A term is w == 0 ? 0 : w * term, a gradient entry w == 0 ? 0 : w * grad: an unobserved entry contributes exactly 0.0
+ *      whatever x is, and w == 1 gives the unweighted bits.  FH_S_FSQ / FH_S_FSQ_ADJ carry sum w (x - b)^2 for least squares.  Weighted: fh_init, fh_setup,
+ *      fh_gradient_at, fh_fwd, fh_adj, fh_fwd_adj, fh_iterate; fh_apply is the plain operator.  The weights belong to the loss: set them AFTER it, and
+ *      fh_set_loss_lsq / fh_set_loss_logistic drop them.  FH_E_STATE: any operator but the identity; no loss set yet; and setting another operator
+ *      on a context that holds weights (a weighted problem never silently runs unweighted) -- fh_set_identity itself drops them with the loss.      */
+int fh_set_loss_weights(fh_ctx* ctx, const double* w);
 /* ---- smooth term f(Z) = sum_i [ logsumexp(Z_i,:) - Z_i,y_i ] over the L columns of a MATRIX unknown (multinomial logistic regression, one column of
  *      X per class), grad f(Z)_i,l = exp(Z_i,l) / sum_k exp(Z_i,k) - [l == y_i]; labels y in {0 .. L-1}^m (csrc/fh_softmax.h).  The arithmetic of a row z:
  *      mx = max_l z_l, e_l = exp(z_l - mx), s = e_0 + e_1 + ... + e_{L-1} in index order, term = (mx + log(s)) - z_y, grad_l = e_l / s - Y_l: the maximum
