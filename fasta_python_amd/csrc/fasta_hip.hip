@@ -1268,29 +1268,115 @@ extern "C" int fh_init(fh_ctx* c, double* scalars) {
 // enough for the one-pass kernel to pay) all of it comes from ONE read of A; everywhere else -- and after a hand-off timeout -- it is
 // the three passes fh_gradient_at x 2 + fh_init, so the call is always available and its results agree to summation-order rounding
 // (bit for bit where the one-pass kernel serves the three passes too).
-static const SetupEntry* setup_entry(fh_ctx* c);
+// the one-read set-up kernel for an (m, n) matrix of the given storage, or nullptr (the three passes then): n <= 65536, large enough to pay.  A pure
+// function of its arguments (word: the low half of FH_TUNE_FUSED_VARIANT; ncu: the CUs the launch may take).
+static const SetupEntry* setup_entry_for(uint64_t m, uint64_t n, uint64_t ld, int f32, int word, int ncu) {
+  if (!fused_pays_for(m, n)) return nullptr;
+  if (f32) {
+    // float32 storage (round 6): a member covers 256 x (at most 4) four-column pieces -- two right-hand sides cost 16 accumulator registers per
+    // piece, five pieces spill into the row loop -- so the team is as large as that needs (n <= 65536: up to 16 members), ONE workgroup per CU;
+    // its own rows of the table (fh_setup_instances.inc, group 2), not the step kernel's shape
+    if (ld % 4 || ncu < 1) return nullptr;
+    const uint64_t pieces = round_up(n, 32) / 4;
+    for (int team = 1; team <= 16; team *= 2) {
+      if (pieces > (uint64_t)team * FH_WG * 4) continue;
+      if (ncu % team) return nullptr;
+      int mpp = (int)((pieces + (uint64_t)team * FH_WG - 1) / ((uint64_t)team * FH_WG));
+      if (mpp == 3 || team > 1) mpp = 4;
+      for (const SetupEntry& k : kSetupTable) if (k.f32 == 1 && k.ppt == mpp && k.team == team) return &k;
+      return nullptr;
+    }
+    return nullptr;
+  }
+  const FusedShape sh = fused_shape_for(n, ld, 0, word, ncu);
+  if (!sh.ppt || sh.xlds) return nullptr;
+  // full 8-piece shapes of 8 / 16 members: 512-thread workgroups (fh_setup_instances.inc); FH_TUNE_FUSED_VARIANT bit 16 keeps the 256-thread form (A/B)
+  const int want_threads = (sh.ppt == 8 && sh.team >= 8 && sh.team <= 16 && !(word & 16)) ? 512 : 256;
+  for (const SetupEntry& k : kSetupTable) if (!k.f32 && k.ppt == sh.ppt && k.team == sh.team && k.pipe == (sh.team == 1 ? 1 : sh.pipe) && k.threads == want_threads) return &k;
+  if (want_threads == 512) for (const SetupEntry& k : kSetupTable) if (!k.f32 && k.ppt == sh.ppt && k.team == sh.team && k.pipe == (sh.team == 1 ? 1 : sh.pipe)) return &k;
+  return nullptr;
+}
+// the one-read set-up kernel of this context's shape, or nullptr: dense least squares (the step kernel's own refusals -- prox kind, multi-column form -- for float64)
+static const SetupEntry* setup_entry(fh_ctx* c) {
+  if (c->op != OP_DENSE || c->loss_kind != LOSS_LSQ) return nullptr;
+  if (!c->f32 && !fused_shape(c).ppt) return nullptr;
+  return setup_entry_for(c->m, c->n, c->ld, c->f32, c->fused_variant, fused_ncu(c));
+}
+// THE GEOMETRY of the set-up launch, stated once (the sibling of fused_launch_for, csrc/fh_host_launch.h): launch_setup_dense takes every number
+// from here; fh_setup_shape / fh_setup_shape_for export it.  e == nullptr: no one-read kernel (fh_setup takes the three passes).
+struct SetupLaunch {
+  const SetupEntry* e;
+  uint32_t nteams, rows_per_team, grid;
+  int variant;                       // the word the kernel receives (without the fault-injection bit)
+  uint32_t ld2, nv2;
+};
+static SetupLaunch setup_launch_for(const SetupEntry* e, uint64_t mp, uint64_t n, int f32, int word, bool variant_auto, int ncu, int min_rows) {
+  SetupLaunch L;
+  memset(&L, 0, sizeof(L));
+  L.e = e;
+  if (!e) return L;
+  L.ld2 = (uint32_t)(f32 ? round_up(n, 32) / 4 : round_up(n, 16) / 2);
+  L.nv2 = L.ld2 * (f32 ? 2u : 1u);
+  L.nteams = fused_teams_for(mp, (uint32_t)(ncu / e->team), min_rows);      // (the set-up kernel's own team size: float32 storage does not follow the step kernel's shape)
+  L.rows_per_team = (uint32_t)((mp + L.nteams - 1) / L.nteams);
+  L.grid = L.nteams * (uint32_t)e->team;
+  // (rows dealt cyclically -- bit 32, the step kernel's default: 65536^2 float64 4.98-5.01 ms wherever the matrix lies, blocked 4.95-5.32; the float32 shapes
+  // are faster blocked, 4.39 vs 4.69 ms: profiles/r06_placement.txt)
+  L.variant = fused_variant_rule(word, variant_auto, L.rows_per_team) & ~(f32 && variant_auto ? 32 : 0);
+  return L;
+}
+static SetupLaunch setup_launch(fh_ctx* c) {
+  return setup_launch_for(setup_entry(c), c->mp, c->n, c->f32, c->fused_variant, c->fused_variant_auto, fused_ncu(c), c->fused_min_rows);
+}
+static void setup_launch_report(const SetupLaunch& L, uint32_t* out) {
+  const uint32_t v[FH_SETUP_SHAPE_LEN] = {(uint32_t)L.e->ppt, (uint32_t)L.e->pipe, (uint32_t)L.e->team, (uint32_t)L.e->threads, (uint32_t)L.e->nr, (uint32_t)L.e->f32,
+                                          1u, L.nteams, L.rows_per_team, L.grid, (uint32_t)L.variant, L.ld2, L.nv2};
+  memcpy(out, v, sizeof(v));
+}
+// read-only: the geometry fh_setup's one-read launch of this context takes (FH_E_STATE where fh_setup runs the three passes instead)
+extern "C" int fh_setup_shape(fh_ctx* c, uint32_t* out) {
+  if (!c || !out) return fail(FH_E_ARG, "fh_setup_shape: null argument");
+  if (!c->shards.empty()) return fail(FH_E_STATE, "fh_setup_shape: a multi-device context launches per shard (ask fh_shard's contexts)");
+  const SetupLaunch L = setup_launch(c);
+  if (!L.e) return fail(FH_E_STATE, "fh_setup_shape: no one-read set-up kernel for this operator / loss / shape (fh_setup takes the three passes)");
+  setup_launch_report(L, out);
+  return 0;
+}
+// ... and the same rule for an (m, n) dense least-squares problem that no context holds: a pure host function, no device needed
+extern "C" int fh_setup_shape_for(uint64_t m, uint64_t n, int dtype, int variant_word, int variant_auto, int cus, int min_rows, uint32_t* out) {
+  if (!out) return fail(FH_E_ARG, "fh_setup_shape_for: null argument");
+  if (m == 0 || n == 0 || m >= (1ull << 31) || n >= (1ull << 31)) return fail(FH_E_ARG, "fh_setup_shape_for: matrix dimensions must be in [1, 2^31)");
+  if (dtype != FH_DTYPE_F64 && dtype != FH_DTYPE_F32_STORAGE) return fail(FH_E_ARG, "fh_setup_shape_for: dtype is FH_DTYPE_F64 or FH_DTYPE_F32_STORAGE");
+  if (variant_word < 0 || variant_word > 0xFFFF) return fail(FH_E_ARG, "fh_setup_shape_for: the scheduling word is the low half of FH_TUNE_FUSED_VARIANT");
+  if (cus < 1 || cus > 65536) return fail(FH_E_ARG, "fh_setup_shape_for: cus (the CUs the launch may take) must be in [1, 65536]");
+  if (min_rows < 0 || min_rows >= 0xFFFF) return fail(FH_E_ARG, "fh_setup_shape_for: min_rows must be in [0, 65535) (0 = no floor)");
+  const int f32 = dtype == FH_DTYPE_F32_STORAGE ? 1 : 0;
+  const SetupLaunch L = setup_launch_for(setup_entry_for(m, n, round_up(n, f32 ? 32 : 16), f32, variant_word, cus), round_up(m, 16), n, f32, variant_word,
+                                         variant_auto != 0, cus, min_rows);
+  if (!L.e) return fail(FH_E_STATE, "fh_setup_shape_for: no one-read set-up kernel for a %llu x %llu matrix (fh_setup takes the three passes)", (unsigned long long)m, (unsigned long long)n);
+  setup_launch_report(L, out);
+  return 0;
+}
+
 // sharded = true: a row block (shard of a multi-device context, or a rank): scalars to device memory, partial sums in T[2] / G[gc], pack behind T[2]
 static int launch_setup_dense(fh_ctx* c, bool* launched, bool sharded = false) {
   *launched = false;
   if (!sharded && (row_sharded(c) || !c->shards.empty())) return 0;
-  const SetupEntry* e = setup_entry(c);
+  const SetupLaunch L = setup_launch(c);             // (the geometry: setup_launch_for above, what fh_setup_shape reports)
+  const SetupEntry* e = L.e;
   if (!e || !co_resident(c)) return 0;
-  struct { int team; } sh = {e->team};               // (the set-up kernel's own team size: float32 storage does not follow the step kernel's shape)
+  struct { int team; } sh = {e->team};
   SetupP p;
   p.A = c->A; p.n = (uint32_t)c->n; p.m = (uint32_t)c->m; p.mp = (uint32_t)c->mp;
-  p.ld2 = (uint32_t)(c->f32 ? round_up(c->n, 32) / 4 : round_up(c->n, 16) / 2);
+  p.ld2 = L.ld2;
   p.ldp = (uint32_t)(c->ld / (c->f32 ? 4 : 2));
-  p.nv2 = p.ld2 * (c->f32 ? 2u : 1u);
-  p.nteams = (uint32_t)(fused_ncu(c) / sh.team);
-  if (c->fused_min_rows > 0) {
-    const uint64_t want = std::max<uint64_t>(8, round_up((c->mp + c->fused_min_rows - 1) / c->fused_min_rows, 8));
-    p.nteams = (uint32_t)std::min<uint64_t>(p.nteams, want);
-  }
-  p.rows_per_team = (uint32_t)((c->mp + p.nteams - 1) / p.nteams);
+  p.nv2 = L.nv2;
+  p.nteams = L.nteams;
+  p.rows_per_team = L.rows_per_team;
   p.x[0] = c->T[0]; p.x[1] = c->T[1]; p.x[2] = c->X[c->xi];
   p.g[0] = c->T[2]; p.g[1] = c->T[3]; p.g[2] = c->G[c->gc];
   p.z = c->Z[c->zc]; p.b = c->b;
-  const unsigned grid = p.nteams * sh.team;
+  const unsigned grid = L.grid;
   const size_t sl = sh.team < 8 ? 8 : sh.team;
   const size_t slots_elems = (size_t)c->mp * e->nr * sl;
   const size_t gpart_elems = (size_t)p.nteams * e->nr * p.nv2 * 2;
@@ -1309,9 +1395,7 @@ static int launch_setup_dense(fh_ctx* c, bool* launched, bool sharded = false) {
   HIP_TRY(hipMemsetAsync(c->counters + CNT_FUSED_BAR, 0, 8 * sizeof(unsigned), c->stream));
   HIP_TRY(hipMemsetAsync(c->gridbar, 0, 2 * GB_WORDS * sizeof(unsigned), c->stream));
   p.bar = c->counters + CNT_FUSED_BAR; p.gbar = c->gridbar; p.err = c->counters + CNT_FUSED_ERR;
-  // (rows dealt cyclically -- bit 32, the step kernel's default: 65536^2 float64 4.98-5.01 ms wherever the matrix lies, blocked 4.95-5.32; the float32 shapes
-  // are faster blocked, 4.39 vs 4.69 ms: profiles/r06_placement.txt)
-  p.variant = (fused_variant_for(c, p.rows_per_team) & ~(c->f32 && c->fused_variant_auto ? 32 : 0)) | ((c->test_hooks & FH_HOOK_WITHHOLD_PARTIAL) ? 64 : 0);
+  p.variant = L.variant | ((c->test_hooks & FH_HOOK_WITHHOLD_PARTIAL) ? 64 : 0);
   p.out = scalar_out(c);
   p.pack = sharded ? c->T[2] + c->nv : nullptr;     // (slack behind every n-side vector: alloc_vectors)
   t_begin(c, FH_K_FUSED);
@@ -1323,33 +1407,6 @@ static int launch_setup_dense(fh_ctx* c, bool* launched, bool sharded = false) {
 }
 
 static __global__ void k_set_pair(double* w, double a, double b) { w[0] = a; w[1] = b; }
-// the one-read set-up kernel of this context's shape, or nullptr (the three passes then): dense float64 least squares, n <= 65536, large enough to pay
-static const SetupEntry* setup_entry(fh_ctx* c) {
-  if (c->op != OP_DENSE || c->loss_kind != LOSS_LSQ || !fused_pays(c)) return nullptr;
-  if (c->f32) {
-    // float32 storage (round 6): a member covers 256 x (at most 4) four-column pieces -- two right-hand sides cost 16 accumulator registers per
-    // piece, five pieces spill into the row loop -- so the team is as large as the row needs (n <= 65536: up to 16 members), ONE workgroup per CU;
-    // its own rows of the table (fh_setup_instances.inc, group 2), not the step kernel's shape
-    if (c->ld % 4 || fused_ncu(c) < 1) return nullptr;
-    const uint64_t pieces = round_up(c->n, 32) / 4;
-    for (int team = 1; team <= 16; team *= 2) {
-      if (pieces > (uint64_t)team * FH_WG * 4) continue;
-      if (fused_ncu(c) % team) return nullptr;
-      int mpp = (int)((pieces + (uint64_t)team * FH_WG - 1) / ((uint64_t)team * FH_WG));
-      if (mpp == 3 || team > 1) mpp = 4;
-      for (const SetupEntry& k : kSetupTable) if (k.f32 == 1 && k.ppt == mpp && k.team == team) return &k;
-      return nullptr;
-    }
-    return nullptr;
-  }
-  const FusedShape sh = fused_shape(c);
-  if (!sh.ppt || sh.xlds) return nullptr;
-  // full 8-piece shapes of 8 / 16 members: 512-thread workgroups (fh_setup_instances.inc); FH_TUNE_FUSED_VARIANT bit 16 keeps the 256-thread form (A/B)
-  const int want_threads = (sh.ppt == 8 && sh.team >= 8 && sh.team <= 16 && !(c->fused_variant & 16)) ? 512 : 256;
-  for (const SetupEntry& k : kSetupTable) if (!k.f32 && k.ppt == sh.ppt && k.team == sh.team && k.pipe == (sh.team == 1 ? 1 : sh.pipe) && k.threads == want_threads) return &k;
-  if (want_threads == 512) for (const SetupEntry& k : kSetupTable) if (!k.f32 && k.ppt == sh.ppt && k.team == sh.team && k.pipe == (sh.team == 1 ? 1 : sh.pipe)) return &k;
-  return nullptr;
-}
 
 static int diff_norm_sq(fh_ctx* c, int vec_a, int vec_b, double* sumsq);
 extern "C" int fh_gradient_at(fh_ctx* c, int src_vec, int dst_vec);

@@ -1808,9 +1808,9 @@ struct FusedShape { int ppt, team, pipe, xlds, nbo; };
 // 1-4 % faster (8192^2, teams of 2 with 64 rows each: 0.112 against 0.114 ms; 4096 x 8192: 0.0705 / 0.0735), from 256 rows per team on the cyclic one
 // is 3-4 % faster on a well-placed matrix and up to 14 % on a badly placed one (profiles/r06_placement.txt) -- matrices of that size are small enough for
 // their placement not to matter.  A word set through FH_TUNE_FUSED_VARIANT is passed on unchanged.
-static int fused_variant_for(const fh_ctx* c, uint32_t rows_per_team) {
-  int v = c->fused_variant;
-  if (c->fused_variant_auto && rows_per_team < 128u) v &= ~32;
+static int fused_variant_rule(int word, bool variant_auto, uint32_t rows_per_team) {
+  int v = word;
+  if (variant_auto && rows_per_team < 128u) v &= ~32;
   return v;
 }
 
@@ -1902,7 +1902,77 @@ extern "C" int fh_fused_shape(uint64_t n, int dtype, int variant, int ncu, int* 
 }
 // the one-pass launch beats K-fwd + K-adj once its fixed cost is amortised: wide rows, or at least 8 Mi elements
 // (profiles/r02_fused_crossover.txt; 32 Mi in round 1, when every launch still refilled its hand-off slots from the host)
-static bool fused_pays(fh_ctx* c) { return c->n >= 16384 || (uint64_t)c->m * c->n >= ((uint64_t)1 << 23); }
+static bool fused_pays_for(uint64_t m, uint64_t n) { return n >= 16384 || m * n >= ((uint64_t)1 << 23); }
+static bool fused_pays(fh_ctx* c) { return fused_pays_for(c->m, c->n); }
+
+// THE GEOMETRY of a one-pass launch, stated once: a pure function of the matrix (mp = round_up(m, 16) rows on the device, n columns, rows of ld
+// elements, storage), the scheduling word (FH_TUNE_FUSED_VARIANT's low half; variant_auto: nobody set it, the host resolves the cyclic bit), the
+// CUs the launch may take (fused_ncu) and the rows-per-team floor (0 = none).  launch_fused_dense takes every number from here;
+// fh_fused_launch_shape / fh_fused_launch_shape_for export it so that a test can assert the path it meant to reach.  sh.ppt == 0: no kernel.
+struct FusedLaunch {
+  FusedShape sh;
+  int f32, wpc;                      // storage; workgroups per CU
+  uint32_t nteams, rows_per_team, grid;
+  int variant;                       // the word the kernel receives (bit 32 resolved; without the fault-injection bit)
+  uint32_t ld2, nv2;                 // 16-byte pieces of a row that hold data; double pairs per n-side vector
+};
+// few rows: fewer teams (at least `min_rows` rows each when possible, and a multiple of 8 teams so that the members of
+// a team stay on one XCD): a smaller grid barrier and fewer g1 partials to sum in the epilogue
+static uint32_t fused_teams_for(uint64_t mp, uint32_t nteams, int min_rows) {
+  if (min_rows > 0) {
+    const uint64_t want = std::max<uint64_t>(8, round_up((mp + min_rows - 1) / min_rows, 8));
+    nteams = (uint32_t)std::min<uint64_t>(nteams, want);
+  }
+  return nteams;
+}
+static FusedLaunch fused_launch_for(uint64_t mp, uint64_t n, uint64_t ld, int f32, int word, bool variant_auto, int ncu, int min_rows) {
+  FusedLaunch L;
+  memset(&L, 0, sizeof(L));
+  L.sh = fused_shape_for(n, ld, f32, word, ncu);
+  if (!L.sh.ppt) return L;
+  L.f32 = f32 ? 1 : 0;
+  L.wpc = fused_wpc_of(L.sh, f32);
+  L.ld2 = (uint32_t)(f32 ? round_up(n, 32) / 4 : round_up(n, 16) / 2);
+  L.nv2 = L.ld2 * (f32 ? 2u : 1u);
+  L.nteams = fused_teams_for(mp, (uint32_t)(ncu * L.wpc / L.sh.team), min_rows);
+  L.rows_per_team = (uint32_t)((mp + L.nteams - 1) / L.nteams);
+  L.grid = L.nteams * (uint32_t)L.sh.team;
+  L.variant = fused_variant_rule(word, variant_auto, L.rows_per_team);
+  return L;
+}
+static FusedLaunch fused_launch(fh_ctx* c) {
+  if (!fused_shape(c).ppt) { FusedLaunch L; memset(&L, 0, sizeof(L)); return L; }
+  return fused_launch_for(c->mp, c->n, c->ld, c->f32, c->fused_variant, c->fused_variant_auto, fused_ncu(c), c->fused_min_rows);
+}
+static void fused_launch_report(const FusedLaunch& L, uint32_t* out) {
+  const uint32_t v[FH_FUSED_LAUNCH_SHAPE_LEN] = {(uint32_t)L.sh.ppt, (uint32_t)L.sh.pipe, (uint32_t)L.sh.team, (uint32_t)L.sh.xlds, (uint32_t)L.sh.nbo, (uint32_t)L.f32,
+                                                 (uint32_t)L.wpc, L.nteams, L.rows_per_team, L.grid, (uint32_t)L.variant, L.ld2, L.nv2};
+  memcpy(out, v, sizeof(v));
+}
+// read-only: the geometry the next fh_step / fh_step_accel of this context launches with (FH_E_STATE where the one-pass kernel has no shape)
+extern "C" int fh_fused_launch_shape(fh_ctx* c, uint32_t* out) {
+  if (!c || !out) return fail(FH_E_ARG, "fh_fused_launch_shape: null argument");
+  if (!c->shards.empty()) return fail(FH_E_STATE, "fh_fused_launch_shape: a multi-device context launches per shard (ask fh_shard's contexts)");
+  const FusedLaunch L = fused_launch(c);
+  if (!L.sh.ppt || !fused_lookup(L.sh, L.f32)) return fail(FH_E_STATE, "fh_fused_launch_shape: no one-pass kernel for this operator / prox / shape (see fh_fused_supported)");
+  fused_launch_report(L, out);
+  return 0;
+}
+// ... and the same rule for an (m, n) dense matrix that no context holds: a pure host function, no device needed
+extern "C" int fh_fused_launch_shape_for(uint64_t m, uint64_t n, int dtype, int variant_word, int variant_auto, int cus, int min_rows, uint32_t* out) {
+  if (!out) return fail(FH_E_ARG, "fh_fused_launch_shape_for: null argument");
+  if (m == 0 || n == 0 || m >= (1ull << 31) || n >= (1ull << 31)) return fail(FH_E_ARG, "fh_fused_launch_shape_for: matrix dimensions must be in [1, 2^31)");
+  if (dtype != FH_DTYPE_F64 && dtype != FH_DTYPE_F32_STORAGE) return fail(FH_E_ARG, "fh_fused_launch_shape_for: dtype is FH_DTYPE_F64 or FH_DTYPE_F32_STORAGE");
+  if (variant_word < 0 || variant_word > 0xFFFF) return fail(FH_E_ARG, "fh_fused_launch_shape_for: the scheduling word is the low half of FH_TUNE_FUSED_VARIANT");
+  if (cus < 1 || cus > 65536) return fail(FH_E_ARG, "fh_fused_launch_shape_for: cus (the CUs the launch may take) must be in [1, 65536]");
+  if (min_rows < 0 || min_rows >= 0xFFFF) return fail(FH_E_ARG, "fh_fused_launch_shape_for: min_rows must be in [0, 65535) (0 = no floor)");
+  const int f32 = dtype == FH_DTYPE_F32_STORAGE ? 1 : 0;
+  const FusedLaunch L = fused_launch_for(round_up(m, 16), n, round_up(n, f32 ? 32 : 16), f32, variant_word, variant_auto != 0, cus, min_rows);
+  if (!L.sh.ppt || !fused_lookup(L.sh, L.f32))
+    return fail(FH_E_STATE, "fh_fused_launch_shape_for: no one-pass kernel for rows of %llu columns on %d CUs (see fh_fused_shape)", (unsigned long long)n, cus);
+  fused_launch_report(L, out);
+  return 0;
+}
 
 // (the prox kind travels in p.px.kind: a run-time switch in the kernel's n-side prologue; FH_PROX_* == PX_* numerically.  The
 // one-pass kernels always stream A with non-temporal loads, +10 % in the dense sweeps: only NT = 1 is built.)
@@ -1928,7 +1998,8 @@ static const ChainEntry* chain_lookup(const FusedShape& sh, int f32) {
 // chain != nullptr: the CHAINED form (k_fused_chain): tau and the solver-state pointers of `io` are placeholders, the launch takes them
 // from chain->st; no per-launch event records (the caller brackets the whole chain) and no sequence number (nobody waits for a single launch)
 static int launch_fused_dense(fh_ctx* c, double tau, const FusedIO& io, const ChainP* chain = nullptr) {
-  const FusedShape sh = fused_shape(c);
+  const FusedLaunch L = fused_launch(c);            // (the geometry: fused_launch_for above, what fh_fused_launch_shape reports)
+  const FusedShape sh = L.sh;
   if (!sh.ppt) return fail(FH_E_STATE, "fused one-pass step: unsupported operator shape (needs a dense A with n <= 262144 and a scalar-separable prox)");
   const FusedEntry* k_fused_dense_entry = fused_lookup(sh, c->f32);
   if (!k_fused_dense_entry)
@@ -1936,24 +2007,18 @@ static int launch_fused_dense(fh_ctx* c, double tau, const FusedIO& io, const Ch
                 sh.ppt, sh.pipe, sh.team, sh.xlds, sh.nbo, c->f32);
   FusedP p;
   p.A = c->A; p.ld = c->ld; p.n = (uint32_t)c->n; p.m = (uint32_t)c->m; p.mp = (uint32_t)c->mp;
-  p.ld2 = (uint32_t)(c->f32 ? round_up(c->n, 32) / 4 : round_up(c->n, 16) / 2);
+  p.ld2 = L.ld2;
   p.ldp = (uint32_t)(c->ld / (c->f32 ? 4 : 2));
-  p.nv2 = p.ld2 * (c->f32 ? 2u : 1u);
-  p.nteams = (uint32_t)(fused_ncu(c) * fused_wpc_of(sh, c->f32) / sh.team);
-  // few rows: fewer teams (at least FUSED_MIN_ROWS rows each when possible, and a multiple of 8 teams so that the members of
-  // a team stay on one XCD): a smaller grid barrier and fewer g1 partials to sum in the epilogue
-  if (c->fused_min_rows > 0) {
-    const uint64_t want = std::max<uint64_t>(8, round_up((c->mp + c->fused_min_rows - 1) / c->fused_min_rows, 8));
-    p.nteams = (uint32_t)std::min<uint64_t>(p.nteams, want);
-  }
-  p.rows_per_team = (uint32_t)((c->mp + p.nteams - 1) / p.nteams);
+  p.nv2 = L.nv2;
+  p.nteams = L.nteams;
+  p.rows_per_team = L.rows_per_team;
   p.x0 = io.x0; p.g0 = io.g0; p.xhat = io.xhat; p.xp = io.xp;
   p.b = c->b; p.z = io.z; p.tau = tau; p.loss = c->loss_kind; p.mode = io.mode;
   p.px = make_prox(c, tau);
   p.px.kind = io.kind;
   p.accel = io.accel; p.restart = io.restart; p.coef = io.coef; p.xacc0 = io.xacc0; p.zacc0 = io.zacc0; p.x1 = io.x1; p.coef_out = io.coef_out;
   p.pack = io.pack;
-  const unsigned grid = p.nteams * sh.team;
+  const unsigned grid = L.grid;
   const size_t slots_elems = ((size_t)c->mp + p.nteams) * (sh.team < 8 ? 8 : sh.team);     // (32 members: four 64-byte lines per row)   // whole 64-byte lines; + one line per team for the restart dot
   const size_t gpart_elems = (size_t)p.nteams * p.nv2 * 2;
   FH_TRY(ensure_ws(c, (gpart_elems + (size_t)grid * 16) * sizeof(double)));
@@ -1968,7 +2033,7 @@ static int launch_fused_dense(fh_ctx* c, double tau, const FusedIO& io, const Ch
   }
   p.g1 = io.g1;
   p.bar = c->counters + CNT_FUSED_BAR; p.gbar = c->gridbar; p.err = c->counters + CNT_FUSED_ERR;
-  p.variant = fused_variant_for(c, p.rows_per_team) | ((c->test_hooks & FH_HOOK_WITHHOLD_PARTIAL) ? 64 : 0);      // (bit 64 of FusedP.variant: the kernel's fault-injection switch)
+  p.variant = L.variant | ((c->test_hooks & FH_HOOK_WITHHOLD_PARTIAL) ? 64 : 0);      // (bit 64 of FusedP.variant: the kernel's fault-injection switch)
   p.out = scalar_out(c);
   const ChainEntry* chain_entry = chain ? chain_lookup(sh, c->f32) : nullptr;
   if (chain && !chain_entry) return fail(FH_E_STATE, "chained one-pass launch: no instantiation for this shape (teams of 1 / 2 / 4 members, float64)");

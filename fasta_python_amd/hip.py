@@ -143,6 +143,10 @@ SIGNATURES = {
     "fh_fused_agree": (_i32, [_ctx, C.POINTER(_i32)]),
     "fh_coresident_probe": (_i32, [_ctx, _i32, C.POINTER(_i32)]),
     "fh_fused_shape": (_i32, [_u64, _i32, _i32, _i32, C.POINTER(_i32), C.POINTER(_i32)]),
+    "fh_fused_launch_shape": (_i32, [_ctx, C.POINTER(C.c_uint32)]),
+    "fh_fused_launch_shape_for": (_i32, [_u64, _u64, _i32, _i32, _i32, _i32, _i32, C.POINTER(C.c_uint32)]),
+    "fh_setup_shape": (_i32, [_ctx, C.POINTER(C.c_uint32)]),
+    "fh_setup_shape_for": (_i32, [_u64, _u64, _i32, _i32, _i32, _i32, _i32, C.POINTER(C.c_uint32)]),
     "fh_fwd_adj": (_i32, [_ctx, _dbl, _pd]),
     "fh_step": (_i32, [_ctx, _dbl, _pd]),
     "fh_step_begin": (_i32, [_ctx, _dbl]),
@@ -240,6 +244,30 @@ def fused_shape(n, storage="f64", variant=2, ncu=256):
     inst = _i32(0)
     _check(lib, lib.fh_fused_shape(int(n), STORAGE[storage], int(variant), int(ncu), shape, C.byref(inst)))
     return tuple(shape), bool(inst.value)
+
+
+FUSED_LAUNCH_SHAPE_LEN = SETUP_SHAPE_LEN = 13
+FusedLaunchShape = collections.namedtuple("FusedLaunchShape", "PPT PIPE TEAM XLDS NBO F32 wpc nteams rows_per_team grid variant ld2 nv2")
+SetupShape = collections.namedtuple("SetupShape", "MPP PIPE TEAM threads NR F32 wpc nteams rows_per_team grid variant ld2 nv2")
+
+
+def fused_launch_shape_for(m, n, storage="f64", variant_word=34, variant_auto=True, cus=256, min_rows=16):
+    """FusedLaunchShape of a one-pass step launch (csrc/fh_fused.h) for an (m, n) dense matrix on `cus` CUs: the template key, workgroups per
+    CU, teams, rows per team, grid, the scheduling word the kernel receives (variant_auto: nobody set FH_TUNE_FUSED_VARIANT, the host clears
+    the cyclic bit below 128 rows per team), ld2, nv2 -- fh_fused_launch_shape_for, the rule the launcher itself calls.  Host-only."""
+    lib = load_library()
+    out = (C.c_uint32 * FUSED_LAUNCH_SHAPE_LEN)()
+    _check(lib, lib.fh_fused_launch_shape_for(int(m), int(n), STORAGE[storage], int(variant_word), 1 if variant_auto else 0, int(cus), int(min_rows), out))
+    return FusedLaunchShape(*(int(v) for v in out))
+
+
+def setup_shape_for(m, n, storage="f64", variant_word=34, variant_auto=True, cus=256, min_rows=16):
+    """SetupShape of fh_setup's one-read launch (csrc/fh_setup.h) for an (m, n) dense least-squares problem: fh_setup_shape_for, the rule the
+    launcher itself calls (E_STATE where fh_setup takes the three passes).  Host-only."""
+    lib = load_library()
+    out = (C.c_uint32 * SETUP_SHAPE_LEN)()
+    _check(lib, lib.fh_setup_shape_for(int(m), int(n), STORAGE[storage], int(variant_word), 1 if variant_auto else 0, int(cus), int(min_rows), out))
+    return SetupShape(*(int(v) for v in out))
 
 
 MULTI_SHAPE_LEN = 14
@@ -861,6 +889,19 @@ class HipContext:
         ok = _i32(0)
         self._call("fh_coresident_probe", int(workgroups), C.byref(ok))
         return bool(ok.value)
+
+    def fused_launch_shape(self):
+        """FusedLaunchShape the next step() / step_accel() of this context launches with (fh_fused_launch_shape).  E_STATE where the one-pass
+        kernel has no shape for the context."""
+        out = (C.c_uint32 * FUSED_LAUNCH_SHAPE_LEN)()
+        self._call("fh_fused_launch_shape", out)
+        return FusedLaunchShape(*(int(v) for v in out))
+
+    def setup_shape(self):
+        """SetupShape the one-read launch of setup() takes on this context (fh_setup_shape).  E_STATE where setup() runs the three passes."""
+        out = (C.c_uint32 * SETUP_SHAPE_LEN)()
+        self._call("fh_setup_shape", out)
+        return SetupShape(*(int(v) for v in out))
 
     def step(self, tau):
         """One-pass K-fwd + K-adj (no acceleration).  Raises HipTimeout if the bounded spins timed out."""

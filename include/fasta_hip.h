@@ -554,6 +554,24 @@ int fh_coresident_probe(fh_ctx* ctx, int workgroups, int* ok);
  * library (csrc/fh_fused_instances.inc).  A pure host function: no device needed.  dtype: fh_dtype; variant: FH_TUNE_FUSED_VARIANT
  * bits; ncu: compute units (256 on MI355X).                                                                                */
 int fh_fused_shape(uint64_t n, int dtype, int variant, int ncu, int* shape5, int* instantiated);
+/* The whole geometry of a one-pass launch, from the one host function the launcher itself takes it from (csrc/fh_host_launch.h:
+ * fused_launch_for), so that a test can assert the path it meant to reach.  out[FH_FUSED_LAUNCH_SHAPE_LEN] = { PPT, PIPE, TEAM, XLDS, NBO, F32
+ * (the template key of k_fused_dense: fh_fused_shape's five numbers and the storage), workgroups per CU, teams, rows per team, workgroups
+ * (teams x TEAM), the scheduling word the kernel receives (bit 32 -- rows dealt cyclically -- resolved: cleared by the host below 128 rows
+ * per team unless FH_TUNE_FUSED_VARIANT set the word), ld2 (16-byte pieces of a row that hold data), nv2 (double pairs per n-side vector) }.
+ * fh_fused_launch_shape reads the context (its matrix, prox kind, FH_TUNE_FUSED_CUS capped by the device's CUs, FH_TUNE_FUSED_VARIANT) and is
+ * FH_E_STATE where the one-pass kernel has no shape; fh_fused_launch_shape_for is the same rule as a pure host function (no device needed) of
+ * an (m, n) matrix of storage `dtype`: variant_word = the low half of FH_TUNE_FUSED_VARIANT (34 by default), variant_auto = 1 if nobody set
+ * it, cus = the CUs the launch may take, min_rows = the rows-per-team floor (16 by default, 0 = none).
+ * fh_setup_shape / fh_setup_shape_for: the same for fh_setup's one-read launch (csrc/fh_setup.h) of a least-squares problem --
+ * out[FH_SETUP_SHAPE_LEN] = { MPP, PIPE, TEAM, threads per workgroup, NR, F32 (the template key of k_setup_dense), workgroups per CU (1), teams,
+ * rows per team, workgroups, the scheduling word, ld2, nv2 }; FH_E_STATE where fh_setup takes the three passes instead.               */
+#define FH_FUSED_LAUNCH_SHAPE_LEN 13
+#define FH_SETUP_SHAPE_LEN 13
+int fh_fused_launch_shape(fh_ctx* ctx, uint32_t* out);
+int fh_fused_launch_shape_for(uint64_t m, uint64_t n, int dtype, int variant_word, int variant_auto, int cus, int min_rows, uint32_t* out);
+int fh_setup_shape(fh_ctx* ctx, uint32_t* out);
+int fh_setup_shape_for(uint64_t m, uint64_t n, int dtype, int variant_word, int variant_auto, int cus, int min_rows, uint32_t* out);
 int fh_step(fh_ctx* ctx, double tau, double* scalars);
 /* fh_step in two halves (the loop body of fasta/__init__.py:171-188 issued now, waited for later): fh_step_begin enqueues the launch
  * on the context's stream and returns at once; fh_step_end waits and delivers the scalar block.  In between the host may drive

@@ -586,7 +586,12 @@ def prove_attempt(Ai, b, x0, g0, xacc0, zacc0, tau, coef, accelerate, kind, bits
     every product is exact and every sum satisfies sum|terms| / lsb < 2^53; returns (sums as float64, vectors as float64) -- what ANY order of
     summation and any fusing of multiply-adds gives in float64 arithmetic."""
     k = -int(round(math.log2(tau)))
-    _need(2.0 ** -k == tau and coef in (0.0, -1.0), "tau is a power of two, the coefficient 0 or -1")
+    _need(2.0 ** -k == tau, "tau is a power of two")
+    # the coefficient as cn / 2^cq (any dyadic number; 0 and -1, what the loop's accelerated cases enter with, have cq = 0): what it multiplies moves
+    # to a scale cq bits finer
+    cq = _scale_of(np.array([coef])) if accelerate else 0
+    cn = int(round(coef * 2.0 ** cq)) if accelerate else 0
+    _need(abs(cn) < (1 << 20), "the coefficient is a short dyadic number")
     _, mu, lo, hi = PROX[kind]
     xa_f = xacc0 if accelerate else np.zeros_like(x0)
     s0 = _scale_of(x0, g0, xa_f, np.array([lo, hi]))
@@ -611,34 +616,34 @@ def prove_attempt(Ai, b, x0, g0, xacc0, zacc0, tau, coef, accelerate, kind, bits
     Sz = max(S, sb)
     Z = _shl(_matvec(Ai, XP, bits, "z = A xprox"), Sz - S)
     B, ZA = _shl(_ints(b, sb), Sz - sb), _shl(_ints(zacc0, sb), Sz - sb)
-    ZX = Z
+    Sr, ZX = Sz + cq, Z                                      # the extrapolated z, the residual and g1: multiples of 2^-Sr
     if accelerate:
         D = _elements(Z - ZA, bits, "z - z_accel0")
-        ZX = _elements(Z + int(coef) * D, bits, "extrapolated z")
-    R, RX = _elements(Z - B, bits, "z - b"), _elements(ZX - B, bits, "residual")
+        ZX = _elements(_shl(Z, cq) + cn * D, bits, "extrapolated z")
+    R, RX = _elements(Z - B, bits, "z - b"), _elements(ZX - _shl(B, cq), bits, "residual")
     sm["FSQ"] = _dot(R, R, bits, "|z - b|^2")
     sm["FSQ_ADJ"] = _dot(RX, RX, bits, "|zx - b|^2") if accelerate else 0
-    G1 = _matvec(Ai.T, RX, bits, "g1 = A^T r")              # multiples of 2^-Sz
+    G1 = _matvec(Ai.T, RX, bits, "g1 = A^T r")              # multiples of 2^-Sr
     # phase B at scale Sb = max(Sz, S - k ... ) : dg = g1 + (xhat - x0) / tau
     Sq = S - k                                               # (xhat - x0) / tau = -g0: multiples of 2^-(S - k) -- exact, a shift
-    Sb = max(Sz, Sq, S)
+    Sb = max(Sr, Sq, S)
     DGq = _shl(XH - X0, Sb - Sq)
-    DG = _elements(_shl(G1, Sb - Sz) + DGq, bits, "dg")
-    X1 = XP
+    DG = _elements(_shl(G1, Sb - Sr) + DGq, bits, "dg")
+    S1, X1 = S + cq, XP                                      # x1: multiples of 2^-S1
     if accelerate:
         D = _elements(XP - XA, bits, "xprox - x_accel0")
-        X1 = _elements(XP + int(coef) * D, bits, "x1")
-    DH1 = _elements(X1 - XH, bits, "x1 - xhat")
+        X1 = _elements(_shl(XP, cq) + cn * D, bits, "x1")
+    DH1 = _elements(X1 - _shl(XH, cq), bits, "x1 - xhat")
     DXb = _shl(DX, Sb - S)
     sm["DXDG"] = _dot(DXb, DG, bits, "<dx, dg>")
     sm["DG2"] = _dot(DG, DG, bits, "|dg|^2")
     sm["XH2_ADJ"] = _dot(DH1, DH1, bits, "|x1 - xhat|^2")
     sm["GSUM_ADJ"], sm["GMAX_ADJ"] = _sum(np.abs(X1), bits, "sum |x1|"), _imax(X1)
-    scale = {"FSQ": 2 * Sz, "FSQ_ADJ": 2 * Sz, "DXG0": 2 * S, "DX2": 2 * S, "XH2": 2 * S, "G02": 2 * S, "GSUM": S, "GMAX": S, "RDOT": 2 * S,
-             "DXDG": 2 * Sb, "DG2": 2 * Sb, "XH2_ADJ": 2 * S, "GSUM_ADJ": S, "GMAX_ADJ": S}
+    scale = {"FSQ": 2 * Sz, "FSQ_ADJ": 2 * Sr, "DXG0": 2 * S, "DX2": 2 * S, "XH2": 2 * S, "G02": 2 * S, "GSUM": S, "GMAX": S, "RDOT": 2 * S,
+             "DXDG": 2 * Sb, "DG2": 2 * Sb, "XH2_ADJ": 2 * S1, "GSUM_ADJ": S1, "GMAX_ADJ": S1}
     sums = [math.ldexp(sm[name], -scale[name]) for name in SUMS]      # (representable: |sum| <= sum|terms|, a multiple of the same lsb)
     vec = lambda N, s: np.ldexp(N.astype(np.float64), -s)
-    return sums, dict(xhat=vec(XH, S), xprox=vec(XP, S), z=vec(Z, Sz), g1=vec(G1, Sz), x1=vec(X1, S))
+    return sums, dict(xhat=vec(XH, S), xprox=vec(XP, S), z=vec(Z, Sz), g1=vec(G1, Sr), x1=vec(X1, S1))
 
 
 def prove(case, steps=None):

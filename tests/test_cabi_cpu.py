@@ -108,3 +108,22 @@ def test_every_row_width_resolves_to_an_instantiated_one_pass_kernel():
                 seen.add((dtype,) + tuple(shape))
     assert lib.fh_fused_shape(262145, hip.DTYPE_F64, 2, 256, shape, C.byref(inst)) == 0 and tuple(shape) == (0, 0, 0, 0, 0)
     assert len(seen) >= 60                                              # ... and nearly the whole table is reachable
+
+
+def test_the_launch_geometry_of_the_one_pass_kernels_is_a_pure_host_function():
+    """fh_fused_launch_shape_for / fh_setup_shape_for (the rules launch_fused_dense / launch_setup_dense call): bound with the context forms, the
+    template key equal to fh_fused_shape's, the default scheduling word resolved by the rows per team, refusals as statuses."""
+    for name, nargs in (("fh_fused_launch_shape", 2), ("fh_fused_launch_shape_for", 8), ("fh_setup_shape", 2), ("fh_setup_shape_for", 8)):
+        assert name in hip.SIGNATURES and len(hip.SIGNATURES[name][1]) == nargs
+    assert hasattr(hip.HipContext, "fused_launch_shape") and hasattr(hip.HipContext, "setup_shape")
+    sh = hip.fused_launch_shape_for(70, 65536)
+    assert sh[:5] == hip.fused_shape(65536)[0] and sh == hip.FusedLaunchShape(8, 2, 16, 0, 0, 0, 1, 8, 10, 128, 2, 32768, 32768)
+    assert hip.fused_launch_shape_for(70, 65536, variant_auto=False, min_rows=0)[7:11] == (16, 5, 256, 34)       # a caller's word is passed on
+    assert hip.fused_launch_shape_for(40000, 4096).variant == 34 and hip.fused_launch_shape_for(40000, 4096).rows_per_team == 157
+    assert hip.fused_launch_shape_for(64, 65536, "f32")[:7] == (4, 1, 16, 0, 4, 1, 2) and hip.fused_launch_shape_for(64, 65536, "f32").grid == 128
+    assert hip.setup_shape_for(150, 65536)[:6] == (8, 2, 16, 512, 2, 0) and hip.setup_shape_for(150, 65536, variant_word=34 | 16)[3] == 256
+    assert hip.setup_shape_for(16400, 512)[:6] == (1, 1, 1, 256, 2, 0) and hip.setup_shape_for(300, 30000, "f32")[:6] == (4, 1, 8, 256, 2, 1)
+    for refused in (lambda: hip.fused_launch_shape_for(3, 262160), lambda: hip.fused_launch_shape_for(0, 16), lambda: hip.fused_launch_shape_for(3, 16, cus=0),
+                    lambda: hip.setup_shape_for(100, 512), lambda: hip.setup_shape_for(40, 131072), lambda: hip.fused_launch_shape_for(3, 70000, cus=8)):
+        with pytest.raises(hip.HipError):
+            refused()
