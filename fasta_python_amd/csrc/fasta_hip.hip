@@ -429,22 +429,59 @@ static int set_tuning_one(fh_ctx* c, int key, long long value) {
 // ------------------------------------------------------------------------------------------------
 // operator set-up
 // ------------------------------------------------------------------------------------------------
+// What the operator setters share; each keeps what is its own -- argument checks, geometry, uploads -- between these calls:
+//   set_refusals     the context states a setter refuses, in the order the setters have always tested them (f32_last: the two that ask about a step
+//                    in flight before they ask about the storage).  The dense setters and fh_set_stencil do not call it: they refuse none of these
+//                    states (fh_set_stencil a shell, in its own words);
+//   set_begin        select the device, wait for the stream, refuse to drop observation weights, give the old operator back, reset what the new
+//                    form does not serve;
+//   vector_geometry  the padded layout of a vector-form operator that stores no matrix;
+//   set_end          the stream's wait, and NO operator left behind on any failure of the setter's allocations and uploads.
+static const char kStepInFlight[] = "a step issued by fh_step_begin is still in flight on this context: call fh_step_end first";
+static int set_refusals(const fh_ctx* c, const char* who, const OpForm& f, bool f32_last = false, const char* noun = nullptr) {
+  if (!noun) noun = f.noun;
+  if (!c->shards.empty() || c->owner) return fail(FH_E_STATE, "%s: a multi-device context has no %s (row sharding is implemented for the dense operator only)", who, noun);
+  if (c->comm) return fail(FH_E_STATE, "%s: a context with a communicator (row-sharded run) has no %s", who, noun);
+  if (f.no_f32 && c->f32 && !(f32_last && c->pending_step)) return fail(FH_E_STATE, f.no_f32, who, noun);
+  if (c->pending_step) return fail(FH_E_STATE, kStepInFlight);
+  return 0;
+}
+// next: the form being set, whose row says which prox kind survives (nullptr: the dense setters and fh_set_stencil keep whatever is held)
+enum { SET_KEEPS_SOLVER_STATE = 1, SET_DROPS_WEIGHTS = 2 };
+static int set_begin(fh_ctx* c, const OpForm* next, int flags = 0) {
+  FH_TRY(use_device(c));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (!(flags & SET_DROPS_WEIGHTS)) FH_TRY(refuse_weighted(c));
+  free_operator(c);                                      // (back to the vector form: L = LB = 0)
+  if (next) reset_unserved(c, *next);
+  if (!(flags & SET_KEEPS_SOLVER_STATE)) { c->loss_kind = LOSS_LSQ; c->lazy = false; c->last_accel = false; c->commits = 0; }
+  return 0;
+}
+static void vector_geometry(fh_ctx* c, uint64_t m, uint64_t n) {
+  c->m = m; c->n = n;
+  c->mp = m; c->ld = n;
+  c->nv = round_up(n, 16); c->mv = round_up(m, 16);
+}
+static int set_end(fh_ctx* c, int rc) {
+  if (rc == 0) rc = finish(c);
+  if (rc != 0) free_operator(c);
+  return rc;
+}
+
 static int setup_dense(fh_ctx* c, uint64_t m, uint64_t n) {
   if (m == 0 || n == 0) return fail(FH_E_ARG, "matrix must be non-empty (got %llu x %llu)", (unsigned long long)m, (unsigned long long)n);
   if (m >= (1ull << 31) || n >= (1ull << 31)) return fail(FH_E_ARG, "matrix dimension exceeds 2^31-1");
-  FH_TRY(use_device(c));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  FH_TRY(refuse_weighted(c));
-  free_operator(c);
+  FH_TRY(set_begin(c, nullptr, SET_KEEPS_SOLVER_STATE));
   c->m = m; c->n = n;
   c->mp = round_up(m, 16);
   c->ld = round_up(n, c->f32 ? 32 : 16) + (uint64_t)c->ld_pad;      // rows stay 128-byte aligned in either storage
   c->nv = c->ld; c->mv = c->mp;
   const size_t a_bytes = (size_t)c->mp * c->ld * (c->f32 ? sizeof(float) : sizeof(double));
   HIP_TRY(acquire_matrix_block(c->device, a_bytes, &c->A, &c->a_block_bytes));      // the block this device kept from an earlier matrix, or a fresh one behind the settle wait (fh_host_ctx.h)
-  FH_TRY(alloc_vectors(c));
-  c->op = OP_DENSE;
-  return 0;
+  c->op = OP_DENSE;                                      // (from here on free_operator gives the block back)
+  const int rc = alloc_vectors(c);
+  if (rc != 0) free_operator(c);
+  return rc;
 }
 
 // Row blocks of a shell: contiguous, the first (m mod p) shards hold ceil(m/p) rows and the others floor(m/p) -- SURVEY.md 8(e)'s
@@ -611,19 +648,12 @@ static int csr_check(const char* who, uint64_t m, uint64_t n, uint64_t nnz, cons
 static int set_matrix_csr(fh_ctx* c, const char* who, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* indptr, const int32_t* indices, const double* values, uint32_t L) {
   if (!c || !indptr || (nnz && (!indices || !values))) return fail(FH_E_ARG, "%s: null argument", who);
   if (L > 16) return fail(FH_E_ARG, "%s: at most 16 columns (got %u)", who, L);
-  if (!c->shards.empty() || c->owner) return fail(FH_E_STATE, "%s: a multi-device context has no sparse operator (row sharding is implemented for the dense operator only)", who);
-  if (c->comm) return fail(FH_E_STATE, "%s: a context with a communicator (row-sharded run) has no sparse operator", who);
-  if (c->f32) return fail(FH_E_STATE, "%s: float32 storage is not implemented for the sparse operator", who);
-  if (c->pending_step) return fail(FH_E_STATE, "a step issued by fh_step_begin is still in flight on this context: call fh_step_end first");
+  const OpForm& form = kForms[L ? F_SPARSE_MC : F_SPARSE];
+  FH_TRY(set_refusals(c, who, form));
   FH_TRY(csr_check(who, m, n, nnz, indptr, indices));
-  const uint32_t LB = L == 0 ? 0u : (L <= 2 ? 2u : (L <= 4 ? 4u : (L <= 8 ? 8u : 16u)));
+  const uint32_t LB = L ? lb_for(L) : 0u;
   const int C = LB ? (int)(LB / 2) : 1;                  // lanes per gathered row of the operand
-  FH_TRY(use_device(c));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  FH_TRY(refuse_weighted(c));
-  free_operator(c);                                      // (back to the vector form: L = LB = 0)
-  if (L ? !mc_prox_ok(c->prox_kind) : !sp_prox_ok(c->prox_kind)) { c->prox_kind = FH_PROX_IDENTITY; c->mu = 0.0; }
-  if (L) { c->loss_kind = LOSS_LSQ; c->lazy = false; c->last_accel = false; c->commits = 0; }
+  FH_TRY(set_begin(c, &form, L ? 0 : SET_KEEPS_SOLVER_STATE));
   c->L = L; c->LB = LB;
   c->m = m; c->n = n;
   c->mp = round_up(m, 16); c->ld = round_up(n, 16);      // vectors keep the vector form's padded layout
@@ -647,9 +677,8 @@ static int set_matrix_csr(fh_ctx* c, const char* who, uint64_t m, uint64_t n, ui
   if (rc == 0) rc = sp_upload_side(c, 1, n, nnz, tptr.data(), tidx.data(), tval.data(), C);
   if (rc == 0) rc = alloc_vectors(c);
   if (rc == 0) rc = alloc_zero(c, &c->sp_r, c->mv * lb_of(c) + 16);
-  if (rc != 0) { free_operator(c); return rc; }
-  c->op = OP_SPARSE;
-  return finish(c);
+  if (rc == 0) c->op = OP_SPARSE;
+  return set_end(c, rc);
 }
 extern "C" int fh_set_matrix_csr(fh_ctx* c, uint64_t m, uint64_t n, uint64_t nnz, const int64_t* indptr, const int32_t* indices, const double* values) {
   return set_matrix_csr(c, "fh_set_matrix_csr", m, n, nnz, indptr, indices, values, 0);
@@ -719,125 +748,74 @@ extern "C" int fh_set_stencil(fh_ctx* c, uint64_t H, uint64_t W) {
   if (H < 1 || W < 1) return fail(FH_E_ARG, "stencil needs H>=1 and W>=1 (got %llu x %llu)", (unsigned long long)H, (unsigned long long)W);
   if (H * W >= (1ull << 31)) return fail(FH_E_ARG, "image too large");
   if (!c->shards.empty() || c->owner) return fail(FH_E_STATE, "row sharding is implemented for the dense operator only");
-  FH_TRY(use_device(c));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  FH_TRY(refuse_weighted(c));
-  free_operator(c);
+  FH_TRY(set_begin(c, nullptr, SET_KEEPS_SOLVER_STATE));
   c->H = H; c->W = W;
-  c->m = H * W; c->n = 2 * H * W;
-  c->mp = c->m; c->ld = c->n;
-  c->nv = round_up(c->n, 16); c->mv = round_up(c->m, 16);
-  c->op_pending_stencil = true;
-  FH_TRY(alloc_vectors(c));
-  c->op_pending_stencil = false;
+  vector_geometry(c, H * W, 2 * H * W);
   c->op = OP_STENCIL;
-  return finish(c);
+  return set_end(c, alloc_vectors(c, true));
 }
 
 // the 3-D stencil (csrc/fh_tv3d.h): vectors in the vector form's padded layout, every buffer stored like any other operator's
 extern "C" int fh_set_stencil3d(fh_ctx* c, uint64_t D, uint64_t H, uint64_t W) {
   if (!c) return fail(FH_E_ARG, "null context");
-  if (!c->shards.empty() || c->owner) return fail(FH_E_STATE, "fh_set_stencil3d: a multi-device context has no 3-D stencil operator (row sharding is implemented for the dense operator only)");
-  if (c->comm) return fail(FH_E_STATE, "fh_set_stencil3d: a context with a communicator (row-sharded run) has no 3-D stencil operator");
-  if (c->pending_step) return fail(FH_E_STATE, "a step issued by fh_step_begin is still in flight on this context: call fh_step_end first");
+  FH_TRY(set_refusals(c, "fh_set_stencil3d", kForms[F_STENCIL3D]));
   Tv3Shape sh;
   FH_TRY(tv3_shape_for(D, H, W, 0, 1, &sh));             // (dimensions >= 1, 3 * D * H * W < 2^31: FH_E_ARG with the sentence)
-  FH_TRY(use_device(c));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  FH_TRY(refuse_weighted(c));
-  free_operator(c);
-  if (!tv3_prox_ok(c->prox_kind)) { c->prox_kind = FH_PROX_IDENTITY; c->mu = 0.0; }
-  c->loss_kind = LOSS_LSQ; c->lazy = false; c->last_accel = false; c->commits = 0;
+  FH_TRY(set_begin(c, &kForms[F_STENCIL3D]));
   c->D = D; c->H = H; c->W = W;
-  c->m = D * H * W; c->n = 3 * c->m;
-  c->mp = c->m; c->ld = c->n;
-  c->nv = round_up(c->n, 16); c->mv = round_up(c->m, 16);
-  const int rc = alloc_vectors(c);
-  if (rc != 0) { free_operator(c); return rc; }
+  vector_geometry(c, D * H * W, 3 * D * H * W);
   c->op = OP_STENCIL3D;
-  return finish(c);
+  return set_end(c, alloc_vectors(c));
 }
 
 // the subsampled DCT (csrc/fh_dct.h): A = diag(d) * C, m = n = N; vectors in the vector form's padded layout, no matrix stored: two twiddle
 // tables built here in long double, a copy of d, and two work buffers of N double2 when the transform takes two levels
 extern "C" int fh_set_dct(fh_ctx* c, uint64_t N, const double* diag) {
   if (!c) return fail(FH_E_ARG, "null context");
-  if (!c->shards.empty() || c->owner) return fail(FH_E_STATE, "fh_set_dct: a multi-device context has no DCT operator (row sharding is implemented for the dense operator only)");
-  if (c->comm) return fail(FH_E_STATE, "fh_set_dct: a context with a communicator (row-sharded run) has no DCT operator");
-  if (c->f32) return fail(FH_E_STATE, "fh_set_dct: float32 storage is a storage mode of a dense matrix; the DCT operator stores no matrix and computes in float64");
-  if (c->pending_step) return fail(FH_E_STATE, "a step issued by fh_step_begin is still in flight on this context: call fh_step_end first");
+  FH_TRY(set_refusals(c, "fh_set_dct", kForms[F_DCT]));
   DctShape sh;
   FH_TRY(dct_shape_for(N, c->dct_row_cap, c->ncu, &sh));   // (N >= 1, prime factors in {2, 3, 5}, a split within the row cap: FH_E_ARG with the sentence)
-  FH_TRY(use_device(c));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  FH_TRY(refuse_weighted(c));
-  free_operator(c);
-  if (!dct_prox_ok(c->prox_kind)) { c->prox_kind = FH_PROX_IDENTITY; c->mu = 0.0; }
-  c->loss_kind = LOSS_LSQ; c->lazy = false; c->last_accel = false; c->commits = 0;
-  c->m = c->n = N;
-  c->mp = c->m; c->ld = c->n;
-  c->nv = round_up(c->n, 16); c->mv = round_up(c->m, 16);
+  FH_TRY(set_begin(c, &kForms[F_DCT]));
+  vector_geometry(c, N, N);
   c->dct_sh = sh;
   c->dct_sc0 = (double)sqrtl(1.0L / (long double)N); c->dct_sck = (double)sqrtl(2.0L / (long double)N);
   c->op = OP_DCT;                                         // (from here on free_operator gives the tables back)
   int rc = alloc_vectors(c);
   if (rc == 0) rc = dct_alloc_tables(c, sh, diag);
-  if (rc != 0) { free_operator(c); return rc; }
-  return finish(c);
+  return set_end(c, rc);
 }
 
 // the subsampled 2-D DCT (csrc/fh_dct2.h): A x = d * (C_H X C_W^T), m = n = H * W; the DCT operator in its 2-D geometry (op == OP_DCT, dct2): vectors in
 // the vector form's padded layout, no matrix stored: a pair of twiddle tables per axis built here in long double, a copy of d, two work images
 extern "C" int fh_set_dct2(fh_ctx* c, uint64_t H, uint64_t W, const double* diag) {
   if (!c) return fail(FH_E_ARG, "null context");
-  if (!c->shards.empty() || c->owner) return fail(FH_E_STATE, "fh_set_dct2: a multi-device context has no 2-D DCT operator (row sharding is implemented for the dense operator only)");
-  if (c->comm) return fail(FH_E_STATE, "fh_set_dct2: a context with a communicator (row-sharded run) has no 2-D DCT operator");
-  if (c->f32) return fail(FH_E_STATE, "fh_set_dct2: float32 storage is a storage mode of a dense matrix; the 2-D DCT operator stores no matrix and computes in float64");
-  if (c->pending_step) return fail(FH_E_STATE, "a step issued by fh_step_begin is still in flight on this context: call fh_step_end first");
+  FH_TRY(set_refusals(c, "fh_set_dct2", kForms[F_DCT], false, "2-D DCT operator"));      // (one form, named by its geometry here)
   Dct2Shape sh;
   FH_TRY(dct2_shape_for(H, W, c->dct_row_cap, c->ncu, &sh));   // (each axis >= 1, at most the row cap, prime factors in {2, 3, 5}: FH_E_ARG with the sentence)
-  FH_TRY(use_device(c));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  FH_TRY(refuse_weighted(c));
-  free_operator(c);
-  if (!dct_prox_ok(c->prox_kind)) { c->prox_kind = FH_PROX_IDENTITY; c->mu = 0.0; }
-  c->loss_kind = LOSS_LSQ; c->lazy = false; c->last_accel = false; c->commits = 0;
+  FH_TRY(set_begin(c, &kForms[F_DCT]));
   c->H = H; c->W = W;
-  c->m = c->n = H * W;
-  c->mp = c->m; c->ld = c->n;
-  c->nv = round_up(c->n, 16); c->mv = round_up(c->m, 16);
+  vector_geometry(c, H * W, H * W);
   c->dct2_sh = sh;
   c->dct_sc0 = (double)sqrtl(1.0L / (long double)H); c->dct_sck = (double)sqrtl(2.0L / (long double)H);
   c->dct2_sc0 = (double)sqrtl(1.0L / (long double)W); c->dct2_sck = (double)sqrtl(2.0L / (long double)W);
   c->op = OP_DCT; c->dct2 = true;                          // (from here on free_operator gives the tables back)
   int rc = alloc_vectors(c);
   if (rc == 0) rc = dct2_alloc_tables(c, sh, diag);
-  if (rc != 0) { free_operator(c); return rc; }
-  return finish(c);
+  return set_end(c, rc);
 }
 
 // the periodic convolution (csrc/fh_conv.h): A x = d * (K conv x), m = n = H * W; vectors in the vector form's padded layout, no matrix stored: the
 // taps stay on the host (they travel in every launch's argument block), d is copied to the device
 extern "C" int fh_set_conv2d(fh_ctx* c, uint64_t H, uint64_t W, uint32_t kh, uint32_t kw, uint32_t oh, uint32_t ow, const double* taps, const double* diag) {
   if (!c) return fail(FH_E_ARG, "null context");
-  if (!c->shards.empty() || c->owner) return fail(FH_E_STATE, "fh_set_conv2d: a multi-device context has no convolution operator (row sharding is implemented for the dense operator only)");
-  if (c->comm) return fail(FH_E_STATE, "fh_set_conv2d: a context with a communicator (row-sharded run) has no convolution operator");
-  if (c->f32) return fail(FH_E_STATE, "fh_set_conv2d: float32 storage is a storage mode of a dense matrix; the convolution operator stores no matrix and computes in float64");
-  if (c->pending_step) return fail(FH_E_STATE, "a step issued by fh_step_begin is still in flight on this context: call fh_step_end first");
+  FH_TRY(set_refusals(c, "fh_set_conv2d", kForms[F_CONV]));
   if (!taps) return fail(FH_E_ARG, "fh_set_conv2d: null taps");
   ConvShape sh;
   FH_TRY(conv_shape_for(H, W, kh, kw, c->ncu, &sh));      // (dimensions >= 1, 1 <= kh, kw <= 16, H * W < 2^31: FH_E_ARG with the sentence)
   if (oh >= kh || ow >= kw) return fail(FH_E_ARG, "fh_set_conv2d: the origin (%u, %u) lies outside the %u x %u kernel", oh, ow, kh, kw);
-  FH_TRY(use_device(c));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  FH_TRY(refuse_weighted(c));
-  free_operator(c);
-  if (!conv_prox_ok(c->prox_kind)) { c->prox_kind = FH_PROX_IDENTITY; c->mu = 0.0; }
-  c->loss_kind = LOSS_LSQ; c->lazy = false; c->last_accel = false; c->commits = 0;
+  FH_TRY(set_begin(c, &kForms[F_CONV]));
   c->H = H; c->W = W;
-  c->m = c->n = H * W;
-  c->mp = c->m; c->ld = c->n;
-  c->nv = round_up(c->n, 16); c->mv = round_up(c->m, 16);
+  vector_geometry(c, H * W, H * W);
   c->conv_kh = kh; c->conv_kw = kw; c->conv_oh = oh; c->conv_ow = ow;
   memset(c->conv_taps, 0, sizeof(c->conv_taps));
   memcpy(c->conv_taps, taps, (size_t)kh * kw * sizeof(double));
@@ -845,42 +823,31 @@ extern "C" int fh_set_conv2d(fh_ctx* c, uint64_t H, uint64_t W, uint32_t kh, uin
   c->op = OP_CONV;                                        // (from here on free_operator gives the diagonal back)
   int rc = alloc_vectors(c);
   if (rc == 0 && diag) rc = conv_alloc_diag(c, diag);
-  if (rc != 0) { free_operator(c); return rc; }
-  return finish(c);
+  return set_end(c, rc);
 }
 
 // the identity operator with an elementwise loss (csrc/fh_nuclear.h): the unknown is an (M, N) matrix in the vector form's buffers, m = n = M * N;
 // nothing is stored for the operator itself
 extern "C" int fh_set_identity(fh_ctx* c, uint64_t M, uint64_t N) {
   if (!c) return fail(FH_E_ARG, "null context");
-  if (!c->shards.empty() || c->owner) return fail(FH_E_STATE, "fh_set_identity: a multi-device context has no identity operator (row sharding is implemented for the dense operator only)");
-  if (c->comm) return fail(FH_E_STATE, "fh_set_identity: a context with a communicator (row-sharded run) has no identity operator");
-  if (c->f32) return fail(FH_E_STATE, "fh_set_identity: float32 storage is a storage mode of a dense matrix; the identity operator stores no matrix and computes in float64");
-  if (c->pending_step) return fail(FH_E_STATE, "a step issued by fh_step_begin is still in flight on this context: call fh_step_end first");
+  FH_TRY(set_refusals(c, "fh_set_identity", kForms[F_IDENTITY]));
   if (M == 0 || N == 0) return fail(FH_E_ARG, "fh_set_identity: the matrix unknown must be non-empty (got %llu x %llu)", (unsigned long long)M, (unsigned long long)N);
   if (M > (1ull << 26) || N > (1ull << 26) || M * N > (1ull << 26)) return fail(FH_E_ARG, "fh_set_identity: at most 2^26 entries (got %llu x %llu)", (unsigned long long)M, (unsigned long long)N);
-  FH_TRY(use_device(c));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  free_operator(c);
-  if (!sp_prox_ok(c->prox_kind)) { c->prox_kind = FH_PROX_IDENTITY; c->mu = 0.0; }
-  c->loss_kind = LOSS_LSQ; c->lazy = false; c->last_accel = false; c->commits = 0;
+  FH_TRY(set_begin(c, &kForms[F_IDENTITY], SET_DROPS_WEIGHTS));      // (the one operator that serves weights: a new one starts without them)
   c->id_M = M; c->id_N = N;
-  c->m = c->n = M * N;
-  c->mp = c->m; c->ld = c->n;
-  c->nv = round_up(c->n, 16); c->mv = round_up(c->m, 16);
+  vector_geometry(c, M * N, M * N);
   c->op = OP_IDENTITY;
-  const int rc = alloc_vectors(c);
-  if (rc != 0) { free_operator(c); return rc; }
-  return finish(c);
+  return set_end(c, alloc_vectors(c));
 }
 
 // FH_PROX_NUCLEAR / FH_PROX_NUCBALL on the identity operator: the geometry (FH_TUNE_NUC_BLOCK_ROWS is read here) and the working buffers
 static int set_prox_jacobi(fh_ctx* c, int kind, double mu, int objective) {
   if (!c) return fail(FH_E_ARG, "null context");
-  if (c->op != OP_IDENTITY && kind == FH_PROX_NUCBALL) return fail(FH_E_STATE, "FH_PROX_NUCBALL (projection of a matrix unknown onto the nuclear-norm ball) is served by the identity operator only: call fh_set_identity first");
-  if (c->op != OP_IDENTITY) return fail(FH_E_STATE, "FH_PROX_NUCLEAR (singular-value soft-threshold of a matrix unknown) is served by the identity operator only: call fh_set_identity first");
+  if (!serves_prox(form_of(c), kind))
+    return fail(FH_E_STATE, "%s is served by the identity operator only: call fh_set_identity first", kind == FH_PROX_NUCBALL ? "FH_PROX_NUCBALL (projection of a matrix unknown onto the nuclear-norm ball)"
+                                                                                                                                : "FH_PROX_NUCLEAR (singular-value soft-threshold of a matrix unknown)");
   if (kind == FH_PROX_NUCBALL && !(mu >= 0.0 && mu <= 1.7976931348623157e308)) return fail(FH_E_ARG, "FH_PROX_NUCBALL: the radius (mu) must be finite and >= 0 (got %g)", mu);
-  if (c->pending_step) return fail(FH_E_STATE, "a step issued by fh_step_begin is still in flight on this context: call fh_step_end first");
+  if (c->pending_step) return fail(FH_E_STATE, kStepInFlight);
   NucShape sh;
   FH_TRY(nuc_shape_for(c->id_M, c->id_N, c->nuc_block_rows, &sh));
   FH_TRY(use_device(c));
@@ -925,20 +892,13 @@ extern "C" int fh_set_rhs(fh_ctx* c, uint32_t L) {
   if (L > 16) return fail(FH_E_ARG, "fh_set_rhs: at most 16 columns (got %u)", L);
   if (!c->shards.empty() || c->owner) return fail(FH_E_STATE, "fh_set_rhs: a multi-device context has no multi-column form");
   if (c->comm) return fail(FH_E_STATE, "fh_set_rhs: a context with a communicator (row-sharded run) has no multi-column form");
-  if (c->pending_step) return fail(FH_E_STATE, "a step issued by fh_step_begin is still in flight on this context: call fh_step_end first");
-  if (c->op == OP_NONE) return fail(FH_E_STATE, "fh_set_rhs: set the dense operator first (fh_set_matrix / fh_generate_matrix)");
-  if (c->op == OP_SPARSE) return fail(FH_E_STATE, "fh_set_rhs: the sparse operator has no multi-column form through fh_set_rhs: its column count is fixed when it is set (fh_set_matrix_csr_rhs)");
-  if (c->op == OP_STENCIL3D) return fail(FH_E_STATE, "fh_set_rhs: the 3-D stencil operator has no multi-column form");
-  if (c->op == OP_DCT) return fail(FH_E_STATE, "fh_set_rhs: the DCT operator has no multi-column form");
-  if (c->op == OP_CONV) return fail(FH_E_STATE, "fh_set_rhs: the convolution operator has no multi-column form");
-  if (c->op == OP_IDENTITY) return fail(FH_E_STATE, "fh_set_rhs: the identity operator has no multi-column form (its unknown is already an (M, N) matrix: fh_set_identity)");
-  if (c->op == OP_QUAD) return fail(FH_E_STATE, "fh_set_rhs: the column count of a quadratic operator is fixed when it is set (fh_set_quadratic)");
-  if (c->op == OP_BILINEAR) return fail(FH_E_STATE, "fh_set_rhs: the column count of a bilinear operator is fixed when it is set (fh_set_factorization)");
-  if (c->op != OP_DENSE) return fail(FH_E_STATE, "fh_set_rhs: the stencil operator has no multi-column form");
+  if (c->pending_step) return fail(FH_E_STATE, kStepInFlight);
+  if (const char* why = form_of(c).no_rhs) return fail(FH_E_STATE, why, form_of(c).noun);
   if (c->f32) return fail(FH_E_STATE, "fh_set_rhs: float32 storage of A has no multi-column form");
-  if (L && c->has_b && c->loss_kind == LOSS_LOGISTIC) return fail(FH_E_STATE, "fh_set_rhs: the logistic loss has no multi-column form");
-  if (L && !mc_prox_ok(c->prox_kind)) return fail(FH_E_STATE, "fh_set_rhs: prox kind %d (LINF / L1BALL / TVBALL) has no multi-column form", c->prox_kind);
-  const uint32_t LB = L == 0 ? 0u : (L <= 2 ? 2u : (L <= 4 ? 4u : (L <= 8 ? 8u : 16u)));
+  const OpForm& next = kForms[L ? F_DENSE_MC : F_DENSE];
+  if (L && c->has_b && !takes_loss(next, c->loss_kind)) return fail(FH_E_STATE, "fh_set_rhs: the logistic loss has no multi-column form");
+  if (L && !serves_prox(next, c->prox_kind)) return refuse_prox(FH_E_STATE, "fh_set_rhs: ", next, c->prox_kind);
+  const uint32_t LB = L ? lb_for(L) : 0u;
   FH_TRY(use_device(c));
   HIP_TRY(hipStreamSynchronize(c->stream));
   // every vector buffer changes its size: they start over as zeros (padding columns stay zero from here on), the loss has to be set again
@@ -946,7 +906,7 @@ extern "C" int fh_set_rhs(fh_ctx* c, uint32_t L) {
   c->L = L; c->LB = LB;
   c->has_b = false; c->loss_kind = LOSS_LSQ;
   c->lazy = false; c->last_accel = false; c->commits = 0;
-  if (!L && c->prox_kind == FH_PROX_GROUP) { c->prox_kind = FH_PROX_IDENTITY; c->mu = 0.0; }
+  if (!L) reset_unserved(c, next);                       // (the row-wise shrink has no vector form)
   FH_TRY(alloc_vectors(c));
   return finish(c);
 }
@@ -971,10 +931,7 @@ static bool first_asymmetry(const double* Q, uint64_t n, uint64_t ld, uint64_t* 
 extern "C" int fh_set_quadratic(fh_ctx* c, const double* Q, uint64_t n, uint64_t ld_host, const double* cvec, uint32_t L) {
   if (!c || !Q) return fail(FH_E_ARG, "fh_set_quadratic: null argument");
   if (L < 1 || L > 16) return fail(FH_E_ARG, "fh_set_quadratic: 1 to 16 columns (got %u)", L);
-  if (!c->shards.empty() || c->owner) return fail(FH_E_STATE, "fh_set_quadratic: a multi-device context has no quadratic operator (row sharding is implemented for the dense operator only)");
-  if (c->comm) return fail(FH_E_STATE, "fh_set_quadratic: a context with a communicator (row-sharded run) has no quadratic operator");
-  if (c->pending_step) return fail(FH_E_STATE, "a step issued by fh_step_begin is still in flight on this context: call fh_step_end first");
-  if (c->f32) return fail(FH_E_STATE, "fh_set_quadratic: float32 storage has no quadratic operator");
+  FH_TRY(set_refusals(c, "fh_set_quadratic", kForms[F_QUAD], true));
   if (n == 0) return fail(FH_E_ARG, "fh_set_quadratic: the matrix must be non-empty");
   if (n >= (1ull << 31)) return fail(FH_E_ARG, "fh_set_quadratic: matrix dimension exceeds 2^31-1");
   if (ld_host < n) return fail(FH_E_ARG, "fh_set_quadratic: ld_host %llu < n %llu", (unsigned long long)ld_host, (unsigned long long)n);
@@ -982,17 +939,12 @@ extern "C" int fh_set_quadratic(fh_ctx* c, const double* Q, uint64_t n, uint64_t
   if (first_asymmetry(Q, n, ld_host, &bi, &bj))
     return fail(FH_E_ARG, "fh_set_quadratic: Q is not symmetric: Q[%llu,%llu] = %.17g but Q[%llu,%llu] = %.17g (pass (Q + Q^T) / 2, or S + S^T as examples/max_norm.py:50 does)",
                 (unsigned long long)bi, (unsigned long long)bj, Q[bi * ld_host + bj], (unsigned long long)bj, (unsigned long long)bi, Q[bj * ld_host + bi]);
-  FH_TRY(use_device(c));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  FH_TRY(refuse_weighted(c));
-  free_operator(c);
-  if (!qd_prox_ok(c->prox_kind)) { c->prox_kind = FH_PROX_IDENTITY; c->mu = 0.0; }
-  c->lazy = false; c->last_accel = false; c->commits = 0;
+  FH_TRY(set_begin(c, &kForms[F_QUAD]));
   c->m = n; c->n = n;
   c->mp = round_up(n, 16);
   c->ld = round_up(n, 16) + (uint64_t)c->ld_pad;
   c->nv = c->ld; c->mv = c->mp;
-  c->L = L; c->LB = L <= 2 ? 2u : (L <= 4 ? 4u : (L <= 8 ? 8u : 16u));
+  c->L = L; c->LB = lb_for(L);
   const size_t q_bytes = (size_t)c->mp * c->ld * sizeof(double);
   HIP_TRY(acquire_matrix_block(c->device, q_bytes, &c->A, &c->a_block_bytes));
   c->op = OP_QUAD;                                       // (from here on free_operator gives the block back)
@@ -1001,32 +953,22 @@ extern "C" int fh_set_quadratic(fh_ctx* c, const double* Q, uint64_t n, uint64_t
   if (rc == 0 && hipMemcpy2DAsync(c->A, c->ld * sizeof(double), Q, ld_host * sizeof(double), n * sizeof(double), n, hipMemcpyHostToDevice, c->stream) != hipSuccess)
     rc = fail(FH_E_STATE, "fh_set_quadratic: the copy of Q to the device failed");
   if (rc == 0 && cvec) rc = copy_in(c, c->b, cvec, n);   // (no C: the buffer stays the zeros it was allocated as)
-  if (rc == 0) rc = finish(c);
-  if (rc != 0) { free_operator(c); return rc; }
-  c->loss_kind = LOSS_QUAD; c->has_b = true;
-  return 0;
+  if (rc == 0) { c->loss_kind = LOSS_QUAD; c->has_b = true; }
+  return set_end(c, rc);
 }
 
 // ---- bilinear smooth term f(Z) = .5 ||S - X Y^T||^2, Z = [X; Y], A = identity (csrc/fh_bilinear.h): operator and loss in one call ----
 extern "C" int fh_set_factorization(fh_ctx* c, const double* S, uint64_t m, uint64_t n, uint64_t ld_host, uint32_t K) {
   if (!c || !S) return fail(FH_E_ARG, "fh_set_factorization: null argument");
   if (K < 1 || K > 16) return fail(FH_E_ARG, "fh_set_factorization: 1 to 16 columns (got %u)", K);
-  if (!c->shards.empty() || c->owner) return fail(FH_E_STATE, "fh_set_factorization: a multi-device context has no bilinear operator (row sharding is implemented for the dense operator only)");
-  if (c->comm) return fail(FH_E_STATE, "fh_set_factorization: a context with a communicator (row-sharded run) has no bilinear operator");
-  if (c->pending_step) return fail(FH_E_STATE, "a step issued by fh_step_begin is still in flight on this context: call fh_step_end first");
-  if (c->f32) return fail(FH_E_STATE, "fh_set_factorization: float32 storage has no bilinear operator");
+  FH_TRY(set_refusals(c, "fh_set_factorization", kForms[F_BILINEAR], true));
   if (m == 0 || n == 0) return fail(FH_E_ARG, "fh_set_factorization: the matrix must be non-empty");
   if (ld_host < n) return fail(FH_E_ARG, "fh_set_factorization: ld_host %llu < n %llu", (unsigned long long)ld_host, (unsigned long long)n);
   if (m >= (1ull << 27) || n >= (1ull << 27)) return fail(FH_E_ARG, "fh_set_factorization: m + n must be below 2^27 (the row offsets (m + n) * LB are kept in 31 bits)");
   const uint32_t LB = lb_for(K);
   const uint64_t ld = round_up(n, 16) + (uint64_t)c->ld_pad;
   if (const char* why = bl_too_large(m, n, bl_shape_for(m, n, ld, LB, c->fwd_cap, c->nt_loads))) return fail(FH_E_ARG, "fh_set_factorization: %s", why);
-  FH_TRY(use_device(c));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  FH_TRY(refuse_weighted(c));
-  free_operator(c);
-  if (!bl_prox_ok(c->prox_kind)) { c->prox_kind = FH_PROX_IDENTITY; c->mu = 0.0; }
-  c->lazy = false; c->last_accel = false; c->commits = 0;
+  FH_TRY(set_begin(c, &kForms[F_BILINEAR]));
   c->bl_m = m; c->bl_n = n;
   c->m = m + n; c->n = m + n;
   c->mp = round_up(m, 16);
@@ -1040,16 +982,14 @@ extern "C" int fh_set_factorization(fh_ctx* c, const double* S, uint64_t m, uint
   if (rc == 0 && hipMemsetAsync(c->A, 0, s_bytes, c->stream) != hipSuccess) rc = fail(FH_E_STATE, "fh_set_factorization: clearing the device copy of S failed");
   if (rc == 0 && hipMemcpy2DAsync(c->A, c->ld * sizeof(double), S, ld_host * sizeof(double), n * sizeof(double), m, hipMemcpyHostToDevice, c->stream) != hipSuccess)
     rc = fail(FH_E_STATE, "fh_set_factorization: the copy of S to the device failed");
-  if (rc == 0) rc = finish(c);
-  if (rc != 0) { free_operator(c); return rc; }
-  c->loss_kind = LOSS_BILINEAR; c->has_b = true;
-  return 0;
+  if (rc == 0) { c->loss_kind = LOSS_BILINEAR; c->has_b = true; }
+  return set_end(c, rc);
 }
 
 extern "C" int fh_set_prox_split(fh_ctx* c, uint64_t split, int kind_top, double mu_top, double lo_top, double hi_top,
                                  int kind_bottom, double lo_bottom, double hi_bottom) {
   if (!c) return fail(FH_E_ARG, "null context");
-  if (c->op != OP_BILINEAR) return fail(FH_E_STATE, "FH_PROX_ROWSPLIT (one elementwise prox on the top rows, another on the others) is served by the bilinear operator only: call fh_set_factorization first");
+  if (!serves_prox(form_of(c), FH_PROX_ROWSPLIT)) return fail(FH_E_STATE, "FH_PROX_ROWSPLIT (one elementwise prox on the top rows, another on the others) is served by the bilinear operator only: call fh_set_factorization first");
   if (split != c->bl_m) return fail(FH_E_ARG, "fh_set_prox_split: split must equal m = %llu, the rows of the first factor (got %llu)", (unsigned long long)c->bl_m, (unsigned long long)split);
   if (kind_top != FH_PROX_IDENTITY && kind_top != FH_PROX_SHRINK && kind_top != FH_PROX_NONNEG && kind_top != FH_PROX_BOX)
     return fail(FH_E_ARG, "fh_set_prox_split: the top rows take IDENTITY, SHRINK, NONNEG or BOX (got kind %d)", kind_top);
@@ -1064,15 +1004,10 @@ extern "C" int fh_set_prox_split(fh_ctx* c, uint64_t split, int kind_top, double
 
 static int set_loss(fh_ctx* c, int kind, const double* b, uint64_t len) {
   if (!c || !b) return fail(FH_E_ARG, "null argument");
-  if (c->op == OP_NONE) return fail(FH_E_STATE, "set the operator before the loss");
-  if (c->op == OP_QUAD) return fail(FH_E_STATE, "the quadratic operator carries its own loss (Q and the linear term of fh_set_quadratic): fh_set_loss_lsq / fh_set_loss_logistic do not apply");
-  if (c->op == OP_BILINEAR) return fail(FH_E_STATE, "the bilinear operator carries its own loss (S of fh_set_factorization): fh_set_loss_lsq / fh_set_loss_logistic do not apply");
+  const OpForm& f = form_of(c);
+  if (!f.losses) return fail(FH_E_STATE, f.no_loss);
   if (len != c->m * l_of(c)) return fail(FH_E_ARG, "b has %llu entries, operator has %llu rows (x %llu columns)", (unsigned long long)len, (unsigned long long)c->m, (unsigned long long)l_of(c));
-  if (kind != LOSS_LSQ && c->LB) return fail(FH_E_STATE, "the logistic loss has no multi-column form (fh_set_rhs / fh_set_matrix_csr_rhs)");
-  if (kind != LOSS_LSQ && c->op == OP_STENCIL3D) return fail(FH_E_STATE, "the 3-D stencil operator serves the least-squares loss only (the logistic loss is implemented for the dense and sparse operators)");
-  if (kind != LOSS_LSQ && c->op == OP_DCT) return fail(FH_E_STATE, "the DCT operator serves the least-squares loss only (the logistic loss is implemented for the dense and sparse operators)");
-  if (kind != LOSS_LSQ && c->op == OP_CONV) return fail(FH_E_STATE, "the convolution operator serves the least-squares loss only (the logistic loss is implemented for the dense and sparse operators)");
-  if (kind != LOSS_LSQ && c->op != OP_DENSE && c->op != OP_SPARSE && c->op != OP_IDENTITY) return fail(FH_E_STATE, "the logistic loss is implemented for the dense operator");
+  if (!takes_loss(f, kind)) return fail(FH_E_STATE, f.no_loss, f.noun);
   if (!c->shards.empty()) {          // shell: b is sharded like the rows
     for (int k = 0; k < nshards(c); ++k) FH_TRY(set_loss(c->shards[k], kind, b + c->shard_row0[k], shard_rows(c, k)));
     c->has_b = true; c->loss_kind = kind;
@@ -1089,8 +1024,8 @@ static int set_loss(fh_ctx* c, int kind, const double* b, uint64_t len) {
 // observation weights of the elementwise loss on the identity operator (csrc/fh_nuclear.h): f(X) = sum_j w_j loss(x_j, b_j); NULL removes them
 extern "C" int fh_set_loss_weights(fh_ctx* c, const double* w) {
   if (!c) return fail(FH_E_ARG, "null context");
-  if (c->pending_step) return fail(FH_E_STATE, "a step issued by fh_step_begin is still in flight on this context: call fh_step_end first");
-  if (c->op != OP_IDENTITY) {
+  if (c->pending_step) return fail(FH_E_STATE, kStepInFlight);
+  if (!form_of(c).weights) {
     if (!w && !c->loss_w) return 0;                      // (nothing held, nothing to remove)
     return fail(FH_E_STATE, "fh_set_loss_weights: observation weights are served by the identity operator only (fh_set_identity, then fh_set_loss_lsq / "
                             "fh_set_loss_logistic, then the weights)");
@@ -1119,14 +1054,10 @@ extern "C" int fh_set_loss_logistic(fh_ctx* c, const double* labels, uint64_t le
 // the softmax loss over the L columns of a matrix unknown (csrc/fh_softmax.h): B becomes the one-hot matrix of the labels
 extern "C" int fh_set_loss_softmax(fh_ctx* c, const int32_t* labels, uint64_t m) {
   if (!c || !labels) return fail(FH_E_ARG, "fh_set_loss_softmax: null argument");
-  if (c->pending_step) return fail(FH_E_STATE, "a step issued by fh_step_begin is still in flight on this context: call fh_step_end first");
+  if (c->pending_step) return fail(FH_E_STATE, kStepInFlight);
   if (c->op == OP_NONE) return fail(FH_E_STATE, "set the operator before the loss");
   if (!c->shards.empty() || c->owner || c->comm) return fail(FH_E_STATE, "fh_set_loss_softmax: a multi-device or row-sharded context has no multi-column form, which the softmax loss needs");
-  if (c->op != OP_DENSE && c->op != OP_SPARSE)
-    return fail(FH_E_STATE, "fh_set_loss_softmax: the softmax loss is implemented for the dense and the sparse operator in multi-column form only "
-                            "(fh_set_matrix + fh_set_rhs, or fh_set_matrix_csr_rhs), not for the stencil, DCT, convolution, identity, quadratic or bilinear operators");
-  if (!c->LB) return fail(FH_E_STATE, "fh_set_loss_softmax: the softmax loss needs the multi-column form, one column of the unknown per class: call fh_set_rhs (dense operator) "
-                                      "or fh_set_matrix_csr_rhs (sparse operator) with L >= 2 first (two classes on a vector unknown: fh_set_loss_logistic)");
+  if (!takes_loss(form_of(c), LOSS_SOFTMAX)) return fail(FH_E_STATE, form_of(c).no_softmax);
   if (c->L < 2) return fail(FH_E_STATE, "fh_set_loss_softmax: the softmax loss needs at least two columns (classes), the context has L = %u", c->L);
   if (m != c->m) return fail(FH_E_ARG, "fh_set_loss_softmax: labels has %llu entries, operator has %llu rows", (unsigned long long)m, (unsigned long long)c->m);
   for (uint64_t i = 0; i < m; ++i)
@@ -1155,16 +1086,11 @@ extern "C" int fh_set_prox(fh_ctx* c, int kind, double mu, double lo, double hi)
   if (kind == FH_PROX_NUCLEAR) return fh_set_prox_nuclear(c, mu, 1);
   if (kind == FH_PROX_NUCBALL) return set_prox_jacobi(c, FH_PROX_NUCBALL, mu, 0);      // g = 0: the norms are never evaluated where they are not free
   if (kind < FH_PROX_IDENTITY || kind > FH_PROX_ROWBALL) return fail(FH_E_ARG, "unknown prox kind %d", kind);
-  if (c->op == OP_IDENTITY && !id_prox_ok(kind)) return fail(FH_E_ARG, "prox kind %d (LINF / L1BALL / TVBALL / GROUP / ROWBALL) is not implemented for the identity operator", kind);
-  if (c->op == OP_BILINEAR && !bl_prox_ok(kind)) return fail(FH_E_ARG, "prox kind %d (LINF / L1BALL / TVBALL / GROUP / ROWBALL) has no bilinear form", kind);
-  if (kind == FH_PROX_ROWBALL && c->op != OP_QUAD) return fail(FH_E_ARG, "FH_PROX_ROWBALL (row-wise projection onto the ball of radius mu) is served by the quadratic operator only: call fh_set_quadratic first");
-  if (c->op == OP_QUAD && !qd_prox_ok(kind)) return fail(FH_E_ARG, "prox kind %d (LINF / L1BALL / TVBALL) has no quadratic form", kind);
+  const OpForm& f = form_of(c);
+  if (f.answers_first && !serves_prox(f, kind)) return refuse_prox(FH_E_ARG, "", f, kind);
+  if (kind == FH_PROX_ROWBALL && !serves_prox(f, kind)) return fail(FH_E_ARG, "FH_PROX_ROWBALL (row-wise projection onto the ball of radius mu) is served by the quadratic operator only: call fh_set_quadratic first");
   if (kind == FH_PROX_GROUP && !c->LB) return fail(FH_E_ARG, "FH_PROX_GROUP (row-wise l2 shrink) needs the multi-column form: call fh_set_rhs (dense operator) or fh_set_matrix_csr_rhs (sparse operator) first");
-  if (c->LB && c->op != OP_QUAD && !mc_prox_ok(kind)) return fail(FH_E_ARG, "prox kind %d (LINF / L1BALL / TVBALL) has no multi-column form", kind);
-  if (c->op == OP_SPARSE && !c->LB && !sp_prox_ok(kind)) return fail(FH_E_ARG, "prox kind %d (LINF / L1BALL / TVBALL / GROUP) is not implemented for the sparse operator", kind);
-  if (c->op == OP_STENCIL3D && !tv3_prox_ok(kind)) return fail(FH_E_ARG, "prox kind %d (LINF / L1BALL / GROUP) is not implemented for the 3-D stencil operator", kind);
-  if (c->op == OP_DCT && !dct_prox_ok(kind)) return fail(FH_E_ARG, "prox kind %d (TVBALL / GROUP) is not implemented for the DCT operator", kind);
-  if (c->op == OP_CONV && !conv_prox_ok(kind)) return fail(FH_E_ARG, "prox kind %d (TVBALL / GROUP) is not implemented for the convolution operator", kind);
+  if (!serves_prox(f, kind)) return refuse_prox(FH_E_ARG, "", f, kind);
   if (kind == FH_PROX_BOX && !(lo <= hi)) return fail(FH_E_ARG, "box prox needs lo <= hi");
   for (fh_ctx* s : c->shards) { s->prox_kind = kind; s->mu = mu; s->lo = lo; s->hi = hi; }      // the prox is replicated work
   c->prox_kind = kind; c->mu = mu; c->lo = lo; c->hi = hi;

@@ -114,7 +114,6 @@ struct fh_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
   int op = OP_NONE;
-  bool op_pending_stencil = false;
   uint64_t m = 0, n = 0;     // logical (local) rows / columns of A   (stencil: m = H*W, n = 2*H*W)
   uint64_t mp = 0, ld = 0;   // padded rows, device leading dimension in elements (dense)
   int f32 = 0;               // storage of A: 0 = float64, 1 = float32 (opt-in, fh_create_ex; vectors and arithmetic stay float64)
@@ -308,6 +307,105 @@ static inline fh_ctx* shard_of(fh_ctx* c, int k) { return c->shards.empty() ? c 
 // a context whose launches leave the sums over rows to an exchange step: a rank of a multi-process run, or a shard of a shell
 static inline bool row_sharded(const fh_ctx* c) { return c->comm != nullptr || c->owner != nullptr; }
 
+// ------------------------------------------------------------------------------------------------
+// operator forms: what each one serves, stated once
+// ------------------------------------------------------------------------------------------------
+// A form is c->op plus whether the unknown has columns (c->LB); the DCT operator is one form in both geometries.  Every entry point that accepts
+// or refuses a prox kind, a loss or a column count asks a row of kForms, and so does every launch-time backstop; the sentences a caller reads
+// stand here, whole, as they always were (the lists in parentheses included: they are behaviour).  A sentence may take the noun as %s.
+enum { F_NONE, F_DENSE, F_DENSE_MC, F_STENCIL, F_SPARSE, F_SPARSE_MC, F_STENCIL3D, F_QUAD, F_BILINEAR, F_DCT, F_IDENTITY, F_CONV, F_COUNT };
+struct OpForm {
+  const char* noun;          // as the sentences name it, without its article
+  unsigned prox;             // bits of FH_PROX_*: the kinds fh_set_prox accepts on this form and a setter of it keeps
+  unsigned prox_run;         // ... the kinds its forward launch lets through, where that is another set (0 = the same)
+  unsigned losses;           // bits of LOSS_*: what fh_set_loss_* may give it (0: it has no loss to set)
+  bool weights;              // fh_set_loss_weights
+  bool answers_first;        // fh_set_prox: this form's own sentence comes before the ROWBALL / GROUP ones
+  const char* no_prox;       // an unserved kind (%d, noun): fh_set_prox, fh_set_rhs
+  const char* no_prox_run;   // ... at launch (nullptr = the same)
+  const char* no_loss;       // fh_set_loss_lsq / _logistic: the loss is refused (noun)
+  const char* no_loss_run;   // ... at launch (nullptr = the same)
+  const char* no_softmax;    // fh_set_loss_softmax
+  const char* no_rhs;        // fh_set_rhs (nullptr: this form takes it)
+  const char* no_f32;        // float32 storage, refused by the form's setter (entry point, noun; nullptr: the setter does not ask)
+};
+#define KIND(k) (1u << FH_PROX_##k)
+#define LOSSBIT(k) (1u << (k))
+static const unsigned KINDS_ELEM = KIND(IDENTITY) | KIND(SHRINK) | KIND(NONNEG) | KIND(BOX), KINDS_LEVEL = KIND(LINF) | KIND(L1BALL);
+static const unsigned KINDS_ALL = (KIND(NUCBALL) << 1) - 1u;
+static const unsigned LOSSES_ELEM = LOSSBIT(LOSS_LSQ) | LOSSBIT(LOSS_LOGISTIC), LOSSES_MC = LOSSBIT(LOSS_LSQ) | LOSSBIT(LOSS_SOFTMAX);
+static const unsigned LOSSES_SET = LOSSES_ELEM | LOSSES_MC;      // what fh_set_loss_* can give at all (the quadratic and the bilinear form bring their own)
+static const char kNoProxMc[] = "prox kind %d (LINF / L1BALL / TVBALL) has no multi-column form";
+static const char kLsqOnly[] = "the %s serves the least-squares loss only (the logistic loss is implemented for the dense and sparse operators)";
+static const char kNoLogisticMc[] = "the logistic loss has no multi-column form (fh_set_rhs / fh_set_matrix_csr_rhs)";
+static const char kMcLsqOnly[] = "the multi-column form serves the least-squares loss only";
+static const char kSoftmaxOps[] = "fh_set_loss_softmax: the softmax loss is implemented for the dense and the sparse operator in multi-column form only "
+                                  "(fh_set_matrix + fh_set_rhs, or fh_set_matrix_csr_rhs), not for the stencil, DCT, convolution, identity, quadratic or bilinear operators";
+static const char kSoftmaxMc[] = "fh_set_loss_softmax: the softmax loss needs the multi-column form, one column of the unknown per class: call fh_set_rhs (dense operator) "
+                                 "or fh_set_matrix_csr_rhs (sparse operator) with L >= 2 first (two classes on a vector unknown: fh_set_loss_logistic)";
+static const char kRhsSparse[] = "fh_set_rhs: the sparse operator has no multi-column form through fh_set_rhs: its column count is fixed when it is set (fh_set_matrix_csr_rhs)";
+static const char kRhsNone[] = "fh_set_rhs: the %s has no multi-column form";
+static const char kF32NoMatrix[] = "%s: float32 storage is a storage mode of a dense matrix; the %s stores no matrix and computes in float64";
+static const char kF32HasNo[] = "%s: float32 storage has no %s";
+static const OpForm kForms[F_COUNT] = {
+  // F_NONE: what an empty context may hold for the operator to come (free_operator drops every other kind)
+  {"operator", KINDS_ELEM | KINDS_LEVEL | KIND(TVBALL) | KIND(GROUP), 0, 0, false, false, nullptr, nullptr, "set the operator before the loss", nullptr, nullptr,
+   "fh_set_rhs: set the dense operator first (fh_set_matrix / fh_generate_matrix)", nullptr},
+  // F_DENSE: accepts the TV-ball kind and refuses it at launch; its launch refuses nothing else
+  {"dense operator", KINDS_ELEM | KINDS_LEVEL | KIND(TVBALL), KINDS_ALL & ~KIND(TVBALL), LOSSES_ELEM, false, false, nullptr, "TV-ball prox needs the stencil operator", nullptr, nullptr,
+   kSoftmaxMc, nullptr, nullptr},
+  {"dense operator", KINDS_ELEM | KIND(GROUP), 0, LOSSES_MC, false, false, kNoProxMc, "prox kind %d has no multi-column form", kNoLogisticMc, kMcLsqOnly, nullptr, nullptr, nullptr},
+  // F_STENCIL: accepts what the dense form accepts, runs the TV-ball prox or none
+  {"stencil operator", KINDS_ELEM | KINDS_LEVEL | KIND(TVBALL), KIND(IDENTITY) | KIND(TVBALL), LOSSBIT(LOSS_LSQ), false, false, nullptr,
+   "the stencil operator supports the TV-ball prox or no prox (got kind %d)", "the logistic loss is implemented for the dense operator", nullptr, kSoftmaxOps, kRhsNone, nullptr},
+  {"sparse operator", KINDS_ELEM, 0, LOSSES_ELEM, false, false, "prox kind %d (LINF / L1BALL / TVBALL / GROUP) is not implemented for the %s", nullptr, nullptr, nullptr, kSoftmaxMc, kRhsSparse,
+   "%s: float32 storage is not implemented for the %s"},
+  {"sparse operator", KINDS_ELEM | KIND(GROUP), 0, LOSSES_MC, false, false, kNoProxMc, "prox kind %d has no multi-column form", kNoLogisticMc, kMcLsqOnly, nullptr, kRhsSparse,
+   "%s: float32 storage is not implemented for the %s"},
+  {"3-D stencil operator", KINDS_ELEM | KIND(TVBALL), 0, LOSSBIT(LOSS_LSQ), false, false, "prox kind %d (LINF / L1BALL / GROUP) is not implemented for the %s", nullptr, kLsqOnly, nullptr, kSoftmaxOps,
+   kRhsNone, nullptr},
+  {"quadratic operator", KINDS_ELEM | KIND(GROUP) | KIND(ROWBALL), 0, 0, false, false, "prox kind %d (LINF / L1BALL / TVBALL) has no quadratic form", nullptr,
+   "the quadratic operator carries its own loss (Q and the linear term of fh_set_quadratic): fh_set_loss_lsq / fh_set_loss_logistic do not apply", nullptr, kSoftmaxOps,
+   "fh_set_rhs: the column count of a quadratic operator is fixed when it is set (fh_set_quadratic)", kF32HasNo},
+  {"bilinear operator", KINDS_ELEM | KIND(ROWSPLIT), 0, 0, false, true, "prox kind %d (LINF / L1BALL / TVBALL / GROUP / ROWBALL) has no bilinear form", nullptr,
+   "the bilinear operator carries its own loss (S of fh_set_factorization): fh_set_loss_lsq / fh_set_loss_logistic do not apply", nullptr, kSoftmaxOps,
+   "fh_set_rhs: the column count of a bilinear operator is fixed when it is set (fh_set_factorization)", kF32HasNo},
+  {"DCT operator", KINDS_ELEM | KINDS_LEVEL, 0, LOSSBIT(LOSS_LSQ), false, false, "prox kind %d (TVBALL / GROUP) is not implemented for the %s", nullptr, kLsqOnly, nullptr, kSoftmaxOps, kRhsNone, kF32NoMatrix},
+  {"identity operator", KINDS_ELEM | KIND(NUCLEAR) | KIND(NUCBALL), 0, LOSSES_ELEM, true, true, "prox kind %d (LINF / L1BALL / TVBALL / GROUP / ROWBALL) is not implemented for the %s",
+   "prox kind %d (LINF / L1BALL / TVBALL / GROUP / ROWBALL / ROWSPLIT) is not implemented for the %s", nullptr, nullptr, kSoftmaxOps,
+   "fh_set_rhs: the %s has no multi-column form (its unknown is already an (M, N) matrix: fh_set_identity)", kF32NoMatrix},
+  {"convolution operator", KINDS_ELEM | KINDS_LEVEL, 0, LOSSBIT(LOSS_LSQ), false, false, "prox kind %d (TVBALL / GROUP) is not implemented for the %s", nullptr, kLsqOnly, nullptr, kSoftmaxOps, kRhsNone, kF32NoMatrix},
+};
+#undef KIND
+#undef LOSSBIT
+static inline const OpForm& form_of(const fh_ctx* c) {
+  static const int of_op[] = {F_NONE, F_DENSE, F_STENCIL, F_SPARSE, F_STENCIL3D, F_QUAD, F_BILINEAR, F_DCT, F_IDENTITY, F_CONV};      // by OP_*
+  const int f = of_op[c->op];
+  return kForms[c->LB && (f == F_DENSE || f == F_SPARSE) ? f + 1 : f];
+}
+static inline bool serves_prox(const OpForm& f, int kind) { return kind >= 0 && kind < 32 && (f.prox >> kind & 1u); }
+static inline bool runs_prox(const OpForm& f, int kind) { return kind >= 0 && kind < 32 && ((f.prox_run ? f.prox_run : f.prox) >> kind & 1u); }
+static inline bool takes_loss(const OpForm& f, int loss) { return loss >= 0 && loss < 32 && (f.losses >> loss & 1u); }
+static int refuse_prox(int code, const char* who, const OpForm& f, int kind) {      // f.no_prox behind the entry point's name
+  char sentence[384];
+  snprintf(sentence, sizeof sentence, "%s%s", who, f.no_prox);
+  return fail(code, sentence, kind, f.noun);
+}
+// the launch-time backstops of launch_fwd_* / launch_adj_* (fh_host_launch.h): what set-up should never have let through
+static int check_prox_run(const fh_ctx* c) {
+  const OpForm& f = form_of(c);
+  return runs_prox(f, c->prox_kind) ? 0 : fail(FH_E_STATE, f.no_prox_run ? f.no_prox_run : f.no_prox, c->prox_kind, f.noun);
+}
+static int check_loss_run(const fh_ctx* c) {
+  const OpForm& f = form_of(c);
+  return takes_loss(f, c->loss_kind) ? 0 : fail(FH_E_STATE, f.no_loss_run ? f.no_loss_run : f.no_loss, f.noun);
+}
+// a context about to change its operator, or with none: the prox kinds and the loss its next operator cannot be assumed to serve go
+static inline void reset_unserved(fh_ctx* c, const OpForm& next) {
+  if (!serves_prox(next, c->prox_kind)) { c->prox_kind = FH_PROX_IDENTITY; c->mu = 0.0; }
+  if (!(LOSSES_SET >> c->loss_kind & 1u)) c->loss_kind = LOSS_LSQ;
+}
+
 static const int kCounterWords = 8192;
 enum { CNT_FWD = 0, CNT_ADJ_FIN = 1, CNT_AUX = 2, CNT_FUSED_BAR = 4, CNT_FUSED_ERR = 8, CNT_PROBE = 12, CNT_RUN_BAR = 14, CNT_ADJ_CC = 16,
        CNT_DIAG = kCounterWords - 8 };     // the last 8 words only ever grow: [0] level searches that fell back to one workgroup, [1] ... that found no level (fh_recovered_count)
@@ -316,6 +414,7 @@ static inline uint64_t round_up(uint64_t v, uint64_t q) { return (v + q - 1) / q
 // multi-column form: doubles per device row of a vector buffer, columns per host row (both 1 in the vector form)
 static inline uint64_t lb_of(const fh_ctx* c) { return c->LB ? c->LB : 1u; }
 static inline uint64_t l_of(const fh_ctx* c) { return c->LB ? c->L : 1u; }
+static inline uint32_t lb_for(uint32_t L) { return L <= 2 ? 2u : (L <= 4 ? 4u : (L <= 8 ? 8u : 16u)); }      // L columns are kept as LB in {2, 4, 8, 16}
 
 // device scratch that is released on every exit path (the HIP_TRY macros return early)
 struct DevBuf {
@@ -461,11 +560,7 @@ static void free_operator(fh_ctx* c) {
   fr(c->loss_w);
   free_vectors(c);
   c->L = c->LB = 0;                  // a new operator starts in the vector form
-  if (c->loss_kind == LOSS_QUAD) c->loss_kind = LOSS_LSQ;                                        // ... and leaves the quadratic form (fh_set_quadratic) behind:
-  if (c->prox_kind == FH_PROX_ROWBALL) { c->prox_kind = FH_PROX_IDENTITY; c->mu = 0.0; }      // its loss and the prox only it serves
-  if (c->loss_kind == LOSS_BILINEAR) c->loss_kind = LOSS_LSQ;                                    // ... and the bilinear form (fh_set_factorization) likewise
-  if (c->prox_kind == FH_PROX_ROWSPLIT) { c->prox_kind = FH_PROX_IDENTITY; c->mu = 0.0; }
-  if (c->prox_kind == FH_PROX_NUCLEAR || c->prox_kind == FH_PROX_NUCBALL) { c->prox_kind = FH_PROX_IDENTITY; c->mu = 0.0; }         // ... and the identity form's (fh_set_identity)
+  reset_unserved(c, kForms[F_NONE]);      // ... and leaves behind the loss a form brought with it and the prox kinds one form alone serves
   fr(c->bl_part); c->bl_part_bytes = 0; c->bl_have_grad = false; c->bl_m = c->bl_n = 0;
   fr(c->ws); c->ws_bytes = 0;
   fr(c->slotbuf); c->slotbuf_bytes = 0; c->slots_sig = 0;
@@ -478,7 +573,8 @@ static int alloc_zero(fh_ctx* c, double** p, uint64_t elems) {
   return 0;
 }
 
-static int alloc_vectors(fh_ctx* c) {
+// stencil_pair: with the 2-D stencil operator's two extra m-side buffers (the extrapolated image of its accelerated step)
+static int alloc_vectors(fh_ctx* c, bool stencil_pair = false) {
   const uint64_t nvl = c->nv * lb_of(c), mvl = c->mv * lb_of(c);
   // +16 slack doubles on the n-side so sharded runs can append scalars to the all-reduce buffer
   for (int i = 0; i < 2; ++i) {
@@ -492,7 +588,7 @@ static int alloc_vectors(fh_ctx* c) {
   for (int i = 0; i < 4; ++i) FH_TRY(alloc_zero(c, &c->T[i], nvl + 16));
   FH_TRY(alloc_zero(c, &c->b, mvl + 16));
   FH_TRY(alloc_zero(c, &c->zt, mvl + 16));
-  if (c->op_pending_stencil) { FH_TRY(alloc_zero(c, &c->ZX[0], mvl + 16)); FH_TRY(alloc_zero(c, &c->ZX[1], mvl + 16)); }
+  if (stencil_pair) { FH_TRY(alloc_zero(c, &c->ZX[0], mvl + 16)); FH_TRY(alloc_zero(c, &c->ZX[1], mvl + 16)); }
   c->pc = c->gc = c->zc = c->zxc = 0;
   c->xi = 0; c->ti = 1; c->bi = 0;
   c->zcur = nullptr;

@@ -56,7 +56,7 @@ static int launch_fwd_dense(fh_ctx* c, int mode, double tau, const double* x0, c
   // to keep as many bytes of A in flight (4 rows: 4.7 TB/s at 65536^2, profiles/r02_f32_storage.txt)
   int R = c->fwd_rows ? c->fwd_rows : (c->ld <= (c->f32 ? 16384u : 32768u) ? 4 : 8);
   if (c->f32 && R == 16) R = 8;
-  if (mode == 0 && c->prox_kind == FH_PROX_TVBALL) return fail(FH_E_STATE, "TV-ball prox needs the stencil operator");
+  if (mode == 0) FH_TRY(check_prox_run(c));
   FwdP p;
   p.A = c->A; p.ld = c->ld; p.ld2 = (uint32_t)(c->ld / (c->f32 ? 4 : 2)); p.nv2 = (uint32_t)(c->nv / 2); p.n = (uint32_t)c->n; p.m = (uint32_t)c->m;
   p.nrg = (uint32_t)(c->mp / R);
@@ -163,9 +163,6 @@ static const McEntry* mc_entry_lb(uint32_t LB) {
   return nullptr;
 }
 static const McEntry* mc_entry(const fh_ctx* c) { return mc_entry_lb(c->LB); }
-static inline bool mc_prox_ok(int kind) {
-  return kind == FH_PROX_IDENTITY || kind == FH_PROX_SHRINK || kind == FH_PROX_NONNEG || kind == FH_PROX_BOX || kind == FH_PROX_GROUP;
-}
 
 // THE GEOMETRY of both multi-column launches, stated once: a pure function of the device shape (mp rows of ld doubles, nv rows of X), the
 // columns per row LB and the three tuning values (FH_TUNE_ADJ_SLAB_ROWS, FH_TUNE_FWD_GRID_CAP, FH_TUNE_NT_LOADS as the context keeps them:
@@ -231,7 +228,7 @@ extern "C" int fh_multi_shape_for(uint64_t m, uint64_t n, uint32_t L, int slab_r
   if (slab_rows < 0 || slab_rows > ADJ_MAX_SLAB || slab_rows % 8) return fail(FH_E_ARG, "ADJ_SLAB_ROWS must be a multiple of 8 in [0,%d]", ADJ_MAX_SLAB);
   if (grid_cap < 0) return fail(FH_E_ARG, "FWD_GRID_CAP must be >= 0");
   if (nt_loads < -1 || nt_loads > 1) return fail(FH_E_ARG, "fh_multi_shape_for: nt_loads is -1 (auto), 0 or 1");
-  const uint32_t LB = L <= 2 ? 2u : (L <= 4 ? 4u : (L <= 8 ? 8u : 16u));
+  const uint32_t LB = lb_for(L);
   const uint64_t ld = round_up(n, 16);
   const McShape s = mc_shape_for(round_up(m, 16), ld, ld, LB, slab_rows, grid_cap, nt_loads);
   if (!s.e) return fail(FH_E_STATE, "multi-column form: no kernel for %u columns per row", LB);
@@ -267,7 +264,6 @@ static int launch_sm_rows(fh_ctx* c, const double* z, const double* zacc0, int a
   e->rows<<<dim3(sm_records(c)), dim3(FH_WG), 0, c->stream>>>(q);
   return 0;
 }
-static inline bool loss_has_multi_form(int kind) { return kind == LOSS_LSQ || kind == LOSS_SOFTMAX; }
 
 // Z := A * (mode 0: prox(X0 - tau G0), by the prologue launch ; mode 1: X0) for LB columns from one read of A
 static int launch_fwd_multi(fh_ctx* c, int mode, double tau, const double* x0, const double* g0, const double* xacc0,
@@ -275,8 +271,8 @@ static int launch_fwd_multi(fh_ctx* c, int mode, double tau, const double* x0, c
   const McShape sh = mc_shape(c);
   const McEntry* e = sh.e;
   if (!e) return fail(FH_E_STATE, "multi-column form: no kernel for %u columns per row", c->LB);
-  if (!loss_has_multi_form(c->loss_kind)) return fail(FH_E_STATE, "the multi-column form serves the least-squares loss only");
-  if (mode == 0 && !mc_prox_ok(c->prox_kind)) return fail(FH_E_STATE, "prox kind %d has no multi-column form", c->prox_kind);
+  FH_TRY(check_loss_run(c));
+  if (mode == 0) FH_TRY(check_prox_run(c));
   const bool sm = sm_on(c, sub_b);                // K-fwd's sum of squares means nothing then: the row pass behind it writes FH_S_FSQ and publishes
   McFwdP p;
   p.A = c->A; p.ld2 = sh.ld2; p.m = (uint32_t)c->m; p.L = c->L;
@@ -324,9 +320,6 @@ static const SpEntry* sp_entry(int g) {
   for (const SpEntry& e : kSpTable) if (e.g == g) return &e;
   return nullptr;
 }
-static inline bool sp_prox_ok(int kind) {
-  return kind == FH_PROX_IDENTITY || kind == FH_PROX_SHRINK || kind == FH_PROX_NONNEG || kind == FH_PROX_BOX;
-}
 // values and indices stream once and were the non-temporal candidates; measured (profiles/sparse_rows.txt), plain loads are as fast or faster at every
 // shape (65536^2: 0.1 % 0.129 against 0.147 ms per pair, 1 % 0.550 / 0.557, 5 % 2.063 / 2.162; 1048576^2, 16 per row: 0.522 / 0.523), so plain is the
 // default and FH_TUNE_NT_LOADS = 1 the opt-in
@@ -337,8 +330,7 @@ static int launch_fwd_sparse(fh_ctx* c, int mode, double tau, const double* x0, 
                              double* xhat, double* xp, double* z, int sub_b) {
   const SpEntry* e = sp_entry(c->sp_G[0]);
   if (!e) return fail(FH_E_STATE, "sparse operator: no kernel for %d lanes per row", c->sp_G[0]);
-  if (mode == 0 && !sp_prox_ok(c->prox_kind))
-    return fail(FH_E_STATE, "prox kind %d (LINF / L1BALL / TVBALL / GROUP) is not implemented for the sparse operator", c->prox_kind);
+  if (mode == 0) FH_TRY(check_prox_run(c));
   SpFwdP p;
   p.a = c->sp[0]; p.m = (uint32_t)c->m;
   const uint32_t npro = mode == 0 ? (uint32_t)((c->n + FH_WG - 1) / FH_WG) : 0u;
@@ -387,7 +379,7 @@ static int launch_adj_multi(fh_ctx* c, const AdjIO& io) {
   const McShape sh = mc_shape(c);
   const McEntry* e = sh.e;
   if (!e) return fail(FH_E_STATE, "multi-column form: no kernel for %u columns per row", c->LB);
-  if (io.sub_b && !loss_has_multi_form(c->loss_kind)) return fail(FH_E_STATE, "the multi-column form serves the least-squares loss only");
+  if (io.sub_b) FH_TRY(check_loss_run(c));
   if (io.mode != 0 && io.mode != 1) return fail(FH_E_STATE, "the multi-column form has no row-sharded adjoint");
   const bool sm = sm_on(c, io.sub_b);
   if (sm && !c->sp_r) return fail(FH_E_STATE, "softmax loss: the residual buffer is missing (call fh_set_loss_softmax after fh_set_rhs)");
@@ -442,7 +434,6 @@ static const QdEntry* qd_entry_lb(uint32_t LB) {
   for (const QdEntry& e : kQdTable) if ((uint32_t)e.lb == LB) return &e;
   return nullptr;
 }
-static inline bool qd_prox_ok(int kind) { return mc_prox_ok(kind) || kind == FH_PROX_ROWBALL; }
 
 // THE GEOMETRY of the quadratic launches, stated once: a pure function of the device shape (mp rows of ld doubles, nv rows of X), the columns per
 // row LB and the tuning values FH_TUNE_FWD_GRID_CAP and FH_TUNE_NT_LOADS as the context keeps them (0 / -1 = auto).  Both launchers take every
@@ -496,7 +487,7 @@ extern "C" int fh_quad_shape_for(uint64_t n, uint32_t L, long long grid_cap, int
   if (L < 1 || L > 16) return fail(FH_E_ARG, "fh_quad_shape_for: 1 to 16 columns (got %u)", L);
   if (grid_cap < 0) return fail(FH_E_ARG, "FWD_GRID_CAP must be >= 0");
   if (nt_loads < -1 || nt_loads > 1) return fail(FH_E_ARG, "fh_quad_shape_for: nt_loads is -1 (auto), 0 or 1");
-  const uint32_t LB = L <= 2 ? 2u : (L <= 4 ? 4u : (L <= 8 ? 8u : 16u));
+  const uint32_t LB = lb_for(L);
   const uint64_t ld = round_up(n, 16);
   const QdShape s = qd_shape_for(ld, ld, ld, LB, grid_cap, nt_loads);
   if (!s.e) return fail(FH_E_STATE, "quadratic operator: no kernel for %u columns per row", LB);
@@ -511,7 +502,7 @@ static int launch_fwd_quad(fh_ctx* c, int mode, double tau, const double* x0, co
   const QdEntry* e = sh.e;
   const McEntry* me = mc_entry_lb(c->LB);               // (k_mc_pack lays a plain operand out for the streaming loop)
   if (!e || !me) return fail(FH_E_STATE, "quadratic operator: no kernel for %u columns per row", c->LB);
-  if (mode == 0 && !qd_prox_ok(c->prox_kind)) return fail(FH_E_STATE, "prox kind %d (LINF / L1BALL / TVBALL) has no quadratic form", c->prox_kind);
+  if (mode == 0) FH_TRY(check_prox_run(c));
   QdFwdP p;
   p.Q = c->A; p.ld2 = sh.ld2; p.n = (uint32_t)c->n; p.L = c->L;
   p.nrg = sh.nrg;
@@ -583,7 +574,6 @@ static const BlEntry* bl_entry_lb(uint32_t LB) {
   for (const BlEntry& e : kBlTable) if ((uint32_t)e.lb == LB) return &e;
   return nullptr;
 }
-static inline bool bl_prox_ok(int kind) { return kind == FH_PROX_IDENTITY || kind == FH_PROX_SHRINK || kind == FH_PROX_NONNEG || kind == FH_PROX_BOX || kind == FH_PROX_ROWSPLIT; }
 
 // THE GEOMETRY of the bilinear launches, stated once: a pure function of S's shape (m, n; device rows of ld doubles), the columns per row LB and
 // the tuning values FH_TUNE_FWD_GRID_CAP and FH_TUNE_NT_LOADS (0 / -1 = auto).  A work item of the pass is a row panel of PR rows x a column tile of
@@ -636,7 +626,6 @@ static const char* bl_too_large(uint64_t m, uint64_t n, const BlShape& s) {
   if (s.px_bytes >= (1ull << 32) || s.py_bytes >= (1ull << 32)) return "a partial buffer (column tiles * m * LB or row panels * n * LB doubles) would reach 4 GiB";
   return nullptr;
 }
-static inline uint32_t lb_for(uint32_t L) { return L <= 2 ? 2u : (L <= 4 ? 4u : (L <= 8 ? 8u : 16u)); }
 // read-only: the geometry the next fh_fwd / fh_adj of this context launches with
 extern "C" int fh_bilinear_shape(fh_ctx* c, uint32_t* out) {
   if (!c || !out) return fail(FH_E_ARG, "fh_bilinear_shape: null argument");
@@ -709,7 +698,7 @@ static int launch_fwd_bilinear(fh_ctx* c, int mode, double tau, const double* x0
   (void)z;
   const BlShape sh = bl_shape(c);
   if (!sh.e) return fail(FH_E_STATE, "bilinear operator: no kernel for %u columns per row", c->LB);
-  if (mode == 0 && !bl_prox_ok(c->prox_kind)) return fail(FH_E_STATE, "prox kind %d (LINF / L1BALL / TVBALL / GROUP / ROWBALL) has no bilinear form", c->prox_kind);
+  if (mode == 0) FH_TRY(check_prox_run(c));
   if (!with_f) return fail(FH_E_STATE, "the bilinear operator has no linear map to apply");
   const uint32_t npro = mode == 0 ? sh.nelem : 0u;
   FH_TRY(ensure_ws(c, ((size_t)npro * 8 + sh.grid) * sizeof(double)));
@@ -832,8 +821,8 @@ static int launch_fwd_spmulti(fh_ctx* c, int mode, double tau, const double* x0,
   const SpmcEntry* e = spmc_entry(c, 0);
   const SpmcLbEntry* lbe = spmc_lb_entry(c);
   if (!e || !lbe) return fail(FH_E_STATE, "sparse multi-column form: no kernel for %d lanes per row at %u columns per row", c->sp_G[0], c->LB);
-  if (!loss_has_multi_form(c->loss_kind)) return fail(FH_E_STATE, "the multi-column form serves the least-squares loss only");
-  if (mode == 0 && !mc_prox_ok(c->prox_kind)) return fail(FH_E_STATE, "prox kind %d has no multi-column form", c->prox_kind);
+  FH_TRY(check_loss_run(c));
+  if (mode == 0) FH_TRY(check_prox_run(c));
   const bool sm = sm_on(c, sub_b);                // as launch_fwd_multi: the row pass behind K-fwd writes FH_S_FSQ and publishes
   SpmcFwdP p;
   p.a = c->sp[0]; p.m = (uint32_t)c->m; p.L = c->L;
@@ -868,7 +857,7 @@ static int launch_adj_spmulti(fh_ctx* c, const AdjIO& io) {
   const SpmcEntry* e = spmc_entry(c, 1);
   const SpmcLbEntry* lbe = spmc_lb_entry(c);
   if (!e || !lbe) return fail(FH_E_STATE, "sparse multi-column form: no kernel for %d lanes per row at %u columns per row", c->sp_G[1], c->LB);
-  if (io.sub_b && !loss_has_multi_form(c->loss_kind)) return fail(FH_E_STATE, "the multi-column form serves the least-squares loss only");
+  if (io.sub_b) FH_TRY(check_loss_run(c));
   if (io.mode != 0 && io.mode != 1) return fail(FH_E_STATE, "the sparse operator has no row-sharded adjoint");
   SpmcAdjP p;
   p.a = c->sp[1]; p.n = (uint32_t)c->n; p.L = c->L;
@@ -925,7 +914,6 @@ static int tv3_shape_for(uint64_t D, uint64_t H, uint64_t W, int planes_tune, in
   sh->grid = (uint32_t)(tiles * chunks);
   return 0;
 }
-static inline bool tv3_prox_ok(int kind) { return sp_prox_ok(kind) || kind == FH_PROX_TVBALL; }
 // plain stores are the default: the non-temporal ones measure within 1.4 % of them from 256^3 on; FH_TUNE_NT_LOADS = 1 opts in
 static inline int tv3_nt_for(const fh_ctx* c) { return c->nt_loads > 0 ? 1 : 0; }
 static void tv3_shape_out(const Tv3Shape& sh, int nt, uint32_t* out) {
@@ -950,9 +938,8 @@ extern "C" int fh_tv3d_shape_for(uint64_t D, uint64_t H, uint64_t W, int planes,
 // z := div(mode 0: prox(x0 - tau g0) ; mode 1: x0), ONE launch
 static int launch_fwd_tv3(fh_ctx* c, int mode, double tau, const double* x0, const double* g0, const double* xacc0,
                           double* xhat, double* xp, double* z, int sub_b) {
-  if (c->loss_kind != LOSS_LSQ) return fail(FH_E_STATE, "the 3-D stencil operator serves the least-squares loss only (the logistic loss is implemented for the dense and sparse operators)");
-  if (mode == 0 && !tv3_prox_ok(c->prox_kind))
-    return fail(FH_E_STATE, "prox kind %d (LINF / L1BALL / GROUP) is not implemented for the 3-D stencil operator", c->prox_kind);
+  FH_TRY(check_loss_run(c));
+  if (mode == 0) FH_TRY(check_prox_run(c));
   Tv3Shape sh;
   FH_TRY(tv3_shape_for(c->D, c->H, c->W, c->tv3_planes, c->ncu, &sh));
   Tv3FwdP p;
@@ -974,7 +961,7 @@ static int launch_fwd_tv3(fh_ctx* c, int mode, double tau, const double* x0, con
 
 // g1 := grad(z' - b) with the residual, the loss at z' and the n-side epilogue in the same launch
 static int launch_adj_tv3(fh_ctx* c, const AdjIO& io) {
-  if (c->loss_kind != LOSS_LSQ) return fail(FH_E_STATE, "the 3-D stencil operator serves the least-squares loss only (the logistic loss is implemented for the dense and sparse operators)");
+  FH_TRY(check_loss_run(c));
   if (io.mode != 0 && io.mode != 1) return fail(FH_E_STATE, "the 3-D stencil operator has no row-sharded adjoint");
   Tv3Shape sh;
   FH_TRY(tv3_shape_for(c->D, c->H, c->W, c->tv3_planes, c->ncu, &sh));
@@ -1019,7 +1006,6 @@ static int conv_shape_for(uint64_t H, uint64_t W, uint32_t kh, uint32_t kw, int 
   sh->lds_bytes = CONV_LDS_DOUBLES * (uint32_t)sizeof(double);
   return 0;
 }
-static inline bool conv_prox_ok(int kind) { return sp_prox_ok(kind) || kind == FH_PROX_LINF || kind == FH_PROX_L1BALL; }
 static void conv_shape_out(const ConvShape& sh, uint32_t* out) {
   out[0] = sh.th; out[1] = sh.tw; out[2] = sh.tiles_h; out[3] = sh.tiles_w; out[4] = sh.grid; out[5] = CONV_RUN; out[6] = FH_WG; out[7] = sh.lds_bytes;
 }
@@ -1052,9 +1038,8 @@ static ConvGeo conv_geo(const fh_ctx* c) {
 // z := d * (K conv (mode 0: prox(x0 - tau g0) ; mode 1: x0)), ONE launch
 static int launch_fwd_conv(fh_ctx* c, int mode, double tau, const double* x0, const double* g0, const double* xacc0,
                            double* xhat, double* xp, double* z, int sub_b) {
-  if (c->loss_kind != LOSS_LSQ) return fail(FH_E_STATE, "the convolution operator serves the least-squares loss only (the logistic loss is implemented for the dense and sparse operators)");
-  if (mode == 0 && !conv_prox_ok(c->prox_kind))
-    return fail(FH_E_STATE, "prox kind %d (TVBALL / GROUP) is not implemented for the convolution operator", c->prox_kind);
+  FH_TRY(check_loss_run(c));
+  if (mode == 0) FH_TRY(check_prox_run(c));
   const ConvShape& sh = c->conv_sh;
   ConvFwdP p;
   p.g = conv_geo(c);
@@ -1075,7 +1060,7 @@ static int launch_fwd_conv(fh_ctx* c, int mode, double tau, const double* x0, co
 
 // g1 := K corr (d * (z' - b)) with the residual, the loss at z' and the n-side epilogue in the same launch
 static int launch_adj_conv(fh_ctx* c, const AdjIO& io) {
-  if (c->loss_kind != LOSS_LSQ) return fail(FH_E_STATE, "the convolution operator serves the least-squares loss only (the logistic loss is implemented for the dense and sparse operators)");
+  FH_TRY(check_loss_run(c));
   if (io.mode != 0 && io.mode != 1) return fail(FH_E_STATE, "the convolution operator has no row-sharded adjoint");
   const ConvShape& sh = c->conv_sh;
   ConvAdjP p;
@@ -1151,7 +1136,6 @@ static int dct_shape_for(uint64_t N, int row_cap, int ncu, DctShape* sh) {
   sh->lds_bytes = std::max(sh->ldsn1, sh->ldsn2) * 2u * (uint32_t)sizeof(d2);
   return 0;
 }
-static inline bool dct_prox_ok(int kind) { return sp_prox_ok(kind) || kind == FH_PROX_LINF || kind == FH_PROX_L1BALL; }
 static void dct_shape_out(const DctShape& sh, uint32_t* out) {
   memset(out, 0, FH_DCT_SHAPE_LEN * sizeof(uint32_t));
   out[0] = sh.levels; out[1] = sh.N1; out[2] = sh.N2; out[3] = sh.cap;
@@ -1385,9 +1369,8 @@ static int launch_adj_dct2(fh_ctx* c, const AdjIO& io) {
 // z := d * C (mode 0: prox(x0 - tau g0) ; mode 1: x0): one launch (N <= row cap) or five
 static int launch_fwd_dct(fh_ctx* c, int mode, double tau, const double* x0, const double* g0, const double* xacc0,
                           double* xhat, double* xp, double* z, int sub_b) {
-  if (c->loss_kind != LOSS_LSQ) return fail(FH_E_STATE, "the DCT operator serves the least-squares loss only (the logistic loss is implemented for the dense and sparse operators)");
-  if (mode == 0 && !dct_prox_ok(c->prox_kind))
-    return fail(FH_E_STATE, "prox kind %d (TVBALL / GROUP) is not implemented for the DCT operator", c->prox_kind);
+  FH_TRY(check_loss_run(c));
+  if (mode == 0) FH_TRY(check_prox_run(c));
   if (c->dct2) return launch_fwd_dct2(c, mode, tau, x0, g0, xacc0, xhat, xp, z, sub_b);
   const DctShape& sh = c->dct_sh;
   DctFwdP p;
@@ -1420,7 +1403,7 @@ static int launch_fwd_dct(fh_ctx* c, int mode, double tau, const double* x0, con
 
 // g1 := C^T (d * (z' - b)) with the residual, the loss at z' and the n-side epilogue: one launch (N <= row cap) or five
 static int launch_adj_dct(fh_ctx* c, const AdjIO& io) {
-  if (c->loss_kind != LOSS_LSQ) return fail(FH_E_STATE, "the DCT operator serves the least-squares loss only (the logistic loss is implemented for the dense and sparse operators)");
+  FH_TRY(check_loss_run(c));
   if (io.mode != 0 && io.mode != 1) return fail(FH_E_STATE, "the DCT operator has no row-sharded adjoint");
   if (c->dct2) return launch_adj_dct2(c, io);
   const DctShape& sh = c->dct_sh;
@@ -1457,7 +1440,6 @@ static int launch_adj_dct(fh_ctx* c, const AdjIO& io) {
 NUC_KERNELS(extern template)
 #endif
 static inline bool nuc_kind(int kind) { return kind == FH_PROX_NUCLEAR || kind == FH_PROX_NUCBALL; }      // the two kinds behind the Jacobi decomposition
-static inline bool id_prox_ok(int kind) { return sp_prox_ok(kind) || nuc_kind(kind); }
 // THE geometry of the thresholding, a pure function of (M, N) and FH_TUNE_NUC_BLOCK_ROWS (0 = auto = NUC_AUTO_BLOCK_ROWS): p = min, q = max, P = p padded to a multiple of
 // Bk, nb = P / Bk blocks, a sweep of nb - 1 steps (nb even; nb for an odd nb, whose steps each give one block a bye; 1 for nb = 1: the self-pair) of
 // ceil(nb / 2) workgroups, rows of [ W | J^T ] of ld = (q padded to even) + (P padded to even) doubles.
@@ -1599,7 +1581,7 @@ static int nuc_norm(fh_ctx* c, const double* x, double* out_gsum, double* out_gm
 // z := prox(x0 - tau g0) (mode 0) or x0 (mode 1), the loss sum and the n-side sums: one elementwise launch (behind the thresholding for FH_PROX_NUCLEAR)
 static int launch_fwd_identity(fh_ctx* c, int mode, double tau, const double* x0, const double* g0, const double* xacc0,
                                double* xhat, double* xp, double* z, int sub_b) {
-  if (mode == 0 && !id_prox_ok(c->prox_kind)) return fail(FH_E_STATE, "prox kind %d (LINF / L1BALL / TVBALL / GROUP / ROWBALL / ROWSPLIT) is not implemented for the identity operator", c->prox_kind);
+  if (mode == 0) FH_TRY(check_prox_run(c));
   const bool nuc = mode == 0 && nuc_kind(c->prox_kind);
   if (nuc) FH_TRY(nuc_prox(c, tau, x0, g0, xhat, xp));
   IdFwdP p;
@@ -1704,8 +1686,7 @@ static int launch_level_search(fh_ctx* c, double tau) {
 static int launch_fwd_tv(fh_ctx* c, int mode, double tau, const double* x0, const double* g0, const double* xacc0,
                          double* xhat, double* xp, double* z, int sub_b) {
   (void)xhat; (void)g0;   // the stencil path materialises neither xhat nor the gradient (fh_tv.h)
-  if (mode == 0 && c->prox_kind != FH_PROX_TVBALL && c->prox_kind != FH_PROX_IDENTITY)
-    return fail(FH_E_STATE, "the stencil operator supports the TV-ball prox or no prox (got kind %d)", c->prox_kind);
+  if (mode == 0) FH_TRY(check_prox_run(c));
   const uint32_t H = (uint32_t)c->H, W = (uint32_t)c->W;
   const uint32_t rows_wg = (uint32_t)(c->tv_rows > 0 ? c->tv_rows : 32);
   const uint32_t row_chunks = (H + rows_wg - 1) / rows_wg;
@@ -2219,8 +2200,7 @@ static int solver_fwd_local(fh_ctx* c, double tau, const char* who) {
 // ---- stencil one-pass launchers ---------------------------------------------------------------------------------------------
 #ifdef FH_EXPERIMENTAL      // the round-1 one-pass stencil kernels that stream z (FH_TUNE_TV_ZFREE = 0, csrc/fh_experimental.h)
 static int launch_fused_tv(fh_ctx* c, double tau) {
-  if (c->prox_kind != FH_PROX_TVBALL && c->prox_kind != FH_PROX_IDENTITY)
-    return fail(FH_E_STATE, "the stencil operator supports the TV-ball prox or no prox (got kind %d)", c->prox_kind);
+  FH_TRY(check_prox_run(c));
   if (!c->zcur) return fail(FH_E_STATE, "fh_step on the stencil operator before fh_init");
   TvStepFwdP p;
   p.H = (uint32_t)c->H; p.W = (uint32_t)c->W;
@@ -2246,8 +2226,7 @@ static int launch_fused_tv(fh_ctx* c, double tau) {
 }
 
 static int launch_fused_tv_accel(fh_ctx* c, double tau, double coef, int restart) {
-  if (c->prox_kind != FH_PROX_TVBALL && c->prox_kind != FH_PROX_IDENTITY)
-    return fail(FH_E_STATE, "the stencil operator supports the TV-ball prox or no prox (got kind %d)", c->prox_kind);
+  FH_TRY(check_prox_run(c));
   TvAccelP p;
   p.H = (uint32_t)c->H; p.W = (uint32_t)c->W;
   p.rows_wg = (uint32_t)(c->tv_rows > 0 ? c->tv_rows : 32);
@@ -2276,8 +2255,7 @@ static int launch_fused_tv_accel(fh_ctx* c, double tau, double coef, int restart
 
 // z-free one-pass stencil step (k_tv_onepass): accel = 0 -> x0 = X[xi]; accel = 1 -> the lazily-kept (P1, P0, c) state
 static int launch_tv_onepass(fh_ctx* c, double tau, int accel, double coef, int restart) {
-  if (c->prox_kind != FH_PROX_TVBALL && c->prox_kind != FH_PROX_IDENTITY)
-    return fail(FH_E_STATE, "the stencil operator supports the TV-ball prox or no prox (got kind %d)", c->prox_kind);
+  FH_TRY(check_prox_run(c));
   TvZP p;
   p.H = (uint32_t)c->H; p.W = (uint32_t)c->W;
   p.strip_groups = ((p.W + TVZ_OWN - 1) / TVZ_OWN + 3) / 4;
