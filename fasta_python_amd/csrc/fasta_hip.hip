@@ -27,6 +27,7 @@
 #include "fh_dct.h"
 #include "fh_dct2.h"
 #include "fh_conv.h"
+#include "fh_gap.h"
 #include "fh_nuclear.h"
 #include "fh_prox.h"
 #include "fh_fused.h"
@@ -142,6 +143,9 @@ DCT_FOR_EACH(DCT2_INSTANTIATE)
 #undef DCT2_INSTANTIATE
 DCT2_TILE_KERNELS(template)
 CONV_KERNELS(template)
+GAP_KERNELS(template)
+#else
+GAP_KERNELS(extern template)
 #endif
 
 #include "fh_host_ctx.h"
@@ -454,7 +458,7 @@ static int set_begin(fh_ctx* c, const OpForm* next, int flags = 0) {
   if (!(flags & SET_DROPS_WEIGHTS)) FH_TRY(refuse_weighted(c));
   free_operator(c);                                      // (back to the vector form: L = LB = 0)
   if (next) reset_unserved(c, *next);
-  if (!(flags & SET_KEEPS_SOLVER_STATE)) { c->loss_kind = LOSS_LSQ; c->lazy = false; c->last_accel = false; c->commits = 0; }
+  if (!(flags & SET_KEEPS_SOLVER_STATE)) { c->loss_kind = LOSS_LSQ; c->lazy = false; c->last_accel = false; c->commits = 0; c->at_state = false; }
   return 0;
 }
 static void vector_geometry(fh_ctx* c, uint64_t m, uint64_t n) {
@@ -905,7 +909,7 @@ extern "C" int fh_set_rhs(fh_ctx* c, uint32_t L) {
   free_vectors(c);
   c->L = L; c->LB = LB;
   c->has_b = false; c->loss_kind = LOSS_LSQ;
-  c->lazy = false; c->last_accel = false; c->commits = 0;
+  c->lazy = false; c->last_accel = false; c->commits = 0; c->at_state = false;
   if (!L) reset_unserved(c, next);                       // (the row-wise shrink has no vector form)
   FH_TRY(alloc_vectors(c));
   return finish(c);
@@ -1018,6 +1022,7 @@ static int set_loss(fh_ctx* c, int kind, const double* b, uint64_t len) {
   FH_TRY(copy_in(c, c->b, b, c->m));
   c->has_b = true;
   c->loss_kind = kind;
+  c->at_state = false;
   return finish(c);
 }
 
@@ -1074,6 +1079,7 @@ extern "C" int fh_set_loss_softmax(fh_ctx* c, const int32_t* labels, uint64_t m)
   FH_TRY(copy_in(c, c->b, onehot.data(), c->m));
   c->has_b = true;
   c->loss_kind = LOSS_SOFTMAX;
+  c->at_state = false;
   return finish(c);
 }
 
@@ -1111,6 +1117,7 @@ extern "C" int fh_set_vector(fh_ctx* c, int which, const double* host, uint64_t 
     return 0;
   }
   if (which == FH_VEC_X0) c->lazy = false;          // a new start: fh_init follows
+  if (which == FH_VEC_X0 || which == FH_VEC_G0 || which == FH_VEC_B) c->at_state = false;
   uint64_t want = 0;
   double* d = vec_ptr(c, which, &want);
   if (!d) return fail(FH_E_ARG, "unknown vector id %d", which);
@@ -1181,6 +1188,7 @@ extern "C" int fh_init(fh_ctx* c, double* scalars) {
     s->bi = s->xi;                         // best iterate := x0 (fasta/__init__.py:167), by reference
     for (int q = 0; q < 3; ++q) if (q != s->xi) { s->ti = q; break; }
     s->last_accel = false;
+    s->at_state = true;
     FH_TRY(launch_gterms(s, x0));
   }
   return fetch_scalars(c, scalars);
@@ -1421,7 +1429,7 @@ extern "C" int fh_setup(fh_ctx* c, double* scalars) {
       c->last_accel = false;
       FH_TRY(launch_gterms(c, x0));
       FH_TRY(fetch_scalars(c, scalars));
-      if (scalars[15] == 0.0) return 0;
+      if (scalars[15] == 0.0) { c->at_state = true; return 0; }
       c->slots_sig = 0;                   // a hand-off timed out (results invalid): the three passes below redo everything
     }
   }
@@ -1445,6 +1453,7 @@ extern "C" int fh_gradient_at(fh_ctx* c, int src_vec, int dst_vec) {
     double* src = vec_ptr(s, src_vec, &l1);
     double* dst = vec_ptr(s, dst_vec, &l2);
     if (!src || !dst || l1 != s->n * l_of(s) || l2 != l1 || m_side(src_vec) || m_side(dst_vec)) return fail(FH_E_ARG, "fh_gradient_at needs two n-length vectors");
+    if (dst_vec == FH_VEC_X0 || dst_vec == FH_VEC_G0) s->at_state = false;      // (written from outside the loop: g0 no longer belongs to x0)
     if (plain_pair_fused_ok(s)) {
       bool ok = false;
       FH_TRY(plain_pair_fused(s, src, s->zt, dst, &ok));
@@ -1491,6 +1500,56 @@ extern "C" int fh_diff_norm(fh_ctx* c, int vec_a, int vec_b, double* out) {
   FH_TRY(diff_norm_sq(c, vec_a, vec_b, &sumsq));
   *out = sqrt(sumsq);
   return 0;
+}
+
+// ---- the duality-gap certificate of the committed iterate (kernels in csrc/fh_gap.h, instantiated by fh_gap_part.hip) ---------------------
+// THE launch geometry of one side: at most 256 slabs of whole rows, a slab a multiple of 64 rows (so the last slabs of a long vector may be empty)
+static void gap_slabs(uint64_t rows, uint32_t* nwg, uint64_t* slab) {
+  const uint64_t k = std::min<uint64_t>(std::max<uint64_t>((rows + FH_WG - 1) / FH_WG, 1), 256);
+  *nwg = (uint32_t)k;
+  *slab = round_up((rows + k - 1) / k, 64);
+}
+extern "C" int fh_dual_gap(fh_ctx* c, double* out) {
+  if (!c || !out) return fail(FH_E_ARG, "fh_dual_gap: null argument");
+  if (c->pending_step) return fail(FH_E_ARG, "fh_dual_gap: a step issued by fh_step_begin is still in flight on this context: call fh_step_end first");
+  if (!c->shards.empty() || c->owner || c->comm)
+    return fail(FH_E_ARG, "fh_dual_gap: a multi-device context or a context with a communicator holds a row block of z = A x0, not z: the certificate is served on a plain context");
+  if (c->loss_w) return fail(FH_E_ARG, "fh_dual_gap: a context that holds observation weights has no duality-gap certificate");
+  const OpForm& f = form_of(c);
+  if (!f.gap) return fail(FH_E_ARG, "fh_dual_gap: the %s has no duality-gap certificate (served: the dense and the sparse operator, vector and multi-column, the DCT and the convolution operator)", f.noun);
+  if (!c->has_b) return fail(FH_E_ARG, "fh_dual_gap: no loss set (fh_set_loss_lsq / fh_set_loss_logistic)");
+  if (c->loss_kind != LOSS_LSQ && c->loss_kind != LOSS_LOGISTIC) return fail(FH_E_ARG, "fh_dual_gap: the certificate is implemented for the least-squares and the logistic loss (the context holds loss %d)", c->loss_kind);
+  if (c->prox_kind != FH_PROX_SHRINK && c->prox_kind != FH_PROX_GROUP) return fail(FH_E_ARG, "fh_dual_gap: the certificate is implemented for FH_PROX_SHRINK and FH_PROX_GROUP (the context holds prox kind %d)", c->prox_kind);
+  if (c->loss_kind == LOSS_LOGISTIC && c->LB) return fail(FH_E_ARG, "fh_dual_gap: the logistic loss has no multi-column form");
+  if (!(c->mu > 0.0)) return fail(FH_E_ARG, "fh_dual_gap: the certificate needs mu > 0 (the context holds mu = %g)", c->mu);
+  if (!c->at_state) return fail(FH_E_ARG, "fh_dual_gap: no committed state: call fh_init or fh_setup first (after the operator, the loss and x0 are set)");
+  if (c->last_accel) return fail(FH_E_ARG, "fh_dual_gap: the latest step was accelerated: x0 is the extrapolated iterate and A x0 is formed inside the adjoint launch, never stored "
+                                          "(Z holds A xprox): the certificate is served after fh_init, fh_setup and steps without acceleration");
+  FH_TRY(use_device(c));
+  GapP p;
+  p.x = c->X[c->xi]; p.g = c->G[c->gc]; p.z = c->Z[c->zc]; p.b = c->b;
+  p.n = c->n; p.m = c->m;
+  p.L = (uint32_t)l_of(c); p.LB = (uint32_t)lb_of(c);
+  gap_slabs(p.n, &p.nwg_n, &p.slab_n);
+  gap_slabs(p.m, &p.nwg_m, &p.slab_m);
+  p.group = c->prox_kind == FH_PROX_GROUP ? 1 : 0;
+  p.mu = c->mu;
+  const uint32_t nrec = p.nwg_n + p.nwg_m;
+  FH_TRY(ensure_ws(c, ((size_t)nrec * 8 + p.nwg_m + FH_GAP_NOUT) * sizeof(double)));
+  p.red = c->ws; p.red2 = c->ws + (size_t)nrec * 8; p.out = p.red2 + p.nwg_m;
+  t_begin(c, FH_K_AUX);
+  if (c->loss_kind == LOSS_LOGISTIC) {
+    k_gap_partials<LOSS_LOGISTIC><<<dim3(nrec), dim3(FH_WG), 0, c->stream>>>(p);
+    k_gap_logistic_dual<LOSS_LOGISTIC><<<dim3(p.nwg_m), dim3(FH_WG), 0, c->stream>>>(p);
+    k_gap_final<LOSS_LOGISTIC><<<dim3(1), dim3(FH_WG), 0, c->stream>>>(p);
+  } else {
+    k_gap_partials<LOSS_LSQ><<<dim3(nrec), dim3(FH_WG), 0, c->stream>>>(p);
+    k_gap_final<LOSS_LSQ><<<dim3(1), dim3(FH_WG), 0, c->stream>>>(p);
+  }
+  t_end(c, FH_K_AUX);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(out, p.out, FH_GAP_NOUT * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  return finish(c);
 }
 
 extern "C" int fh_fwd(fh_ctx* c, double tau, double* scalars) {

@@ -184,6 +184,7 @@ struct fh_ctx {
   double* T[4] = {nullptr, nullptr, nullptr, nullptr};
   int pc = 0, gc = 0, zc = 0;
   bool last_accel = false;
+  bool at_state = false;     // x0, g0 and Z[zc] = A x0 belong together: set by fh_init / fh_setup, lost with the operator, the loss, the column count or a vector set from outside (fh_dual_gap asks)
   // m-side
   double* b = nullptr;
   double* Z[2] = {nullptr, nullptr};
@@ -328,6 +329,7 @@ struct OpForm {
   const char* no_softmax;    // fh_set_loss_softmax
   const char* no_rhs;        // fh_set_rhs (nullptr: this form takes it)
   const char* no_f32;        // float32 storage, refused by the form's setter (entry point, noun; nullptr: the setter does not ask)
+  bool gap;                  // fh_dual_gap (csrc/fh_gap.h): x0, g0, z = A x0 and b of this form are what the certificate reads
 };
 #define KIND(k) (1u << FH_PROX_##k)
 #define LOSSBIT(k) (1u << (k))
@@ -350,31 +352,31 @@ static const char kF32HasNo[] = "%s: float32 storage has no %s";
 static const OpForm kForms[F_COUNT] = {
   // F_NONE: what an empty context may hold for the operator to come (free_operator drops every other kind)
   {"operator", KINDS_ELEM | KINDS_LEVEL | KIND(TVBALL) | KIND(GROUP), 0, 0, false, false, nullptr, nullptr, "set the operator before the loss", nullptr, nullptr,
-   "fh_set_rhs: set the dense operator first (fh_set_matrix / fh_generate_matrix)", nullptr},
+   "fh_set_rhs: set the dense operator first (fh_set_matrix / fh_generate_matrix)", nullptr, false},
   // F_DENSE: accepts the TV-ball kind and refuses it at launch; its launch refuses nothing else
   {"dense operator", KINDS_ELEM | KINDS_LEVEL | KIND(TVBALL), KINDS_ALL & ~KIND(TVBALL), LOSSES_ELEM, false, false, nullptr, "TV-ball prox needs the stencil operator", nullptr, nullptr,
-   kSoftmaxMc, nullptr, nullptr},
-  {"dense operator", KINDS_ELEM | KIND(GROUP), 0, LOSSES_MC, false, false, kNoProxMc, "prox kind %d has no multi-column form", kNoLogisticMc, kMcLsqOnly, nullptr, nullptr, nullptr},
+   kSoftmaxMc, nullptr, nullptr, true},
+  {"dense operator", KINDS_ELEM | KIND(GROUP), 0, LOSSES_MC, false, false, kNoProxMc, "prox kind %d has no multi-column form", kNoLogisticMc, kMcLsqOnly, nullptr, nullptr, nullptr, true},
   // F_STENCIL: accepts what the dense form accepts, runs the TV-ball prox or none
   {"stencil operator", KINDS_ELEM | KINDS_LEVEL | KIND(TVBALL), KIND(IDENTITY) | KIND(TVBALL), LOSSBIT(LOSS_LSQ), false, false, nullptr,
-   "the stencil operator supports the TV-ball prox or no prox (got kind %d)", "the logistic loss is implemented for the dense operator", nullptr, kSoftmaxOps, kRhsNone, nullptr},
+   "the stencil operator supports the TV-ball prox or no prox (got kind %d)", "the logistic loss is implemented for the dense operator", nullptr, kSoftmaxOps, kRhsNone, nullptr, false},
   {"sparse operator", KINDS_ELEM, 0, LOSSES_ELEM, false, false, "prox kind %d (LINF / L1BALL / TVBALL / GROUP) is not implemented for the %s", nullptr, nullptr, nullptr, kSoftmaxMc, kRhsSparse,
-   "%s: float32 storage is not implemented for the %s"},
+   "%s: float32 storage is not implemented for the %s", true},
   {"sparse operator", KINDS_ELEM | KIND(GROUP), 0, LOSSES_MC, false, false, kNoProxMc, "prox kind %d has no multi-column form", kNoLogisticMc, kMcLsqOnly, nullptr, kRhsSparse,
-   "%s: float32 storage is not implemented for the %s"},
+   "%s: float32 storage is not implemented for the %s", true},
   {"3-D stencil operator", KINDS_ELEM | KIND(TVBALL), 0, LOSSBIT(LOSS_LSQ), false, false, "prox kind %d (LINF / L1BALL / GROUP) is not implemented for the %s", nullptr, kLsqOnly, nullptr, kSoftmaxOps,
-   kRhsNone, nullptr},
+   kRhsNone, nullptr, false},
   {"quadratic operator", KINDS_ELEM | KIND(GROUP) | KIND(ROWBALL), 0, 0, false, false, "prox kind %d (LINF / L1BALL / TVBALL) has no quadratic form", nullptr,
    "the quadratic operator carries its own loss (Q and the linear term of fh_set_quadratic): fh_set_loss_lsq / fh_set_loss_logistic do not apply", nullptr, kSoftmaxOps,
-   "fh_set_rhs: the column count of a quadratic operator is fixed when it is set (fh_set_quadratic)", kF32HasNo},
+   "fh_set_rhs: the column count of a quadratic operator is fixed when it is set (fh_set_quadratic)", kF32HasNo, false},
   {"bilinear operator", KINDS_ELEM | KIND(ROWSPLIT), 0, 0, false, true, "prox kind %d (LINF / L1BALL / TVBALL / GROUP / ROWBALL) has no bilinear form", nullptr,
    "the bilinear operator carries its own loss (S of fh_set_factorization): fh_set_loss_lsq / fh_set_loss_logistic do not apply", nullptr, kSoftmaxOps,
-   "fh_set_rhs: the column count of a bilinear operator is fixed when it is set (fh_set_factorization)", kF32HasNo},
-  {"DCT operator", KINDS_ELEM | KINDS_LEVEL, 0, LOSSBIT(LOSS_LSQ), false, false, "prox kind %d (TVBALL / GROUP) is not implemented for the %s", nullptr, kLsqOnly, nullptr, kSoftmaxOps, kRhsNone, kF32NoMatrix},
+   "fh_set_rhs: the column count of a bilinear operator is fixed when it is set (fh_set_factorization)", kF32HasNo, false},
+  {"DCT operator", KINDS_ELEM | KINDS_LEVEL, 0, LOSSBIT(LOSS_LSQ), false, false, "prox kind %d (TVBALL / GROUP) is not implemented for the %s", nullptr, kLsqOnly, nullptr, kSoftmaxOps, kRhsNone, kF32NoMatrix, true},
   {"identity operator", KINDS_ELEM | KIND(NUCLEAR) | KIND(NUCBALL), 0, LOSSES_ELEM, true, true, "prox kind %d (LINF / L1BALL / TVBALL / GROUP / ROWBALL) is not implemented for the %s",
    "prox kind %d (LINF / L1BALL / TVBALL / GROUP / ROWBALL / ROWSPLIT) is not implemented for the %s", nullptr, nullptr, kSoftmaxOps,
-   "fh_set_rhs: the %s has no multi-column form (its unknown is already an (M, N) matrix: fh_set_identity)", kF32NoMatrix},
-  {"convolution operator", KINDS_ELEM | KINDS_LEVEL, 0, LOSSBIT(LOSS_LSQ), false, false, "prox kind %d (TVBALL / GROUP) is not implemented for the %s", nullptr, kLsqOnly, nullptr, kSoftmaxOps, kRhsNone, kF32NoMatrix},
+   "fh_set_rhs: the %s has no multi-column form (its unknown is already an (M, N) matrix: fh_set_identity)", kF32NoMatrix, false},
+  {"convolution operator", KINDS_ELEM | KINDS_LEVEL, 0, LOSSBIT(LOSS_LSQ), false, false, "prox kind %d (TVBALL / GROUP) is not implemented for the %s", nullptr, kLsqOnly, nullptr, kSoftmaxOps, kRhsNone, kF32NoMatrix, true},
 };
 #undef KIND
 #undef LOSSBIT

@@ -84,6 +84,17 @@ class HostFBS:
         self.backtrack, self.shrink_by = backtrack, stepsize_shrink
         self.window, self.max_backtracks, self.restart = window, max_backtracks, restart
         self.evaluate_objective, self.record_iterates, self.func = evaluate_objective, record_iterates, func
+        self.gap_rule = None
+        if isinstance(stop_rule, stopping.DualityGap):      # a tag: the existing loop under a rule that cannot fire (resid < 0), checked between chunks
+            from .certificates import _tags
+            self.gap_rule, self.stop_rule, self.tolerance = stop_rule, stopping.residual, 0.0
+            self.gap_tags = _tags(f, proxg)                 # (TypeError with a sentence unless f / proxg belong to a tagged loss / prox the certificate is stated for)
+
+    def certificate(self):
+        """certificates.duality_gap of the current iterate (needs a tagged loss and prox)."""
+        from .certificates import _tags, duality_gap
+        loss, prox = self.gap_tags if self.gap_rule is not None else _tags(self.f, self.proxg)
+        return duality_gap(self.A, loss, prox, self.x)
 
     # ---- phases -----------------------------------------------------------------------------------
     def _gradient(self, z):
@@ -216,8 +227,28 @@ class HostFBS:
         self.i = i + 1
         return bool(self.stop_rule(i, self.residuals[i], self.norm_residuals[i], self.max_residual, self.tolerance))
 
+    def _run_to_gap(self):
+        """The loop under stopping.DualityGap: a certificate at the start and at every multiple of `every`."""
+        from .solver import Convergence
+        rule, gaps = self.gap_rule, []
+        while True:
+            cert = self.certificate()
+            gaps.append((self.i, cert.gap))
+            if rule.met(cert) or self.i >= self.max_iters:
+                break
+            target = rule.next_check(self.i, self.max_iters)
+            while self.i < target:
+                self.step()
+        self.times[self.i] = time()
+        conv = Convergence(self.residuals, self.norm_residuals, self.stepsizes, self.total_backtracks, self.times,
+                           self.i, self.x, self.objectives, self.iterates, self.function_hist)
+        conv.certificate, conv.gaps = cert, gaps
+        return conv
+
     def run(self):
         from .solver import Convergence
+        if self.gap_rule is not None:
+            return self._run_to_gap()
         while self.i < self.max_iters:
             if self.step():
                 break

@@ -70,6 +70,8 @@ class RunState(C.Structure):                # fh_run_state
 
 
 # every exported symbol with its signature; tests assert the .so exports exactly these ------------
+GAP_NOUT = 8            # FH_GAP_NOUT: P, D, gap, f(z), Omega(x0), Omega°(g0), s, f(0)
+
 SIGNATURES = {
     "fh_last_error": (C.c_char_p, []),
     "fh_device_count": (_i32, [C.POINTER(_i32)]),
@@ -132,6 +134,7 @@ SIGNATURES = {
     "fh_fwd": (_i32, [_ctx, _dbl, _pd]),
     "fh_adj": (_i32, [_ctx, _dbl, _i32, _dbl, _pd]),
     "fh_commit": (_i32, [_ctx, _i32]),
+    "fh_dual_gap": (_i32, [_ctx, _pd]),
     "fh_abi_sizes": (_i32, [C.POINTER(_u64)]),
     "fh_run_supported": (_i32, [_ctx, C.POINTER(_i32)]),
     "fh_run": (_i32, [_ctx, _i32, C.POINTER(RunOpts), C.POINTER(RunState), _pd, C.POINTER(_i32)]),
@@ -978,6 +981,15 @@ class HipContext:
 
     def commit(self, save_best=False):
         self._call("fh_commit", 1 if save_best else 0)
+
+    def dual_gap(self):
+        """fh_dual_gap: the duality-gap certificate of the committed iterate x0 from x0, g0, z = A x0 and b as they lie in device memory, with the
+        mu and the prox kind the context holds -- a certificates.Certificate (primal, dual, gap, f, omega, dual_norm, scale, f0).  Changes nothing
+        in the context; HipError with the library's sentence where the certificate is not served."""
+        from .certificates import Certificate
+        out = np.empty(GAP_NOUT)
+        self._call("fh_dual_gap", out.ctypes.data_as(_pd))
+        return Certificate(*(float(v) for v in out))
 
     def apply(self, v, adjoint=False):
         m, n = self.shape()

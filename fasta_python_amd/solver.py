@@ -433,6 +433,14 @@ class FBSolver:
             stepsize_shrink = 0.2 if adaptive else 0.5
         self.adaptive, self.accelerate, self.verbose = adaptive, accelerate, verbose
         self.max_iters, self.tolerance, self.stop_rule = max_iters, tolerance, stop_rule
+        self.gap_rule = None
+        if isinstance(stop_rule, stopping.DualityGap):
+            # a tag, not a callable: the existing loop runs under the library rule `residual` at tolerance 0.0, which cannot fire (resid < 0),
+            # in chunks that end on multiples of `every`, with ctx.dual_gap() between them (run())
+            if accelerate:
+                raise ValueError("stop_rule=DualityGap on the device needs accelerate=False: an accelerated step commits the extrapolated iterate, whose "
+                                 "image A x0 the adjoint launch forms on the fly and never stores (fh_dual_gap refuses that state)")
+            self.gap_rule, self.stop_rule, self.tolerance = stop_rule, stopping.residual, 0.0
         self.L, self.tau0 = L, tau0
         self.backtrack, self.stepsize_shrink = backtrack, stepsize_shrink
         self.window, self.max_backtracks, self.restart = window, max_backtracks, restart
@@ -762,11 +770,30 @@ class FBSolver:
                     self.step()
         return self.done
 
+    def certificate(self):
+        """The duality-gap certificate of the committed iterate x0 (HipContext.dual_gap: fh_dual_gap), on demand under any stop rule."""
+        return self.ctx.dual_gap()
+
+    def _run_to_gap(self):
+        """The loop under stopping.DualityGap: a certificate at the start and at every multiple of `every`; stops at gap <= tolerance * f(0)."""
+        rule = self.gap_rule
+        self.gaps = []
+        while True:
+            self.last_certificate = cert = self.ctx.dual_gap()
+            self.gaps.append((self.i, cert.gap))
+            if rule.met(cert) or self.i >= self.max_iters:
+                break
+            self.done = False
+            self.advance(rule.next_check(self.i, self.max_iters) - self.i)
+        self.done = True
+
     def run(self):
         with warnings.catch_warnings():
             # the reference relies on float64 inf/nan semantics (e.g. 0/0 in the BB rule once converged)
             warnings.simplefilter("ignore", RuntimeWarning)
             with np.errstate(all="ignore"):
+                if self.gap_rule is not None:
+                    self._run_to_gap()
                 while self.i < self.max_iters and not self.done:
                     if self._run_opts is not None:
                         self._library_call()
@@ -776,17 +803,22 @@ class FBSolver:
 
     def result(self):
         self.times[self.i] = time()                                     # :315
-        solution = self.ctx.get_vector(hip.VEC_BEST, self.n).reshape(self.shape)
+        # (under stopping.DualityGap: the iterate the last certificate was evaluated at -- x0 of the committed state, not the best-quality one)
+        solution = self.ctx.get_vector(hip.VEC_X0 if self.gap_rule is not None else hip.VEC_BEST, self.n).reshape(self.shape)
         conv = Convergence(self.residuals, self.norm_residuals, self.stepsizes, self.total_backtracks, self.times,
                            self.i, solution, self.objectives, self.iterates, self.function_hist)
         conv.device_steps = self.device_steps         # (build-only diagnostics: iterations that ran inside persistent launches -- fh_run --
         conv.library_steps = self.library_steps       #  and iterations driven by the library's host-side loop -- fh_iterate)
+        if self.gap_rule is not None and hasattr(self, "gaps"):
+            conv.certificate, conv.gaps = self.last_certificate, self.gaps
         return conv
 
 
 def fasta(A, *operands, backend="auto", **options):
     """Run FASTA.  Same positional forms, keyword options and defaults as the reference (fasta/__init__.py:38-53);
     returns `Convergence`.  Build-only keywords:
+      stop_rule = stopping.DualityGap(tol, every) -- a tag: stop at duality gap <= tol * f(0), checked every `every` iterations; the `tolerance`
+                           option is then unused, `solution` is the certified iterate, `certificate` and `gaps` are added to the record;
       backend = "auto"  -- device loop for device-recognisable operands (raises if the GPU path is unavailable), generic
                            host loop for operands that cannot run in a kernel (closures, callable pair, None, host LinearMap);
                 "hip"   -- device loop or TypeError;   "numpy" -- generic host loop (operands are called as given);

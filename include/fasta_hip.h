@@ -668,6 +668,25 @@ int fh_recovered_count(fh_ctx* ctx, int what, uint64_t* count);
 /* x0 <- x1, g0 <- g1, acceleration history rotates (:176-177, :222-226); save_best != 0 also
  * copies x1 into FH_VEC_BEST (:298-300).                                                         */
 int fh_commit(fh_ctx* ctx, int save_best);
+/* ---- duality-gap certificate of the committed iterate (csrc/fh_gap.h; the host statement is fasta_python_amd/certificates.py) --------------------
+ * For min_x f(A x) + mu * Omega(x), from FH_VEC_X0, FH_VEC_G0 = A^H grad f(A x0), z = A x0 and FH_VEC_B as they lie in device memory, with the mu
+ * and the prox kind the context holds: Omega = sum |x_ij| and Omega° = max |g_ij| for FH_PROX_SHRINK, Omega = sum_j ||x_j,:||_2 and
+ * Omega° = max_j ||g_j,:||_2 (row norms summed in column order) for FH_PROX_GROUP; s = 1 if Omega° <= mu else mu / Omega°; u = s * grad f(z) is dual
+ * feasible; P = f(z) + mu * Omega, D = -f*(u), gap = P - D >= 0 bounds the suboptimality of x0.  Least squares (r = z - b):
+ * D = -.5 s^2 ||r||^2 - s <r, b>, f(0) = .5 ||b||^2.  Logistic: D = -sum h(y_i + s (sigma(z_i) - y_i)), h(p) = p log p + (1 - p) log(1 - p) evaluated
+ * without cancellation, f(0) = m log 2.  out[FH_GAP_NOUT] = { P, D, gap, f(z), Omega(x0), Omega°(g0), s, f(0) }; at x0 = 0, out[5] is the critical mu
+ * above which the solution is zero.  Two ordinary launches (three for the logistic loss), no float atomics, fixed summation order, bitwise
+ * repeatable; no vector, scalar or state of the context changes (the shared workspace holds the partial sums); fh_timing_* reports the launches under FH_K_AUX.
+ * z = A x0 is Z[zc], the image every committed state keeps of its latest prox output -- NOT what FH_VEC_Z addresses (the image of the prox output
+ * of the latest forward launch, the next z1).  Valid after fh_init, fh_setup, and fh_commit / a returned fh_iterate / fh_run WITHOUT acceleration:
+ * an accelerated step commits the extrapolated x1, whose image the adjoint launch forms on the fly and never stores.
+ * Served: the dense and the sparse operator, vector and multi-column, either storage of A, the DCT in both geometries and the convolution;
+ * least squares with FH_PROX_SHRINK (any L) or FH_PROX_GROUP; the logistic loss with FH_PROX_SHRINK on the vector forms.
+ * Refused, FH_E_ARG with one sentence each: any other prox kind or loss; mu <= 0; a context that holds observation weights; the identity, stencil,
+ * quadratic and bilinear forms; a multi-device context or one with a communicator; no committed state (no fh_init / fh_setup since the operator, the
+ * loss, the column count, x0, g0 or b were set); a step in flight (fh_step_begin); a latest step that was accelerated.                          */
+#define FH_GAP_NOUT 8
+int fh_dual_gap(fh_ctx* ctx, double* out);
 /* plain operator application on host vectors (tests, synthetic b): adjoint=0: out(m) = A in(n);
  * adjoint=1: out(n) = A^H in(m).                                                                 */
 int fh_apply(fh_ctx* ctx, int adjoint, const double* in, double* out);
