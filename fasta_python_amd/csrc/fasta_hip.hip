@@ -450,7 +450,8 @@ static int set_refusals(const fh_ctx* c, const char* who, const OpForm& f, bool 
   if (c->pending_step) return fail(FH_E_STATE, kStepInFlight);
   return 0;
 }
-// next: the form being set, whose row says which prox kind survives (nullptr: the dense setters and fh_set_stencil keep whatever is held)
+// next: the form being set, whose row says which prox kind survives (nullptr: the dense setters and fh_set_stencil keep whatever kind is held).
+// Every setter drops lazy, last_accel and the scalar block; SET_KEEPS_SOLVER_STATE keeps loss_kind, commits and at_state.
 enum { SET_KEEPS_SOLVER_STATE = 1, SET_DROPS_WEIGHTS = 2 };
 static int set_begin(fh_ctx* c, const OpForm* next, int flags = 0) {
   FH_TRY(use_device(c));
@@ -458,7 +459,13 @@ static int set_begin(fh_ctx* c, const OpForm* next, int flags = 0) {
   if (!(flags & SET_DROPS_WEIGHTS)) FH_TRY(refuse_weighted(c));
   free_operator(c);                                      // (back to the vector form: L = LB = 0)
   if (next) reset_unserved(c, *next);
-  if (!(flags & SET_KEEPS_SOLVER_STATE)) { c->loss_kind = LOSS_LSQ; c->lazy = false; c->last_accel = false; c->commits = 0; c->at_state = false; }
+  // What describes the vectors free_operator just gave back goes with them, whatever the flags: the lazily-kept iterate of the one-pass
+  // accelerated stencil step (a dense setter kept it: fh_fwd on the new operator was refused as "lazy" until the next fh_init), last_accel
+  // (fh_commit after fh_fwd on the new operator rotated as after an accelerated adjoint), and the scalar block, whose halves a launch that
+  // does not compute them leaves alone (fh_fwd on the new operator returned the old operator's adjoint half).  The stream is idle here.
+  c->lazy = false; c->last_accel = false; c->tvz_pending = false; c->zcur_stale = false;
+  if (c->hscal) memset(c->hscal, 0, FH_NSCALARS * sizeof(double));
+  if (!(flags & SET_KEEPS_SOLVER_STATE)) { c->loss_kind = LOSS_LSQ; c->commits = 0; c->at_state = false; }      // (what the flag still keeps)
   return 0;
 }
 static void vector_geometry(fh_ctx* c, uint64_t m, uint64_t n) {
@@ -909,7 +916,7 @@ extern "C" int fh_set_rhs(fh_ctx* c, uint32_t L) {
   free_vectors(c);
   c->L = L; c->LB = LB;
   c->has_b = false; c->loss_kind = LOSS_LSQ;
-  c->lazy = false; c->last_accel = false; c->commits = 0; c->at_state = false;
+  c->last_accel = false; c->commits = 0; c->at_state = false;      // (lazy: the 2-D stencil alone sets it, and it has no multi-column form)
   if (!L) reset_unserved(c, next);                       // (the row-wise shrink has no vector form)
   FH_TRY(alloc_vectors(c));
   return finish(c);
@@ -1162,6 +1169,9 @@ extern "C" int fh_init(fh_ctx* c, double* scalars) {
   // z_accel1 := A x0 lands in Z[zc] so the first iteration finds it as z_accel0 (fasta/__init__.py:154-157)
   bool fused_done = false;
   for (int k = 0; k < ns; ++k) { fh_ctx* s = shard_of(c, k); s->lazy = false; s->commits = 0; s->tvz_pending = false; s->zcur_stale = false; }
+  // the 2-D stencil forms no gradient here (no K-adj below): the adjoint half of the block and the clipping level would otherwise be whatever the launch before this
+  // one left there -- of another solve, or of another operator.  (The stream is idle: every call ends with its wait; the block is host memory.)
+  if (c->shards.empty() && c->op == OP_STENCIL) for (int q = FH_S_DXDG; q <= FH_S_ALPHA; ++q) c->hscal[q] = 0.0;
   if (plain_pair_fused_ok(c)) FH_TRY(plain_pair_fused(c, c->X[c->xi], c->Z[c->zc], c->G[c->gc], &fused_done));   // one pass: z, f, gradient
   if (!fused_done) {
     for (int k = 0; k < ns; ++k) {

@@ -152,6 +152,29 @@ def test_the_step_is_bitwise_repeatable_and_timed():
         assert np.array_equal(runs[0][key], runs[1][key]), key
 
 
+def assert_rownorm_step(got, want, terms, n, L, kind, tag):
+    """what run_step returned against the np.longdouble model of a GroupShrink / RowBall step, at the tolerances of tests/quad_cases.py (shared with
+    the stations of tests/carry_cases.py)"""
+    for name in QC.MATRICES:
+        rtol, atol = QC.ROWNORM_TOL[name]
+        np.testing.assert_allclose(got[name], want[name].astype(np.float64), rtol=rtol, atol=atol, err_msg=name)
+    worst = 0.0
+    for block in QC.BLOCKS:
+        for slot, v in want[block].items():
+            rtol, atol = QC.scalar_tol(block, slot)
+            if slot in (hip.S_FSQ, hip.S_FSQ_ADJ, hip.S_DXG0, hip.S_DXDG, hip.S_RDOT):
+                # a signed sum: the bound of a summation of depth <= 64 on the magnitudes of its terms
+                atol += 64 * EPS * float(np.sum(np.abs(terms[(block, slot)])))
+            dev = abs(got[block][slot] - float(v))
+            print(f"\n{kind} n={n} L={L} {block}[{slot}]: device {got[block][slot]!r}, model {float(v)!r}", end="")
+            assert dev <= rtol * abs(float(v)) + atol, (block, slot, got[block][slot], float(v))
+            worst = max(worst, dev / max(abs(float(v)), 1e-300))
+    zero_rows = np.all(got["XPROX"] == 0, axis=1).mean()
+    print(f"\n{kind} n={n} L={L}: worst relative deviation of a scalar {worst:.2e}; rows brought to zero {zero_rows:.2f}", end="")
+    if kind == "rowball":
+        assert np.linalg.norm(got["XPROX"], axis=1).max() <= tag.mu * (1 + 4 * EPS)
+
+
 # ---- GroupShrink and RowBall -----------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("n,L,kind,nt", QC.rownorm_cases(), ids=lambda v: str(v))
 def test_rownorm_step_matches_the_extended_precision_model(n, L, kind, nt):
@@ -163,24 +186,7 @@ def test_rownorm_step_matches_the_extended_precision_model(n, L, kind, nt):
     try:
         assert c.quad_shape() == QC.expected_shape(case)
         got = run_step(c, n, L, X0, tag, tau, QC.COEF)
-        for name in QC.MATRICES:
-            rtol, atol = QC.ROWNORM_TOL[name]
-            np.testing.assert_allclose(got[name], want[name].astype(np.float64), rtol=rtol, atol=atol, err_msg=name)
-        worst = 0.0
-        for block in QC.BLOCKS:
-            for slot, v in want[block].items():
-                rtol, atol = QC.scalar_tol(block, slot)
-                if slot in (hip.S_FSQ, hip.S_FSQ_ADJ, hip.S_DXG0, hip.S_DXDG, hip.S_RDOT):
-                    # a signed sum: the bound of a summation of depth <= 64 on the magnitudes of its terms
-                    atol += 64 * EPS * float(np.sum(np.abs(terms[(block, slot)])))
-                dev = abs(got[block][slot] - float(v))
-                print(f"\n{kind} n={n} L={L} {block}[{slot}]: device {got[block][slot]!r}, model {float(v)!r}", end="")
-                assert dev <= rtol * abs(float(v)) + atol, (block, slot, got[block][slot], float(v))
-                worst = max(worst, dev / max(abs(float(v)), 1e-300))
-        zero_rows = np.all(got["XPROX"] == 0, axis=1).mean()
-        print(f"\n{kind} n={n} L={L}: worst relative deviation of a scalar {worst:.2e}; rows brought to zero {zero_rows:.2f}", end="")
-        if kind == "rowball":
-            assert np.linalg.norm(got["XPROX"], axis=1).max() <= tag.mu * (1 + 4 * EPS)
+        assert_rownorm_step(got, want, terms, n, L, kind, tag)
         for which in (hip.VEC_XPROX, hip.VEC_X1, hip.VEC_G1):
             assert padding_is_zero(c, which, n, L), which
     finally:

@@ -111,6 +111,11 @@ def test_the_row_pass_is_bitwise_repeatable(form):
 
 
 # ---- one whole step ---------------------------------------------------------------------------------------------------------------------------
+# how the step test holds the device against NumPy (rtol, atol): shared with the stations of tests/carry_cases.py
+STEP_TOL = {"G0": dict(rtol=1e-12, atol=1e-13), "F0": dict(rtol=1e-12), "Z": dict(rtol=1e-12, atol=1e-13), "G1": dict(rtol=1e-11, atol=1e-13),
+            "fwd scalars": dict(rtol=1e-11, atol=1e-13)}
+
+
 def empty_row_matrix():
     S = sp.random(120, 90, density=0.1, format="lil", random_state=np.random.RandomState(15), data_rvs=np.random.RandomState(16).standard_normal)
     S[7, :] = 0
@@ -153,8 +158,8 @@ def test_single_step_scalars_match_numpy(L, kind, operator):
         s0 = c.init()
         Z0 = A @ X0
         G0 = mat(hip.VEC_G0, n)
-        np.testing.assert_allclose(G0, At @ sm.gradf(Z0), rtol=1e-12, atol=1e-13)
-        np.testing.assert_allclose(s0[hip.S_FSQ], sm.f(Z0), rtol=1e-12)
+        np.testing.assert_allclose(G0, At @ sm.gradf(Z0), **STEP_TOL["G0"])
+        np.testing.assert_allclose(s0[hip.S_FSQ], sm.f(Z0), **STEP_TOL["F0"])
         np.testing.assert_allclose(s0[hip.S_GSUM], gsum(X0), rtol=1e-12)
         s = c.fwd(tau)
         Xh = X0 - tau * G0
@@ -163,15 +168,15 @@ def test_single_step_scalars_match_numpy(L, kind, operator):
         np.testing.assert_allclose(mat(hip.VEC_XPROX, n), Xp, rtol=1e-12, atol=1e-14)
         Xp, Z = mat(hip.VEC_XPROX, n), mat(hip.VEC_Z, m)                 # the device's own vectors from here on
         dX = Xp - X0
-        np.testing.assert_allclose(Z, A @ Xp, rtol=1e-12, atol=1e-13)
+        np.testing.assert_allclose(Z, A @ Xp, **STEP_TOL["Z"])
         want = {hip.S_FSQ: sm.f(Z), hip.S_DXG0: np.sum(dX * G0), hip.S_DX2: np.sum(dX * dX), hip.S_XH2: np.sum((Xp - Xh) ** 2),
                 hip.S_G02: np.sum(G0 * G0), hip.S_GSUM: gsum(Xp), hip.S_GMAX: np.abs(Xp).max(), hip.S_RDOT: np.sum((X0 - Xp) * (Xp - X0))}
         for k, v in want.items():
-            np.testing.assert_allclose(s[k], v, rtol=1e-11, atol=1e-13, err_msg=str(k))
+            np.testing.assert_allclose(s[k], v, err_msg=str(k), **STEP_TOL["fwd scalars"])
         a = c.adj(tau)
         G1 = At @ sm.gradf(Z)
         dG = G1 + (Xh - X0) / tau
-        np.testing.assert_allclose(mat(hip.VEC_G1, n), G1, rtol=1e-11, atol=1e-13)
+        np.testing.assert_allclose(mat(hip.VEC_G1, n), G1, **STEP_TOL["G1"])
         np.testing.assert_allclose(a[hip.S_DXDG], np.sum(dX * dG), rtol=1e-10, atol=1e-13)
         np.testing.assert_allclose(a[hip.S_DG2], np.sum(dG * dG), rtol=1e-10, atol=1e-13)
         np.testing.assert_allclose(a[hip.S_FSQ_ADJ], sm.f(Z), rtol=1e-11)
