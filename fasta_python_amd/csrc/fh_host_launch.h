@@ -1648,6 +1648,26 @@ static int launch_gterms(fh_ctx* c, const double* x) {
   return 0;
 }
 
+// Which search kernel a vector of n entries takes (csrc/fh_prox.h): the ONE rule, which launch_level_search calls and fh_level_shape_for exports.
+//   n <= 1024: k_level_search<4, 256>;  <= 4096: <16, 256>;  <= 8192: <32, 256>;  <= 16384: <16> on 1024 threads;
+//   <= 262144: k_level_search_multi on ceil(n / 8192) workgroups of 1024 threads, 8 entries per thread;  beyond: k_level_search<0> (re-read every pass)
+struct LevelShape { uint32_t multi, threads, ept, workgroups; };
+static LevelShape level_shape_for(uint32_t n) {
+  if (n <= 4u * 256u) return {0u, 256u, 4u, 1u};
+  if (n <= 16u * 256u) return {0u, 256u, 16u, 1u};
+  if (n <= 32u * 256u) return {0u, 256u, 32u, 1u};
+  if (n <= 16u * LVL_WG) return {0u, LVL_WG, 16u, 1u};
+  if (n <= (uint32_t)LVL_MAXG * LVL_MEPT * LVL_WG) return {1u, LVL_WG, LVL_MEPT, (n + LVL_MEPT * LVL_WG - 1) / (LVL_MEPT * LVL_WG)};
+  return {0u, LVL_WG, 0u, 1u};
+}
+extern "C" int fh_level_shape_for(uint64_t n, uint32_t* out) {
+  if (!out) return fail(FH_E_ARG, "fh_level_shape_for: null argument");
+  if (n == 0 || n >= (1ull << 31)) return fail(FH_E_ARG, "fh_level_shape_for: the vector length must be in [1, 2^31)");
+  const LevelShape sh = level_shape_for((uint32_t)n);
+  out[0] = sh.multi; out[1] = sh.threads; out[2] = sh.ept; out[3] = sh.workgroups;
+  return 0;
+}
+
 // clipping level alpha for FH_PROX_LINF (radius tau*mu) / FH_PROX_L1BALL (radius mu) -> dscal[FH_NSCALARS]
 static int launch_level_search(fh_ctx* c, double tau) {
   if (c->op != OP_DENSE && c->op != OP_DCT && c->op != OP_CONV) return fail(FH_E_STATE, "LINF / L1BALL prox need the dense operator");      // (the search reads x0, g0 and n only)
@@ -1656,14 +1676,15 @@ static int launch_level_search(fh_ctx* c, double tau) {
   const double* g0 = c->G[c->gc];
   double* out = c->dscal + FH_NSCALARS;
   const uint32_t n = (uint32_t)c->n;
-  if (n > 16u * LVL_WG && n <= (uint32_t)LVL_MAXG * LVL_MEPT * LVL_WG) {      // several workgroups, LVL_MEPT values per thread (csrc/fh_prox.h)
+  const LevelShape sh = level_shape_for(n);
+  if (sh.multi) {      // several workgroups, LVL_MEPT values per thread (csrc/fh_prox.h)
     if (!c->lvl_rec) {
       HIP_TRY(hipMalloc((void**)&c->lvl_rec, (size_t)LVL_MAXPASS * LVL_MAXG * 2 * sizeof(double)));
       HIP_TRY(hipMalloc((void**)&c->lvl_cnt, (LVL_MAXPASS + 1) * sizeof(unsigned)));
       HIP_TRY(hipMemsetAsync(c->lvl_cnt, 0, (LVL_MAXPASS + 1) * sizeof(unsigned), c->stream));
     }
     LevelWs ws = {c->lvl_rec, c->lvl_cnt, c->counters + CNT_DIAG};
-    const unsigned G = (n + LVL_MEPT * LVL_WG - 1) / (LVL_MEPT * LVL_WG);
+    const unsigned G = sh.workgroups;
     const int hooks = ((c->test_hooks & FH_HOOK_LEVEL_WITHHOLD) ? LVL_HOOK_WITHHOLD : 0) | ((c->test_hooks & FH_HOOK_LEVEL_NO_FALLBACK) ? LVL_HOOK_NO_FALLBACK : 0);
     t_begin(c, FH_K_LEVEL);
     k_level_search_multi<<<dim3(G), dim3(LVL_WG), 0, c->stream>>>(x0, g0, n, tau, radius, out, ws, hooks);
@@ -1672,11 +1693,12 @@ static int launch_level_search(fh_ctx* c, double tau) {
     return 0;
   }
   t_begin(c, FH_K_LEVEL);
-  if (n <= 4u * 256u) k_level_search<4, 256><<<dim3(1), dim3(256), 0, c->stream>>>(x0, g0, n, tau, radius, out);
-  else if (n <= 16u * 256u) k_level_search<16, 256><<<dim3(1), dim3(256), 0, c->stream>>>(x0, g0, n, tau, radius, out);
-  else if (n <= 32u * 256u) k_level_search<32, 256><<<dim3(1), dim3(256), 0, c->stream>>>(x0, g0, n, tau, radius, out);
-  else if (n <= 16u * LVL_WG) k_level_search<16><<<dim3(1), dim3(LVL_WG), 0, c->stream>>>(x0, g0, n, tau, radius, out);
-  else if (n <= 64u * LVL_WG) k_level_search<64><<<dim3(1), dim3(LVL_WG), 0, c->stream>>>(x0, g0, n, tau, radius, out);
+  if (sh.threads == 256u) {
+    if (sh.ept == 4u) k_level_search<4, 256><<<dim3(1), dim3(256), 0, c->stream>>>(x0, g0, n, tau, radius, out);
+    else if (sh.ept == 16u) k_level_search<16, 256><<<dim3(1), dim3(256), 0, c->stream>>>(x0, g0, n, tau, radius, out);
+    else k_level_search<32, 256><<<dim3(1), dim3(256), 0, c->stream>>>(x0, g0, n, tau, radius, out);
+  }
+  else if (sh.ept == 16u) k_level_search<16><<<dim3(1), dim3(LVL_WG), 0, c->stream>>>(x0, g0, n, tau, radius, out);
   else k_level_search<0><<<dim3(1), dim3(LVL_WG), 0, c->stream>>>(x0, g0, n, tau, radius, out);
   t_end(c, FH_K_LEVEL);
   HIP_TRY(hipGetLastError());

@@ -6,8 +6,14 @@
 //     alpha_0 = (sum_i |x_i| - t) / n ;   A_k = { i : |x_i| > alpha_k } ;
 //     alpha_{k+1} = (sum_{A_k} |x_i| - t) / |A_k| ,   stop when |A_k| stops shrinking.
 // alpha_k increases monotonically to the root; the result differs from the sort-based value only by
-// the rounding of the sums (~1e-16 relative).  One 1024-thread workgroup; the |xhat_i| = |x0_i - tau*g0_i|
-// live in registers (EPT per thread) for n <= 65536 and are re-read from L2 beyond that.
+// the rounding of the sums (~1e-16 relative).  The |xhat_i| = |x0_i - tau*g0_i| live in registers wherever they fit; which kernel a length
+// takes is ONE rule on the host (csrc/fh_host_launch.h: level_shape_for, exported as fh_level_shape_for):
+//     n <= 1024     k_level_search<4, 256>      one workgroup of 256 threads, 4 entries per thread
+//     n <= 4096     k_level_search<16, 256>     ... 16 per thread
+//     n <= 8192     k_level_search<32, 256>     ... 32 per thread
+//     n <= 16384    k_level_search<16>          one workgroup of 1024 threads, 16 per thread
+//     n <= 262144   k_level_search_multi        ceil(n / 8192) <= 32 workgroups of 1024 threads, 8 per thread (below)
+//     beyond        k_level_search<0>           one workgroup of 1024 threads that re-reads the entries from L2 in every pass
 #pragma once
 #include "fh_device.h"
 
@@ -42,7 +48,7 @@ __global__ __launch_bounds__(WG) void k_level_search(const double* x0, const dou
   __shared__ __attribute__((aligned(16))) double sa[WG / 64];
   __shared__ __attribute__((aligned(16))) double sb[WG / 64];
   const uint32_t tid = threadIdx.x;
-  constexpr int PAIRS = EPT >= 2 ? EPT / 2 : 0;           // EPT = 1: one element per thread; EPT = 0: re-read every pass (n > 65536)
+  constexpr int PAIRS = EPT >= 2 ? EPT / 2 : 0;           // EPT = 1: one element per thread; EPT = 0: re-read every pass (n > 262144)
   double ax[EPT > 0 ? EPT : 1];
   if (EPT == 1) ax[0] = tid < n ? fabs(fwd_point(x0[tid], g0[tid], tau)) : -INFINITY;   // -inf is never "> alpha"
   if (PAIRS > 0) {

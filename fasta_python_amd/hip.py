@@ -125,6 +125,7 @@ SIGNATURES = {
     "fh_set_loss_weights": (_i32, [_ctx, _pd]),
     "fh_set_loss_softmax": (_i32, [_ctx, C.POINTER(C.c_int32), _u64]),
     "fh_set_prox": (_i32, [_ctx, _i32, _dbl, _dbl, _dbl]),
+    "fh_level_shape_for": (_i32, [_u64, C.POINTER(C.c_uint32)]),
     "fh_set_vector": (_i32, [_ctx, _i32, _pd, _u64]),
     "fh_get_vector": (_i32, [_ctx, _i32, _pd, _u64]),
     "fh_init": (_i32, [_ctx, _pd]),
@@ -414,6 +415,19 @@ def nuclear_shape(M, N, block_rows=0, ncu=256):
     out = (_u64 * NUCLEAR_SHAPE_LEN)()
     _check(lib, lib.fh_nuclear_shape_for(int(M), int(N), int(block_rows), int(ncu), out))
     return NuclearShape(*(int(v) for v in out))
+
+
+LEVEL_SHAPE_LEN = 4
+LevelShape = collections.namedtuple("LevelShape", "multi threads ept workgroups")
+
+
+def level_shape_for(n):
+    """LevelShape of the clipping-level search (csrc/fh_prox.h) for an unknown of n entries: several workgroups or one, threads per workgroup,
+    entries a thread keeps in registers (0: re-read in every pass), workgroups -- fh_level_shape_for, the rule the launcher calls.  Host-only."""
+    lib = load_library()
+    out = (C.c_uint32 * LEVEL_SHAPE_LEN)()
+    _check(lib, lib.fh_level_shape_for(int(n), out))
+    return LevelShape(*(int(v) for v in out))
 
 
 CONV_SHAPE_LEN = 8

@@ -498,6 +498,12 @@ int fh_set_loss_weights(fh_ctx* ctx, const double* w);
 int fh_set_loss_softmax(fh_ctx* ctx, const int32_t* labels, uint64_t m);
 /* ---- prox term (kinds above); mu as in the closures, lo/hi for FH_PROX_BOX only              */
 int fh_set_prox(fh_ctx* ctx, int kind, double mu, double lo, double hi);
+/* read-only: which kernel the clipping-level search of FH_PROX_LINF / FH_PROX_L1BALL (csrc/fh_prox.h) takes for an unknown of n entries -- the ONE rule
+ * the launcher calls (csrc/fh_host_launch.h: level_shape_for), as a pure host function (no device needed), so that a test can assert the kernel it
+ * meant to reach.  out[FH_LEVEL_SHAPE_LEN]: [0] 1 = the search on several workgroups (k_level_search_multi), 0 = one workgroup (k_level_search),
+ * [1] threads per workgroup, [2] entries a thread keeps in registers (0: none, re-read in every pass), [3] workgroups.  FH_E_ARG unless 1 <= n < 2^31. */
+#define FH_LEVEL_SHAPE_LEN 4
+int fh_level_shape_for(uint64_t n, uint32_t* out);
 
 int fh_set_vector(fh_ctx* ctx, int which, const double* host, uint64_t len);
 int fh_get_vector(fh_ctx* ctx, int which, double* host, uint64_t len);
