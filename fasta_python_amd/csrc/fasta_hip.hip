@@ -1413,6 +1413,9 @@ static int setup_row_blocks(fh_ctx* c, double* scalars, bool* done) {
   scalars[FH_S_FSQ] = fsq;
   scalars[FH_S_DG2] = dg2;
   scalars[15] = 0.0;
+  // ... and into every block's host copy: the launch left each block's LOCAL loss sum and ||A_k^T A_k d||^2 there, and "every shard holds the same block"
+  // (collect_scalars) is what the rest of the library and fh_last_scalars go by
+  for (int k = 0; k < ns; ++k) { fh_ctx* s = shard_of(c, k); s->hscal[FH_S_FSQ] = fsq; s->hscal[FH_S_DG2] = dg2; s->hscal[15] = 0.0; }
   *done = true;
   return 0;
 }
@@ -2379,6 +2382,16 @@ extern "C" int fh_shard(fh_ctx* c, int k, fh_ctx** shard, uint64_t* row0, uint64
   const bool laid_out = !c->shards.empty() && c->shard_row0.size() == c->shards.size() + 1;
   if (row0) *row0 = laid_out ? c->shard_row0[(size_t)k] : 0;
   if (rows) *rows = laid_out ? shard_rows(c, k) : c->m;
+  return 0;
+}
+// read-only: the FH_S_* block the context's latest call left on the host, as it stands -- of a shard lent by fh_shard, that shard's own copy
+// (a shell's: shard 0's, what its calls return).  No launch; waits for the stream first.
+extern "C" int fh_last_scalars(fh_ctx* c, double* scalars) {
+  if (!c || !scalars) return fail(FH_E_ARG, "fh_last_scalars: null argument");
+  if (c->pending_step) return fail(FH_E_STATE, "a step issued by fh_step_begin is still in flight on this context: call fh_step_end first");
+  if (c->shards.empty()) FH_TRY(use_device(c));
+  FH_TRY(finish(c));
+  memcpy(scalars, shard_of(c, 0)->hscal, FH_NSCALARS * sizeof(double));
   return 0;
 }
 

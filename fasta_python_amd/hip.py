@@ -79,6 +79,7 @@ SIGNATURES = {
     "fh_create_ex": (_i32, [_i32, C.POINTER(_i32), _i32, C.POINTER(_ctx)]),
     "fh_shard_count": (_i32, [_ctx, C.POINTER(_i32)]),
     "fh_shard": (_i32, [_ctx, _i32, C.POINTER(_ctx), C.POINTER(_u64), C.POINTER(_u64)]),
+    "fh_last_scalars": (_i32, [_ctx, _pd]),
     "fh_destroy": (_i32, [_ctx]),
     "fh_sync": (_i32, [_ctx]),
     "fh_set_tuning": (_i32, [_ctx, _i32, C.c_longlong]),
@@ -567,6 +568,12 @@ class HipContext:
         self._call("fh_shard", int(k), C.byref(h), C.byref(r0), C.byref(rows))
         dev = self.devices[k] if self.devices else self.device
         return HipContext._borrowed(self.lib, h, dev, self.storage), int(r0.value), int(rows.value)
+
+    def last_scalars(self):
+        """The FH_S_* block the latest call left on this context (fh_last_scalars): of a shard view, that shard's own copy."""
+        out = np.empty(NSCALARS)
+        self._call("fh_last_scalars", out.ctypes.data_as(_pd))
+        return out
 
     # ---- lifetime ------------------------------------------------------------------------------
     def close(self):

@@ -197,6 +197,9 @@ int fh_create_ex(int ndev, const int* dev_ids, int dtype, fh_ctx** out);
  * replicated vector from every shard).                                                                                   */
 int fh_shard_count(fh_ctx* ctx, int* count);
 int fh_shard(fh_ctx* ctx, int k, fh_ctx** shard, uint64_t* row0, uint64_t* rows);
+/* read-only: the FH_S_* block (FH_NSCALARS doubles) the latest call left on the host side of `ctx` -- of a shard lent by fh_shard,
+ * that shard's own copy, which no other entry point returns (a multi-device context's calls return shard 0's).  No launch.      */
+int fh_last_scalars(fh_ctx* ctx, double* scalars);
 int fh_destroy(fh_ctx* ctx);
 int fh_sync(fh_ctx* ctx);
 int fh_set_tuning(fh_ctx* ctx, int key, long long value);

@@ -177,11 +177,31 @@ VECTOR_M, VECTOR_N = 2070, N_WIDE
 VECTOR_SLAB, VECTOR_CAP = 1032, 3            # mp = 2080: two slabs of 1032 rows and a last one of 16; 520 / R row groups on 3 workgroups
 
 
-def vector_cases():
+N_RAGGED_F32 = 1029                          # float32 storage: n % 4 = 1 and n % 32 = 5 -- a last four-column piece with one live column
+
+
+def vector_cases(storage="f64"):
     """(tuning, prox kind) of the exact step in the vector form: FH_TUNE_FWD_ROWS x FH_TUNE_NT_LOADS, then FH_TUNE_ADJ_CPT x NT x
-    FH_TUNE_ADJ_CYCLIC, all under the forced slab (a ragged last slab) and grid cap; the four exact prox kinds rotate."""
+    FH_TUNE_ADJ_CYCLIC, all under the forced slab (a ragged last slab) and grid cap; the four exact prox kinds rotate.
+
+    storage="f32": (tuning, prox kind, n) of k_fwd_dense<4|8, 1, KIND, 1> / k_adj_dense<1|2|4, 1, 1>.  Float32 storage loads non-temporally
+    whatever FH_TUNE_NT_LOADS says, so the axis is left out: every exact prox kind at every FH_TUNE_FWD_ROWS (16 launches the 8-row form: only
+    then is every row of Z written), FH_TUNE_ADJ_CPT x FH_TUNE_ADJ_CYCLIC, a width with n % 4 != 0 and n % 32 != 0 under the automatic
+    CPT (keyed on ld / 4) and one case with FH_TUNE_LD_PAD = 32."""
     base = {hip.TUNE_ADJ_SLAB_ROWS: VECTOR_SLAB, hip.TUNE_FWD_GRID_CAP: VECTOR_CAP}
     out = []
+    if storage == "f32":
+        for R in (4, 8, 16):
+            for kind in SL.PROX_KINDS:
+                out.append(({**base, hip.TUNE_FWD_ROWS: R}, kind, N_WIDE))
+        for cpt in (1, 2, 4):
+            for cyclic in (0, 1):
+                out.append(({**base, hip.TUNE_ADJ_CPT: cpt, hip.TUNE_ADJ_CYCLIC: cyclic}, SL.PROX_KINDS[len(out) % 4], N_WIDE))
+        out.append(({**base, hip.TUNE_FWD_ROWS: 4}, "box", N_RAGGED_F32))
+        out.append(({**base, hip.TUNE_FWD_ROWS: 8, hip.TUNE_ADJ_CPT: 2, hip.TUNE_ADJ_CYCLIC: 1}, "shrink", N_RAGGED_F32))
+        out.append(({**base, hip.TUNE_LD_PAD: 32, hip.TUNE_FWD_ROWS: 4, hip.TUNE_ADJ_CPT: 1}, "nonneg", N_WIDE))
+        return out
+    assert storage == "f64", storage
     for R in (4, 8, 16):
         for nt in (0, 1):
             out.append(({**base, hip.TUNE_FWD_ROWS: R, hip.TUNE_NT_LOADS: nt}, SL.PROX_KINDS[len(out) % 4]))
@@ -192,7 +212,14 @@ def vector_cases():
     return out
 
 
-TUNE_NAMES = {hip.TUNE_FWD_ROWS: "R", hip.TUNE_NT_LOADS: "nt", hip.TUNE_ADJ_CPT: "cpt", hip.TUNE_ADJ_CYCLIC: "cyclic"}
+def vector_level_cases(storage="f32"):
+    """(tuning, level prox) of k_fwd_dense<4|8, ., PX_LINF | PX_L1BALL, F32>: each once per rows-per-pass form, on tests/level_cases.py's
+    step problem at VECTOR_M x N_WIDE (the level falls exactly on 2, so the step stays exact)."""
+    base = {hip.TUNE_ADJ_SLAB_ROWS: VECTOR_SLAB, hip.TUNE_FWD_GRID_CAP: VECTOR_CAP}
+    return [({**base, hip.TUNE_FWD_ROWS: R}, prox) for R in (4, 8) for prox in ("linf", "l1ball")]
+
+
+TUNE_NAMES = {hip.TUNE_FWD_ROWS: "R", hip.TUNE_NT_LOADS: "nt", hip.TUNE_ADJ_CPT: "cpt", hip.TUNE_ADJ_CYCLIC: "cyclic", hip.TUNE_LD_PAD: "pad"}
 
 
 def vector_id(v):
