@@ -716,14 +716,8 @@ extern "C" int fh_nnz(fh_ctx* c, uint64_t* nnz) {
 
 extern "C" int fh_get_matrix_rows(fh_ctx* c, uint64_t row0, uint64_t nrows, double* out) {
   if (!c || !out) return fail(FH_E_ARG, "null argument");
-  if (c->op == OP_SPARSE) return fail(FH_E_STATE, "fh_get_matrix_rows: the sparse operator keeps no dense rows");
-  if (c->op == OP_STENCIL3D) return fail(FH_E_STATE, "fh_get_matrix_rows: the 3-D stencil operator keeps no dense rows");
-  if (c->op == OP_DCT) return fail(FH_E_STATE, "fh_get_matrix_rows: the DCT operator keeps no dense rows");
-  if (c->op == OP_CONV) return fail(FH_E_STATE, "fh_get_matrix_rows: the convolution operator keeps no dense rows");
-  if (c->op == OP_IDENTITY) return fail(FH_E_STATE, "fh_get_matrix_rows: the identity operator keeps no matrix");
-  if (c->op == OP_QUAD) return fail(FH_E_STATE, "fh_get_matrix_rows: the quadratic operator is not read back (the caller holds Q)");
-  if (c->op == OP_BILINEAR) return fail(FH_E_STATE, "fh_get_matrix_rows: the bilinear operator is not read back (the caller holds S)");
-  if (c->op != OP_DENSE) return fail(FH_E_STATE, "no dense matrix set");
+  const OpForm& f = form_of(c);
+  if (!(f.can & CAN_ROWS)) return f.no_rows ? fail(FH_E_STATE, "fh_get_matrix_rows: the %s %s", f.noun, f.no_rows) : fail(FH_E_STATE, "no dense matrix set");
   if (row0 + nrows > c->m) return fail(FH_E_ARG, "rows [%llu,%llu) out of range (m=%llu)", (unsigned long long)row0,
                                        (unsigned long long)(row0 + nrows), (unsigned long long)c->m);
   if (!c->shards.empty()) {          // shell: gather from the shards that hold the rows
@@ -1177,7 +1171,7 @@ extern "C" int fh_init(fh_ctx* c, double* scalars) {
     for (int k = 0; k < ns; ++k) {
       fh_ctx* s = shard_of(c, k);
       FH_TRY(use_device(s));
-      FH_TRY(op_fwd(s, 1, 0.0, s->X[s->xi], nullptr, nullptr, nullptr, nullptr, s->Z[s->zc], 1));
+      FH_TRY(op_fwd(s, apply_fwd_io(s->X[s->xi], s->Z[s->zc], 1)));
     }
     FH_TRY(reduce_fsq_over_ranks(c));
     for (int k = 0; k < ns; ++k) {
@@ -1473,7 +1467,7 @@ extern "C" int fh_gradient_at(fh_ctx* c, int src_vec, int dst_vec) {
       if (ok) return 0;
     }
     FH_TRY(use_device(s));
-    FH_TRY(op_fwd(s, 1, 0.0, src, nullptr, nullptr, nullptr, nullptr, s->zt, 1));
+    FH_TRY(op_fwd(s, apply_fwd_io(src, s->zt, 1)));
     AdjIO io = {s->zt, nullptr, 1, 0, 0.0, 1, 1.0, nullptr, nullptr, nullptr, nullptr, nullptr, dst};
     FH_TRY(adj_local(s, io));
   }
@@ -1724,14 +1718,8 @@ static int dense_step(fh_ctx* c, double tau, int accel, double coef, int restart
 // Writes the complete FH_S_* block; scalars[15] != 0 reports a spin timeout (results invalid: use the two-launch path).
 static int step_body(fh_ctx* c, double tau, double* scalars, bool wait) {
   FH_TRY(check_ready(c, true));
-  if (c->op == OP_SPARSE) return fail(FH_E_STATE, "fh_step: the sparse operator has no one-pass kernel: use fh_fwd / fh_adj / fh_fwd_adj / fh_iterate");
-  if (c->op == OP_STENCIL3D) return fail(FH_E_STATE, "fh_step: the 3-D stencil operator has no one-pass kernel: use fh_fwd / fh_adj / fh_fwd_adj / fh_iterate");
-  if (c->op == OP_DCT) return fail(FH_E_STATE, "fh_step: the DCT operator has no one-pass kernel: use fh_fwd / fh_adj / fh_fwd_adj / fh_iterate");
-  if (c->op == OP_CONV) return fail(FH_E_STATE, "fh_step: the convolution operator has no one-pass kernel: use fh_fwd / fh_adj / fh_fwd_adj / fh_iterate");
-  if (c->op == OP_IDENTITY) return fail(FH_E_STATE, "fh_step: the identity operator has no one-pass kernel: use fh_fwd / fh_adj / fh_fwd_adj / fh_iterate");
-  if (c->op == OP_QUAD) return fail(FH_E_STATE, "fh_step: the quadratic operator has no one-pass kernel: use fh_fwd / fh_adj / fh_fwd_adj / fh_iterate");
-  if (c->op == OP_BILINEAR) return fail(FH_E_STATE, "fh_step: the bilinear operator has no one-pass kernel: use fh_fwd / fh_adj / fh_fwd_adj / fh_iterate");
-  if (c->LB) return fail(FH_E_STATE, "fh_step: the multi-column form (fh_set_rhs) has no one-pass kernel: use fh_fwd / fh_adj / fh_iterate");
+  FH_TRY(check_can(c, CAN_STEP, "fh_step: the %s has no one-pass kernel: use fh_fwd / fh_adj / fh_fwd_adj / fh_iterate",
+                   "fh_step: the multi-column form (fh_set_rhs) has no one-pass kernel: use fh_fwd / fh_adj / fh_iterate"));
   for (int k = 0; k < nshards(c); ++k) FH_TRY(not_lazy(shard_of(c, k), "fh_step"));
   if (c->op == OP_STENCIL) {
     if (row_sharded(c)) return fail(FH_E_STATE, "row sharding is implemented for the dense operator only");
@@ -1776,14 +1764,8 @@ extern "C" int fh_step_end(fh_ctx* c, double* scalars) {
 // travels to the separate n-side epilogue through a device scalar.
 extern "C" int fh_step_accel(fh_ctx* c, double tau, double coef, int restart, double* scalars) {
   FH_TRY(check_ready(c, true));
-  if (c->op == OP_SPARSE) return fail(FH_E_STATE, "fh_step_accel: the sparse operator has no one-pass kernel: use fh_fwd / fh_adj / fh_iterate");
-  if (c->op == OP_STENCIL3D) return fail(FH_E_STATE, "fh_step_accel: the 3-D stencil operator has no one-pass kernel: use fh_fwd / fh_adj / fh_iterate");
-  if (c->op == OP_DCT) return fail(FH_E_STATE, "fh_step_accel: the DCT operator has no one-pass kernel: use fh_fwd / fh_adj / fh_iterate");
-  if (c->op == OP_CONV) return fail(FH_E_STATE, "fh_step_accel: the convolution operator has no one-pass kernel: use fh_fwd / fh_adj / fh_iterate");
-  if (c->op == OP_IDENTITY) return fail(FH_E_STATE, "fh_step_accel: the identity operator has no one-pass kernel: use fh_fwd / fh_adj / fh_iterate");
-  if (c->op == OP_QUAD) return fail(FH_E_STATE, "fh_step_accel: the quadratic operator has no one-pass kernel: use fh_fwd / fh_adj / fh_iterate");
-  if (c->op == OP_BILINEAR) return fail(FH_E_STATE, "fh_step_accel: the bilinear operator has no one-pass kernel: use fh_fwd / fh_adj / fh_iterate");
-  if (c->LB) return fail(FH_E_STATE, "fh_step_accel: the multi-column form (fh_set_rhs) has no one-pass kernel: use fh_fwd / fh_adj / fh_iterate");
+  FH_TRY(check_can(c, CAN_STEP, "fh_step_accel: the %s has no one-pass kernel: use fh_fwd / fh_adj / fh_iterate",
+                   "fh_step_accel: the multi-column form (fh_set_rhs) has no one-pass kernel: use fh_fwd / fh_adj / fh_iterate"));
   if (c->op == OP_STENCIL) {
     if (row_sharded(c)) return fail(FH_E_STATE, "row sharding is implemented for the dense operator only");
     if (!c->lazy) {      // first accelerated one-pass step after fh_init: x0 = X[xi] (c = 0), z(x0) = Z[zc], best = x0
@@ -1958,14 +1940,7 @@ extern "C" int fh_run(fh_ctx* c, int max_steps, const fh_run_opts* o, fh_run_sta
   if (max_steps < 0 || max_steps > 65536) return fail(FH_E_ARG, "fh_run: max_steps must be in [0, 65536]");
   if (o->window < 1 || o->window > FH_RUN_WINDOW_MAX) return fail(FH_E_ARG, "fh_run: window must be in [1, %d]", FH_RUN_WINDOW_MAX);
   if (o->stop_rule < 0 || o->stop_rule > 3) return fail(FH_E_ARG, "fh_run: stop_rule must be 0..3 (the four rules of fasta/stopping.py)");
-  if (c->op == OP_SPARSE) return fail(FH_E_STATE, "fh_run: the sparse operator has no device-side loop: use fh_iterate");
-  if (c->op == OP_STENCIL3D) return fail(FH_E_STATE, "fh_run: the 3-D stencil operator has no device-side loop: use fh_iterate");
-  if (c->op == OP_DCT) return fail(FH_E_STATE, "fh_run: the DCT operator has no device-side loop: use fh_iterate");
-  if (c->op == OP_CONV) return fail(FH_E_STATE, "fh_run: the convolution operator has no device-side loop: use fh_iterate");
-  if (c->op == OP_IDENTITY) return fail(FH_E_STATE, "fh_run: the identity operator has no device-side loop: use fh_iterate");
-  if (c->op == OP_QUAD) return fail(FH_E_STATE, "fh_run: the quadratic operator has no device-side loop: use fh_iterate");
-  if (c->op == OP_BILINEAR) return fail(FH_E_STATE, "fh_run: the bilinear operator has no device-side loop: use fh_iterate");
-  if (c->LB) return fail(FH_E_STATE, "fh_run: the multi-column form (fh_set_rhs) has no device-side loop: use fh_iterate");
+  FH_TRY(check_can(c, CAN_RUN, "fh_run: the %s has no device-side loop: use fh_iterate", "fh_run: the multi-column form (fh_set_rhs) has no device-side loop: use fh_iterate"));
   const RunShape sh = run_shape(c);
   const RunEntry* e = sh.e;
   if (!e && chain_ok(c) && co_resident(c)) return run_chain(c, max_steps, o, state, history, steps_done);
@@ -2037,7 +2012,7 @@ static int run_adopt(fh_ctx* c, const fh_run_opts* o, const RunState* hs, double
     c->run_timeouts += 1;
     // One corner: a workgroup whose wait ended in time may have begun the NEXT attempt before it ran into the missing one, and then its rows of
     // that attempt's z target -- the completed iteration's z_accel0, which only FISTA reads -- are overwritten.  z_accel0 = A x_accel0: form it again.
-    if (o->accelerate) FH_TRY(op_fwd(c, 1, 0.0, c->P[c->pc], nullptr, nullptr, nullptr, nullptr, c->Z[c->zc], 0));
+    if (o->accelerate) FH_TRY(op_fwd(c, apply_fwd_io(c->P[c->pc], c->Z[c->zc], 0)));
     FH_TRY(finish(c));
     return fail(FH_E_TIMEOUT, "fh_run: a grid barrier / team hand-off of %s timed out after %d completed iterations (workgroups not co-resident?); "
                               "the state of the last completed iteration is in place -- continue with fh_iterate / fh_step", what, done);
@@ -2149,7 +2124,7 @@ extern "C" int fh_commit(fh_ctx* c, int save_best) {
 
 extern "C" int fh_apply(fh_ctx* c, int adjoint, const double* in, double* out) {
   FH_TRY(check_ready(c, false));
-  if (c->op == OP_BILINEAR) return fail(FH_E_STATE, "fh_apply: the bilinear operator has no linear map to apply (A is the identity; S enters through the smooth term: fh_gradient_at)");
+  if (form_of(c).no_apply) return fail(FH_E_STATE, form_of(c).no_apply, form_of(c).noun);
   if (!in || !out) return fail(FH_E_ARG, "null argument");
   const int ns = nshards(c);
   const bool shell = !c->shards.empty();
@@ -2160,7 +2135,7 @@ extern "C" int fh_apply(fh_ctx* c, int adjoint, const double* in, double* out) {
     if (s->op == OP_QUAD) adjoint = 0;                     // Q is symmetric: both flags are out = Q in
     if (!adjoint) {
       FH_TRY(copy_in(s, s->T[3], in, s->n));
-      FH_TRY(op_fwd(s, 1, 0.0, s->T[3], nullptr, nullptr, nullptr, nullptr, s->zt, 0));
+      FH_TRY(op_fwd(s, apply_fwd_io(s->T[3], s->zt, 0)));
       FH_TRY(copy_out(s, out + r0, s->zt, s->m));
     } else {
       FH_TRY(copy_in(s, s->zt, in + r0, s->m));
@@ -2192,14 +2167,7 @@ extern "C" int fh_comm_unique_id(void* id128) {
 extern "C" int fh_comm_init(fh_ctx* c, int nranks, int rank, const void* id128) {
   if (!c || !id128) return fail(FH_E_ARG, "null argument");
   if (nranks < 1 || rank < 0 || rank >= nranks) return fail(FH_E_ARG, "bad rank %d of %d", rank, nranks);
-  if (c->op == OP_SPARSE) return fail(FH_E_STATE, "fh_comm_init: a context with a sparse operator cannot be row-sharded");
-  if (c->op == OP_STENCIL3D) return fail(FH_E_STATE, "fh_comm_init: a context with a 3-D stencil operator cannot be row-sharded");
-  if (c->op == OP_DCT) return fail(FH_E_STATE, "fh_comm_init: a context with a DCT operator cannot be row-sharded");
-  if (c->op == OP_CONV) return fail(FH_E_STATE, "fh_comm_init: a context with a convolution operator cannot be row-sharded");
-  if (c->op == OP_IDENTITY) return fail(FH_E_STATE, "fh_comm_init: a context with the identity operator cannot be row-sharded");
-  if (c->op == OP_QUAD) return fail(FH_E_STATE, "fh_comm_init: a context with a quadratic operator cannot be row-sharded");
-  if (c->op == OP_BILINEAR) return fail(FH_E_STATE, "fh_comm_init: a context with a bilinear operator cannot be row-sharded");
-  if (c->LB) return fail(FH_E_STATE, "fh_comm_init: a context in multi-column form (fh_set_rhs) cannot be row-sharded");
+  FH_TRY(check_can(c, CAN_SHARD, "fh_comm_init: a context with %s cannot be row-sharded", "fh_comm_init: a context in multi-column form (fh_set_rhs) cannot be row-sharded", true));
   if (!c->shards.empty() || c->owner)
     return fail(FH_E_STATE, "fh_comm_init: a multi-device context (fh_create_ex, ndev > 1) already shards the rows in-process");
   FH_TRY(rccl_load());
@@ -2398,14 +2366,9 @@ extern "C" int fh_last_scalars(fh_ctx* c, double* scalars) {
 extern "C" int fh_stream_read_ms(fh_ctx* c, int reps, double* ms_per_pass, uint64_t* bytes_per_pass) {
   FH_TRY(check_ready(c, false));
   if (!c->shards.empty()) return fh_stream_read_ms(c->shards[0], reps, ms_per_pass, bytes_per_pass);     // shard 0's block on its device
-  if (c->op == OP_SPARSE) return fail(FH_E_STATE, "fh_stream_read_ms: the stream-read ceiling is measured on a dense matrix, not on the sparse operator");
-  if (c->op == OP_STENCIL3D) return fail(FH_E_STATE, "fh_stream_read_ms: the stream-read ceiling is measured on a dense matrix, not on the 3-D stencil operator");
-  if (c->op == OP_DCT) return fail(FH_E_STATE, "fh_stream_read_ms: the stream-read ceiling is measured on a dense matrix, not on the DCT operator");
-  if (c->op == OP_CONV) return fail(FH_E_STATE, "fh_stream_read_ms: the stream-read ceiling is measured on a dense matrix, not on the convolution operator");
-  if (c->op == OP_IDENTITY) return fail(FH_E_STATE, "fh_stream_read_ms: the stream-read ceiling is measured on a dense matrix, not on the identity operator");
-  if (c->op == OP_QUAD) return fail(FH_E_STATE, "fh_stream_read_ms: the stream-read ceiling is measured on a dense matrix, not on the quadratic operator");
-  if (c->op == OP_BILINEAR) return fail(FH_E_STATE, "fh_stream_read_ms: the stream-read ceiling is measured on a dense matrix, not on the bilinear operator");
-  if (c->op != OP_DENSE) return fail(FH_E_STATE, "stream-read ceiling needs a dense matrix");
+  const OpForm& f = form_of(c);
+  if (!(f.can & CAN_ROWS)) return f.no_rows ? fail(FH_E_STATE, "fh_stream_read_ms: the stream-read ceiling is measured on a dense matrix, not on the %s", f.noun)
+                                            : fail(FH_E_STATE, "stream-read ceiling needs a dense matrix");
   if (reps < 1) reps = 1;
   // k_stream_probe<16,1> as described in include/fasta_hip.h: persistent workgroups, 1 per CU by default, three rotating buffers of 16 nt loads per lane
   const uint64_t npieces = c->mp * (c->ld / (c->f32 ? 4 : 2));

@@ -314,9 +314,18 @@ static inline bool row_sharded(const fh_ctx* c) { return c->comm != nullptr || c
 // A form is c->op plus whether the unknown has columns (c->LB); the DCT operator is one form in both geometries.  Every entry point that accepts
 // or refuses a prox kind, a loss or a column count asks a row of kForms, and so does every launch-time backstop; the sentences a caller reads
 // stand here, whole, as they always were (the lists in parentheses included: they are behaviour).  A sentence may take the noun as %s.
+// What a form can do beyond fwd / adj is a bit of `can`: a row that does not say so is refused by every entry point that asks (check_can), each
+// in its own sentence with the row's noun; a new form is refused everywhere until its row says otherwise.  The launchers of a form: kLaunch,
+// fh_host_launch.h.
+enum { CAN_STEP = 1, CAN_RUN = 2, CAN_SHARD = 4, CAN_ROWS = 8 };      // the one-pass step; the device-side loop; row sharding; dense rows to read
 enum { F_NONE, F_DENSE, F_DENSE_MC, F_STENCIL, F_SPARSE, F_SPARSE_MC, F_STENCIL3D, F_QUAD, F_BILINEAR, F_DCT, F_IDENTITY, F_CONV, F_COUNT };
 struct OpForm {
   const char* noun;          // as the sentences name it, without its article
+  const char* article;       // ... which fh_comm_init puts in front of it
+  unsigned can;              // bits of CAN_*
+  bool by_columns;           // an entry point that refuses answers with its sentence about the multi-column form, not with the noun's
+  const char* no_rows;       // without CAN_ROWS: why fh_get_matrix_rows has nothing to read (nullptr: the entry points' sentences without a noun)
+  const char* no_apply;      // fh_apply (noun; nullptr: the form is a linear map)
   unsigned prox;             // bits of FH_PROX_*: the kinds fh_set_prox accepts on this form and a setter of it keeps
   unsigned prox_run;         // ... the kinds its forward launch lets through, where that is another set (0 = the same)
   unsigned losses;           // bits of LOSS_*: what fh_set_loss_* may give it (0: it has no loss to set)
@@ -349,42 +358,57 @@ static const char kRhsSparse[] = "fh_set_rhs: the sparse operator has no multi-c
 static const char kRhsNone[] = "fh_set_rhs: the %s has no multi-column form";
 static const char kF32NoMatrix[] = "%s: float32 storage is a storage mode of a dense matrix; the %s stores no matrix and computes in float64";
 static const char kF32HasNo[] = "%s: float32 storage has no %s";
+static const char kNoApply[] = "fh_apply: the %s has no linear map to apply (A is the identity; S enters through the smooth term: fh_gradient_at)";
 static const OpForm kForms[F_COUNT] = {
-  // F_NONE: what an empty context may hold for the operator to come (free_operator drops every other kind)
-  {"operator", KINDS_ELEM | KINDS_LEVEL | KIND(TVBALL) | KIND(GROUP), 0, 0, false, false, nullptr, nullptr, "set the operator before the loss", nullptr, nullptr,
+  // F_NONE: what an empty context may hold for the operator to come (free_operator drops every other kind); a communicator may come before the operator
+  {"operator", "an", CAN_SHARD, false, nullptr, nullptr,
+   KINDS_ELEM | KINDS_LEVEL | KIND(TVBALL) | KIND(GROUP), 0, 0, false, false, nullptr, nullptr, "set the operator before the loss", nullptr, nullptr,
    "fh_set_rhs: set the dense operator first (fh_set_matrix / fh_generate_matrix)", nullptr, false},
   // F_DENSE: accepts the TV-ball kind and refuses it at launch; its launch refuses nothing else
-  {"dense operator", KINDS_ELEM | KINDS_LEVEL | KIND(TVBALL), KINDS_ALL & ~KIND(TVBALL), LOSSES_ELEM, false, false, nullptr, "TV-ball prox needs the stencil operator", nullptr, nullptr,
+  {"dense operator", "a", CAN_STEP | CAN_RUN | CAN_SHARD | CAN_ROWS, false, nullptr, nullptr,
+   KINDS_ELEM | KINDS_LEVEL | KIND(TVBALL), KINDS_ALL & ~KIND(TVBALL), LOSSES_ELEM, false, false, nullptr, "TV-ball prox needs the stencil operator", nullptr, nullptr,
    kSoftmaxMc, nullptr, nullptr, true},
-  {"dense operator", KINDS_ELEM | KIND(GROUP), 0, LOSSES_MC, false, false, kNoProxMc, "prox kind %d has no multi-column form", kNoLogisticMc, kMcLsqOnly, nullptr, nullptr, nullptr, true},
-  // F_STENCIL: accepts what the dense form accepts, runs the TV-ball prox or none
-  {"stencil operator", KINDS_ELEM | KINDS_LEVEL | KIND(TVBALL), KIND(IDENTITY) | KIND(TVBALL), LOSSBIT(LOSS_LSQ), false, false, nullptr,
+  {"dense operator", "a", CAN_ROWS, true, nullptr, nullptr,
+   KINDS_ELEM | KIND(GROUP), 0, LOSSES_MC, false, false, kNoProxMc, "prox kind %d has no multi-column form", kNoLogisticMc, kMcLsqOnly, nullptr, nullptr, nullptr, true},
+  // F_STENCIL: accepts what the dense form accepts, runs the TV-ball prox or none; fh_run and fh_comm_init let it pass (the loop then finds no kernel for it
+  // and says so in its own words; a row-sharded launch refuses)
+  {"stencil operator", "a", CAN_STEP | CAN_RUN | CAN_SHARD, false, nullptr, nullptr,
+   KINDS_ELEM | KINDS_LEVEL | KIND(TVBALL), KIND(IDENTITY) | KIND(TVBALL), LOSSBIT(LOSS_LSQ), false, false, nullptr,
    "the stencil operator supports the TV-ball prox or no prox (got kind %d)", "the logistic loss is implemented for the dense operator", nullptr, kSoftmaxOps, kRhsNone, nullptr, false},
-  {"sparse operator", KINDS_ELEM, 0, LOSSES_ELEM, false, false, "prox kind %d (LINF / L1BALL / TVBALL / GROUP) is not implemented for the %s", nullptr, nullptr, nullptr, kSoftmaxMc, kRhsSparse,
+  {"sparse operator", "a", 0, false, "keeps no dense rows", nullptr,
+   KINDS_ELEM, 0, LOSSES_ELEM, false, false, "prox kind %d (LINF / L1BALL / TVBALL / GROUP) is not implemented for the %s", nullptr, nullptr, nullptr, kSoftmaxMc, kRhsSparse,
    "%s: float32 storage is not implemented for the %s", true},
-  {"sparse operator", KINDS_ELEM | KIND(GROUP), 0, LOSSES_MC, false, false, kNoProxMc, "prox kind %d has no multi-column form", kNoLogisticMc, kMcLsqOnly, nullptr, kRhsSparse,
+  {"sparse operator", "a", 0, false, "keeps no dense rows", nullptr,
+   KINDS_ELEM | KIND(GROUP), 0, LOSSES_MC, false, false, kNoProxMc, "prox kind %d has no multi-column form", kNoLogisticMc, kMcLsqOnly, nullptr, kRhsSparse,
    "%s: float32 storage is not implemented for the %s", true},
-  {"3-D stencil operator", KINDS_ELEM | KIND(TVBALL), 0, LOSSBIT(LOSS_LSQ), false, false, "prox kind %d (LINF / L1BALL / GROUP) is not implemented for the %s", nullptr, kLsqOnly, nullptr, kSoftmaxOps,
+  {"3-D stencil operator", "a", 0, false, "keeps no dense rows", nullptr,
+   KINDS_ELEM | KIND(TVBALL), 0, LOSSBIT(LOSS_LSQ), false, false, "prox kind %d (LINF / L1BALL / GROUP) is not implemented for the %s", nullptr, kLsqOnly, nullptr, kSoftmaxOps,
    kRhsNone, nullptr, false},
-  {"quadratic operator", KINDS_ELEM | KIND(GROUP) | KIND(ROWBALL), 0, 0, false, false, "prox kind %d (LINF / L1BALL / TVBALL) has no quadratic form", nullptr,
+  {"quadratic operator", "a", 0, false, "is not read back (the caller holds Q)", nullptr,
+   KINDS_ELEM | KIND(GROUP) | KIND(ROWBALL), 0, 0, false, false, "prox kind %d (LINF / L1BALL / TVBALL) has no quadratic form", nullptr,
    "the quadratic operator carries its own loss (Q and the linear term of fh_set_quadratic): fh_set_loss_lsq / fh_set_loss_logistic do not apply", nullptr, kSoftmaxOps,
    "fh_set_rhs: the column count of a quadratic operator is fixed when it is set (fh_set_quadratic)", kF32HasNo, false},
-  {"bilinear operator", KINDS_ELEM | KIND(ROWSPLIT), 0, 0, false, true, "prox kind %d (LINF / L1BALL / TVBALL / GROUP / ROWBALL) has no bilinear form", nullptr,
+  {"bilinear operator", "a", 0, false, "is not read back (the caller holds S)", kNoApply,
+   KINDS_ELEM | KIND(ROWSPLIT), 0, 0, false, true, "prox kind %d (LINF / L1BALL / TVBALL / GROUP / ROWBALL) has no bilinear form", nullptr,
    "the bilinear operator carries its own loss (S of fh_set_factorization): fh_set_loss_lsq / fh_set_loss_logistic do not apply", nullptr, kSoftmaxOps,
    "fh_set_rhs: the column count of a bilinear operator is fixed when it is set (fh_set_factorization)", kF32HasNo, false},
-  {"DCT operator", KINDS_ELEM | KINDS_LEVEL, 0, LOSSBIT(LOSS_LSQ), false, false, "prox kind %d (TVBALL / GROUP) is not implemented for the %s", nullptr, kLsqOnly, nullptr, kSoftmaxOps, kRhsNone, kF32NoMatrix, true},
-  {"identity operator", KINDS_ELEM | KIND(NUCLEAR) | KIND(NUCBALL), 0, LOSSES_ELEM, true, true, "prox kind %d (LINF / L1BALL / TVBALL / GROUP / ROWBALL) is not implemented for the %s",
+  {"DCT operator", "a", 0, false, "keeps no dense rows", nullptr,
+   KINDS_ELEM | KINDS_LEVEL, 0, LOSSBIT(LOSS_LSQ), false, false, "prox kind %d (TVBALL / GROUP) is not implemented for the %s", nullptr, kLsqOnly, nullptr, kSoftmaxOps, kRhsNone, kF32NoMatrix, true},
+  {"identity operator", "the", 0, false, "keeps no matrix", nullptr,
+   KINDS_ELEM | KIND(NUCLEAR) | KIND(NUCBALL), 0, LOSSES_ELEM, true, true, "prox kind %d (LINF / L1BALL / TVBALL / GROUP / ROWBALL) is not implemented for the %s",
    "prox kind %d (LINF / L1BALL / TVBALL / GROUP / ROWBALL / ROWSPLIT) is not implemented for the %s", nullptr, nullptr, kSoftmaxOps,
    "fh_set_rhs: the %s has no multi-column form (its unknown is already an (M, N) matrix: fh_set_identity)", kF32NoMatrix, false},
-  {"convolution operator", KINDS_ELEM | KINDS_LEVEL, 0, LOSSBIT(LOSS_LSQ), false, false, "prox kind %d (TVBALL / GROUP) is not implemented for the %s", nullptr, kLsqOnly, nullptr, kSoftmaxOps, kRhsNone, kF32NoMatrix, true},
+  {"convolution operator", "a", 0, false, "keeps no dense rows", nullptr,
+   KINDS_ELEM | KINDS_LEVEL, 0, LOSSBIT(LOSS_LSQ), false, false, "prox kind %d (TVBALL / GROUP) is not implemented for the %s", nullptr, kLsqOnly, nullptr, kSoftmaxOps, kRhsNone, kF32NoMatrix, true},
 };
 #undef KIND
 #undef LOSSBIT
-static inline const OpForm& form_of(const fh_ctx* c) {
+static inline int form_index(const fh_ctx* c) {
   static const int of_op[] = {F_NONE, F_DENSE, F_STENCIL, F_SPARSE, F_STENCIL3D, F_QUAD, F_BILINEAR, F_DCT, F_IDENTITY, F_CONV};      // by OP_*
   const int f = of_op[c->op];
-  return kForms[c->LB && (f == F_DENSE || f == F_SPARSE) ? f + 1 : f];
+  return c->LB && (f == F_DENSE || f == F_SPARSE) ? f + 1 : f;
 }
+static inline const OpForm& form_of(const fh_ctx* c) { return kForms[form_index(c)]; }
 static inline bool serves_prox(const OpForm& f, int kind) { return kind >= 0 && kind < 32 && (f.prox >> kind & 1u); }
 static inline bool runs_prox(const OpForm& f, int kind) { return kind >= 0 && kind < 32 && ((f.prox_run ? f.prox_run : f.prox) >> kind & 1u); }
 static inline bool takes_loss(const OpForm& f, int loss) { return loss >= 0 && loss < 32 && (f.losses >> loss & 1u); }
@@ -401,6 +425,16 @@ static int check_prox_run(const fh_ctx* c) {
 static int check_loss_run(const fh_ctx* c) {
   const OpForm& f = form_of(c);
   return takes_loss(f, c->loss_kind) ? 0 : fail(FH_E_STATE, f.no_loss_run ? f.no_loss_run : f.no_loss, f.noun);
+}
+// an entry point beyond fwd / adj on a form whose row lacks `cap`: the entry point's own sentence with the noun (with_article: "a sparse operator"),
+// or the one it has for the multi-column form
+static int check_can(const fh_ctx* c, unsigned cap, const char* sentence, const char* sentence_columns, bool with_article = false) {
+  const OpForm& f = form_of(c);
+  if (f.can & cap) return 0;
+  if (f.by_columns) return fail(FH_E_STATE, "%s", sentence_columns);
+  char name[64];
+  snprintf(name, sizeof name, "%s%s%s", with_article ? f.article : "", with_article ? " " : "", f.noun);
+  return fail(FH_E_STATE, sentence, name);
 }
 // a context about to change its operator, or with none: the prox kinds and the loss its next operator cannot be assumed to serve go
 static inline void reset_unserved(fh_ctx* c, const OpForm& next) {
@@ -841,10 +875,17 @@ static int copy_out(fh_ctx* c, double* host, const double* dev, uint64_t rows) {
   return 0;
 }
 
-static int launch_fwd_tv(fh_ctx* c, int mode, double tau, const double* x0, const double* g0, const double* xacc0,
-                         double* xhat, double* xp, double* z, int sub_b);      // fh_host_launch.h
+// the operands of a forward launch (launch_fwd_*, op_fwd: fh_host_launch.h), as AdjIO holds the adjoint's.  mode 0: z = A prox(x0 - tau g0),
+// with xhat, xp and the n-side sums; mode 1: z = A x0.  sub_b: subtract b and sum the loss
+struct FwdIO {
+  int mode; double tau;
+  const double* x0; const double* g0; const double* xacc0; double* xhat; double* xp; double* z; int sub_b;
+};
+// "apply to this vector": z = A x (the solver-state operands: solver_fwd_io, fh_host_launch.h)
+static inline FwdIO apply_fwd_io(const double* x, double* z, int sub_b) { return FwdIO{1, 0.0, x, nullptr, nullptr, nullptr, nullptr, z, sub_b}; }
+static int launch_fwd_tv(fh_ctx* c, const FwdIO& io);      // fh_host_launch.h
 // z = div(x) into `z` (plain stencil pass; the scalar block is scratch afterwards)
-static int tv_image(fh_ctx* c, const double* x, double* z) { return launch_fwd_tv(c, 1, 0.0, x, nullptr, nullptr, nullptr, nullptr, z, 0); }
+static int tv_image(fh_ctx* c, const double* x, double* z) { return launch_fwd_tv(c, apply_fwd_io(x, z, 0)); }
 // the two-launch stencil kernels read the stored image of x0: bring it up to date after z-free steps
 static int tv_refresh_zcur(fh_ctx* c) {
   if (c->op != OP_STENCIL || !c->zcur_stale) return 0;

@@ -49,23 +49,22 @@ static void launch_fwd_r(fh_ctx* c, const FwdP& p, unsigned grid, int kind) {
 }
 
 // z := A * (mode 0: prox(x0 - tau g0) ; mode 1: x0) on the dense operator
-static int launch_fwd_dense(fh_ctx* c, int mode, double tau, const double* x0, const double* g0, const double* xacc0,
-                            double* xhat, double* xp, double* z, int sub_b) {
+static int launch_fwd_dense(fh_ctx* c, const FwdIO& io) {
   // rows per pass (sweep, profiles/r01_tune_sizes.txt): 4 up to n = 32768, 8 beyond
   // float32 storage: the x0/g0 pieces of a trip are twice as many per byte of A, so it takes 8 rows per pass from n = 32768 on
   // to keep as many bytes of A in flight (4 rows: 4.7 TB/s at 65536^2, profiles/r02_f32_storage.txt)
   int R = c->fwd_rows ? c->fwd_rows : (c->ld <= (c->f32 ? 16384u : 32768u) ? 4 : 8);
   if (c->f32 && R == 16) R = 8;
-  if (mode == 0) FH_TRY(check_prox_run(c));
+  if (io.mode == 0) FH_TRY(check_prox_run(c));
   FwdP p;
   p.A = c->A; p.ld = c->ld; p.ld2 = (uint32_t)(c->ld / (c->f32 ? 4 : 2)); p.nv2 = (uint32_t)(c->nv / 2); p.n = (uint32_t)c->n; p.m = (uint32_t)c->m;
   p.nrg = (uint32_t)(c->mp / R);
   p.nchunks = (p.nv2 + FH_WG - 1) / FH_WG;
-  p.x0 = x0; p.g0 = g0; p.xacc0 = xacc0; p.xhat = xhat; p.xp = xp;
-  p.b = c->b; p.z = z; p.tau = tau; p.sub_b = sub_b; p.loss = c->loss_kind;
-  p.px = make_prox(c, tau);
-  const int kind = mode == 0 ? c->prox_kind : (int)PX_PLAIN;
-  unsigned grid = std::max(p.nrg, mode == 0 ? p.nchunks : 1u);
+  p.x0 = io.x0; p.g0 = io.g0; p.xacc0 = io.xacc0; p.xhat = io.xhat; p.xp = io.xp;
+  p.b = c->b; p.z = io.z; p.tau = io.tau; p.sub_b = io.sub_b; p.loss = c->loss_kind;
+  p.px = make_prox(c, io.tau);
+  const int kind = io.mode == 0 ? c->prox_kind : (int)PX_PLAIN;
+  unsigned grid = std::max(p.nrg, io.mode == 0 ? p.nchunks : 1u);
   // measured on MI355X (profiles/r01_tune_dense.txt, r01_tune_sizes.txt): 2 persistent workgroups per CU
   // grid-striding over the row groups beat one workgroup per row group by 5-12 %
   grid = (unsigned)std::min<long long>(grid, c->fwd_cap > 0 ? c->fwd_cap : 512);
@@ -266,41 +265,40 @@ static int launch_sm_rows(fh_ctx* c, const double* z, const double* zacc0, int a
 }
 
 // Z := A * (mode 0: prox(X0 - tau G0), by the prologue launch ; mode 1: X0) for LB columns from one read of A
-static int launch_fwd_multi(fh_ctx* c, int mode, double tau, const double* x0, const double* g0, const double* xacc0,
-                            double* xhat, double* xp, double* z, int sub_b) {
+static int launch_fwd_multi(fh_ctx* c, const FwdIO& io) {
   const McShape sh = mc_shape(c);
   const McEntry* e = sh.e;
   if (!e) return fail(FH_E_STATE, "multi-column form: no kernel for %u columns per row", c->LB);
   FH_TRY(check_loss_run(c));
-  if (mode == 0) FH_TRY(check_prox_run(c));
-  const bool sm = sm_on(c, sub_b);                // K-fwd's sum of squares means nothing then: the row pass behind it writes FH_S_FSQ and publishes
+  if (io.mode == 0) FH_TRY(check_prox_run(c));
+  const bool sm = sm_on(c, io.sub_b);             // K-fwd's sum of squares means nothing then: the row pass behind it writes FH_S_FSQ and publishes
   McFwdP p;
   p.A = c->A; p.ld2 = sh.ld2; p.m = (uint32_t)c->m; p.L = c->L;
   p.nrg = sh.nrg;
-  const uint32_t npro = mode == 0 ? sh.npro : 0u;
+  const uint32_t npro = io.mode == 0 ? sh.npro : 0u;
   p.nred_n = npro;
   const unsigned grid = sh.fwd_grid;
   FH_TRY(ensure_ws(c, ((size_t)npro * 8 + grid + (sm ? sm_records(c) : 0u)) * sizeof(double)));
   p.red_n = c->ws; p.red_m = c->ws + (size_t)npro * 8;
   p.x = c->xs;                      // the operand in K-fwd's streaming layout: written by the prologue, or packed from a plain operand below
-  p.b = c->b; p.z = z; p.sub_b = sub_b;
+  p.b = c->b; p.z = io.z; p.sub_b = io.sub_b;
   p.counter = c->counters + CNT_FWD;
   p.out = scalar_out(c);
   t_begin(c, FH_K_FWD);
-  if (mode == 0) {
+  if (io.mode == 0) {
     McProP q;
     q.n = (uint32_t)c->n; q.L = c->L; q.nv = (uint32_t)c->nv;
-    q.x0 = x0; q.g0 = g0; q.xacc0 = xacc0; q.xhat = xhat; q.xp = xp; q.tau = tau;
+    q.x0 = io.x0; q.g0 = io.g0; q.xacc0 = io.xacc0; q.xhat = io.xhat; q.xp = io.xp; q.tau = io.tau;
     q.xs = c->xs; q.ld2 = p.ld2;
-    q.px = make_prox(c, tau);
+    q.px = make_prox(c, io.tau);
     q.red_n = c->ws;
     e->pro<<<dim3(npro), dim3(FH_WG), 0, c->stream>>>(q);
   } else {
-    e->pack<<<dim3(sh.npro), dim3(FH_WG), 0, c->stream>>>(x0, c->xs, (uint32_t)c->nv, p.ld2);
+    e->pack<<<dim3(sh.npro), dim3(FH_WG), 0, c->stream>>>(io.x0, c->xs, (uint32_t)c->nv, p.ld2);
   }
   p.seq = sm ? 0u : seq_offer(c);
   e->fwd[sh.nt]<<<dim3(grid), dim3(FH_WG), 0, c->stream>>>(p);
-  if (sm) FH_TRY(launch_sm_rows(c, z, nullptr, 0, 0.0, nullptr, p.red_m + grid, true, FH_S_FSQ, seq_offer(c)));
+  if (sm) FH_TRY(launch_sm_rows(c, io.z, nullptr, 0, 0.0, nullptr, p.red_m + grid, true, FH_S_FSQ, seq_offer(c)));
   t_end(c, FH_K_FWD);
   HIP_TRY(hipGetLastError());
   return 0;
@@ -326,27 +324,26 @@ static const SpEntry* sp_entry(int g) {
 static inline int sp_nt_for(const fh_ctx* c) { return c->nt_loads > 0 ? 1 : 0; }
 
 // z := A * (mode 0: prox(x0 - tau g0), by the prologue launch ; mode 1: x0)
-static int launch_fwd_sparse(fh_ctx* c, int mode, double tau, const double* x0, const double* g0, const double* xacc0,
-                             double* xhat, double* xp, double* z, int sub_b) {
+static int launch_fwd_sparse(fh_ctx* c, const FwdIO& io) {
   const SpEntry* e = sp_entry(c->sp_G[0]);
   if (!e) return fail(FH_E_STATE, "sparse operator: no kernel for %d lanes per row", c->sp_G[0]);
-  if (mode == 0) FH_TRY(check_prox_run(c));
+  if (io.mode == 0) FH_TRY(check_prox_run(c));
   SpFwdP p;
   p.a = c->sp[0]; p.m = (uint32_t)c->m;
-  const uint32_t npro = mode == 0 ? (uint32_t)((c->n + FH_WG - 1) / FH_WG) : 0u;
+  const uint32_t npro = io.mode == 0 ? (uint32_t)((c->n + FH_WG - 1) / FH_WG) : 0u;
   p.nred_n = npro;
   const unsigned grid = p.a.nwg + p.a.nlong;
   FH_TRY(ensure_ws(c, ((size_t)npro * 8 + grid) * sizeof(double)));
   p.red_n = c->ws; p.red_m = c->ws + (size_t)npro * 8;
-  p.x = mode == 0 ? xp : x0;
-  p.b = c->b; p.z = z; p.sub_b = sub_b; p.loss = c->loss_kind;
+  p.x = io.mode == 0 ? io.xp : io.x0;
+  p.b = c->b; p.z = io.z; p.sub_b = io.sub_b; p.loss = c->loss_kind;
   p.counter = c->counters + CNT_FWD;
   p.out = scalar_out(c);
   t_begin(c, FH_K_FWD);
-  if (mode == 0) {
+  if (io.mode == 0) {
     SpProP q;
-    q.n = (uint32_t)c->n; q.x0 = x0; q.g0 = g0; q.xacc0 = xacc0; q.xhat = xhat; q.xp = xp; q.tau = tau;
-    q.px = make_prox(c, tau);
+    q.n = (uint32_t)c->n; q.x0 = io.x0; q.g0 = io.g0; q.xacc0 = io.xacc0; q.xhat = io.xhat; q.xp = io.xp; q.tau = io.tau;
+    q.px = make_prox(c, io.tau);
     q.red_n = c->ws;
     k_sp_prologue<<<dim3(npro), dim3(FH_WG), 0, c->stream>>>(q);
   }
@@ -496,38 +493,37 @@ extern "C" int fh_quad_shape_for(uint64_t n, uint32_t L, long long grid_cap, int
 }
 
 // W := Q * (mode 0: prox(X0 - tau G0), by the prologue launch ; mode 1: X0) for LB columns from one read of Q; with_f: the loss sum over (n, L)
-static int launch_fwd_quad(fh_ctx* c, int mode, double tau, const double* x0, const double* g0, const double* xacc0,
-                           double* xhat, double* xp, double* w, int with_f) {
+static int launch_fwd_quad(fh_ctx* c, const FwdIO& io) {
   const QdShape sh = qd_shape(c);
   const QdEntry* e = sh.e;
   const McEntry* me = mc_entry_lb(c->LB);               // (k_mc_pack lays a plain operand out for the streaming loop)
   if (!e || !me) return fail(FH_E_STATE, "quadratic operator: no kernel for %u columns per row", c->LB);
-  if (mode == 0) FH_TRY(check_prox_run(c));
+  if (io.mode == 0) FH_TRY(check_prox_run(c));
   QdFwdP p;
   p.Q = c->A; p.ld2 = sh.ld2; p.n = (uint32_t)c->n; p.L = c->L;
   p.nrg = sh.nrg;
-  const uint32_t npro = mode == 0 ? sh.npro : 0u;
+  const uint32_t npro = io.mode == 0 ? sh.npro : 0u;
   p.nred_n = npro;
   const unsigned grid = sh.fwd_grid;
   FH_TRY(ensure_ws(c, ((size_t)npro * 8 + grid) * sizeof(double)));
   p.red_n = c->ws; p.red_m = c->ws + (size_t)npro * 8;
   p.x = c->xs;
-  p.xrow = mode == 0 ? xp : x0;
-  p.c = c->b; p.w = w; p.with_f = with_f;
+  p.xrow = io.mode == 0 ? io.xp : io.x0;
+  p.c = c->b; p.w = io.z; p.with_f = io.sub_b;
   p.counter = c->counters + CNT_FWD;
   p.out = scalar_out(c);
   t_begin(c, FH_K_FWD);
-  if (mode == 0) {
+  if (io.mode == 0) {
     McProP q;
     q.n = (uint32_t)c->n; q.L = c->L; q.nv = (uint32_t)c->nv;
-    q.x0 = x0; q.g0 = g0; q.xacc0 = xacc0; q.xhat = xhat; q.xp = xp; q.tau = tau;
+    q.x0 = io.x0; q.g0 = io.g0; q.xacc0 = io.xacc0; q.xhat = io.xhat; q.xp = io.xp; q.tau = io.tau;
     q.xs = c->xs; q.ld2 = p.ld2;
-    q.px = make_prox(c, tau);
+    q.px = make_prox(c, io.tau);
     if (c->prox_kind == FH_PROX_ROWBALL) q.px.thr = c->mu;         // the radius itself: this projection does not scale with the step
     q.red_n = c->ws;
     e->pro<<<dim3(npro), dim3(FH_WG), 0, c->stream>>>(q);
   } else {
-    me->pack<<<dim3(sh.npro), dim3(FH_WG), 0, c->stream>>>(x0, c->xs, (uint32_t)c->nv, p.ld2);
+    me->pack<<<dim3(sh.npro), dim3(FH_WG), 0, c->stream>>>(io.x0, c->xs, (uint32_t)c->nv, p.ld2);
   }
   p.seq = seq_offer(c);
   e->fwd[sh.nt]<<<dim3(grid), dim3(FH_WG), 0, c->stream>>>(p);
@@ -693,27 +689,25 @@ static void bl_make_prox(fh_ctx* c, double tau, BlProP* q) {
 // mode 0: xhat, xprox = prox(X0 - tau G0) and the n-side sums by the prologue launch, then the pass at xprox; mode 1: the pass at X0.  The pass
 // of mode 0 leaves the gradient out when the context's latest adjoint launch was accelerated (the next one then wants the gradient at another
 // point anyway); launch_adj_bilinear makes up for a wrong guess, and f has the same bits either way.
-static int launch_fwd_bilinear(fh_ctx* c, int mode, double tau, const double* x0, const double* g0, const double* xacc0,
-                               double* xhat, double* xp, double* z, int with_f) {
-  (void)z;
+static int launch_fwd_bilinear(fh_ctx* c, const FwdIO& io) {
   const BlShape sh = bl_shape(c);
   if (!sh.e) return fail(FH_E_STATE, "bilinear operator: no kernel for %u columns per row", c->LB);
-  if (mode == 0) FH_TRY(check_prox_run(c));
-  if (!with_f) return fail(FH_E_STATE, "the bilinear operator has no linear map to apply");
-  const uint32_t npro = mode == 0 ? sh.nelem : 0u;
+  if (io.mode == 0) FH_TRY(check_prox_run(c));
+  if (!io.sub_b) return fail(FH_E_STATE, "the bilinear operator has no linear map to apply");
+  const uint32_t npro = io.mode == 0 ? sh.nelem : 0u;
   FH_TRY(ensure_ws(c, ((size_t)npro * 8 + sh.grid) * sizeof(double)));
   FH_TRY(bl_ensure_part(c, sh));
   t_begin(c, FH_K_FWD);
-  if (mode == 0) {
+  if (io.mode == 0) {
     BlProP q;
     q.a.n = (uint32_t)c->n; q.a.L = c->L; q.a.nv = (uint32_t)c->nv;
-    q.a.x0 = x0; q.a.g0 = g0; q.a.xacc0 = xacc0; q.a.xhat = xhat; q.a.xp = xp; q.a.tau = tau;
+    q.a.x0 = io.x0; q.a.g0 = io.g0; q.a.xacc0 = io.xacc0; q.a.xhat = io.xhat; q.a.xp = io.xp; q.a.tau = io.tau;
     q.a.xs = nullptr; q.a.ld2 = 0;
-    bl_make_prox(c, tau, &q);
+    bl_make_prox(c, io.tau, &q);
     q.a.red_n = c->ws;
     sh.e->pro<<<dim3(npro), dim3(FH_WG), 0, c->stream>>>(q);
   }
-  const int rc = bl_launch_pass(c, sh, mode == 0 ? xp : x0, (mode == 1 || !c->last_accel) ? 1 : 0, 1, npro);
+  const int rc = bl_launch_pass(c, sh, io.mode == 0 ? io.xp : io.x0, (io.mode == 1 || !c->last_accel) ? 1 : 0, 1, npro);
   t_end(c, FH_K_FWD);
   FH_TRY(rc);
   HIP_TRY(hipGetLastError());
@@ -816,37 +810,36 @@ static const SpmcEntry* spmc_entry(const fh_ctx* c, int side) {
 }
 
 // Z := A * (mode 0: prox(X0 - tau G0), by the prologue launch ; mode 1: X0), LB columns per gathered row
-static int launch_fwd_spmulti(fh_ctx* c, int mode, double tau, const double* x0, const double* g0, const double* xacc0,
-                              double* xhat, double* xp, double* z, int sub_b) {
+static int launch_fwd_spmulti(fh_ctx* c, const FwdIO& io) {
   const SpmcEntry* e = spmc_entry(c, 0);
   const SpmcLbEntry* lbe = spmc_lb_entry(c);
   if (!e || !lbe) return fail(FH_E_STATE, "sparse multi-column form: no kernel for %d lanes per row at %u columns per row", c->sp_G[0], c->LB);
   FH_TRY(check_loss_run(c));
-  if (mode == 0) FH_TRY(check_prox_run(c));
-  const bool sm = sm_on(c, sub_b);                // as launch_fwd_multi: the row pass behind K-fwd writes FH_S_FSQ and publishes
+  if (io.mode == 0) FH_TRY(check_prox_run(c));
+  const bool sm = sm_on(c, io.sub_b);             // as launch_fwd_multi: the row pass behind K-fwd writes FH_S_FSQ and publishes
   SpmcFwdP p;
   p.a = c->sp[0]; p.m = (uint32_t)c->m; p.L = c->L;
-  const uint32_t npro = mode == 0 ? (uint32_t)((c->nv + FH_WG - 1) / FH_WG) : 0u;
+  const uint32_t npro = io.mode == 0 ? (uint32_t)((c->nv + FH_WG - 1) / FH_WG) : 0u;
   p.nred_n = npro;
   const unsigned grid = p.a.nwg + p.a.nlong;
   FH_TRY(ensure_ws(c, ((size_t)npro * 8 + grid + (sm ? sm_records(c) : 0u)) * sizeof(double)));
   p.red_n = c->ws; p.red_m = c->ws + (size_t)npro * 8;
-  p.x = mode == 0 ? xp : x0;
-  p.b = c->b; p.z = z; p.sub_b = sub_b;
+  p.x = io.mode == 0 ? io.xp : io.x0;
+  p.b = c->b; p.z = io.z; p.sub_b = io.sub_b;
   p.counter = c->counters + CNT_FWD;
   p.out = scalar_out(c);
   t_begin(c, FH_K_FWD);
-  if (mode == 0) {
+  if (io.mode == 0) {
     SpmcProP q;
     q.n = (uint32_t)c->n; q.L = c->L; q.nv = (uint32_t)c->nv;
-    q.x0 = x0; q.g0 = g0; q.xacc0 = xacc0; q.xhat = xhat; q.xp = xp; q.tau = tau;
-    q.px = make_prox(c, tau);
+    q.x0 = io.x0; q.g0 = io.g0; q.xacc0 = io.xacc0; q.xhat = io.xhat; q.xp = io.xp; q.tau = io.tau;
+    q.px = make_prox(c, io.tau);
     q.red_n = c->ws;
     lbe->pro<<<dim3(npro), dim3(FH_WG), 0, c->stream>>>(q);
   }
   p.seq = sm ? 0u : seq_offer(c);
   e->fwd[sp_nt_for(c) ? 1 : 0]<<<dim3(grid), dim3(FH_WG), 0, c->stream>>>(p);
-  if (sm) FH_TRY(launch_sm_rows(c, z, nullptr, 0, 0.0, nullptr, p.red_m + grid, true, FH_S_FSQ, seq_offer(c)));
+  if (sm) FH_TRY(launch_sm_rows(c, io.z, nullptr, 0, 0.0, nullptr, p.red_m + grid, true, FH_S_FSQ, seq_offer(c)));
   t_end(c, FH_K_FWD);
   HIP_TRY(hipGetLastError());
   return 0;
@@ -936,20 +929,19 @@ extern "C" int fh_tv3d_shape_for(uint64_t D, uint64_t H, uint64_t W, int planes,
 }
 
 // z := div(mode 0: prox(x0 - tau g0) ; mode 1: x0), ONE launch
-static int launch_fwd_tv3(fh_ctx* c, int mode, double tau, const double* x0, const double* g0, const double* xacc0,
-                          double* xhat, double* xp, double* z, int sub_b) {
+static int launch_fwd_tv3(fh_ctx* c, const FwdIO& io) {
   FH_TRY(check_loss_run(c));
-  if (mode == 0) FH_TRY(check_prox_run(c));
+  if (io.mode == 0) FH_TRY(check_prox_run(c));
   Tv3Shape sh;
   FH_TRY(tv3_shape_for(c->D, c->H, c->W, c->tv3_planes, c->ncu, &sh));
   Tv3FwdP p;
   p.D = (uint32_t)c->D; p.H = (uint32_t)c->H; p.W = (uint32_t)c->W; p.planes = sh.planes; p.tiles_h = sh.tiles_h; p.tiles_w = sh.tiles_w;
-  p.mode = mode; p.sub_b = sub_b;
-  p.x0 = x0; p.g0 = g0; p.xacc0 = xacc0; p.xhat = xhat; p.xp = xp; p.b = c->b; p.z = z; p.tau = tau;
-  p.px = make_prox(c, tau);
+  p.mode = io.mode; p.sub_b = io.sub_b;
+  p.x0 = io.x0; p.g0 = io.g0; p.xacc0 = io.xacc0; p.xhat = io.xhat; p.xp = io.xp; p.b = c->b; p.z = io.z; p.tau = io.tau;
+  p.px = make_prox(c, io.tau);
   FH_TRY(ensure_ws(c, (size_t)sh.grid * 8 * sizeof(double)));
   p.red = c->ws; p.counter = c->counters + CNT_FWD; p.out = scalar_out(c);
-  const bool ball = mode == 0 && c->prox_kind == FH_PROX_TVBALL;
+  const bool ball = io.mode == 0 && c->prox_kind == FH_PROX_TVBALL;
   t_begin(c, FH_K_FWD);
   p.seq = seq_offer(c);
   if (tv3_nt_for(c)) { if (ball) k_tv3_fwd<0, 1><<<dim3(sh.grid), dim3(FH_WG), 0, c->stream>>>(p); else k_tv3_fwd<1, 1><<<dim3(sh.grid), dim3(FH_WG), 0, c->stream>>>(p); }
@@ -1036,22 +1028,21 @@ static ConvGeo conv_geo(const fh_ctx* c) {
 }
 
 // z := d * (K conv (mode 0: prox(x0 - tau g0) ; mode 1: x0)), ONE launch
-static int launch_fwd_conv(fh_ctx* c, int mode, double tau, const double* x0, const double* g0, const double* xacc0,
-                           double* xhat, double* xp, double* z, int sub_b) {
+static int launch_fwd_conv(fh_ctx* c, const FwdIO& io) {
   FH_TRY(check_loss_run(c));
-  if (mode == 0) FH_TRY(check_prox_run(c));
+  if (io.mode == 0) FH_TRY(check_prox_run(c));
   const ConvShape& sh = c->conv_sh;
   ConvFwdP p;
   p.g = conv_geo(c);
-  p.sub_b = sub_b;
-  p.x0 = x0; p.g0 = g0; p.xacc0 = xacc0; p.xhat = xhat; p.xp = xp; p.b = c->b; p.z = z; p.diag = c->conv_diag; p.tau = tau;
-  p.px = make_prox(c, tau);
+  p.sub_b = io.sub_b;
+  p.x0 = io.x0; p.g0 = io.g0; p.xacc0 = io.xacc0; p.xhat = io.xhat; p.xp = io.xp; p.b = c->b; p.z = io.z; p.diag = c->conv_diag; p.tau = io.tau;
+  p.px = make_prox(c, io.tau);
   memcpy(p.taps, c->conv_taps, sizeof(p.taps));
   FH_TRY(ensure_ws(c, (size_t)sh.grid * 8 * sizeof(double)));
   p.red = c->ws; p.counter = c->counters + CNT_FWD; p.out = scalar_out(c);
   t_begin(c, FH_K_FWD);
   p.seq = seq_offer(c);
-  if (mode == 0) k_conv_fwd<0><<<dim3(sh.grid), dim3(FH_WG), 0, c->stream>>>(p);
+  if (io.mode == 0) k_conv_fwd<0><<<dim3(sh.grid), dim3(FH_WG), 0, c->stream>>>(p);
   else k_conv_fwd<1><<<dim3(sh.grid), dim3(FH_WG), 0, c->stream>>>(p);
   t_end(c, FH_K_FWD);
   HIP_TRY(hipGetLastError());
@@ -1319,15 +1310,14 @@ static void dct2_launch_adj_rows(fh_ctx* c, uint32_t ldsn, uint32_t grid, const 
 }
 
 // z := d * (C_H X C_W^T), X = prox(x0 - tau g0) (mode 0) or x0 (mode 1): four launches; the checks are launch_fwd_dct's
-static int launch_fwd_dct2(fh_ctx* c, int mode, double tau, const double* x0, const double* g0, const double* xacc0,
-                           double* xhat, double* xp, double* z, int sub_b) {
+static int launch_fwd_dct2(fh_ctx* c, const FwdIO& io) {
   const Dct2Shape& sh = c->dct2_sh;
   Dct2FwdP p;
   memset(&p.f.op, 0, sizeof(p.f.op));                     // (the 1-D operator's block: the 2-D kernels do not read it)
   p.o = dct2_op_params(c, sh);
-  p.f.mode = mode; p.f.sub_b = sub_b;
-  p.f.x0 = x0; p.f.g0 = g0; p.f.xacc0 = xacc0; p.f.xhat = xhat; p.f.xp = xp; p.f.b = c->b; p.f.z = z; p.f.tau = tau;
-  p.f.px = make_prox(c, tau);
+  p.f.mode = io.mode; p.f.sub_b = io.sub_b;
+  p.f.x0 = io.x0; p.f.g0 = io.g0; p.f.xacc0 = io.xacc0; p.f.xhat = io.xhat; p.f.xp = io.xp; p.f.b = c->b; p.f.z = io.z; p.f.tau = io.tau;
+  p.f.px = make_prox(c, io.tau);
   p.f.seq = 0u; p.f.nred_n = 0u;
   FH_TRY(ensure_ws(c, ((size_t)sh.tiles + sh.grid_w) * 8 * sizeof(double)));
   p.f.red = c->ws; p.f.red_n = c->ws + (size_t)sh.tiles * 8; p.f.counter = c->counters + CNT_FWD; p.f.out = scalar_out(c);
@@ -1335,7 +1325,7 @@ static int launch_fwd_dct2(fh_ctx* c, int mode, double tau, const double* x0, co
   dct2_launch_fwd_rows<1>(c, sh.ldsn_w, sh.grid_w, p);
   k_dct2_tr<DCT_TT><<<dim3(sh.tiles), dim3(FH_WG), 0, c->stream>>>(c->dct2_w0, c->dct2_w1, sh.H, sh.W);
   dct2_launch_fwd_rows<0>(c, sh.ldsn_h, sh.grid_h, p);
-  p.f.nred_n = mode == 0 ? sh.grid_w : 0u;
+  p.f.nred_n = io.mode == 0 ? sh.grid_w : 0u;
   p.f.seq = seq_offer(c);
   k_dct2_post_fwd<DCT_TT><<<dim3(sh.tiles), dim3(FH_WG), 0, c->stream>>>(p);
   t_end(c, FH_K_FWD);
@@ -1367,17 +1357,16 @@ static int launch_adj_dct2(fh_ctx* c, const AdjIO& io) {
 }
 
 // z := d * C (mode 0: prox(x0 - tau g0) ; mode 1: x0): one launch (N <= row cap) or five
-static int launch_fwd_dct(fh_ctx* c, int mode, double tau, const double* x0, const double* g0, const double* xacc0,
-                          double* xhat, double* xp, double* z, int sub_b) {
+static int launch_fwd_dct(fh_ctx* c, const FwdIO& io) {
   FH_TRY(check_loss_run(c));
-  if (mode == 0) FH_TRY(check_prox_run(c));
-  if (c->dct2) return launch_fwd_dct2(c, mode, tau, x0, g0, xacc0, xhat, xp, z, sub_b);
+  if (io.mode == 0) FH_TRY(check_prox_run(c));
+  if (c->dct2) return launch_fwd_dct2(c, io);
   const DctShape& sh = c->dct_sh;
   DctFwdP p;
   p.op = dct_op_params(c, sh);
-  p.mode = mode; p.sub_b = sub_b;
-  p.x0 = x0; p.g0 = g0; p.xacc0 = xacc0; p.xhat = xhat; p.xp = xp; p.b = c->b; p.z = z; p.tau = tau;
-  p.px = make_prox(c, tau);
+  p.mode = io.mode; p.sub_b = io.sub_b;
+  p.x0 = io.x0; p.g0 = io.g0; p.xacc0 = io.xacc0; p.xhat = io.xhat; p.xp = io.xp; p.b = c->b; p.z = io.z; p.tau = io.tau;
+  p.px = make_prox(c, io.tau);
   p.seq = 0u; p.nred_n = 0u; p.red_n = nullptr;
   const uint32_t grid = sh.levels == 1 ? 1u : sh.tiles;
   FH_TRY(ensure_ws(c, (size_t)grid * 16 * sizeof(double)));
@@ -1392,7 +1381,7 @@ static int launch_fwd_dct(fh_ctx* c, int mode, double tau, const double* x0, con
     p.red_n = c->ws + (size_t)grid * 8;
     k_dct_pre_fwd<DCT_TT><<<dim3(grid), dim3(FH_WG), 0, c->stream>>>(p);
     dct_launch_middle(c, sh, 0);
-    p.nred_n = mode == 0 ? grid : 0u;
+    p.nred_n = io.mode == 0 ? grid : 0u;
     p.seq = seq_offer(c);
     k_dct_post_fwd<DCT_TT><<<dim3(grid), dim3(FH_WG), 0, c->stream>>>(p);
   }
@@ -1579,15 +1568,14 @@ static int nuc_norm(fh_ctx* c, const double* x, double* out_gsum, double* out_gm
 }
 
 // z := prox(x0 - tau g0) (mode 0) or x0 (mode 1), the loss sum and the n-side sums: one elementwise launch (behind the thresholding for FH_PROX_NUCLEAR)
-static int launch_fwd_identity(fh_ctx* c, int mode, double tau, const double* x0, const double* g0, const double* xacc0,
-                               double* xhat, double* xp, double* z, int sub_b) {
-  if (mode == 0) FH_TRY(check_prox_run(c));
-  const bool nuc = mode == 0 && nuc_kind(c->prox_kind);
-  if (nuc) FH_TRY(nuc_prox(c, tau, x0, g0, xhat, xp));
+static int launch_fwd_identity(fh_ctx* c, const FwdIO& io) {
+  if (io.mode == 0) FH_TRY(check_prox_run(c));
+  const bool nuc = io.mode == 0 && nuc_kind(c->prox_kind);
+  if (nuc) FH_TRY(nuc_prox(c, io.tau, io.x0, io.g0, io.xhat, io.xp));
   IdFwdP p;
-  p.n = c->n; p.mode = mode; p.given = nuc ? 1 : 0; p.sub_b = sub_b; p.loss = c->loss_kind;
-  p.x0 = x0; p.g0 = g0; p.xacc0 = xacc0; p.xhat = xhat; p.xp = xp; p.z = z; p.b = c->b; p.tau = tau;
-  p.px = make_prox(c, tau);
+  p.n = c->n; p.mode = io.mode; p.given = nuc ? 1 : 0; p.sub_b = io.sub_b; p.loss = c->loss_kind;
+  p.x0 = io.x0; p.g0 = io.g0; p.xacc0 = io.xacc0; p.xhat = io.xhat; p.xp = io.xp; p.z = io.z; p.b = c->b; p.tau = io.tau;
+  p.px = make_prox(c, io.tau);
   p.nuc = c->nuc_scal ? c->nuc_scal + 1 : nullptr;
   const unsigned grid = (unsigned)std::min<uint64_t>((c->n + FH_WG - 1) / FH_WG, 2048);
   FH_TRY(ensure_ws(c, (size_t)grid * 8 * sizeof(double)));
@@ -1705,19 +1693,18 @@ static int launch_level_search(fh_ctx* c, double tau) {
   return 0;
 }
 
-static int launch_fwd_tv(fh_ctx* c, int mode, double tau, const double* x0, const double* g0, const double* xacc0,
-                         double* xhat, double* xp, double* z, int sub_b) {
-  (void)xhat; (void)g0;   // the stencil path materialises neither xhat nor the gradient (fh_tv.h)
-  if (mode == 0) FH_TRY(check_prox_run(c));
+static int launch_fwd_tv(fh_ctx* c, const FwdIO& io) {
+  // (the stencil path materialises neither xhat nor the gradient, fh_tv.h: io.xhat and io.g0 are not read)
+  if (io.mode == 0) FH_TRY(check_prox_run(c));
   const uint32_t H = (uint32_t)c->H, W = (uint32_t)c->W;
   const uint32_t rows_wg = (uint32_t)(c->tv_rows > 0 ? c->tv_rows : 32);
   const uint32_t row_chunks = (H + rows_wg - 1) / rows_wg;
-  if (mode == 0) {
+  if (io.mode == 0) {
     if (!c->zcur) return fail(FH_E_STATE, "fh_fwd on the stencil operator before fh_init");
     TvStepFwdP p;
     p.H = H; p.W = W; p.rows_wg = rows_wg;
     p.strip_groups = ((W + TVS_FWD_OWN - 1) / TVS_FWD_OWN + 3) / 4;
-    p.x0 = x0; p.xacc0 = xacc0; p.xp = xp; p.zc = c->zcur; p.b = c->b; p.zn = z; p.tau = tau;
+    p.x0 = io.x0; p.xacc0 = io.xacc0; p.xp = io.xp; p.zc = c->zcur; p.b = c->b; p.zn = io.z; p.tau = io.tau;
     const unsigned grid = p.strip_groups * row_chunks;
     FH_TRY(ensure_ws(c, (size_t)grid * 8 * sizeof(double)));
     p.red = c->ws; p.counter = c->counters + CNT_FWD; p.out = scalar_out(c);
@@ -1737,8 +1724,7 @@ static int launch_fwd_tv(fh_ctx* c, int mode, double tau, const double* x0, cons
   TvFwdP p;
   p.H = H; p.W = W; p.rows_wg = rows_wg;
   p.strip_groups = ((W + TV_SW - 1) / TV_SW + 3) / 4;
-  (void)xp; (void)tau;
-  p.x0 = x0; p.b = c->b; p.z = z; p.sub_b = sub_b;
+  p.x0 = io.x0; p.b = c->b; p.z = io.z; p.sub_b = io.sub_b;
   const unsigned grid = p.strip_groups * row_chunks;
   FH_TRY(ensure_ws(c, (size_t)grid * 8 * sizeof(double)));
   p.red = c->ws; p.counter = c->counters + CNT_FWD; p.out = scalar_out(c);
@@ -2136,20 +2122,17 @@ static int plain_pair_fused(fh_ctx* c, const double* x, double* z, double* g, bo
 }
 
 // ---- operator-generic wrappers ---------------------------------------------------------------------
-static int op_fwd(fh_ctx* c, int mode, double tau, const double* x0, const double* g0, const double* xacc0,
-                  double* xhat, double* xp, double* z, int sub_b) {
-  if (c->op == OP_DENSE && c->LB) return launch_fwd_multi(c, mode, tau, x0, g0, xacc0, xhat, xp, z, sub_b);
-  if (c->op == OP_DENSE) return launch_fwd_dense(c, mode, tau, x0, g0, xacc0, xhat, xp, z, sub_b);
-  if (c->op == OP_STENCIL) return launch_fwd_tv(c, mode, tau, x0, g0, xacc0, xhat, xp, z, sub_b);
-  if (c->op == OP_SPARSE) return c->LB ? launch_fwd_spmulti(c, mode, tau, x0, g0, xacc0, xhat, xp, z, sub_b) : launch_fwd_sparse(c, mode, tau, x0, g0, xacc0, xhat, xp, z, sub_b);
-  if (c->op == OP_STENCIL3D) return launch_fwd_tv3(c, mode, tau, x0, g0, xacc0, xhat, xp, z, sub_b);
-  if (c->op == OP_DCT) return launch_fwd_dct(c, mode, tau, x0, g0, xacc0, xhat, xp, z, sub_b);
-  if (c->op == OP_CONV) return launch_fwd_conv(c, mode, tau, x0, g0, xacc0, xhat, xp, z, sub_b);
-  if (c->op == OP_IDENTITY) return launch_fwd_identity(c, mode, tau, x0, g0, xacc0, xhat, xp, z, sub_b);
-  if (c->op == OP_QUAD) return launch_fwd_quad(c, mode, tau, x0, g0, xacc0, xhat, xp, z, sub_b);
-  if (c->op == OP_BILINEAR) return launch_fwd_bilinear(c, mode, tau, x0, g0, xacc0, xhat, xp, z, sub_b);
-  return fail(FH_E_STATE, "no operator set");
-}
+// the launchers of each operator form, by F_* (csrc/fh_host_ctx.h: kForms holds what the form serves)
+struct FormLaunch { int (*fwd)(fh_ctx*, const FwdIO&); int (*adj)(fh_ctx*, const AdjIO&); };
+static int no_operator_fwd(fh_ctx*, const FwdIO&) { return fail(FH_E_STATE, "no operator set"); }
+static int no_operator_adj(fh_ctx*, const AdjIO&) { return fail(FH_E_STATE, "no operator set"); }
+static const FormLaunch kLaunch[] = {
+  {no_operator_fwd, no_operator_adj}, {launch_fwd_dense, launch_adj_dense}, {launch_fwd_multi, launch_adj_multi}, {launch_fwd_tv, launch_adj_tv},
+  {launch_fwd_sparse, launch_adj_sparse}, {launch_fwd_spmulti, launch_adj_spmulti}, {launch_fwd_tv3, launch_adj_tv3}, {launch_fwd_quad, launch_adj_quad},
+  {launch_fwd_bilinear, launch_adj_bilinear}, {launch_fwd_dct, launch_adj_dct}, {launch_fwd_identity, launch_adj_identity}, {launch_fwd_conv, launch_adj_conv},
+};
+static_assert(sizeof(kLaunch) / sizeof(kLaunch[0]) == F_COUNT, "one pair of launchers per operator form, in the order of F_*");
+static int op_fwd(fh_ctx* c, const FwdIO& io) { return kLaunch[form_index(c)].fwd(c, io); }
 
 // ---- the adjoint launch in three stages, so that a shell can run stage 1 on every shard, ONE exchange, stage 3 on every shard ----
 // stage 1, local: row-sharded contexts leave the n-side epilogue (mode 0) to adj_tail, which needs the summed g1
@@ -2157,17 +2140,7 @@ static int adj_local(fh_ctx* c, const AdjIO& io_in) {
   AdjIO io = io_in;
   if (row_sharded(c) && c->op != OP_DENSE) return fail(FH_E_STATE, "row sharding is implemented for the dense operator only");
   if (row_sharded(c) && io.mode == 0) io.mode = 2;
-  if (c->op == OP_DENSE && c->LB) return launch_adj_multi(c, io);
-  if (c->op == OP_DENSE) return launch_adj_dense(c, io);
-  if (c->op == OP_STENCIL) return launch_adj_tv(c, io);
-  if (c->op == OP_SPARSE) return c->LB ? launch_adj_spmulti(c, io) : launch_adj_sparse(c, io);
-  if (c->op == OP_STENCIL3D) return launch_adj_tv3(c, io);
-  if (c->op == OP_DCT) return launch_adj_dct(c, io);
-  if (c->op == OP_CONV) return launch_adj_conv(c, io);
-  if (c->op == OP_IDENTITY) return launch_adj_identity(c, io);
-  if (c->op == OP_QUAD) return launch_adj_quad(c, io);
-  if (c->op == OP_BILINEAR) return launch_adj_bilinear(c, io);
-  return fail(FH_E_STATE, "no operator set");
+  return kLaunch[form_index(c)].adj(c, io);
 }
 // stage 2, exchange: A_k^T r_k partials (nv doubles at g1(shard)) and the local loss sums (FH_S_FSQ_ADJ) summed over the row blocks
 template <typename Sel>
@@ -2209,6 +2182,9 @@ static AdjIO solver_adj_io(fh_ctx* c, double tau, int accel, double coef) {
   io.x1 = c->X[c->ti]; io.g1 = c->G[c->gc ^ 1]; io.g0 = c->G[c->gc];
   return io;
 }
+static FwdIO solver_fwd_io(fh_ctx* c, double tau) {
+  return FwdIO{0, tau, c->X[c->xi], c->G[c->gc], c->P[c->pc], c->xhat, c->P[c->pc ^ 1], c->Z[c->zc ^ 1], 1};
+}
 // K-fwd of the solver state (level search for the two sort-free prox kinds first)
 static int solver_fwd_local(fh_ctx* c, double tau, const char* who) {
   FH_TRY(use_device(c));
@@ -2216,7 +2192,7 @@ static int solver_fwd_local(fh_ctx* c, double tau, const char* who) {
   FH_TRY(tv_refresh_zcur(c));
   c->tvz_pending = false;
   if (c->prox_kind == FH_PROX_LINF || c->prox_kind == FH_PROX_L1BALL) FH_TRY(launch_level_search(c, tau));
-  return op_fwd(c, 0, tau, c->X[c->xi], c->G[c->gc], c->P[c->pc], c->xhat, c->P[c->pc ^ 1], c->Z[c->zc ^ 1], 1);
+  return op_fwd(c, solver_fwd_io(c, tau));
 }
 
 // ---- stencil one-pass launchers ---------------------------------------------------------------------------------------------

@@ -6,10 +6,13 @@ the GPU, and compared with `==`; it must be taken again (scripts/make_refusal_go
 
 A case is (id, state, calls).  `state` names how the context is made (STATES); `calls` is a tuple of (entry point, arguments) in order.  Every
 call of a case is recorded.  Arguments are plain Python values: numbers, None (a NULL pointer), ("f64" | "i64" | "i32" | "f32", values) for an
-array and ("out", count) for `count` doubles the library writes; `marshal` turns them into ctypes by the entry point's row in hip.SIGNATURES.
+array, ("out", count) for `count` doubles the library writes and ("struct", name, fields) for one of hip.py's structures (fh_run's two); `marshal`
+turns them into ctypes by the entry point's row in hip.SIGNATURES.
 
 The shapes are the smallest each setter accepts, a few rows and a few columns: the calls either return from host code or run one tiny launch of
-the kind the operator's own suite runs (init and one forward step)."""
+the kind the operator's own suite runs (init and one forward step).  The family entry/<form>/<entry point> asks every entry point that answers
+by operator form -- the one-pass step, the device-side loop, row sharding, the dense rows, fh_apply, the read-only reports -- on every form, one
+pair per context; where the form serves the call it runs at the shape the suite of that launch runs (DENSE_SERVED_AT)."""
 import ctypes as C
 import json
 import os
@@ -112,6 +115,53 @@ def launch_calls(form, L=None):
     return loss + (("fh_init", (SCALARS,)), ("fh_fwd", (TAU, SCALARS)))
 
 
+def dense_at(m, n):
+    """The dense form at a shape at which a launch that serves it runs (the matrix of the in-flight states, and of fh_run)."""
+    return ("fh_set_matrix", (f64(*[((3 * i) % 11 - 5) / 64.0 for i in range(m * n)]), m, n, n))
+
+
+# ---- the entry points that answer by operator form: no one-pass kernel, no device-side loop, no row sharding, no dense rows, ... --------------------
+RUN_M, RUN_N = 20, 600                              # the smallest problem the device loop's suite runs (tests/run_paths.py: stale_best)
+ROOM = 128                                          # doubles / words behind every pointer: more than any report or vector of these shapes takes
+WORDS, WORDS64 = ("i32", (0,) * ROOM), ("i64", (0,) * ROOM)
+RUN_OPTS = ("struct", "RunOpts", (("window", 1), ("max_backtracks", 20), ("stepsize_shrink", 0.5)))
+RUN_STATE = ("struct", "RunState", (("tau_next", 0.25), ("alpha1", 1.0), ("max_residual", float("-inf")), ("best_quality", float("inf"))))
+SHAPE_EXPORTS = ("fh_multi_shape", "fh_quad_shape", "fh_bilinear_shape", "fh_tv3d_shape", "fh_conv_shape", "fh_dct_shape", "fh_dct2_shape", "fh_nuclear_shape")
+# name in the case's id -> the calls, with valid arguments: the answer is the form's own.  ("uid",): replay puts a fresh RCCL id there.
+ENTRIES = {
+    "fh_step": (("fh_step", (TAU, SCALARS)),),
+    "fh_step_begin": (("fh_step_begin", (TAU,)), ("fh_step_end", (SCALARS,))),
+    "fh_step_accel": (("fh_step_accel", (TAU, 0.0, 0, SCALARS)),),
+    "fh_run": (("fh_run", (1, RUN_OPTS, RUN_STATE, ("out", hip.RUN_HIST), ("i32", (0,)))),),
+    "fh_comm_init": (("fh_comm_init", (1, 0, ("uid",))),),
+    "fh_get_matrix_rows": (("fh_get_matrix_rows", (0, 1, ("out", ROOM))),),
+    "fh_stream_read_ms": (("fh_stream_read_ms", (1, ("out", 1), ("i64", (0,)))),),
+    "fh_apply_forward": (("fh_apply", (0, ones(ROOM), ("out", ROOM))),),
+    "fh_apply_adjoint": (("fh_apply", (1, ones(ROOM), ("out", ROOM))),),
+    "fh_sparse_lanes": (("fh_sparse_lanes", (0, WORDS, WORDS, WORDS)),),
+}
+ENTRIES.update({name: ((name, (WORDS64 if name == "fh_nuclear_shape" else WORDS,)),) for name in SHAPE_EXPORTS})
+assert len(ENTRIES) == 18
+# the dense form serves these: they run at the shape the suite of the launch runs them
+DENSE_SERVED_AT = {"fh_step": (IN_FLIGHT_M, IN_FLIGHT_N), "fh_step_begin": (IN_FLIGHT_M, IN_FLIGHT_N), "fh_step_accel": (IN_FLIGHT_M, IN_FLIGHT_N),
+                   "fh_run": (RUN_M, RUN_N)}
+
+
+def entry_cases():
+    """entry/<form>/<entry point>: the form, a loss where it takes one, fh_init, then the one call (fh_step_begin: and fh_step_end), each pair on a
+    context of its own."""
+    out = []
+    for form, (setup, m, _, _) in FORMS.items():
+        for entry, calls in ENTRIES.items():
+            if form == "dense" and entry in DENSE_SERVED_AT:
+                m_at, n_at = DENSE_SERVED_AT[entry]
+                prelude = (dense_at(m_at, n_at), ("fh_set_loss_lsq", (ones(m_at), m_at)), ("fh_init", (SCALARS,)))
+            else:
+                prelude = setup + launch_calls(form)[:-1]          # (without the forward step)
+            out.append((f"entry/{form}/{entry}", "plain", prelude + calls))
+    return out
+
+
 def cases():
     out = []
     for form, (setup, m, n, L) in FORMS.items():
@@ -144,7 +194,7 @@ def cases():
     held = FORMS["identity"][0] + (("fh_set_loss_lsq", (ones(15), 15)), ("fh_set_loss_weights", (ones(15),)))
     for name, (setup, _, _, _) in SETTERS.items():
         out.append((f"weights/{name}", "plain", held + setup + (("fh_set_loss_weights", (None,)),)))
-    return out
+    return out + entry_cases()
 
 
 CASES = cases()
@@ -169,6 +219,9 @@ def marshal(name, args, keep):
     for t, a in zip(types, args):
         if a is None:
             out.append(None)
+        elif isinstance(a, tuple) and a[0] == "struct":
+            keep.append(getattr(hip, a[1])(**dict(a[2])))
+            out.append(C.byref(keep[-1]))
         elif isinstance(a, tuple):
             arr = np.zeros(a[1]) if a[0] == "out" else np.array(a[1], dtype=_NP[a[0]])
             keep.append(arr)
@@ -196,9 +249,8 @@ def _open(lib, state):
     elif state in ("in_flight", "f32_in_flight"):
         must(lib.fh_create(0, C.byref(h)) if state == "in_flight" else lib.fh_create_ex(1, (C.c_int * 1)(0), hip.DTYPE_F32_STORAGE, C.byref(h)))
         keep = []
-        m, n = IN_FLIGHT_M, IN_FLIGHT_N
-        A = f64(*[((3 * i) % 11 - 5) / 64.0 for i in range(m * n)])
-        for name, args in (("fh_set_matrix", (A, m, n, n)), ("fh_set_loss_lsq", (ones(m), m)), set_prox(hip.PROX_SHRINK), ("fh_init", (SCALARS,)),
+        m = IN_FLIGHT_M
+        for name, args in (dense_at(m, IN_FLIGHT_N), ("fh_set_loss_lsq", (ones(m), m)), set_prox(hip.PROX_SHRINK), ("fh_init", (SCALARS,)),
                            ("fh_step_begin", (0.25,))):
             must(getattr(lib, name)(h, *marshal(name, args, keep)))
     else:
@@ -220,6 +272,9 @@ def replay(lib, case):
                 status = lib.fh_rhs(h, C.byref(L))
                 got.append([int(status), f"L = {L.value}"])
                 continue
+            if name == "fh_comm_init":  # a one-rank communicator as the state "comm" makes it: the id is RCCL's, fresh per call
+                keep.append(C.create_string_buffer(hip.comm_unique_id(), hip.UNIQUE_ID_BYTES))
+                args = args[:2] + (keep[-1],)
             status = getattr(lib, name)(h, *marshal(name, args, keep))
             got.append([int(status), lib.fh_last_error().decode() if status else ""])
     finally:
