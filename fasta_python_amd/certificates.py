@@ -10,6 +10,13 @@ LeastSquares(b), r = z - b:  D = -.5 s^2 ||r||^2 - s <r, b>,  f(0) = .5 ||b||^2.
 LogisticLoss(b), f(z) = sum log(1 + e^z) - y z with y = [b == 1]:  D = -sum h(y_i + s (sigma(z_i) - y_i)),  h(p) = p log p + (1 - p) log(1 - p)
 with 0 log 0 = 0, evaluated without cancellation (y = 1: q = s sigma(-z), h = (1 - q) log1p(-q) + q log q; y = 0: the same in p = s sigma(z));
 f(0) = m log 2.  At x = 0 the record's dual norm is the critical mu: for every mu at or above it the gap at 0 is exactly 0.
+
+Gap-safe screening (`screen`; on the device fh_screen, csrc/fh_screen.h), least squares only.  With norms2_j = sum_i a_ij^2 (rows in index order):
+    gap_safe = gap + kappa * eps * (P + f + 2 sqrt(f f0)),  rho = sqrt(2 gap_safe)
+    feature j is zero at every solution when each of its L entries has  (s |g_jl| + rho sqrt(norms2_j)) (1 + 2^-48) < mu
+(GroupShrink: s ||g_j,:||_2 in place of s |g_jl|).  The second term of gap_safe bounds what rounding can take from the computed gap:
+kappa = `screen_kappa`, the longest addition chain of the certificate's sums.  At x = 0 with s = 1 the gap is zero as an identity (r = -b makes P and
+D the same sums) and the radius is 0.  One rounded operation per term, nothing contracted: on exactly representable data the device agrees with ==.
 """
 
 from collections import namedtuple
@@ -20,7 +27,8 @@ from .linalg import is_sparse_matrix
 from .losses import LeastSquares, LogisticLoss
 from .proximal import GroupShrink, Shrink
 
-__all__ = ["Certificate", "duality_gap", "critical_mu", "certificate_from_parts", "logistic_dual_terms", "logistic_loss_terms", "LN2"]
+__all__ = ["Certificate", "duality_gap", "critical_mu", "certificate_from_parts", "logistic_dual_terms", "logistic_loss_terms", "LN2",
+           "Screen", "screen", "screen_from_parts", "screen_kappa", "gap_safe", "column_norms2", "SCREEN_ONE_PLUS"]
 
 LN2 = 0.6931471805599453          # log(2) rounded to nearest (csrc/fh_gap.h: FH_GAP_LN2)
 
@@ -152,3 +160,107 @@ def critical_mu(A, loss, prox_class, shape):
         raise TypeError(f"critical_mu: the certificate is stated for proximal.Shrink and proximal.GroupShrink (got {getattr(prox_class, '__name__', prox_class)!r})")
     shape = (shape,) if isinstance(shape, (int, np.integer)) else tuple(shape)
     return duality_gap(A, loss, prox_class(1.0), np.zeros(shape)).dual_norm
+
+
+# ---- gap-safe screening ---------------------------------------------------------------------------------------------------------------------
+Screen = namedtuple("Screen", "keep radius certificate norms2")      # keep: n booleans (True = the feature stays); radius = rho
+SCREEN_ONE_PLUS = 1.0 + 2.0 ** -48
+_EPS = 2.0 ** -52
+
+
+def _gap_slabs(rows):
+    """The slab rule of k_gap_partials (csrc/fasta_hip.hip: gap_slabs): (workgroups, rows per slab) of one side."""
+    k = min(max((rows + 255) // 256, 1), 256)
+    return k, ((rows + k - 1) // k + 63) // 64 * 64
+
+
+def screen_kappa(m, n, L=1):
+    """The longest addition chain of the certificate's sums for an (m, n) operator and L columns: terms per lane, the depth of block_reduce
+    (10), records per lane in add_records, 8 for the closing arithmetic -- the mirror of fh_screen_shape_for's last entry (csrc/fh_screen.h)."""
+    (nwg_n, slab_n), (nwg_m, slab_m) = _gap_slabs(int(n)), _gap_slabs(int(m))
+    terms = (max(slab_n, slab_m) + 255) // 256 * max(int(L), 1)
+    return terms + 10 + (nwg_n + nwg_m + 255) // 256 + 8
+
+
+def gap_safe(cert, kappa):
+    """gap + kappa * eps * (P + f + 2 sqrt(f f0)), never below 0; exactly 0 at x = 0 inside the dual ball.  One rounded operation per line."""
+    if cert.omega == 0.0 and cert.scale == 1.0:
+        return 0.0
+    t1 = cert.f * cert.f0
+    t2 = float(np.sqrt(t1))
+    t3 = 2.0 * t2
+    t4 = cert.primal + cert.f
+    t5 = t4 + t3
+    ke = float(kappa) * _EPS
+    t6 = ke * t5
+    t7 = cert.gap + t6
+    return max(t7, 0.0)
+
+
+def _columns_of(A):
+    """The stored matrix behind A (an ndarray or a scipy.sparse matrix), or TypeError with a sentence."""
+    if isinstance(A, np.ndarray) or is_sparse_matrix(A):
+        return A
+    M = getattr(A, "matrix", None)
+    if M is not None and (isinstance(M, np.ndarray) or is_sparse_matrix(M)):
+        return A._host_matrix() if hasattr(A, "_host_matrix") else M
+    raise TypeError("screen: A must be an ndarray, a scipy.sparse matrix or a map that holds its matrix (A.matrix): a general map cannot give its columns")
+
+
+def column_norms2(A):
+    """sum_i a_ij^2 per column, rows added in index order (a sparse matrix: its stored entries in row order)."""
+    A = _columns_of(A)
+    if is_sparse_matrix(A):
+        S = A.tocsc()
+        S.sort_indices()
+        ptr, val = S.indptr, np.asarray(S.data, dtype=np.float64)
+        acc = np.zeros(S.shape[1])
+        lens = np.diff(ptr)
+        for k in range(int(lens.max()) if lens.size else 0):
+            sel = np.nonzero(lens > k)[0]
+            v = val[ptr[sel] + k]
+            acc[sel] = acc[sel] + v * v
+        return acc
+    A = np.asarray(A, dtype=np.float64)
+    acc = np.zeros(A.shape[1])
+    for i in range(A.shape[0]):
+        acc = acc + A[i] * A[i]
+    return acc
+
+
+def screen_from_parts(cert, g, norms2, prox, kappa):
+    """The test from a certificate, g = A^H (A x - b) and norms2 as given: (keep, rho).  One rounded operation per term."""
+    prox = getattr(prox, "__self__", prox)
+    mu = float(prox.mu)
+    G = _rows(g)
+    rho = float(np.sqrt(2.0 * gap_safe(cert, kappa)))
+    d = rho * np.sqrt(np.asarray(norms2, dtype=np.float64))
+    s = cert.scale
+    if type(prox) is GroupShrink:
+        a = s * _row_norms(G)
+        discard = (a + d) * SCREEN_ONE_PLUS < mu
+    else:
+        a = s * np.abs(G)
+        discard = np.all((a + d[:, None]) * SCREEN_ONE_PLUS < mu, axis=1)
+    return ~discard, rho
+
+
+def screen(A, loss, prox, x, norms2=None):
+    """The gap-safe test at x for min .5 ||A x - b||^2 + mu * Omega(x): Screen(keep, radius, certificate, norms2).  A feature with keep False is zero
+    at every solution.  A: an ndarray, a scipy.sparse matrix or a map that holds its matrix; loss: a tagged LeastSquares (no weights); prox: a tagged
+    Shrink or GroupShrink with mu > 0.  norms2: column_norms2(A) if the caller already has it.  Anything else: TypeError."""
+    loss, prox = _tags(loss, prox)
+    if type(loss) is not LeastSquares:
+        raise TypeError("screen: the screening radius is stated for losses.LeastSquares (the constant of the logistic loss differs)")
+    M = _columns_of(A)
+    x = np.asarray(x, dtype=np.float64)
+    z = np.asarray(M @ x, dtype=np.float64)
+    if z.shape != loss.b.shape:
+        raise TypeError(f"screen: A x has shape {z.shape}, the loss holds b of shape {loss.b.shape}")
+    g = np.asarray(M.T @ loss.gradf(z), dtype=np.float64)
+    cert = certificate_from_parts(x, g, z, loss, prox)
+    if norms2 is None:
+        norms2 = column_norms2(M)
+    L = x.shape[1] if x.ndim == 2 else 1
+    keep, rho = screen_from_parts(cert, g, norms2, prox, screen_kappa(M.shape[0], M.shape[1], L))
+    return Screen(keep, rho, cert, norms2)

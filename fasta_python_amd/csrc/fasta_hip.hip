@@ -28,6 +28,10 @@
 #include "fh_dct2.h"
 #include "fh_conv.h"
 #include "fh_gap.h"
+#ifdef FH_SINGLE_TU
+#define FH_SCREEN_DEFINE
+#endif
+#include "fh_screen.h"
 #include "fh_nuclear.h"
 #include "fh_prox.h"
 #include "fh_fused.h"
@@ -144,8 +148,10 @@ DCT_FOR_EACH(DCT2_INSTANTIATE)
 DCT2_TILE_KERNELS(template)
 CONV_KERNELS(template)
 GAP_KERNELS(template)
+SCREEN_KERNELS(template)
 #else
 GAP_KERNELS(extern template)
+SCREEN_KERNELS(extern template)
 #endif
 
 #include "fh_host_ctx.h"
@@ -911,6 +917,7 @@ extern "C" int fh_set_rhs(fh_ctx* c, uint32_t L) {
   c->L = L; c->LB = LB;
   c->has_b = false; c->loss_kind = LOSS_LSQ;
   c->last_accel = false; c->commits = 0; c->at_state = false;      // (lazy: the 2-D stencil alone sets it, and it has no multi-column form)
+  c->cn2_held = false;                                             // (fh_column_norms forms them again)
   if (!L) reset_unserved(c, next);                       // (the row-wise shrink has no vector form)
   FH_TRY(alloc_vectors(c));
   return finish(c);
@@ -1516,24 +1523,27 @@ static void gap_slabs(uint64_t rows, uint32_t* nwg, uint64_t* slab) {
   *nwg = (uint32_t)k;
   *slab = round_up((rows + k - 1) / k, 64);
 }
-extern "C" int fh_dual_gap(fh_ctx* c, double* out) {
-  if (!c || !out) return fail(FH_E_ARG, "fh_dual_gap: null argument");
-  if (c->pending_step) return fail(FH_E_ARG, "fh_dual_gap: a step issued by fh_step_begin is still in flight on this context: call fh_step_end first");
+// what fh_dual_gap refuses, in its order; fh_screen (csrc/fh_screen.h) carries the same preconditions under its own name
+static int gap_refusals(fh_ctx* c, const char* who) {
+  if (c->pending_step) return fail(FH_E_ARG, "%s: a step issued by fh_step_begin is still in flight on this context: call fh_step_end first", who);
   if (!c->shards.empty() || c->owner || c->comm)
-    return fail(FH_E_ARG, "fh_dual_gap: a multi-device context or a context with a communicator holds a row block of z = A x0, not z: the certificate is served on a plain context");
-  if (c->loss_w) return fail(FH_E_ARG, "fh_dual_gap: a context that holds observation weights has no duality-gap certificate");
+    return fail(FH_E_ARG, "%s: a multi-device context or a context with a communicator holds a row block of z = A x0, not z: the certificate is served on a plain context", who);
+  if (c->loss_w) return fail(FH_E_ARG, "%s: a context that holds observation weights has no duality-gap certificate", who);
   const OpForm& f = form_of(c);
-  if (!f.gap) return fail(FH_E_ARG, "fh_dual_gap: the %s has no duality-gap certificate (served: the dense and the sparse operator, vector and multi-column, the DCT and the convolution operator)", f.noun);
-  if (!c->has_b) return fail(FH_E_ARG, "fh_dual_gap: no loss set (fh_set_loss_lsq / fh_set_loss_logistic)");
-  if (c->loss_kind != LOSS_LSQ && c->loss_kind != LOSS_LOGISTIC) return fail(FH_E_ARG, "fh_dual_gap: the certificate is implemented for the least-squares and the logistic loss (the context holds loss %d)", c->loss_kind);
-  if (c->prox_kind != FH_PROX_SHRINK && c->prox_kind != FH_PROX_GROUP) return fail(FH_E_ARG, "fh_dual_gap: the certificate is implemented for FH_PROX_SHRINK and FH_PROX_GROUP (the context holds prox kind %d)", c->prox_kind);
-  if (c->loss_kind == LOSS_LOGISTIC && c->LB) return fail(FH_E_ARG, "fh_dual_gap: the logistic loss has no multi-column form");
-  if (!(c->mu > 0.0)) return fail(FH_E_ARG, "fh_dual_gap: the certificate needs mu > 0 (the context holds mu = %g)", c->mu);
-  if (!c->at_state) return fail(FH_E_ARG, "fh_dual_gap: no committed state: call fh_init or fh_setup first (after the operator, the loss and x0 are set)");
-  if (c->last_accel) return fail(FH_E_ARG, "fh_dual_gap: the latest step was accelerated: x0 is the extrapolated iterate and A x0 is formed inside the adjoint launch, never stored "
-                                          "(Z holds A xprox): the certificate is served after fh_init, fh_setup and steps without acceleration");
-  FH_TRY(use_device(c));
-  GapP p;
+  if (!f.gap) return fail(FH_E_ARG, "%s: the %s has no duality-gap certificate (served: the dense and the sparse operator, vector and multi-column, the DCT and the convolution operator)", who, f.noun);
+  if (!c->has_b) return fail(FH_E_ARG, "%s: no loss set (fh_set_loss_lsq / fh_set_loss_logistic)", who);
+  if (c->loss_kind != LOSS_LSQ && c->loss_kind != LOSS_LOGISTIC) return fail(FH_E_ARG, "%s: the certificate is implemented for the least-squares and the logistic loss (the context holds loss %d)", who, c->loss_kind);
+  if (c->prox_kind != FH_PROX_SHRINK && c->prox_kind != FH_PROX_GROUP) return fail(FH_E_ARG, "%s: the certificate is implemented for FH_PROX_SHRINK and FH_PROX_GROUP (the context holds prox kind %d)", who, c->prox_kind);
+  if (c->loss_kind == LOSS_LOGISTIC && c->LB) return fail(FH_E_ARG, "%s: the logistic loss has no multi-column form", who);
+  if (!(c->mu > 0.0)) return fail(FH_E_ARG, "%s: the certificate needs mu > 0 (the context holds mu = %g)", who, c->mu);
+  if (!c->at_state) return fail(FH_E_ARG, "%s: no committed state: call fh_init or fh_setup first (after the operator, the loss and x0 are set)", who);
+  if (c->last_accel) return fail(FH_E_ARG, "%s: the latest step was accelerated: x0 is the extrapolated iterate and A x0 is formed inside the adjoint launch, never stored "
+                                          "(Z holds A xprox): the certificate is served after fh_init, fh_setup and steps without acceleration", who);
+  return 0;
+}
+// the certificate's geometry and its launches; `extra` bytes of the workspace are kept behind its own (*tail: where they begin)
+static int gap_issue(fh_ctx* c, GapP* pp, size_t extra, double** tail) {
+  GapP& p = *pp;
   p.x = c->X[c->xi]; p.g = c->G[c->gc]; p.z = c->Z[c->zc]; p.b = c->b;
   p.n = c->n; p.m = c->m;
   p.L = (uint32_t)l_of(c); p.LB = (uint32_t)lb_of(c);
@@ -1542,8 +1552,9 @@ extern "C" int fh_dual_gap(fh_ctx* c, double* out) {
   p.group = c->prox_kind == FH_PROX_GROUP ? 1 : 0;
   p.mu = c->mu;
   const uint32_t nrec = p.nwg_n + p.nwg_m;
-  FH_TRY(ensure_ws(c, ((size_t)nrec * 8 + p.nwg_m + FH_GAP_NOUT) * sizeof(double)));
+  FH_TRY(ensure_ws(c, ((size_t)nrec * 8 + p.nwg_m + FH_GAP_NOUT) * sizeof(double) + extra));
   p.red = c->ws; p.red2 = c->ws + (size_t)nrec * 8; p.out = p.red2 + p.nwg_m;
+  if (tail) *tail = p.out + FH_GAP_NOUT;
   t_begin(c, FH_K_AUX);
   if (c->loss_kind == LOSS_LOGISTIC) {
     k_gap_partials<LOSS_LOGISTIC><<<dim3(nrec), dim3(FH_WG), 0, c->stream>>>(p);
@@ -1555,8 +1566,149 @@ extern "C" int fh_dual_gap(fh_ctx* c, double* out) {
   }
   t_end(c, FH_K_AUX);
   HIP_TRY(hipGetLastError());
+  return 0;
+}
+extern "C" int fh_dual_gap(fh_ctx* c, double* out) {
+  if (!c || !out) return fail(FH_E_ARG, "fh_dual_gap: null argument");
+  FH_TRY(gap_refusals(c, "fh_dual_gap"));
+  FH_TRY(use_device(c));
+  GapP p;
+  FH_TRY(gap_issue(c, &p, 0, nullptr));
   HIP_TRY(hipMemcpyAsync(out, p.out, FH_GAP_NOUT * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   return finish(c);
+}
+
+// ---- gap-safe screening (kernels in csrc/fh_screen.h, instantiated by fh_screen_part.hip) --------------------------------------------------
+// the forms that store columns: the dense and the sparse operator, vector and multi-column
+static int screen_form_refusal(const fh_ctx* c, const char* who) {
+  const int f = form_index(c);
+  if (f == F_DENSE || f == F_DENSE_MC || f == F_SPARSE || f == F_SPARSE_MC) return 0;
+  if (f == F_NONE) return fail(FH_E_STATE, "%s: no operator set", who);
+  return fail(FH_E_STATE, "%s: the %s stores no columns (served: the dense and the sparse operator, vector and multi-column)", who, kForms[f].noun);
+}
+// the norms' launches, if the context does not hold them yet (no host wait)
+static int column_norms_issue(fh_ctx* c) {
+  if (c->cn2_held) return 0;
+  if (!c->cn2) FH_TRY(alloc_zero(c, &c->cn2, c->nv + 16));
+  if (c->op == OP_SPARSE) {
+    const SpMatP& a = c->sp[1];
+    const uint32_t nshort = (uint32_t)((c->n + FH_WG - 1) / FH_WG);
+    t_begin(c, FH_K_AUX);
+    k_colnorm_csr<<<dim3(nshort + a.nlong), dim3(FH_WG), 0, c->stream>>>(a, nshort, c->cn2);
+    t_end(c, FH_K_AUX);
+  } else {
+    const ScreenShape sh = screen_shape(c->mp, c->ld, c->f32, c->ncu, c->m, c->n, (uint32_t)l_of(c));
+    FH_TRY(ensure_ws(c, (size_t)sh.nslab * c->ld * sizeof(double)));
+    ColnormP p;
+    p.A = c->A; p.mp = c->mp; p.ld = c->ld; p.n = c->n;
+    p.slab = sh.slab; p.nslab = sh.nslab; p.tiles = sh.tiles;
+    p.part = c->ws; p.out = c->cn2;
+    t_begin(c, FH_K_AUX);
+    if (c->f32) k_colnorm_dense<1><<<dim3(sh.grid), dim3(FH_WG), 0, c->stream>>>(p);
+    else k_colnorm_dense<0><<<dim3(sh.grid), dim3(FH_WG), 0, c->stream>>>(p);
+    k_colnorm_final<<<dim3((unsigned)((c->n + FH_WG - 1) / FH_WG)), dim3(FH_WG), 0, c->stream>>>(p);
+    t_end(c, FH_K_AUX);
+  }
+  HIP_TRY(hipGetLastError());
+  c->cn2_held = true;
+  return 0;
+}
+extern "C" int fh_column_norms(fh_ctx* c, double* out) {
+  if (!c) return fail(FH_E_ARG, "fh_column_norms: null context");
+  if (!c->shards.empty() || c->owner) return fail(FH_E_STATE, "fh_column_norms: a multi-device context holds row blocks of A, not its columns: the norms are served on a plain context");
+  if (c->comm) return fail(FH_E_STATE, "fh_column_norms: a context with a communicator (row-sharded run) holds a row block of A, not its columns");
+  if (c->pending_step) return fail(FH_E_STATE, "fh_column_norms: %s", kStepInFlight);
+  FH_TRY(screen_form_refusal(c, "fh_column_norms"));
+  FH_TRY(use_device(c));
+  const int rc = column_norms_issue(c);
+  if (rc != 0) { c->cn2_held = false; return rc; }
+  if (out) HIP_TRY(hipMemcpyAsync(out, c->cn2, c->n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  return finish(c);
+}
+extern "C" int fh_screen(fh_ctx* c, double* report, uint8_t* keep) {
+  if (!c || !report) return fail(FH_E_ARG, "fh_screen: null argument");
+  FH_TRY(gap_refusals(c, "fh_screen"));
+  if (c->loss_kind != LOSS_LSQ) return fail(FH_E_ARG, "fh_screen: the screening radius is stated for the least-squares loss (the constant of the logistic loss differs)");
+  FH_TRY(screen_form_refusal(c, "fh_screen"));
+  FH_TRY(use_device(c));
+  FH_TRY(column_norms_issue(c));      // (its partials lie in the workspace: the certificate's launches follow on the stream)
+  const uint32_t nwg = (uint32_t)((c->n + FH_WG - 1) / FH_WG);
+  const size_t extra = (FH_SCREEN_NOUT + (size_t)(nwg + 1) / 2) * sizeof(double) + round_up(c->n, 16);
+  GapP g;
+  double* tail = nullptr;
+  FH_TRY(gap_issue(c, &g, extra, &tail));
+  ScreenP p;
+  p.g = g.g; p.norms2 = c->cn2; p.cert = g.out;
+  p.n = c->n; p.L = g.L; p.LB = g.LB; p.nwg = nwg;
+  p.kappa = screen_kappa(c->m, c->n, g.L);
+  p.mu = c->mu;
+  p.report = tail;
+  p.counts = reinterpret_cast<uint32_t*>(tail + FH_SCREEN_NOUT);
+  p.keep = reinterpret_cast<uint8_t*>(tail + FH_SCREEN_NOUT + (size_t)(nwg + 1) / 2);
+  t_begin(c, FH_K_AUX);
+  if (g.group) k_screen<1><<<dim3(nwg), dim3(FH_WG), 0, c->stream>>>(p);
+  else k_screen<0><<<dim3(nwg), dim3(FH_WG), 0, c->stream>>>(p);
+  k_screen_final<<<dim3(1), dim3(FH_WG), 0, c->stream>>>(p);
+  t_end(c, FH_K_AUX);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(report, p.report, FH_SCREEN_NOUT * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (keep) HIP_TRY(hipMemcpyAsync(keep, p.keep, c->n, hipMemcpyDeviceToHost, c->stream));
+  return finish(c);
+}
+// a plain context that holds a dense matrix in either form, or what it is instead
+static int gather_plain(const fh_ctx* c, const char* which) {
+  if (!c->shards.empty() || c->owner) return fail(FH_E_STATE, "fh_gather_columns: the %s is a multi-device context: columns are gathered between plain contexts", which);
+  if (c->comm) return fail(FH_E_STATE, "fh_gather_columns: the %s holds a communicator (row-sharded run): columns are gathered between plain contexts", which);
+  if (c->pending_step) return fail(FH_E_STATE, "fh_gather_columns: on the %s, %s", which, kStepInFlight);
+  return 0;
+}
+extern "C" int fh_gather_columns(fh_ctx* dst, fh_ctx* src, const int32_t* idx, uint64_t count) {
+  if (!dst || !src || !idx) return fail(FH_E_ARG, "fh_gather_columns: null argument");
+  if (dst == src) return fail(FH_E_ARG, "fh_gather_columns: the destination is the source: the kept columns go into a second context");
+  FH_TRY(gather_plain(src, "source"));
+  FH_TRY(gather_plain(dst, "destination"));
+  if (src->op != OP_DENSE) return fail(FH_E_STATE, "fh_gather_columns: the source holds no dense matrix (fh_set_matrix / fh_generate_matrix)");
+  if (dst->loss_w) return fail(FH_E_STATE, "fh_gather_columns: the destination holds observation weights (fh_set_loss_weights): remove them before an operator is set");
+  if (dst->device != src->device) return fail(FH_E_ARG, "fh_gather_columns: the destination lives on device %d, the source on device %d: the copy stays on one device", dst->device, src->device);
+  if (dst->f32 != src->f32) return fail(FH_E_ARG, "fh_gather_columns: the destination stores A in %s, the source in %s: the copy does not convert", dst->f32 ? "float32" : "float64", src->f32 ? "float32" : "float64");
+  if (count == 0) return fail(FH_E_ARG, "fh_gather_columns: every feature is screened: the solution is zero");
+  if (count > src->n) return fail(FH_E_ARG, "fh_gather_columns: %llu columns asked of a matrix that has %llu", (unsigned long long)count, (unsigned long long)src->n);
+  for (uint64_t t = 0; t < count; ++t) {
+    if (idx[t] < 0 || (uint64_t)idx[t] >= src->n) return fail(FH_E_ARG, "fh_gather_columns: column index %d at position %llu is out of range (n = %llu)", idx[t], (unsigned long long)t, (unsigned long long)src->n);
+    if (t && idx[t] <= idx[t - 1]) return fail(FH_E_ARG, "fh_gather_columns: the column indices are not strictly increasing at position %llu", (unsigned long long)t);
+  }
+  FH_TRY(use_device(src));
+  HIP_TRY(hipStreamSynchronize(src->stream));      // (the source's launches are over: the copy runs on the destination's stream)
+  FH_TRY(setup_dense(dst, src->m, count));
+  int rc = ensure_ws(dst, round_up(count * sizeof(int32_t), 16));
+  if (rc == 0) {
+    GatherP p;
+    p.src = src->A; p.dst = dst->A; p.idx = reinterpret_cast<const int*>(dst->ws);
+    p.m = src->m; p.mp = dst->mp; p.ld_src = src->ld; p.ld_dst = dst->ld; p.count = count;
+    const uint64_t nwg = std::min<uint64_t>(dst->mp / 16, 8ull * (uint64_t)std::max(1, dst->ncu));
+    p.slab = round_up((dst->mp + nwg - 1) / nwg, 16);
+    const unsigned grid = (unsigned)((dst->mp + p.slab - 1) / p.slab);
+    hipError_t e = hipMemcpyAsync(dst->ws, idx, count * sizeof(int32_t), hipMemcpyHostToDevice, dst->stream);
+    if (e == hipSuccess) {
+      t_begin(dst, FH_K_AUX);
+      if (dst->f32) k_gather_cols<1><<<dim3(grid), dim3(FH_WG), 0, dst->stream>>>(p);
+      else k_gather_cols<0><<<dim3(grid), dim3(FH_WG), 0, dst->stream>>>(p);
+      t_end(dst, FH_K_AUX);
+      e = hipGetLastError();
+    }
+    if (e != hipSuccess) rc = fail((int)e, "fh_gather_columns: %s", hipGetErrorString(e));
+  }
+  return set_end(dst, rc);
+}
+extern "C" int fh_screen_shape_for(uint64_t m, uint64_t n, uint32_t L, int dtype, int ncu, uint32_t* out) {
+  if (!out) return fail(FH_E_ARG, "fh_screen_shape_for: null argument");
+  if (m == 0 || n == 0 || m >= (1ull << 31) || n >= (1ull << 31)) return fail(FH_E_ARG, "fh_screen_shape_for: dimensions in [1, 2^31) (got %llu x %llu)", (unsigned long long)m, (unsigned long long)n);
+  if (L > 16) return fail(FH_E_ARG, "fh_screen_shape_for: at most 16 columns (got %u)", L);
+  if (dtype != FH_DTYPE_F64 && dtype != FH_DTYPE_F32_STORAGE) return fail(FH_E_ARG, "fh_screen_shape_for: dtype is FH_DTYPE_F64 or FH_DTYPE_F32_STORAGE");
+  const int f32 = dtype == FH_DTYPE_F32_STORAGE;
+  const ScreenShape s = screen_shape(round_up(m, 16), round_up(n, f32 ? 32 : 16), f32, ncu, m, n, L);
+  out[0] = s.slab; out[1] = s.nslab; out[2] = s.tile_cols; out[3] = s.tiles; out[4] = s.grid; out[5] = s.kappa;
+  return 0;
 }
 
 extern "C" int fh_fwd(fh_ctx* c, double tau, double* scalars) {

@@ -171,6 +171,9 @@ struct fh_ctx {
   uint64_t nnz = 0;
   double* sp_r = nullptr;
   double* A = nullptr;
+  // squared column norms of A (fh_column_norms, csrc/fh_screen.h): nv doubles, kept until the operator goes; cn2_held: they are those of the operator held
+  double* cn2 = nullptr;
+  bool cn2_held = false;
   size_t a_block_bytes = 0;  // size of the block A lives in (>= the matrix: a kept block may be up to twice as large, see acquire_matrix_block)
   // n-side
   // iterate pool: X[xi] = x0, X[ti] = where the next x1 lands, X[bi] = best-quality iterate (may alias X[xi]):
@@ -585,6 +588,7 @@ static void free_operator(fh_ctx* c) {
     a = SpMatP();
   }
   fr(c->sp_r); c->nnz = 0;
+  fr(c->cn2); c->cn2_held = false;
   for (d2** q : {&c->dct_tw, &c->dct_pw, &c->dct_w0, &c->dct_w1}) if (*q) { (void)hipFree(*q); *q = nullptr; }
   for (d2** q : {&c->dct2_tw, &c->dct2_pw}) if (*q) { (void)hipFree(*q); *q = nullptr; }
   fr(c->dct_diag); fr(c->dct2_w0); fr(c->dct2_w1); c->dct2 = false;

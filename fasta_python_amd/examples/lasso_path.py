@@ -2,8 +2,10 @@
 a geometric grid, every solve warm-started from the one before and stopped at gap <= 1e-6 * f(0) (fasta.path, fasta.stopping.DualityGap).
 LASSO by default; --logistic: sparse logistic regression; --columns L: L right-hand sides and the row-wise l2 penalty (MMV); --sparse DENSITY: a
 scipy.sparse design matrix.  On the device the matrix is uploaded once and the certificate is one call (fh_dual_gap, csrc/fh_gap.h).
+--screen (least squares): gap-safe screening, every round solved over the columns the certificate could not prove zero (fasta.path(screen=True);
+fh_screen and fh_gather_columns, csrc/fh_screen.h); the table then also lists the columns kept and the rounds of each point.
 
-    python -m fasta.examples.lasso_path [--backend hip|numpy] [--rows M] [--features N] [--sparse DENSITY] [--logistic] [--columns L]
+    python -m fasta.examples.lasso_path [--backend hip|numpy] [--rows M] [--features N] [--sparse DENSITY] [--logistic] [--columns L] [--screen]
 
 Three modes as in the other examples (adaptive, accelerated, plain); per point: mu, iterations, support size, relative gap.  The device does not
 certify an accelerated iterate (the image of the extrapolated point is never stored): that mode reports the library's sentence on backend hip.
@@ -40,7 +42,7 @@ def construct(M=200, N=1000, K=10, density=None, logistic=False, columns=1, sigm
     return A, LeastSquares(z + sigma * rng.randn(*z.shape)), (Shrink if columns == 1 else GroupShrink)
 
 
-def run_modes(A, loss, prox_class, backend, n_mus=10, ratio=1e-2, gap_tolerance=1e-6, max_iters=5000, modes=MODES):
+def run_modes(A, loss, prox_class, backend, n_mus=10, ratio=1e-2, gap_tolerance=1e-6, max_iters=5000, modes=MODES, screen=False):
     """The path in each mode; prints one line per point and returns {mode: list of Convergence, or the refusal's sentence}."""
     out = {}
     if backend == "hip" and not hasattr(A, "ctx"):      # one upload for all three modes
@@ -54,17 +56,18 @@ def run_modes(A, loss, prox_class, backend, n_mus=10, ratio=1e-2, gap_tolerance=
             np.random.seed(1)                           # the Lipschitz probes: the same draws for both backends
             try:
                 pts = path(A, loss, prox_class, n_mus=n_mus, ratio=ratio, gap_tolerance=gap_tolerance, backend=backend, adaptive=adaptive,
-                           accelerate=accelerate, max_iters=max_iters)
+                           accelerate=accelerate, max_iters=max_iters, **(dict(screen=True) if screen else {}))
             except ValueError as refusal:
                 if backend != "hip" or not accelerate:
                     raise
                 print("not served on the device: {}".format(refusal))
                 out[label] = str(refusal)
                 continue
-            print("{:>14}  {:>10}  {:>8}  {:>12}".format("mu", "iterations", "support", "relative gap"))
+            print("{:>14}  {:>10}  {:>8}  {:>12}".format("mu", "iterations", "support", "relative gap") + ("  {:>8}  {:>6}".format("kept", "rounds") if screen else ""))
             for p in pts:
                 rows = np.abs(np.reshape(p.solution, (p.solution.shape[0], -1))).sum(axis=1)
-                print("{:14.6e}  {:10d}  {:8d}  {:12.3e}".format(p.mu, p.iteration_count, int(np.count_nonzero(rows)), p.certificate.relative))
+                print("{:14.6e}  {:10d}  {:8d}  {:12.3e}".format(p.mu, p.iteration_count, int(np.count_nonzero(rows)), p.certificate.relative)
+                      + ("  {:8d}  {:6d}".format(p.kept, p.rounds) if screen else ""))
             out[label] = pts
     finally:
         if hasattr(A, "close") and backend == "hip":
@@ -84,7 +87,9 @@ def main(argv=None):
     A, loss, prox_class = construct(M, N, density=density, logistic="--logistic" in argv, columns=columns)
     print("Constructed a {} path problem on a {} x {} {} design matrix, {} column(s).".format(
         "sparse logistic" if "--logistic" in argv else ("LASSO" if columns == 1 else "MMV"), M, N, "dense" if density is None else "sparse", columns))
-    return run_modes(A, loss, prox_class, backend)
+    if "--screen" in argv and "--logistic" in argv:
+        raise SystemExit("--screen goes with least squares (the screening radius of the logistic loss has another constant)")
+    return run_modes(A, loss, prox_class, backend, screen="--screen" in argv)
 
 
 if __name__ == "__main__":

@@ -71,6 +71,8 @@ class RunState(C.Structure):                # fh_run_state
 
 # every exported symbol with its signature; tests assert the .so exports exactly these ------------
 GAP_NOUT = 8            # FH_GAP_NOUT: P, D, gap, f(z), Omega(x0), Omega°(g0), s, f(0)
+SCREEN_NOUT = 4         # FH_SCREEN_NOUT: rho, features kept, gap_safe, mu
+SCREEN_SHAPE_LEN = 6    # FH_SCREEN_SHAPE_LEN: rows per slab, slabs, columns per tile, tiles, workgroups of the norms kernel, kappa
 
 SIGNATURES = {
     "fh_last_error": (C.c_char_p, []),
@@ -137,6 +139,10 @@ SIGNATURES = {
     "fh_adj": (_i32, [_ctx, _dbl, _i32, _dbl, _pd]),
     "fh_commit": (_i32, [_ctx, _i32]),
     "fh_dual_gap": (_i32, [_ctx, _pd]),
+    "fh_column_norms": (_i32, [_ctx, _pd]),
+    "fh_screen": (_i32, [_ctx, _pd, C.POINTER(C.c_uint8)]),
+    "fh_gather_columns": (_i32, [_ctx, _ctx, C.POINTER(C.c_int32), _u64]),
+    "fh_screen_shape_for": (_i32, [_u64, _u64, C.c_uint32, _i32, _i32, C.POINTER(C.c_uint32)]),
     "fh_abi_sizes": (_i32, [C.POINTER(_u64)]),
     "fh_run_supported": (_i32, [_ctx, C.POINTER(_i32)]),
     "fh_run": (_i32, [_ctx, _i32, C.POINTER(RunOpts), C.POINTER(RunState), _pd, C.POINTER(_i32)]),
@@ -273,6 +279,18 @@ def setup_shape_for(m, n, storage="f64", variant_word=34, variant_auto=True, cus
     out = (C.c_uint32 * SETUP_SHAPE_LEN)()
     _check(lib, lib.fh_setup_shape_for(int(m), int(n), STORAGE[storage], int(variant_word), 1 if variant_auto else 0, int(cus), int(min_rows), out))
     return SetupShape(*(int(v) for v in out))
+
+
+ScreenShape = collections.namedtuple("ScreenShape", "slab nslab tile_cols tiles grid kappa")
+
+
+def screen_shape_for(m, n, L=0, storage="f64", ncu=256):
+    """ScreenShape of fh_column_norms' launch on an (m, n) dense matrix and kappa, the longest addition chain of the certificate's sums for an
+    unknown of L columns (0 = a vector): fh_screen_shape_for, the rule the launchers themselves call.  Host-only."""
+    lib = load_library()
+    out = (C.c_uint32 * SCREEN_SHAPE_LEN)()
+    _check(lib, lib.fh_screen_shape_for(int(m), int(n), int(L), STORAGE[storage], int(ncu), out))
+    return ScreenShape(*(int(v) for v in out))
 
 
 MULTI_SHAPE_LEN = 14
@@ -1011,6 +1029,38 @@ class HipContext:
         out = np.empty(GAP_NOUT)
         self._call("fh_dual_gap", out.ctypes.data_as(_pd))
         return Certificate(*(float(v) for v in out))
+
+    def _columns(self):
+        """n, or 0 where the context holds no operator (the call that follows then answers with the library's own sentence)."""
+        try:
+            return self.shape()[1]
+        except HipError:
+            return 0
+
+    def column_norms(self):
+        """fh_column_norms: the squared column norms of the dense or sparse operator, n doubles; the context keeps them until the operator goes
+        (a second call launches nothing)."""
+        out = np.empty(self._columns())
+        self._call("fh_column_norms", out.ctypes.data_as(_pd) if out.size else None)
+        return out
+
+    def screen(self):
+        """fh_screen: the gap-safe test at the committed iterate -- (keep: n booleans, report: rho, features kept, gap_safe, mu).  Changes nothing
+        in the context but the workspace and the kept norms; HipError with the library's sentence where it is not served."""
+        keep = np.empty(self._columns(), dtype=np.uint8)
+        report = np.empty(SCREEN_NOUT)
+        self._call("fh_screen", report.ctypes.data_as(_pd), keep.ctypes.data_as(C.POINTER(C.c_uint8)))
+        return keep.astype(bool), report
+
+    def gather_columns(self, src, idx):
+        """fh_gather_columns: this context <- the columns idx (strictly increasing) of the dense matrix `src` holds, device to device; it comes out
+        as after a dense setter, in vector form."""
+        idx = np.ascontiguousarray(idx)
+        if idx.dtype != np.int32:
+            if idx.dtype.kind not in "iu" or (idx.size and (int(idx.min()) < -2 ** 31 or int(idx.max()) >= 2 ** 31)):
+                raise TypeError("gather_columns: idx must be integers that fit 32 bits")
+            idx = idx.astype(np.int32)
+        _check(self.lib, self.lib.fh_gather_columns(self._h, src._h, idx.ctypes.data_as(C.POINTER(C.c_int32)), int(idx.size)))
 
     def apply(self, v, adjoint=False):
         m, n = self.shape()

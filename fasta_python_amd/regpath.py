@@ -1,5 +1,11 @@
 """Regularisation paths:  min_x f(A x) + mu * Omega(x)  over a decreasing sequence of mu, each solve warm-started from the one before and
-stopped by its duality gap (stopping.DualityGap).  The operator is built -- a matrix uploaded -- once, and the step-size estimate is made once."""
+stopped by its duality gap (stopping.DualityGap).  The operator is built -- a matrix uploaded -- once, and the step-size estimate is made once.
+
+screen=True (least squares): gap-safe screening (certificates.screen; on the device fh_screen / fh_gather_columns, csrc/fh_screen.h).  Per mu, in
+rounds: certify the warm start on the FULL problem; if the gap is not met, discard the features the certificate proves zero, solve over the kept
+columns in a second, working operator down to max(gap_tolerance * f0, screen_shrink * gap), scatter the solution back with zeros, certify again.  A
+round that would discard fewer than SCREEN_MIN_DISCARD of the features runs on the full operator (the copy costs a pass and buys less than one);
+after screen_max_rounds rounds the point is finished there.  The certificate a point reports is always the full problem's."""
 
 import numpy as np
 
@@ -28,12 +34,18 @@ def _unknown_shape(A, loss, x0):
     return (A.shape[1],) + tuple(loss.b.shape[1:])
 
 
-def path(A, loss, prox_class, mus=None, n_mus=20, ratio=1e-3, x0=None, gap_tolerance=1e-6, backend="auto", every=10, **options):
+SCREEN_MIN_DISCARD = 0.5      # a round compacts only if at least this share of the features goes: below it the copy costs more than it saves
+
+
+def path(A, loss, prox_class, mus=None, n_mus=20, ratio=1e-3, x0=None, gap_tolerance=1e-6, backend="auto", every=10,
+         screen=False, screen_shrink=0.1, screen_max_rounds=8, **options):
     """Solve the problem for every mu of `mus` (default: mu_grid from the critical mu, above which the solution is zero, down to ratio times it).
     A: what fasta() takes as its operator; loss: a tagged LeastSquares / LogisticLoss; prox_class: proximal.Shrink or proximal.GroupShrink.
     Returns one Convergence per mu (with `.mu`, `.certificate`, `.gaps`); each solve starts from the previous solution and stops at
     gap <= gap_tolerance * f(0).  On the device the critical mu is element 5 of fh_dual_gap at x0 = 0, the context is created once, and L / tau0
-    of the first solve's estimate serve the later ones.  backend="numpy" runs the same thing on the host loop.  Other options go to the solver."""
+    of the first solve's estimate serve the later ones.  backend="numpy" runs the same thing on the host loop.  Other options go to the solver.
+    screen=True: gap-safe screening as the module text says; each Convergence then also carries `.kept` (features of the last working set) and
+    `.rounds`, `.solution` has full length and `.certificate` is the full problem's.  screen=False is the path without any of it."""
     if prox_class not in (Shrink, GroupShrink):
         raise TypeError(f"path: prox_class must be proximal.Shrink or proximal.GroupShrink (got {getattr(prox_class, '__name__', prox_class)!r})")
     if backend not in ("auto", "hip", "numpy"):
@@ -45,6 +57,14 @@ def path(A, loss, prox_class, mus=None, n_mus=20, ratio=1e-3, x0=None, gap_toler
     x = np.zeros(shape) if x0 is None else np.array(x0, dtype=np.float64)
     options.setdefault("verbose", False)
     rule = stopping.DualityGap(gap_tolerance, every)
+    if screen:
+        from .losses import LeastSquares
+        if type(getattr(loss, "__self__", loss)) is not LeastSquares:
+            raise TypeError("path: screen=True is stated for losses.LeastSquares (the radius of the logistic loss has another constant)")
+        if not 0 < screen_shrink < 1 or int(screen_max_rounds) < 0:
+            raise ValueError("path: needs 0 < screen_shrink < 1 and screen_max_rounds >= 0")
+        side = _HostScreen if backend == "numpy" else _DeviceScreen
+        return _screened_path(side, A, loss, prox_class, mus, n_mus, ratio, x, rule, float(screen_shrink), int(screen_max_rounds), options)
     if backend == "numpy":
         return _host_path(A, loss, prox_class, mus, n_mus, ratio, x, rule, options)
     return _device_path(A, loss, prox_class, mus, n_mus, ratio, x, rule, options)
@@ -98,3 +118,178 @@ def _device_path(A, loss, prox_class, mus, n_mus, ratio, x, rule, options):
     finally:
         if owns:
             op.close()
+
+
+# ---- the path with gap-safe screening ---------------------------------------------------------------------------------------------------------
+def _screened_path(side_class, A, loss, prox_class, mus, n_mus, ratio, x, rule, shrink, max_rounds, options):
+    side = side_class(A, loss, prox_class, x, options)
+    try:
+        if mus is None:
+            mus = mu_grid(side.critical_mu(x.shape), n_mus, ratio)
+        side.estimate(prox_class(float(mus[0])), x)
+        out = []
+        for mu in mus:
+            conv = _screened_point(side, prox_class(float(mu)), x, rule, shrink, max_rounds)
+            conv.mu = float(mu)
+            x = np.array(conv.solution, dtype=np.float64)
+            out.append(conv)
+        return out
+    finally:
+        side.close()
+
+
+def _screened_point(side, reg, x, rule, shrink, max_rounds):
+    from .solver import Convergence
+    n = x.shape[0]
+    parts, gaps, iters, rounds, kept = [], [], 0, 0, n
+    while True:
+        cert, keep = side.certify(reg, x, want_mask=lambda c: not rule.met(c) and rounds < max_rounds)
+        gaps.append((iters, cert.gap))
+        if rule.met(cert) or iters >= side.max_iters:
+            break
+        if keep is None:                                # the rounds are spent: finish on the full operator
+            conv = side.solve_full(reg, x, rule)
+        else:
+            rounds += 1
+            idx = np.flatnonzero(keep)
+            target = stopping.DualityGap(max(rule.tolerance, shrink * cert.gap / cert.f0), rule.every)
+            if idx.size == 0:                           # every feature is screened: the solution is zero
+                x, kept = np.zeros_like(x), 0
+                continue
+            if n - idx.size < SCREEN_MIN_DISCARD * n:
+                conv = side.solve_full(reg, x, target)
+            else:
+                kept = int(idx.size)
+                conv = side.solve_kept(reg, idx, x[idx], target)
+                full = np.zeros_like(x)
+                full[idx] = conv.solution
+                conv.solution = full
+        x = np.array(conv.solution, dtype=np.float64)
+        iters += conv.iteration_count
+        parts.append(conv)
+    cat = lambda name: np.concatenate([np.asarray(getattr(p, name))[:p.iteration_count] for p in parts]) if parts else np.zeros(0)
+    conv = Convergence(cat("residuals"), cat("norm_residuals"), cat("stepsizes"), sum(p.backtracks for p in parts), cat("times"), iters, x)
+    conv.certificate, conv.gaps, conv.kept, conv.rounds = cert, gaps, kept, rounds
+    return conv
+
+
+class _HostScreen:
+    """The host side of the screened path: certificates.screen, column slices, the generic host loop."""
+
+    def __init__(self, A, loss, prox_class, x, options):
+        from .generic import host_map
+        for name in ("fused", "device_iters", "driver"):
+            options.pop(name, None)
+        self.M = certificates._columns_of(A)
+        self.loss, self.options = loss, options
+        self.op = host_map(self.M, None, x)
+        self.norms2 = certificates.column_norms2(self.M)
+        self.L, self.tau0 = options.pop("L", None), options.pop("tau0", None)
+        self.max_iters = options.get("max_iters", 1000)
+        self.prox_class = prox_class
+
+    def critical_mu(self, shape):
+        return certificates.critical_mu(self.op, self.loss, self.prox_class, shape)
+
+    def _solver(self, op, reg, x, rule):
+        from .generic import HostFBS
+        return HostFBS(op, self.loss.f, self.loss.gradf, reg.g, reg.prox, x, L=self.L, tau0=self.tau0, stop_rule=rule, **self.options)
+
+    def estimate(self, reg, x):
+        if not self.L or not self.tau0:
+            solver = self._solver(self.op, reg, x, stopping.DualityGap(0.0, 1)).setup()
+            self.L, self.tau0 = solver.L, solver.tau0
+
+    def certify(self, reg, x, want_mask):
+        sc = certificates.screen(self.M, self.loss, reg, x, norms2=self.norms2)
+        return sc.certificate, (sc.keep if want_mask(sc.certificate) else None)
+
+    def solve_full(self, reg, x, rule):
+        return self._solver(self.op, reg, x, rule).setup().run()
+
+    def solve_kept(self, reg, idx, x, rule):
+        from .generic import host_map
+        return self._solver(host_map(self.M[:, idx], None, x), reg, x, rule).setup().run()
+
+    def close(self):
+        pass
+
+
+class _DeviceScreen:
+    """The device side: fh_init + fh_dual_gap + fh_screen on the full context; the kept columns go device to device into a working context
+    (fh_gather_columns) for a dense matrix, through a host slice and the CSR setter for a sparse one.  One working operator per path."""
+
+    def __init__(self, A, loss, prox_class, x, options):
+        from .solver import _recognise, _unrecognised
+        probe = prox_class(1.0)
+        why_not = _unrecognised(A, None, loss.f, loss.gradf, probe.g, probe.prox, x)
+        if why_not is not None:
+            raise TypeError("path(): " + why_not + ' (backend="numpy" runs the path on the host loop)')
+        self.owns = isinstance(A, np.ndarray) or is_sparse_matrix(A)
+        self.op, self.loss, _ = _recognise(A, None, loss.f, loss.gradf, probe.g, probe.prox, x)
+        self.work = None
+        self.prox_class, self.options = prox_class, options
+        self.L, self.tau0 = options.pop("L", None), options.pop("tau0", None)
+        self.max_iters = options.get("max_iters", 1000)
+        self.cols = x.shape[1] if x.ndim == 2 else None
+
+    def _at(self, reg, x):
+        from . import hip
+        c = self.op.ctx
+        self.loss.bind(c)
+        c.set_prox(reg.kind, reg.mu, 0.0, 0.0)
+        c.set_vector(hip.VEC_X0, x)
+        c.init()
+        return c
+
+    def critical_mu(self, shape):
+        return self._at(self.prox_class(1.0), np.zeros(shape)).dual_gap().dual_norm
+
+    def _solver(self, op, reg, x, rule):
+        from .solver import FBSolver
+        return FBSolver(op, self.loss, reg, x, L=self.L, tau0=self.tau0, stop_rule=rule, **self.options)
+
+    def estimate(self, reg, x):
+        if not self.L or not self.tau0:
+            solver = self._solver(self.op, reg, x, stopping.DualityGap(0.0, 1)).setup()
+            self.L, self.tau0 = solver.L, solver.tau0
+
+    def certify(self, reg, x, want_mask):
+        c = self._at(reg, x)
+        cert = c.dual_gap()
+        return cert, (c.screen()[0] if want_mask(cert) else None)
+
+    def solve_full(self, reg, x, rule):
+        return self._solver(self.op, reg, x, rule).setup().run()
+
+    def solve_kept(self, reg, idx, x, rule):
+        from .linalg import DenseMatrixMap, SparseMatrixMap
+        m = self.op.shape[0]
+        cols = () if self.cols is None else (self.cols,)
+        if isinstance(self.op, SparseMatrixMap):
+            S = self.op.matrix[:, idx]
+            if self.work is None:
+                self.work = SparseMatrixMap(S, device=self.op.device, rhs=self.cols)
+                self.work.ctx
+            else:                                       # the same context takes the next slice through the CSR setter
+                from .linalg import canonical_csr
+                data, indices, indptr, shape = canonical_csr(S)
+                w = self.work
+                w.csr, w.shape, w._host = (data, indices, indptr), shape, S.tocsr()
+                w._on_context(w.ctx)
+        else:
+            if self.work is None:
+                self.work = DenseMatrixMap(_defer=True, device=self.op.device, storage=self.op.storage, rhs=self.cols)
+            w = self.work
+            w.ctx.gather_columns(self.op.ctx, idx)
+            if self.cols is not None:
+                w.ctx.set_rhs(self.cols)
+            w.shape = (m, int(idx.size))
+        self.work.Vshape, self.work.Wshape = (int(idx.size),) + cols, (m,) + cols
+        return self._solver(self.work, reg, x, rule).setup().run()
+
+    def close(self):
+        if self.work is not None:
+            self.work.close()
+        if self.owns:
+            self.op.close()

@@ -696,6 +696,36 @@ int fh_commit(fh_ctx* ctx, int save_best);
  * loss, the column count, x0, g0 or b were set); a step in flight (fh_step_begin); a latest step that was accelerated.                          */
 #define FH_GAP_NOUT 8
 int fh_dual_gap(fh_ctx* ctx, double* out);
+/* ---- gap-safe screening (csrc/fh_screen.h; the host statement is fasta_python_amd/certificates.py: screen) ----------------------------------------
+ * Least squares with FH_PROX_SHRINK (any L) or FH_PROX_GROUP.  With the certificate above at the committed iterate and norms2_j = sum_i a_ij^2:
+ *   gap_safe = gap + kappa * eps * (P + f + 2 sqrt(f * f(0))),  rho = sqrt(2 * gap_safe),
+ *   feature j is zero at every solution when each of its L entries has (s * |g0_jl| + rho * sqrt(norms2_j)) * (1 + 2^-48) < mu
+ * (FH_PROX_GROUP: s * ||g0_j,:||_2 in place of s * |g0_jl|).  kappa * eps * (...) bounds what rounding can take from the computed gap: kappa is the
+ * longest addition chain of the certificate's sums at this shape (fh_screen_shape_for reports it); at x0 = 0 inside the dual ball (Omega = 0, s = 1) the
+ * gap is zero as an identity and so is rho.  Ordinary launches, no float atomics, fixed summation order, bitwise repeatable; FH_K_AUX.
+ * fh_column_norms: norms2 of the dense operator (vector and multi-column, either storage: one streaming read of A) or of the sparse operator (its
+ * by-columns copy, entries in stored order), kept in the context until the operator goes -- any operator setter and fh_set_rhs drop them -- so a second
+ * call launches nothing; out: n doubles, or NULL.  Refused, FH_E_STATE with one sentence each: every other form, an empty context, a multi-device
+ * context, one with a communicator, a step in flight.
+ * fh_screen: the certificate's launches, the norms if they are not held, the test.  report[FH_SCREEN_NOUT] = { rho, features kept, gap_safe, mu };
+ * keep: one byte per feature (1 = kept), or NULL.  The preconditions and refusals of fh_dual_gap under its own name (FH_E_ARG), then the logistic loss
+ * (FH_E_ARG) and the forms fh_column_norms refuses (FH_E_STATE: the DCT and the convolution store no columns).  Nothing of the context changes but the
+ * workspace and the kept norms.
+ * fh_gather_columns: dst <- the `count` columns idx[0] < idx[1] < ... of src's dense matrix, device to device, as fh_generate_matrix would have set an
+ * (m, count) matrix: dst comes out in vector form and keeps its prox kind and loss as a dense setter keeps them; padding rows and columns are zero.
+ * src: a plain context holding a dense matrix (vector or multi-column form), never written.  dst: another plain context on the same device with the same
+ * storage.  Refused with one sentence each: dst == src, another device, another storage, an index out of [0, n), indices not strictly increasing,
+ * count > n (FH_E_ARG); count == 0 (FH_E_ARG: "every feature is screened: the solution is zero"); a multi-device context, a communicator or a step in
+ * flight on either side, a source without a dense matrix, observation weights on dst (FH_E_STATE).  If an allocation fails dst is left without an
+ * operator; src is untouched.
+ * fh_screen_shape_for: the pure rule, out[FH_SCREEN_SHAPE_LEN] = { rows per slab, slabs, columns per tile, tiles, workgroups of the norms kernel, kappa }
+ * for an (m, n) matrix, L columns of the unknown (0 = a vector), on ncu CUs (<= 0: 256).                                                          */
+#define FH_SCREEN_NOUT 4
+#define FH_SCREEN_SHAPE_LEN 6
+int fh_column_norms(fh_ctx* ctx, double* out);
+int fh_screen(fh_ctx* ctx, double* report, uint8_t* keep);
+int fh_gather_columns(fh_ctx* dst, fh_ctx* src, const int32_t* idx, uint64_t count);
+int fh_screen_shape_for(uint64_t m, uint64_t n, uint32_t L, int dtype, int ncu, uint32_t* out);
 /* plain operator application on host vectors (tests, synthetic b): adjoint=0: out(m) = A in(n);
  * adjoint=1: out(n) = A^H in(m).                                                                 */
 int fh_apply(fh_ctx* ctx, int adjoint, const double* in, double* out);
