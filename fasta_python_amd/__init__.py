@@ -14,15 +14,16 @@ losses.LogisticLoss(B) / LeastSquares(B) and a 2-D x0 of B's shape (the identity
 (`generic.py`, the reference's semantics).  `backend="hip"` / `backend="numpy"` force either.
 """
 
-from . import certificates, generic, hip, linalg, losses, proximal, regpath, stopping
+from . import certificates, generic, hip, linalg, losses, preprocess, proximal, regpath, stopping
 from .certificates import Certificate, critical_mu, duality_gap
 from .linalg import BilinearMap, ConvMap, DCTMap, DenseMatrixMap, GradDivMap, IdentityMap, LinearMap, LinearOperator, QuadraticMap, ShardedDenseMatrixMap, SparseMatrixMap
 from .losses import Factorization, LeastSquares, LogisticLoss, Quadratic, SoftmaxLoss
+from .preprocess import Standardization, standardize
 from .proximal import Box, GroupShrink, L1Ball, LinfProx, NonNeg, NoProx, NuclearBall, NuclearShrink, RowBall, RowSplit, Shrink, TVDualBall
 from .regpath import path
 from .solver import EPSILON, Convergence, FBSolver, fasta
 from .stopping import DualityGap
 
-__all__ = ["fasta", "Convergence", "FBSolver", "EPSILON", "linalg", "proximal", "stopping", "losses", "hip", "certificates", "path", "duality_gap", "critical_mu", "Certificate", "DualityGap",
+__all__ = ["fasta", "Convergence", "FBSolver", "EPSILON", "linalg", "proximal", "stopping", "losses", "hip", "certificates", "preprocess", "standardize", "Standardization", "path", "duality_gap", "critical_mu", "Certificate", "DualityGap",
            "LinearMap", "LinearOperator", "DenseMatrixMap", "ShardedDenseMatrixMap", "SparseMatrixMap", "GradDivMap", "DCTMap", "ConvMap", "QuadraticMap", "BilinearMap", "IdentityMap", "LeastSquares", "LogisticLoss", "SoftmaxLoss", "Quadratic", "Factorization",
            "Shrink", "NonNeg", "LinfProx", "L1Ball", "Box", "TVDualBall", "GroupShrink", "RowBall", "RowSplit", "NuclearShrink", "NuclearBall", "NoProx"]

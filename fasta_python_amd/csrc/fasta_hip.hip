@@ -32,6 +32,10 @@
 #define FH_SCREEN_DEFINE
 #endif
 #include "fh_screen.h"
+#ifdef FH_SINGLE_TU
+#define FH_STANDARDIZE_DEFINE
+#endif
+#include "fh_standardize.h"
 #include "fh_nuclear.h"
 #include "fh_prox.h"
 #include "fh_fused.h"
@@ -149,9 +153,11 @@ DCT2_TILE_KERNELS(template)
 CONV_KERNELS(template)
 GAP_KERNELS(template)
 SCREEN_KERNELS(template)
+STD_KERNELS(template)
 #else
 GAP_KERNELS(extern template)
 SCREEN_KERNELS(extern template)
+STD_KERNELS(extern template)
 #endif
 
 #include "fh_host_ctx.h"
@@ -1700,6 +1706,88 @@ extern "C" int fh_gather_columns(fh_ctx* dst, fh_ctx* src, const int32_t* idx, u
   }
   return set_end(dst, rc);
 }
+// ---- standardised features (kernels in csrc/fh_standardize.h, instantiated by fh_standardize_part.hip) ------------------------------------
+// the launches over the dense block: [sums, means,] [centred squares,] scales, rewrite; mean / scl: ld doubles each in the workspace
+static int standardize_dense(fh_ctx* c, int center, int scale, double** mean, double** scl) {
+  const ScreenShape sh = screen_shape(c->mp, c->ld, c->f32, c->ncu, c->m, c->n, (uint32_t)l_of(c));
+  FH_TRY(ensure_ws(c, ((size_t)sh.nslab + 2) * c->ld * sizeof(double)));
+  StdP p;
+  p.A = c->A; p.m = c->m; p.n = c->n; p.mp = c->mp; p.ld = c->ld;
+  p.slab = sh.slab; p.nslab = sh.nslab; p.tiles = sh.tiles;
+  p.which = 0; p.want = scale ? 1 : 0;
+  p.part = c->ws; p.mean = c->ws + (size_t)sh.nslab * c->ld; p.scl = p.mean + c->ld;
+  *mean = p.mean; *scl = p.scl;
+  const dim3 grid(sh.grid), wg(FH_WG), cols((unsigned)((c->ld + FH_WG - 1) / FH_WG));
+  if (center) {
+    t_begin(c, FH_K_AUX);
+    if (c->f32) k_std_pass_dense<1, 0><<<grid, wg, 0, c->stream>>>(p);
+    else k_std_pass_dense<0, 0><<<grid, wg, 0, c->stream>>>(p);
+    k_std_final<<<cols, wg, 0, c->stream>>>(p);
+    t_end(c, FH_K_AUX);
+  } else {
+    HIP_TRY(hipMemsetAsync(p.mean, 0, c->ld * sizeof(double), c->stream));
+  }
+  p.which = 1;
+  t_begin(c, FH_K_AUX);
+  if (scale) {
+    if (c->f32) k_std_pass_dense<1, 1><<<grid, wg, 0, c->stream>>>(p);
+    else k_std_pass_dense<0, 1><<<grid, wg, 0, c->stream>>>(p);
+  }
+  k_std_final<<<cols, wg, 0, c->stream>>>(p);      // (scale not asked: ones)
+  t_end(c, FH_K_AUX);
+  t_begin(c, FH_K_AUX);
+  if (c->f32) k_std_rewrite_dense<1><<<grid, wg, 0, c->stream>>>(p);
+  else k_std_rewrite_dense<0><<<grid, wg, 0, c->stream>>>(p);
+  t_end(c, FH_K_AUX);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+// the sparse operator: norms2 of the by-columns copy, the scales from them, both copies divided
+static int standardize_sparse(fh_ctx* c, double** mean, double** scl) {
+  FH_TRY(ensure_ws(c, 2 * (size_t)c->nv * sizeof(double)));
+  const SpMatP& at = c->sp[1];
+  const uint32_t nshort = (uint32_t)((c->n + FH_WG - 1) / FH_WG);
+  StdP p = {};
+  p.m = c->m; p.n = c->n; p.ld = c->n;
+  p.which = 1; p.want = 1;
+  p.mean = c->ws; p.scl = c->ws + c->nv;
+  *mean = p.mean; *scl = p.scl;
+  HIP_TRY(hipMemsetAsync(p.mean, 0, c->nv * sizeof(double), c->stream));
+  const unsigned rows_grid = (unsigned)std::min<uint64_t>(std::max<uint64_t>((c->nnz + FH_WG - 1) / FH_WG, 1), 8ull * (uint64_t)std::max(1, c->ncu));
+  t_begin(c, FH_K_AUX);
+  k_colnorm_csr<<<dim3(nshort + at.nlong), dim3(FH_WG), 0, c->stream>>>(at, nshort, p.scl);
+  k_std_final<<<dim3(nshort), dim3(FH_WG), 0, c->stream>>>(p);
+  t_end(c, FH_K_AUX);
+  t_begin(c, FH_K_AUX);
+  k_std_scale_cols<<<dim3(nshort + at.nlong), dim3(FH_WG), 0, c->stream>>>(at, nshort, p.scl);
+  k_std_scale_rows<<<dim3(rows_grid), dim3(FH_WG), 0, c->stream>>>(c->sp[0], (unsigned long long)c->nnz, p.scl);
+  t_end(c, FH_K_AUX);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+extern "C" int fh_standardize(fh_ctx* c, int center, int scale, double* means, double* scales) {
+  if (!c) return fail(FH_E_ARG, "fh_standardize: null context");
+  if (!center && !scale) return fail(FH_E_ARG, "fh_standardize: neither center nor scale is asked: nothing to do");
+  if (!c->shards.empty() || c->owner) return fail(FH_E_STATE, "fh_standardize: a multi-device context holds row blocks of A, not its columns: the columns are standardised on a plain context");
+  if (c->comm) return fail(FH_E_STATE, "fh_standardize: a context with a communicator (row-sharded run) holds a row block of A, not its columns");
+  if (c->pending_step) return fail(FH_E_STATE, "fh_standardize: %s", kStepInFlight);
+  if (c->loss_w) return fail(FH_E_STATE, "fh_standardize: the context holds observation weights (fh_set_loss_weights), which the identity operator alone serves: it stores no columns");
+  FH_TRY(screen_form_refusal(c, "fh_standardize"));
+  if (center && c->op == OP_SPARSE) return fail(FH_E_ARG, "fh_standardize: centring would fill the sparse matrix: the sparse operator is served with scale alone (center = 0)");
+  FH_TRY(use_device(c));
+  // as after an operator setter: no committed state, the kept norms are those of the old columns, the scalar block is the old operator's
+  c->last_accel = false; c->commits = 0; c->at_state = false;
+  c->cn2_held = false;
+  double* mean = nullptr;
+  double* scl = nullptr;
+  int rc = c->op == OP_SPARSE ? standardize_sparse(c, &mean, &scl) : standardize_dense(c, center, scale, &mean, &scl);
+  if (rc == 0 && means) { const hipError_t e = hipMemcpyAsync(means, mean, c->n * sizeof(double), hipMemcpyDeviceToHost, c->stream); if (e != hipSuccess) rc = fail((int)e, "fh_standardize: %s", hipGetErrorString(e)); }
+  if (rc == 0 && scales) { const hipError_t e = hipMemcpyAsync(scales, scl, c->n * sizeof(double), hipMemcpyDeviceToHost, c->stream); if (e != hipSuccess) rc = fail((int)e, "fh_standardize: %s", hipGetErrorString(e)); }
+  const int rs = finish(c);
+  if (c->hscal) memset(c->hscal, 0, FH_NSCALARS * sizeof(double));
+  return rc != 0 ? rc : rs;
+}
+
 extern "C" int fh_screen_shape_for(uint64_t m, uint64_t n, uint32_t L, int dtype, int ncu, uint32_t* out) {
   if (!out) return fail(FH_E_ARG, "fh_screen_shape_for: null argument");
   if (m == 0 || n == 0 || m >= (1ull << 31) || n >= (1ull << 31)) return fail(FH_E_ARG, "fh_screen_shape_for: dimensions in [1, 2^31) (got %llu x %llu)", (unsigned long long)m, (unsigned long long)n);

@@ -143,6 +143,7 @@ SIGNATURES = {
     "fh_screen": (_i32, [_ctx, _pd, C.POINTER(C.c_uint8)]),
     "fh_gather_columns": (_i32, [_ctx, _ctx, C.POINTER(C.c_int32), _u64]),
     "fh_screen_shape_for": (_i32, [_u64, _u64, C.c_uint32, _i32, _i32, C.POINTER(C.c_uint32)]),
+    "fh_standardize": (_i32, [_ctx, _i32, _i32, _pd, _pd]),
     "fh_abi_sizes": (_i32, [C.POINTER(_u64)]),
     "fh_run_supported": (_i32, [_ctx, C.POINTER(_i32)]),
     "fh_run": (_i32, [_ctx, _i32, C.POINTER(RunOpts), C.POINTER(RunState), _pd, C.POINTER(_i32)]),
@@ -1061,6 +1062,16 @@ class HipContext:
                 raise TypeError("gather_columns: idx must be integers that fit 32 bits")
             idx = idx.astype(np.int32)
         _check(self.lib, self.lib.fh_gather_columns(self._h, src._h, idx.ctypes.data_as(C.POINTER(C.c_int32)), int(idx.size)))
+
+    def standardize(self, center=True, scale=True):
+        """fh_standardize: the dense or sparse matrix the context holds rewritten in place as (a - mean) / scale per column (csrc/fh_standardize.h;
+        the host statement is preprocess.standardize) -- (means, scales), n doubles each.  A sparse operator is served with center=False.  The
+        context comes out as after an operator setter: init() before the next certificate; prox kind, loss, b, x0 and the column count stay."""
+        n = self._columns()
+        means, scales = np.empty(n), np.empty(n)
+        self._call("fh_standardize", 1 if center else 0, 1 if scale else 0,
+                   means.ctypes.data_as(_pd) if n else None, scales.ctypes.data_as(_pd) if n else None)
+        return means, scales
 
     def apply(self, v, adjoint=False):
         m, n = self.shape()

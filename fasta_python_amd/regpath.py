@@ -5,7 +5,11 @@ screen=True (least squares): gap-safe screening (certificates.screen; on the dev
 rounds: certify the warm start on the FULL problem; if the gap is not met, discard the features the certificate proves zero, solve over the kept
 columns in a second, working operator down to max(gap_tolerance * f0, screen_shrink * gap), scatter the solution back with zeros, certify again.  A
 round that would discard fewer than SCREEN_MIN_DISCARD of the features runs on the full operator (the copy costs a pass and buys less than one);
-after screen_max_rounds rounds the point is finished there.  The certificate a point reports is always the full problem's."""
+after screen_max_rounds rounds the point is finished there.  The certificate a point reports is always the full problem's.
+
+standardize=True / intercept=True: the problem solved is the one on standardised columns (preprocess.standardize; on the device fh_standardize,
+csrc/fh_standardize.h, once, right after the upload) and, with an intercept, on b - mean(b); every point keeps the solution, the certificate and the
+gaps of THAT problem -- the one the certificate certifies -- and gains `.coefficients` and `.intercept` in the caller's units."""
 
 import numpy as np
 
@@ -38,14 +42,23 @@ SCREEN_MIN_DISCARD = 0.5      # a round compacts only if at least this share of 
 
 
 def path(A, loss, prox_class, mus=None, n_mus=20, ratio=1e-3, x0=None, gap_tolerance=1e-6, backend="auto", every=10,
-         screen=False, screen_shrink=0.1, screen_max_rounds=8, **options):
+         screen=False, screen_shrink=0.1, screen_max_rounds=8, standardize=False, intercept=False, **options):
     """Solve the problem for every mu of `mus` (default: mu_grid from the critical mu, above which the solution is zero, down to ratio times it).
     A: what fasta() takes as its operator; loss: a tagged LeastSquares / LogisticLoss; prox_class: proximal.Shrink or proximal.GroupShrink.
     Returns one Convergence per mu (with `.mu`, `.certificate`, `.gaps`); each solve starts from the previous solution and stops at
     gap <= gap_tolerance * f(0).  On the device the critical mu is element 5 of fh_dual_gap at x0 = 0, the context is created once, and L / tau0
     of the first solve's estimate serve the later ones.  backend="numpy" runs the same thing on the host loop.  Other options go to the solver.
     screen=True: gap-safe screening as the module text says; each Convergence then also carries `.kept` (features of the last working set) and
-    `.rounds`, `.solution` has full length and `.certificate` is the full problem's.  screen=False is the path without any of it."""
+    `.rounds`, `.solution` has full length and `.certificate` is the full problem's.  screen=False is the path without any of it.
+    intercept=True (LeastSquares without weights, a dense matrix): the columns are centred and the solve uses LeastSquares(b - mean(b)), the mean per
+    column of b.  standardize=True (a dense matrix; a sparse one: scaling only): the columns are scaled to unit root-mean-square, about the mean with
+    intercept=True.  A is then an ndarray or a scipy.sparse matrix -- the path uploads it and rewrites its own copy.  `.solution`, `.certificate` and
+    `.gaps` are those of the standardised problem; each Convergence gains `.coefficients` and `.intercept` (a float, or L floats) in the caller's
+    units, and the first one carries `.standardization` (preprocess.Standardization).  With both False nothing of this runs."""
+    if standardize or intercept:
+        return _standardized_path(A, loss, prox_class, bool(standardize), bool(intercept), x0, backend,
+                                  dict(mus=mus, n_mus=n_mus, ratio=ratio, gap_tolerance=gap_tolerance, every=every, screen=screen,
+                                       screen_shrink=screen_shrink, screen_max_rounds=screen_max_rounds, **options))
     if prox_class not in (Shrink, GroupShrink):
         raise TypeError(f"path: prox_class must be proximal.Shrink or proximal.GroupShrink (got {getattr(prox_class, '__name__', prox_class)!r})")
     if backend not in ("auto", "hip", "numpy"):
@@ -293,3 +306,69 @@ class _DeviceScreen:
             self.work.close()
         if self.owns:
             self.op.close()
+
+
+# ---- the path on standardised features ----------------------------------------------------------------------------------------------------------
+def _standardized_path(A, loss, prox_class, scale, center, x0, backend, keywords):
+    """The refusals, the standardised operator (the device's own copy rewritten by fh_standardize, or preprocess.standardize on the host), the path
+    on it through path() itself, then the way back to the caller's units."""
+    from . import preprocess
+    from .linalg import DenseMatrixMap, ShardedDenseMatrixMap, SparseMatrixMap, _DeviceMap
+    from .losses import LeastSquares, LogisticLoss
+    if prox_class not in (Shrink, GroupShrink):
+        raise TypeError(f"path: prox_class must be proximal.Shrink or proximal.GroupShrink (got {getattr(prox_class, '__name__', prox_class)!r})")
+    if backend not in ("auto", "hip", "numpy"):
+        raise ValueError('backend must be "auto", "hip" or "numpy"')
+    tag = getattr(loss, "__self__", loss)
+    if center and isinstance(tag, LogisticLoss):
+        raise TypeError("path: intercept=True is served for losses.LeastSquares without weights on a dense matrix: the intercept of the logistic loss "
+                        "has no closed form")
+    if center and (type(tag) is not LeastSquares or tag.weights is not None):
+        raise TypeError("path: intercept=True is served for losses.LeastSquares without weights on a dense matrix")
+    if isinstance(A, ShardedDenseMatrixMap):
+        raise TypeError("path: standardize / intercept are served for an ndarray (dense) or a scipy.sparse matrix (scaling only), not for a sharded map: "
+                        "a row-sharded context holds row blocks, not columns")
+    if isinstance(A, _DeviceMap):
+        raise TypeError(f"path: standardize / intercept are served for an ndarray (dense) or a scipy.sparse matrix (scaling only): a {type(A).__name__} "
+                        "owns its context, which is the caller's to rewrite -- call map.ctx.standardize() and map the coefficients back with "
+                        "preprocess.Standardization")
+    sparse = is_sparse_matrix(A)
+    if not sparse and not isinstance(A, np.ndarray):
+        raise TypeError("path: standardize / intercept are served for an ndarray (dense) or a scipy.sparse matrix (scaling only): a general map cannot "
+                        "give its columns")
+    if sparse and center:
+        raise TypeError("path: intercept=True is served for losses.LeastSquares without weights on a dense matrix: " + preprocess.SPARSE_CENTER_REFUSAL
+                        + " (standardize=True alone is served)")
+    b_mean = 0.0 if tag.b.ndim == 1 else np.zeros(tag.b.shape[1])
+    if center:
+        b_mean = tag.b.mean(axis=0)
+        b_mean = float(b_mean) if tag.b.ndim == 1 else b_mean
+        loss = LeastSquares(tag.b - b_mean)
+    if backend == "numpy":
+        A_std, st = preprocess.standardize(A, center=center, scale=scale)
+        out = path(A_std, loss, prox_class, x0=x0, backend=backend, **keywords)
+    else:
+        from .solver import _unrecognised
+        shape = _unknown_shape(A, loss, x0)
+        probe = prox_class(1.0)
+        why_not = _unrecognised(A, None, loss.f, loss.gradf, probe.g, probe.prox, np.zeros(shape))
+        if why_not is not None:
+            raise TypeError("path(): " + why_not + ' (backend="numpy" runs the path on the host loop)')
+        op = SparseMatrixMap(A) if sparse else DenseMatrixMap(A, rhs=shape[1] if len(shape) == 2 else None)
+        try:
+            st = preprocess.Standardization(*op.ctx.standardize(center=center, scale=scale), op.shape[0])
+            if sparse:                                  # the host copy the map applies and the screened path slices: the same division, the same bits
+                data, indices, indptr = op.csr
+                op.csr = (data / st.scales[indices], indices, indptr)
+                op._host = type(op._host)((op.csr[0], indices, indptr), shape=op.shape)
+            else:
+                op.matrix = None                        # (the caller's array is not what the context holds any more: the map applies the device copy)
+            out = path(op, loss, prox_class, x0=x0, backend=backend, **keywords)
+        finally:
+            op.close()
+    for conv in out:
+        conv.coefficients = st.coefficients(conv.solution)
+        conv.intercept = st.intercept(conv.solution, b_mean)
+    if out:
+        out[0].standardization = st
+    return out

@@ -726,6 +726,21 @@ int fh_column_norms(fh_ctx* ctx, double* out);
 int fh_screen(fh_ctx* ctx, double* report, uint8_t* keep);
 int fh_gather_columns(fh_ctx* dst, fh_ctx* src, const int32_t* idx, uint64_t count);
 int fh_screen_shape_for(uint64_t m, uint64_t n, uint32_t L, int dtype, int ncu, uint32_t* out);
+/* ---- standardised features (csrc/fh_standardize.h; the host statement is fasta_python_amd/preprocess.py: standardize) -------------------------------
+ * The matrix the context holds is rewritten in place, in float64 arithmetic, every line one rounded operation:
+ *   mean_j = (sum_i a_ij) / m   (center != 0; else 0),      d_ij = a_ij - mean_j   (float32 storage promoted to double first),
+ *   scale_j = sqrt((sum_i d_ij^2) / m), 1 where that is 0   (scale != 0; else 1),   a_ij <- d_ij / scale_j   (float32 storage: rounded on the store).
+ * Dense operator, vector and multi-column, either storage: the launches of fh_column_norms' geometry (fh_screen_shape_for) -- the sums (skipped
+ * when center == 0), the centred squares (skipped when scale == 0), the rewrite of rows i < m and columns j < n: the zero padding of the block
+ * stays zero.  Sparse operator: scale alone (centring would fill the matrix), scale_j = sqrt(norms2_j / m) from its by-columns copy, both stored
+ * copies divided, identical bits in both.  Ordinary launches, no float atomics, fixed summation order, bitwise repeatable; FH_K_AUX.
+ * means, scales: n doubles each on the host, or NULL; the statistics are those of the float64 values before a float32 store rounds them.
+ * Afterwards the context is as after an operator setter: no committed state (fh_dual_gap and the others answer as before fh_init), the kept column
+ * norms dropped; the prox kind, the loss, b, x0 and the column count stay.  A second call standardises what is there.  If a launch fails the
+ * context is left without committed state.  Refused with one sentence each: a null context, center == 0 && scale == 0, center != 0 on the sparse
+ * operator (FH_E_ARG); no operator, a form that stores no columns, a multi-device context, a communicator, a step in flight, observation
+ * weights (FH_E_STATE).                                                                                                                         */
+int fh_standardize(fh_ctx* ctx, int center, int scale, double* means, double* scales);
 /* plain operator application on host vectors (tests, synthetic b): adjoint=0: out(m) = A in(n);
  * adjoint=1: out(n) = A^H in(m).                                                                 */
 int fh_apply(fh_ctx* ctx, int adjoint, const double* in, double* out);
