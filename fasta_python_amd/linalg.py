@@ -294,6 +294,24 @@ class DenseMatrixMap(_DeviceMap):
         self.rows = (row0, m if m_total is None else m_total)
         return self
 
+    def take_columns(self, src, idx):
+        """This map <- the columns idx (strictly increasing) of the dense map `src`, device to device on one device (fh_gather_columns); the
+        column count of the unknown stays.  The map has no host copy afterwards: it applies its device copy."""
+        self.ctx.gather_columns(src.ctx, idx)
+        if self.rhs is not None:
+            self.ctx.set_rhs(self.rhs)
+        cols = () if self.rhs is None else (self.rhs,)
+        m, n = src.shape[0], int(np.size(idx))
+        self.matrix, self.shape = None, (m, n)
+        self.Vshape, self.Wshape = (n,) + cols, (m,) + cols
+
+    def standardize(self, center=True, scale=True):
+        """The device copy rewritten in place as (a - mean) / scale per column (fh_standardize) -- (means, scales).  The caller's array is
+        not what the context holds any more, so the map lets go of it and applies its device copy."""
+        means, scales = self.ctx.standardize(center=center, scale=scale)
+        self.matrix = None
+        return means, scales
+
     def host_rows(self, row0, nrows):
         """Rows of the DEVICE copy of A pulled back to the host."""
         return self.ctx.get_matrix_rows(row0, nrows)
@@ -408,15 +426,33 @@ class SparseMatrixMap(_DeviceMap):
         self.rhs = None if rhs is None else int(rhs)
         if self.rhs is not None and not 1 <= self.rhs <= hip.MAX_RHS:
             raise ValueError(f"rhs must be in 1..{hip.MAX_RHS} columns (got {rhs})")
+        self.storage = "f64"
+        self._tuning = dict(tuning or {})
+        self._ctx = None
+        self.set_matrix(A)
+        _DeviceMap.__init__(self, self.Vshape, self.Wshape, device, lazy=True)
+
+    def set_matrix(self, A):
+        """Replace the matrix (any form the constructor takes); the column count of the unknown stays.  Host copy, shapes and -- where the map
+        has one -- the context, through the CSR setter it was filled by, hold the new matrix afterwards."""
         data, indices, indptr, shape = canonical_csr(A)
         self.csr = (data, indices, indptr)
         self.shape = shape
-        self.storage = "f64"
-        self._tuning = dict(tuning or {})
         from scipy.sparse import csr_matrix            # (SciPy is needed from here on, not at module import)
         self._host = csr_matrix((data, indices, indptr), shape=shape)
         cols = () if self.rhs is None else (self.rhs,)
-        _DeviceMap.__init__(self, (shape[1],) + cols, (shape[0],) + cols, device, lazy=True)
+        self.Vshape, self.Wshape = (shape[1],) + cols, (shape[0],) + cols
+        if self._ctx is not None:
+            self._on_context(self._ctx)
+
+    def standardize(self, center=False, scale=True):
+        """The device copy rescaled in place, a / scale per column (fh_standardize: a sparse operator is served with center=False) -- (means,
+        scales).  The host copy the map applies takes the same division, so it holds the same bits."""
+        means, scales = self.ctx.standardize(center=center, scale=scale)
+        data, indices, indptr = self.csr
+        self.csr = (data / scales[indices], indices, indptr)
+        self._host = type(self._host)(self.csr, shape=self.shape)
+        return means, scales
 
     @property
     def nnz(self):

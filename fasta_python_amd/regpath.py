@@ -38,6 +38,24 @@ def _unknown_shape(A, loss, x0):
     return (A.shape[1],) + tuple(loss.b.shape[1:])
 
 
+def _check_arguments(prox_class, backend):
+    if prox_class not in (Shrink, GroupShrink):
+        raise TypeError(f"path: prox_class must be proximal.Shrink or proximal.GroupShrink (got {getattr(prox_class, '__name__', prox_class)!r})")
+    if backend not in ("auto", "hip", "numpy"):
+        raise ValueError('backend must be "auto", "hip" or "numpy"')
+
+
+def _recognised(A, loss, prox_class, x, build=True):
+    """(device map, loss tag, whether the map is the path's to close) of the path's operands, or TypeError with the front end's sentence.
+    build=False: the sentence or nothing (the standardised path builds its own map, and meets a shape that does not fit later, as path() does)."""
+    from .solver import _front_end, _unrecognised
+    probe = prox_class(1.0)
+    found = (_front_end if build else _unrecognised)(A, None, loss.f, loss.gradf, probe.g, probe.prox, x)
+    if isinstance(found, str):
+        raise TypeError("path(): " + found + ' (backend="numpy" runs the path on the host loop)')
+    return found and (found[0], found[1], found[3])
+
+
 SCREEN_MIN_DISCARD = 0.5      # a round compacts only if at least this share of the features goes: below it the copy costs more than it saves
 
 
@@ -59,10 +77,7 @@ def path(A, loss, prox_class, mus=None, n_mus=20, ratio=1e-3, x0=None, gap_toler
         return _standardized_path(A, loss, prox_class, bool(standardize), bool(intercept), x0, backend,
                                   dict(mus=mus, n_mus=n_mus, ratio=ratio, gap_tolerance=gap_tolerance, every=every, screen=screen,
                                        screen_shrink=screen_shrink, screen_max_rounds=screen_max_rounds, **options))
-    if prox_class not in (Shrink, GroupShrink):
-        raise TypeError(f"path: prox_class must be proximal.Shrink or proximal.GroupShrink (got {getattr(prox_class, '__name__', prox_class)!r})")
-    if backend not in ("auto", "hip", "numpy"):
-        raise ValueError('backend must be "auto", "hip" or "numpy"')
+    _check_arguments(prox_class, backend)
     for name in ("stop_rule", "tolerance"):
         if name in options:
             raise TypeError(f"path: every solve is stopped by its duality gap (gap_tolerance); {name} does not apply")
@@ -76,73 +91,17 @@ def path(A, loss, prox_class, mus=None, n_mus=20, ratio=1e-3, x0=None, gap_toler
             raise TypeError("path: screen=True is stated for losses.LeastSquares (the radius of the logistic loss has another constant)")
         if not 0 < screen_shrink < 1 or int(screen_max_rounds) < 0:
             raise ValueError("path: needs 0 < screen_shrink < 1 and screen_max_rounds >= 0")
-        side = _HostScreen if backend == "numpy" else _DeviceScreen
-        return _screened_path(side, A, loss, prox_class, mus, n_mus, ratio, x, rule, float(screen_shrink), int(screen_max_rounds), options)
-    if backend == "numpy":
-        return _host_path(A, loss, prox_class, mus, n_mus, ratio, x, rule, options)
-    return _device_path(A, loss, prox_class, mus, n_mus, ratio, x, rule, options)
-
-
-def _host_path(A, loss, prox_class, mus, n_mus, ratio, x, rule, options):
-    from .generic import HostFBS, host_map
-    for name in ("fused", "device_iters", "driver"):
-        options.pop(name, None)
-    op = host_map(A, None, x)
-    if mus is None:
-        mus = mu_grid(certificates.critical_mu(op, loss, prox_class, x.shape), n_mus, ratio)
-    out, L, tau0 = [], options.pop("L", None), options.pop("tau0", None)
-    for mu in mus:
-        reg = prox_class(float(mu))
-        solver = HostFBS(op, loss.f, loss.gradf, reg.g, reg.prox, x, L=L, tau0=tau0, stop_rule=rule, **options).setup()
-        L, tau0 = solver.L, solver.tau0
-        conv = solver.run()
-        conv.mu = float(mu)
-        x = np.array(conv.solution, dtype=np.float64)
-        out.append(conv)
-    return out
-
-
-def _device_path(A, loss, prox_class, mus, n_mus, ratio, x, rule, options):
-    from . import hip
-    from .solver import FBSolver, _recognise, _unrecognised
-    probe = prox_class(1.0)
-    why_not = _unrecognised(A, None, loss.f, loss.gradf, probe.g, probe.prox, x)
-    if why_not is not None:
-        raise TypeError("path(): " + why_not + ' (backend="numpy" runs the path on the host loop)')
-    owns = isinstance(A, np.ndarray) or is_sparse_matrix(A)
-    op, loss, _ = _recognise(A, None, loss.f, loss.gradf, probe.g, probe.prox, x)
-    try:
-        c = op.ctx
-        if mus is None:                  # the critical mu from the device: x0 = 0, fh_init, element 5 of fh_dual_gap
-            loss.bind(c)
-            c.set_prox(probe.kind, 1.0, 0.0, 0.0)
-            c.set_vector(hip.VEC_X0, np.zeros(x.shape))
-            c.init()
-            mus = mu_grid(c.dual_gap().dual_norm, n_mus, ratio)
-        out, L, tau0 = [], options.pop("L", None), options.pop("tau0", None)
-        for mu in mus:
-            solver = FBSolver(op, loss, prox_class(float(mu)), x, L=L, tau0=tau0, stop_rule=rule, **options).setup()
-            L, tau0 = solver.L, solver.tau0
-            conv = solver.run()
-            conv.mu = float(mu)
-            x = np.array(conv.solution, dtype=np.float64)
-            out.append(conv)
-        return out
-    finally:
-        if owns:
-            op.close()
-
-
-# ---- the path with gap-safe screening ---------------------------------------------------------------------------------------------------------
-def _screened_path(side_class, A, loss, prox_class, mus, n_mus, ratio, x, rule, shrink, max_rounds, options):
-    side = side_class(A, loss, prox_class, x, options)
+    # the one warm-start loop: a side (host or device) solves a point, plainly or in screening rounds
+    side = _HostSide(A, loss, prox_class, x, options, screen) if backend == "numpy" else _DeviceSide(A, loss, prox_class, x, options)
     try:
         if mus is None:
             mus = mu_grid(side.critical_mu(x.shape), n_mus, ratio)
-        side.estimate(prox_class(float(mus[0])), x)
+        if screen:
+            side.estimate(prox_class(float(mus[0])), x)
         out = []
         for mu in mus:
-            conv = _screened_point(side, prox_class(float(mu)), x, rule, shrink, max_rounds)
+            reg = prox_class(float(mu))
+            conv = _screened_point(side, reg, x, rule, float(screen_shrink), int(screen_max_rounds)) if screen else side.solve_full(reg, x, rule)
             conv.mu = float(mu)
             x = np.array(conv.solution, dtype=np.float64)
             out.append(conv)
@@ -151,6 +110,7 @@ def _screened_path(side_class, A, loss, prox_class, mus, n_mus, ratio, x, rule, 
         side.close()
 
 
+# ---- a point with gap-safe screening ----------------------------------------------------------------------------------------------------------
 def _screened_point(side, reg, x, rule, shrink, max_rounds):
     from .solver import Convergence
     n = x.shape[0]
@@ -186,20 +146,41 @@ def _screened_point(side, reg, x, rule, shrink, max_rounds):
     return conv
 
 
-class _HostScreen:
-    """The host side of the screened path: certificates.screen, column slices, the generic host loop."""
+class _Side:
+    """What the host and the device side of the path share: the options of every solve and the step-size estimate, made once."""
 
-    def __init__(self, A, loss, prox_class, x, options):
+    def __init__(self, loss, prox_class, options):
+        self.loss, self.prox_class, self.options = loss, prox_class, options
+        self.L, self.tau0 = options.pop("L", None), options.pop("tau0", None)
+        self.max_iters = options.get("max_iters", 1000)
+
+    def estimate(self, reg, x):
+        if not self.L or not self.tau0:
+            solver = self._solver(self.op, reg, x, stopping.DualityGap(0.0, 1)).setup()
+            self.L, self.tau0 = solver.L, solver.tau0
+
+    def solve_full(self, reg, x, rule):
+        """One solve on the full operator; the first one's L / tau0 serve the later ones."""
+        solver = self._solver(self.op, reg, x, rule).setup()
+        self.L, self.tau0 = solver.L, solver.tau0
+        return solver.run()
+
+    def close(self):
+        pass
+
+
+class _HostSide(_Side):
+    """The host side: the generic host loop; with screening certificates.screen and column slices (only then must A give its columns)."""
+
+    def __init__(self, A, loss, prox_class, x, options, screen):
         from .generic import host_map
         for name in ("fused", "device_iters", "driver"):
             options.pop(name, None)
-        self.M = certificates._columns_of(A)
-        self.loss, self.options = loss, options
-        self.op = host_map(self.M, None, x)
-        self.norms2 = certificates.column_norms2(self.M)
-        self.L, self.tau0 = options.pop("L", None), options.pop("tau0", None)
-        self.max_iters = options.get("max_iters", 1000)
-        self.prox_class = prox_class
+        if screen:
+            A = self.M = certificates._columns_of(A)
+            self.norms2 = certificates.column_norms2(self.M)
+        self.op = host_map(A, None, x)
+        _Side.__init__(self, loss, prox_class, options)
 
     def critical_mu(self, shape):
         return certificates.critical_mu(self.op, self.loss, self.prox_class, shape)
@@ -208,43 +189,24 @@ class _HostScreen:
         from .generic import HostFBS
         return HostFBS(op, self.loss.f, self.loss.gradf, reg.g, reg.prox, x, L=self.L, tau0=self.tau0, stop_rule=rule, **self.options)
 
-    def estimate(self, reg, x):
-        if not self.L or not self.tau0:
-            solver = self._solver(self.op, reg, x, stopping.DualityGap(0.0, 1)).setup()
-            self.L, self.tau0 = solver.L, solver.tau0
-
     def certify(self, reg, x, want_mask):
         sc = certificates.screen(self.M, self.loss, reg, x, norms2=self.norms2)
         return sc.certificate, (sc.keep if want_mask(sc.certificate) else None)
-
-    def solve_full(self, reg, x, rule):
-        return self._solver(self.op, reg, x, rule).setup().run()
 
     def solve_kept(self, reg, idx, x, rule):
         from .generic import host_map
         return self._solver(host_map(self.M[:, idx], None, x), reg, x, rule).setup().run()
 
-    def close(self):
-        pass
 
-
-class _DeviceScreen:
-    """The device side: fh_init + fh_dual_gap + fh_screen on the full context; the kept columns go device to device into a working context
-    (fh_gather_columns) for a dense matrix, through a host slice and the CSR setter for a sparse one.  One working operator per path."""
+class _DeviceSide(_Side):
+    """The device side: FBSolver on one context; with screening fh_init + fh_dual_gap + fh_screen on it, and the kept columns in a working context
+    (device to device, fh_gather_columns, for a dense matrix; a host slice through the CSR setter for a sparse one).  One working operator per path."""
 
     def __init__(self, A, loss, prox_class, x, options):
-        from .solver import _recognise, _unrecognised
-        probe = prox_class(1.0)
-        why_not = _unrecognised(A, None, loss.f, loss.gradf, probe.g, probe.prox, x)
-        if why_not is not None:
-            raise TypeError("path(): " + why_not + ' (backend="numpy" runs the path on the host loop)')
-        self.owns = isinstance(A, np.ndarray) or is_sparse_matrix(A)
-        self.op, self.loss, _ = _recognise(A, None, loss.f, loss.gradf, probe.g, probe.prox, x)
+        self.op, loss, self.owns = _recognised(A, loss, prox_class, x)
         self.work = None
-        self.prox_class, self.options = prox_class, options
-        self.L, self.tau0 = options.pop("L", None), options.pop("tau0", None)
-        self.max_iters = options.get("max_iters", 1000)
         self.cols = x.shape[1] if x.ndim == 2 else None
+        _Side.__init__(self, loss, prox_class, options)
 
     def _at(self, reg, x):
         from . import hip
@@ -262,43 +224,24 @@ class _DeviceScreen:
         from .solver import FBSolver
         return FBSolver(op, self.loss, reg, x, L=self.L, tau0=self.tau0, stop_rule=rule, **self.options)
 
-    def estimate(self, reg, x):
-        if not self.L or not self.tau0:
-            solver = self._solver(self.op, reg, x, stopping.DualityGap(0.0, 1)).setup()
-            self.L, self.tau0 = solver.L, solver.tau0
-
     def certify(self, reg, x, want_mask):
         c = self._at(reg, x)
         cert = c.dual_gap()
         return cert, (c.screen()[0] if want_mask(cert) else None)
 
-    def solve_full(self, reg, x, rule):
-        return self._solver(self.op, reg, x, rule).setup().run()
-
     def solve_kept(self, reg, idx, x, rule):
         from .linalg import DenseMatrixMap, SparseMatrixMap
-        m = self.op.shape[0]
-        cols = () if self.cols is None else (self.cols,)
         if isinstance(self.op, SparseMatrixMap):
             S = self.op.matrix[:, idx]
             if self.work is None:
                 self.work = SparseMatrixMap(S, device=self.op.device, rhs=self.cols)
                 self.work.ctx
             else:                                       # the same context takes the next slice through the CSR setter
-                from .linalg import canonical_csr
-                data, indices, indptr, shape = canonical_csr(S)
-                w = self.work
-                w.csr, w.shape, w._host = (data, indices, indptr), shape, S.tocsr()
-                w._on_context(w.ctx)
+                self.work.set_matrix(S)
         else:
             if self.work is None:
                 self.work = DenseMatrixMap(_defer=True, device=self.op.device, storage=self.op.storage, rhs=self.cols)
-            w = self.work
-            w.ctx.gather_columns(self.op.ctx, idx)
-            if self.cols is not None:
-                w.ctx.set_rhs(self.cols)
-            w.shape = (m, int(idx.size))
-        self.work.Vshape, self.work.Wshape = (int(idx.size),) + cols, (m,) + cols
+            self.work.take_columns(self.op, idx)
         return self._solver(self.work, reg, x, rule).setup().run()
 
     def close(self):
@@ -313,12 +256,9 @@ def _standardized_path(A, loss, prox_class, scale, center, x0, backend, keywords
     """The refusals, the standardised operator (the device's own copy rewritten by fh_standardize, or preprocess.standardize on the host), the path
     on it through path() itself, then the way back to the caller's units."""
     from . import preprocess
-    from .linalg import DenseMatrixMap, ShardedDenseMatrixMap, SparseMatrixMap, _DeviceMap
+    from .linalg import ShardedDenseMatrixMap, _DeviceMap
     from .losses import LeastSquares, LogisticLoss
-    if prox_class not in (Shrink, GroupShrink):
-        raise TypeError(f"path: prox_class must be proximal.Shrink or proximal.GroupShrink (got {getattr(prox_class, '__name__', prox_class)!r})")
-    if backend not in ("auto", "hip", "numpy"):
-        raise ValueError('backend must be "auto", "hip" or "numpy"')
+    _check_arguments(prox_class, backend)
     tag = getattr(loss, "__self__", loss)
     if center and isinstance(tag, LogisticLoss):
         raise TypeError("path: intercept=True is served for losses.LeastSquares without weights on a dense matrix: the intercept of the logistic loss "
@@ -348,21 +288,12 @@ def _standardized_path(A, loss, prox_class, scale, center, x0, backend, keywords
         A_std, st = preprocess.standardize(A, center=center, scale=scale)
         out = path(A_std, loss, prox_class, x0=x0, backend=backend, **keywords)
     else:
-        from .solver import _unrecognised
+        from .linalg import DenseMatrixMap, SparseMatrixMap
         shape = _unknown_shape(A, loss, x0)
-        probe = prox_class(1.0)
-        why_not = _unrecognised(A, None, loss.f, loss.gradf, probe.g, probe.prox, np.zeros(shape))
-        if why_not is not None:
-            raise TypeError("path(): " + why_not + ' (backend="numpy" runs the path on the host loop)')
+        _recognised(A, loss, prox_class, np.zeros(shape), build=False)
         op = SparseMatrixMap(A) if sparse else DenseMatrixMap(A, rhs=shape[1] if len(shape) == 2 else None)
         try:
-            st = preprocess.Standardization(*op.ctx.standardize(center=center, scale=scale), op.shape[0])
-            if sparse:                                  # the host copy the map applies and the screened path slices: the same division, the same bits
-                data, indices, indptr = op.csr
-                op.csr = (data / st.scales[indices], indices, indptr)
-                op._host = type(op._host)((op.csr[0], indices, indptr), shape=op.shape)
-            else:
-                op.matrix = None                        # (the caller's array is not what the context holds any more: the map applies the device copy)
+            st = preprocess.Standardization(*op.standardize(center=center, scale=scale), op.shape[0])
             out = path(op, loss, prox_class, x0=x0, backend=backend, **keywords)
         finally:
             op.close()

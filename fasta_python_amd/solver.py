@@ -30,9 +30,10 @@ from time import time
 import numpy as np
 
 from . import hip, stopping
-from .linalg import BilinearMap, ConvMap, DCTMap, DenseMatrixMap, GradDivMap, IdentityMap, LinearMap, QuadraticMap, SparseMatrixMap, _DeviceMap, is_sparse_matrix
+from .linalg import (BilinearMap, ConvMap, DCTMap, DenseMatrixMap, GradDivMap, IdentityMap, LinearMap, QuadraticMap, ShardedDenseMatrixMap, SparseMatrixMap,
+                     _DeviceMap, is_sparse_matrix)
 from .losses import Factorization, LeastSquares, LogisticLoss, Quadratic, SoftmaxLoss
-from .proximal import NoProx, NuclearBall, NuclearShrink, ProxTag
+from .proximal import Box, GroupShrink, L1Ball, LinfProx, NonNeg, NoProx, NuclearBall, NuclearShrink, ProxTag, RowBall, RowSplit, Shrink, TVDualBall
 
 __all__ = ["fasta", "Convergence", "FBSolver", "EPSILON"]
 
@@ -71,22 +72,51 @@ def _tag_of(obj, cls):
     return owner if isinstance(owner, cls) else None
 
 
+# ---- recognition: which operands run on the device, and in which words the others are declined ---------------------------------------------------
+# One walk (`_front_end`) decides the form of the seven operands (a row of _FORMS), asks the form why it does not serve them, and builds the map.
+# Every sentence and the order in which the checks win are pinned by tests/golden/refusals/front_end.json (tests/front_end_cases.py).
+_ELEMENTWISE = (LeastSquares, LogisticLoss)
+_LEVEL_SEARCH = (LinfProx, L1Ball, TVDualBall)      # the prox kinds that search a clipping level: the vector forms of a stored or implicit operator only
+_WEIGHTS_ELSEWHERE = ("observation weights (losses.LeastSquares(B, weights=W) / losses.LogisticLoss(B, weights=W)) are served on the device by the identity operator "
+                      "only: fasta(None, None, loss.f, loss.gradf, g, prox, X0) with a 2-D X0 of B's shape and NuclearShrink, NuclearBall, Shrink, NonNeg, Box or no prox")
+_IDENTITY_ONLY = ("proximal.{} is served on the device by the identity operator only: fasta(None, None, loss.f, loss.gradf, reg.g, reg.prox, X0) "
+                  "with loss = losses.LogisticLoss(B) or losses.LeastSquares(B) and a 2-D X0 of B's shape")
+# the prox kinds one form alone serves, and where that is
+_ELSEWHERE = {
+    hip.PROX_NUCLEAR: _IDENTITY_ONLY.format("NuclearShrink"),
+    hip.PROX_NUCBALL: _IDENTITY_ONLY.format("NuclearBall"),
+    hip.PROX_ROWBALL: "proximal.RowBall is served on the device with a quadratic loss only: fasta(None, None, q.f, q.gradf, ...) with q = losses.Quadratic(Q, c)",
+    hip.PROX_ROWSPLIT: "proximal.RowSplit is served on the device with a factorization loss only: fasta(None, None, fz.f, fz.gradf, ...) with fz = losses.Factorization(S)",
+}
+
+
+def _one_loss(f, gradf, cls):
+    """The one tag of class `cls` behind both f and gradf, or None."""
+    tag = _tag_of(f, cls)
+    return tag if tag is not None and tag is _tag_of(gradf, cls) else None
+
+
+def _one_prox(g, proxg, served):
+    """(the one tag behind g and proxg -- None for `None, None` --, None), or (None, the sentence that names the kinds the form serves)."""
+    if g is None and proxg is None:
+        return None, None
+    prox, owner_g = _tag_of(proxg, ProxTag), _tag_of(g, ProxTag)
+    if prox is None or (owner_g is not None and owner_g is not prox) or (owner_g is None and g is not None):
+        return None, f"g and proxg must be the `.g` / `.prox` of one proximal.* tag object ({served})"
+    return prox, None
+
+
 def _matrix_form_refusal(A, loss, prox, x0):
     """A 2-D x0 over a dense matrix is a MATRIX unknown (n, L): the device serves it in the multi-column form (csrc/fh_multi.h), which has
     no level-search prox kinds, no logistic loss, no float32 storage and no row sharding, and at most 16 columns.  None, or the reason."""
-    from .linalg import ShardedDenseMatrixMap
-    from .proximal import GroupShrink, L1Ball, LinfProx, TVDualBall
-    if isinstance(A, SparseMatrixMap) or is_sparse_matrix(A):
-        return None                                    # (_sparse_form_refusal has the say)
-    dense = isinstance(A, np.ndarray) or isinstance(A, DenseMatrixMap)
-    matrix_form = dense and x0 is not None and np.ndim(x0) == 2
+    matrix_form = isinstance(A, (np.ndarray, DenseMatrixMap)) and x0 is not None and np.ndim(x0) == 2
     if isinstance(prox, GroupShrink) and not matrix_form:
         return "proximal.GroupShrink couples the columns of a row: it needs a dense matrix operator and a 2-D x0 of shape (n, L)"
     if not matrix_form:
         return None
     if np.shape(x0)[1] > hip.MAX_RHS:
         return f"a matrix unknown has at most {hip.MAX_RHS} columns on the device (x0 has {np.shape(x0)[1]})"
-    if isinstance(prox, (LinfProx, L1Ball, TVDualBall)):
+    if isinstance(prox, _LEVEL_SEARCH):
         return f"proximal.{type(prox).__name__} has no matrix (multi-column) form on the device"
     if isinstance(loss, LogisticLoss):
         return "losses.LogisticLoss has no matrix (multi-column) form on the device"
@@ -101,17 +131,14 @@ def _sparse_form_refusal(A, loss, prox, x0):
     """A sparse operator serves vector unknowns with the elementwise prox kinds and both losses (csrc/fh_sparse.h) and, as an explicit
     SparseMatrixMap(S, rhs=L), matrix unknowns (n, L) with least squares and the elementwise kinds or GroupShrink (csrc/fh_spmulti.h).
     (Float32 storage is refused where it could be asked for: LinearMap.from_matrix.)  None, or the reason."""
-    from .proximal import GroupShrink, L1Ball, LinfProx, TVDualBall
-    if not (isinstance(A, SparseMatrixMap) or is_sparse_matrix(A)):
-        return None
     matrix_form = isinstance(A, SparseMatrixMap) and A.rhs is not None
-    if isinstance(prox, (LinfProx, L1Ball, TVDualBall)):
+    if isinstance(prox, _LEVEL_SEARCH):
         return (f"proximal.{type(prox).__name__} is not implemented for a sparse operator on the device "
                 f"(Shrink, NonNeg, Box or no prox are{'; GroupShrink too over a matrix unknown' if matrix_form else ''})")
     if matrix_form:
         if isinstance(loss, LogisticLoss):
             return "losses.LogisticLoss has no matrix (multi-column) form over a sparse operator on the device: least squares only"
-        return None                                    # (a shape that does not fit is _recognise's `x0 has shape` AssertionError)
+        return None                                    # (a shape that does not fit is the `x0 has shape` AssertionError of _build_matrix)
     if isinstance(prox, GroupShrink):
         return ("proximal.GroupShrink is not implemented for a sparse operator with a vector unknown on the device: it couples the columns "
                 "of a row of a matrix unknown -- pass linalg.SparseMatrixMap(S, rhs=L) and a 2-D x0 of shape (n, L)")
@@ -121,98 +148,97 @@ def _sparse_form_refusal(A, loss, prox, x0):
     return None
 
 
-def _dct_form_refusal(A, loss, prox, x0):
-    """A DCTMap serves a vector unknown of length N with least squares and Shrink, NonNeg, Box, LinfProx, L1Ball or no prox (csrc/fh_dct.h); a length
-    the device refuses (DCTMap.refusal: the library's sentence) stays on the host.  None, or the reason."""
-    from .proximal import GroupShrink, TVDualBall
-    if not isinstance(A, DCTMap):
-        return None
+def _implicit_form_refusal(A, loss, prox, x0):
+    """A DCTMap (csrc/fh_dct.h, fh_dct2.h) or a ConvMap (csrc/fh_conv.h) serves an unknown of its own shape with least squares and Shrink, NonNeg,
+    Box, LinfProx, L1Ball or no prox; a length or a kernel the device refuses (`refusal`: the library's sentence) stays on the host.  None, or the reason."""
+    noun = "DCT" if isinstance(A, DCTMap) else "convolution"
     if A.refusal is not None:
         return A.refusal
     if isinstance(loss, LogisticLoss):
-        return "losses.LogisticLoss is not implemented for a DCT operator on the device: least squares only"
+        return f"losses.LogisticLoss is not implemented for a {noun} operator on the device: least squares only"
     if isinstance(prox, (TVDualBall, GroupShrink)):
-        return (f"proximal.{type(prox).__name__} is not implemented for a DCT operator on the device "
+        return (f"proximal.{type(prox).__name__} is not implemented for a {noun} operator on the device "
                 "(Shrink, NonNeg, Box, LinfProx, L1Ball or no prox are)")
-    if len(A.Vshape) == 2:                                 # the 2-D operator (csrc/fh_dct2.h): an unknown of the image's shape
-        if x0 is not None and tuple(np.shape(x0)) != A.Vshape:
-            return f"a DCT operator on an image of shape {A.Vshape} takes an unknown of that shape on the device (x0 has shape {tuple(np.shape(x0))})"
-        return None
-    if x0 is not None and np.ndim(x0) != 1:
-        return f"a DCT operator takes a vector unknown of shape ({A.N},) on the device (x0 has {np.ndim(x0)} dimensions)"
+    shape = None if x0 is None else tuple(np.shape(x0))
+    if isinstance(A, ConvMap):
+        if shape is not None and shape != A.Vshape:
+            return f"a convolution operator on {A.Vshape} takes an unknown of that shape on the device (x0 has shape {shape})"
+    elif len(A.Vshape) == 2:                               # the 2-D operator (csrc/fh_dct2.h): an unknown of the image's shape
+        if shape is not None and shape != A.Vshape:
+            return f"a DCT operator on an image of shape {A.Vshape} takes an unknown of that shape on the device (x0 has shape {shape})"
+    elif shape is not None and len(shape) != 1:
+        return f"a DCT operator takes a vector unknown of shape ({A.N},) on the device (x0 has {len(shape)} dimensions)"
     return None
 
 
-def _conv_form_refusal(A, loss, prox, x0):
-    """A ConvMap serves an unknown of the image's shape with least squares and Shrink, NonNeg, Box, LinfProx, L1Ball or no prox (csrc/fh_conv.h); a
-    kernel the device refuses (ConvMap.refusal: the library's sentence) stays on the host.  None, or the reason."""
-    from .proximal import GroupShrink, TVDualBall
-    if not isinstance(A, ConvMap):
-        return None
-    if A.refusal is not None:
-        return A.refusal
-    if isinstance(loss, LogisticLoss):
-        return "losses.LogisticLoss is not implemented for a convolution operator on the device: least squares only"
-    if isinstance(prox, (TVDualBall, GroupShrink)):
-        return (f"proximal.{type(prox).__name__} is not implemented for a convolution operator on the device "
-                "(Shrink, NonNeg, Box, LinfProx, L1Ball or no prox are)")
-    if x0 is not None and tuple(np.shape(x0)) != A.Vshape:
-        return f"a convolution operator on {A.Vshape} takes an unknown of that shape on the device (x0 has shape {tuple(np.shape(x0))})"
-    return None
+def _matrix_refusal(A, At, f, gradf, g, proxg, x0):
+    """A stored or implicit operator (a matrix, a sparse matrix, a device map) with an elementwise loss."""
+    if not isinstance(A, (np.ndarray, _DeviceMap)) and not is_sparse_matrix(A):
+        return ("operator A is not device-resident (pass a 2-D float64 ndarray, a scipy.sparse matrix, a linalg.DenseMatrixMap / "
+                "LinearMap.from_matrix(A), a linalg.SparseMatrixMap, a linalg.GradDivMap, a linalg.DCTMap or a linalg.ConvMap); arbitrary Python callables cannot run inside the fused HIP kernels")
+    loss = _one_loss(f, gradf, _ELEMENTWISE)
+    if loss is None:
+        return "f and gradf must be the `.f` / `.gradf` of one losses.LeastSquares(b) or losses.LogisticLoss(b) object"
+    if loss.weights is not None:
+        return _WEIGHTS_ELSEWHERE
+    prox, why_not = _one_prox(g, proxg, "Shrink, NonNeg, LinfProx, L1Ball, Box, TVDualBall, GroupShrink")
+    if why_not is None and prox is not None:
+        why_not = _ELSEWHERE.get(prox.kind)
+    if why_not is not None:
+        return why_not
+    sparse = isinstance(A, SparseMatrixMap) or is_sparse_matrix(A)      # what the operator itself does not serve: by its kind
+    of_operator = _implicit_form_refusal if isinstance(A, (DCTMap, ConvMap)) else _sparse_form_refusal if sparse else _matrix_form_refusal
+    return of_operator(A, loss, prox, x0)
 
 
-def _quadratic_form_refusal(A, At, loss_f, loss_g, g, proxg, x0):
+def _quadratic_refusal(A, At, f, gradf, g, proxg, x0):
     """`fasta(None, None, q.f, q.gradf, g, prox, x0)` with q = losses.Quadratic(Q, c): the device serves it through fh_set_quadratic
-    (csrc/fh_quad.h) for a vector or a matrix unknown of at most 16 columns, with the elementwise prox kinds, GroupShrink and RowBall.
-    None, or the reason."""
-    from .proximal import GroupShrink, L1Ball, LinfProx, RowBall, TVDualBall
-    if loss_f is None or loss_f is not loss_g:
+    (csrc/fh_quad.h) for a vector or a matrix unknown of at most 16 columns, with the elementwise prox kinds, GroupShrink and RowBall."""
+    tag = _tag_of(proxg, ProxTag)
+    if tag is not None and tag.kind in (hip.PROX_ROWSPLIT, hip.PROX_NUCLEAR, hip.PROX_NUCBALL):
+        return _ELSEWHERE[tag.kind]
+    loss = _one_loss(f, gradf, Quadratic)
+    if loss is None:
         return "f and gradf must be the `.f` / `.gradf` of one losses.Quadratic(Q, c) object"
     if A is not None or At is not None:
         return "A must be None with a quadratic loss: losses.Quadratic(Q, c) holds the matrix, the operator is the identity"
-    n = loss_f.Q.shape[0]
+    n = loss.Q.shape[0]
     shape = None if x0 is None else tuple(np.shape(x0))
     if shape is not None and (len(shape) not in (1, 2) or shape[0] != n):
         return f"x0 has shape {shape}: a quadratic loss on a {n} x {n} matrix takes an unknown of shape ({n},) or ({n}, L)"
     if shape is not None and len(shape) == 2 and not 1 <= shape[1] <= hip.MAX_RHS:
         return f"a 2-D x0 has at most {hip.MAX_RHS} columns on the device (x0 has {shape[1]})"
-    if shape is not None and loss_f.c is not None and loss_f.c.shape != shape:
-        return f"c must have x0's shape (c has {loss_f.c.shape}, x0 has {shape})"
-    if g is None and proxg is None:
-        return None
-    prox, owner_g = _tag_of(proxg, ProxTag), _tag_of(g, ProxTag)
-    if prox is None or (owner_g is not None and owner_g is not prox) or (owner_g is None and g is not None):
-        return ("g and proxg must be the `.g` / `.prox` of one proximal.* tag object "
-                "(Shrink, NonNeg, Box, GroupShrink, RowBall)")
-    if isinstance(prox, (LinfProx, L1Ball, TVDualBall)):
+    if shape is not None and loss.c is not None and loss.c.shape != shape:
+        return f"c must have x0's shape (c has {loss.c.shape}, x0 has {shape})"
+    prox, why_not = _one_prox(g, proxg, "Shrink, NonNeg, Box, GroupShrink, RowBall")
+    if why_not is not None:
+        return why_not
+    if isinstance(prox, _LEVEL_SEARCH):
         return f"proximal.{type(prox).__name__} has no quadratic form on the device (LinfProx, L1Ball and TVDualBall have no quadratic form)"
     if isinstance(prox, (RowBall, GroupShrink)) and shape is not None and len(shape) != 2:
         return f"proximal.{type(prox).__name__} couples the columns of a row: RowBall and GroupShrink need a 2-D x0 of shape (n, L)"
     return None
 
 
-def _factorization_form_refusal(A, At, loss_f, loss_g, g, proxg, x0):
+def _factorization_refusal(A, At, f, gradf, g, proxg, x0):
     """`fasta(None, None, fz.f, fz.gradf, g, prox, Z0)` with fz = losses.Factorization(S), S of shape (m, n): the device serves it through
     fh_set_factorization (csrc/fh_bilinear.h) for Z0 of shape (m + n, K), K <= 16, with the elementwise prox kinds on all rows or a
-    proximal.RowSplit at m.  None, or the reason."""
-    from .proximal import GroupShrink, L1Ball, LinfProx, RowBall, RowSplit, TVDualBall
-    if loss_f is None or loss_f is not loss_g:
+    proximal.RowSplit at m."""
+    loss = _one_loss(f, gradf, Factorization)
+    if loss is None:
         return "f and gradf must be the `.f` / `.gradf` of one losses.Factorization(S) object"
     if A is not None or At is not None:
         return "A must be None with a factorization loss: losses.Factorization(S) holds the matrix, the operator is the identity"
-    m, n = loss_f.m, loss_f.n
+    m, n = loss.m, loss.n
     shape = None if x0 is None else tuple(np.shape(x0))
     if shape is not None and (len(shape) != 2 or shape[0] != m + n):
         return f"Z0 has shape {shape}: a factorization of a {m} x {n} matrix takes Z0 = [X0; Y0] of shape ({m + n}, K)"
     if shape is not None and not 1 <= shape[1] <= hip.MAX_RHS:
         return f"Z0 has at most {hip.MAX_RHS} columns on the device (Z0 has {shape[1]})"
-    if g is None and proxg is None:
-        return None
-    prox, owner_g = _tag_of(proxg, ProxTag), _tag_of(g, ProxTag)
-    if prox is None or (owner_g is not None and owner_g is not prox) or (owner_g is None and g is not None):
-        return ("g and proxg must be the `.g` / `.prox` of one proximal.* tag object "
-                "(RowSplit, Shrink, NonNeg, Box)")
-    if isinstance(prox, (LinfProx, L1Ball, TVDualBall)):
+    prox, why_not = _one_prox(g, proxg, "RowSplit, Shrink, NonNeg, Box")
+    if why_not is not None:
+        return why_not
+    if isinstance(prox, _LEVEL_SEARCH):
         return f"proximal.{type(prox).__name__} has no bilinear form on the device (the level-search kinds LinfProx, L1Ball and TVDualBall have none)"
     if isinstance(prox, (GroupShrink, RowBall)):
         return f"proximal.{type(prox).__name__} has no bilinear form on the device (the row-norm kinds GroupShrink and RowBall have none)"
@@ -221,13 +247,12 @@ def _factorization_form_refusal(A, At, loss_f, loss_g, g, proxg, x0):
     return None
 
 
-def _softmax_form_refusal(A, At, loss_f, loss_g, g, proxg, x0):
+def _softmax_refusal(A, At, f, gradf, g, proxg, x0):
     """`fasta(A, At, sm.f, sm.gradf, g, prox, X0)` with sm = losses.SoftmaxLoss(y): the device serves it over a matrix unknown (n, L), L = sm.classes,
     on a dense operator (a 2-D ndarray, DenseMatrixMap(A, rhs=L)) or SparseMatrixMap(S, rhs=L), with Shrink, NonNeg, Box, GroupShrink or no prox
-    (csrc/fh_softmax.h).  None, or the reason -- every sentence names SoftmaxLoss, except the raw scipy.sparse matrix with a 2-D x0, which keeps its own."""
-    from .linalg import ShardedDenseMatrixMap
-    from .proximal import Box, GroupShrink, NonNeg, Shrink
-    if loss_f is None or loss_f is not loss_g:
+    (csrc/fh_softmax.h).  Every sentence names SoftmaxLoss, except the raw scipy.sparse matrix with a 2-D x0, which keeps its own."""
+    loss = _one_loss(f, gradf, SoftmaxLoss)
+    if loss is None:
         return "f and gradf must be the `.f` / `.gradf` of one losses.SoftmaxLoss(y) object"
     if A is None or isinstance(A, IdentityMap):
         return ("losses.SoftmaxLoss is not implemented for the identity operator (A=None / linalg.IdentityMap) on the device: "
@@ -241,22 +266,19 @@ def _softmax_form_refusal(A, At, loss_f, loss_g, g, proxg, x0):
     if not isinstance(A, (np.ndarray, DenseMatrixMap, SparseMatrixMap)) and not is_sparse_matrix(A):
         return ("losses.SoftmaxLoss: operator A is not device-resident (pass a 2-D float64 ndarray, a linalg.DenseMatrixMap(A, rhs=L) or a "
                 "linalg.SparseMatrixMap(S, rhs=L)); arbitrary Python callables cannot run inside the fused HIP kernels")
-    prox = None
-    if not (g is None and proxg is None):
-        prox, owner_g = _tag_of(proxg, ProxTag), _tag_of(g, ProxTag)
-        if prox is None or (owner_g is not None and owner_g is not prox) or (owner_g is None and g is not None):
-            return ("losses.SoftmaxLoss: g and proxg must be the `.g` / `.prox` of one proximal.* tag object "
-                    "(Shrink, NonNeg, Box, GroupShrink)")
-        if not isinstance(prox, (Shrink, NonNeg, Box, GroupShrink)) and type(prox) is not NoProx:
-            return (f"proximal.{type(prox).__name__} is not served with losses.SoftmaxLoss on the device "
-                    "(Shrink, NonNeg, Box, GroupShrink or no prox are)")
+    prox, why_not = _one_prox(g, proxg, "Shrink, NonNeg, Box, GroupShrink")
+    if why_not is not None:
+        return "losses.SoftmaxLoss: " + why_not
+    if prox is not None and not isinstance(prox, (Shrink, NonNeg, Box, GroupShrink)) and type(prox) is not NoProx:
+        return (f"proximal.{type(prox).__name__} is not served with losses.SoftmaxLoss on the device "
+                "(Shrink, NonNeg, Box, GroupShrink or no prox are)")
     if is_sparse_matrix(A) and x0 is not None and np.ndim(x0) == 2:
-        return _sparse_form_refusal(A, loss_f, prox, x0)          # (its existing sentence: pass linalg.SparseMatrixMap(S, rhs=L))
+        return _sparse_form_refusal(A, loss, prox, x0)            # (its existing sentence: pass linalg.SparseMatrixMap(S, rhs=L))
     if isinstance(A, ShardedDenseMatrixMap):
         return "losses.SoftmaxLoss needs the matrix (multi-column) form, which a row-sharded operator does not have on the device"
     if isinstance(A, DenseMatrixMap) and A.storage != "f64":
         return 'losses.SoftmaxLoss needs the matrix (multi-column) form, which storage="f32" does not have on the device'
-    L = loss_f.classes
+    L = loss.classes
     if x0 is not None and np.ndim(x0) != 2:
         return (f"losses.SoftmaxLoss needs a MATRIX unknown on the device: a 2-D x0 of shape (n, {L}), one column per class "
                 f"(x0 has shape {tuple(np.shape(x0))}); two classes over a vector unknown are losses.LogisticLoss")
@@ -270,19 +292,13 @@ def _softmax_form_refusal(A, At, loss_f, loss_g, g, proxg, x0):
     return None
 
 
-_WEIGHTS_ELSEWHERE = ("observation weights (losses.LeastSquares(B, weights=W) / losses.LogisticLoss(B, weights=W)) are served on the device by the identity operator "
-                      "only: fasta(None, None, loss.f, loss.gradf, g, prox, X0) with a 2-D X0 of B's shape and NuclearShrink, NuclearBall, Shrink, NonNeg, Box or no prox")
-_NUCBALL_ELSEWHERE = ("proximal.NuclearBall is served on the device by the identity operator only: fasta(None, None, loss.f, loss.gradf, reg.g, reg.prox, X0) "
-                      "with loss = losses.LogisticLoss(B) or losses.LeastSquares(B) and a 2-D X0 of B's shape")
-_NUCLEAR_ELSEWHERE = ("proximal.NuclearShrink is served on the device by the identity operator only: fasta(None, None, loss.f, loss.gradf, reg.g, reg.prox, X0) "
-                      "with loss = losses.LogisticLoss(B) or losses.LeastSquares(B) and a 2-D X0 of B's shape")
-
-
-def _identity_form_refusal(A, loss, g, proxg, x0):
+def _identity_refusal(A, At, f, gradf, g, proxg, x0):
     """`fasta(None, None, loss.f, loss.gradf, g, prox, X0)` with loss = losses.LogisticLoss(B) or LeastSquares(B), or the same with an explicit
     linalg.IdentityMap: the device serves it through fh_set_identity (csrc/fh_nuclear.h) for a 2-D X0 of B's shape with NuclearShrink, NuclearBall,
-    Shrink, NonNeg, Box or no prox, with or without observation weights on the loss.  None, or the reason."""
-    from .proximal import Box, NonNeg, Shrink
+    Shrink, NonNeg, Box or no prox, with or without observation weights on the loss."""
+    loss = _one_loss(f, gradf, _ELEMENTWISE)
+    if loss is None:
+        return "f and gradf must be the `.f` / `.gradf` of one losses.LeastSquares(B) or losses.LogisticLoss(B) object"
     shape = None if x0 is None else tuple(np.shape(x0))
     if shape is not None and len(shape) != 2:
         return (f"the identity operator takes a MATRIX unknown on the device: x0 must be 2-D of shape (M, N) (x0 has shape {shape}); "
@@ -293,13 +309,10 @@ def _identity_form_refusal(A, loss, g, proxg, x0):
         return f"x0 has shape {shape}, the IdentityMap was built for {A.Vshape}"
     if shape is not None and (min(shape) < 1 or shape[0] * shape[1] > IdentityMap.MAX_ENTRIES):
         return f"the identity operator serves 1 to 2^26 entries on the device (x0 has shape {shape})"
-    if g is None and proxg is None:
-        return None
-    prox, owner_g = _tag_of(proxg, ProxTag), _tag_of(g, ProxTag)
-    if prox is None or (owner_g is not None and owner_g is not prox) or (owner_g is None and g is not None):
-        return ("g and proxg must be the `.g` / `.prox` of one proximal.* tag object "
-                "(NuclearShrink, NuclearBall, Shrink, NonNeg, Box)")
-    if not isinstance(prox, (NuclearShrink, NuclearBall, Shrink, NonNeg, Box)) and type(prox) is not NoProx:
+    prox, why_not = _one_prox(g, proxg, "NuclearShrink, NuclearBall, Shrink, NonNeg, Box")
+    if why_not is not None:
+        return why_not
+    if prox is not None and not isinstance(prox, (NuclearShrink, NuclearBall, Shrink, NonNeg, Box)) and type(prox) is not NoProx:
         return (f"proximal.{type(prox).__name__} is not implemented for the identity operator on the device "
                 "(NuclearShrink, NuclearBall, Shrink, NonNeg, Box or no prox are)")
     if isinstance(prox, (NuclearShrink, NuclearBall)) and shape is not None and min(shape) > IdentityMap.MAX_NUCLEAR_RANK:
@@ -308,68 +321,8 @@ def _identity_form_refusal(A, loss, g, proxg, x0):
     return None
 
 
-def _unrecognised(A, At, f, gradf, g, proxg, x0=None):
-    """None when the seven operands can run on the device, else the reason they cannot (a sentence)."""
-    fz_f, fz_g = _tag_of(f, Factorization), _tag_of(gradf, Factorization)
-    if fz_f is not None or fz_g is not None:
-        return _factorization_form_refusal(A, At, fz_f, fz_g, g, proxg, x0)
-    quad_f, quad_g = _tag_of(f, Quadratic), _tag_of(gradf, Quadratic)
-    if quad_f is not None or quad_g is not None:
-        if _tag_of(proxg, ProxTag) is not None and _tag_of(proxg, ProxTag).kind == hip.PROX_ROWSPLIT:
-            return "proximal.RowSplit is served on the device with a factorization loss only: fasta(None, None, fz.f, fz.gradf, ...) with fz = losses.Factorization(S)"
-        if isinstance(_tag_of(proxg, ProxTag), NuclearShrink):
-            return _NUCLEAR_ELSEWHERE
-        if isinstance(_tag_of(proxg, ProxTag), NuclearBall):
-            return _NUCBALL_ELSEWHERE
-        return _quadratic_form_refusal(A, At, quad_f, quad_g, g, proxg, x0)
-    sm_f, sm_g = _tag_of(f, SoftmaxLoss), _tag_of(gradf, SoftmaxLoss)
-    if sm_f is not None or sm_g is not None:
-        return _softmax_form_refusal(A, At, sm_f, sm_g, g, proxg, x0)
-    # A = None with the `.f` / `.gradf` of ONE elementwise loss tag, or an explicit IdentityMap: the identity operator (csrc/fh_nuclear.h).
-    # Every other call with A = None keeps the answer below.
-    loss_f, loss_g = _tag_of(f, (LeastSquares, LogisticLoss)), _tag_of(gradf, (LeastSquares, LogisticLoss))
-    if isinstance(A, IdentityMap) or (A is None and At is None and loss_f is not None and loss_f is loss_g):
-        if loss_f is None or loss_f is not loss_g:
-            return "f and gradf must be the `.f` / `.gradf` of one losses.LeastSquares(B) or losses.LogisticLoss(B) object"
-        return _identity_form_refusal(A, loss_f, g, proxg, x0)
-    if not isinstance(A, (np.ndarray, _DeviceMap)) and not is_sparse_matrix(A):
-        return ("operator A is not device-resident (pass a 2-D float64 ndarray, a scipy.sparse matrix, a linalg.DenseMatrixMap / "
-                "LinearMap.from_matrix(A), a linalg.SparseMatrixMap, a linalg.GradDivMap, a linalg.DCTMap or a linalg.ConvMap); arbitrary Python callables cannot run inside the fused HIP kernels")
-    loss_f, loss_g = _tag_of(f, (LeastSquares, LogisticLoss)), _tag_of(gradf, (LeastSquares, LogisticLoss))
-    if loss_f is None or loss_f is not loss_g:
-        return "f and gradf must be the `.f` / `.gradf` of one losses.LeastSquares(b) or losses.LogisticLoss(b) object"
-    if loss_f.weights is not None:
-        return _WEIGHTS_ELSEWHERE
-    if g is None and proxg is None:
-        return _dct_form_refusal(A, loss_f, None, x0) or _conv_form_refusal(A, loss_f, None, x0) or _sparse_form_refusal(A, loss_f, None, x0) or _matrix_form_refusal(A, loss_f, None, x0)
-    prox, owner_g = _tag_of(proxg, ProxTag), _tag_of(g, ProxTag)
-    if prox is None or (owner_g is not None and owner_g is not prox) or (owner_g is None and g is not None):
-        return ("g and proxg must be the `.g` / `.prox` of one proximal.* tag object "
-                "(Shrink, NonNeg, LinfProx, L1Ball, Box, TVDualBall, GroupShrink)")
-    if prox.kind == hip.PROX_NUCLEAR:
-        return _NUCLEAR_ELSEWHERE
-    if prox.kind == hip.PROX_NUCBALL:
-        return _NUCBALL_ELSEWHERE
-    if prox.kind == hip.PROX_ROWBALL:
-        return "proximal.RowBall is served on the device with a quadratic loss only: fasta(None, None, q.f, q.gradf, ...) with q = losses.Quadratic(Q, c)"
-    if prox.kind == hip.PROX_ROWSPLIT:
-        return "proximal.RowSplit is served on the device with a factorization loss only: fasta(None, None, fz.f, fz.gradf, ...) with fz = losses.Factorization(S)"
-    return _dct_form_refusal(A, loss_f, prox, x0) or _conv_form_refusal(A, loss_f, prox, x0) or _sparse_form_refusal(A, loss_f, prox, x0) or _matrix_form_refusal(A, loss_f, prox, x0)
-
-
-def _recognise(A, At, f, gradf, g, proxg, x0):
-    """Map the reference's seven operands onto device objects (call only when `_unrecognised` returned None)."""
-    fz = _tag_of(f, Factorization)
-    if fz is not None:                                 # A = None: the identity; S travels with the operator
-        prox = NoProx() if (g is None and proxg is None) else _tag_of(proxg, ProxTag)
-        return BilinearMap(fz, x0.shape), fz, prox
-    quad = _tag_of(f, Quadratic)
-    if quad is not None:                               # A = None: the identity; Q and c travel with the operator
-        prox = NoProx() if (g is None and proxg is None) else _tag_of(proxg, ProxTag)
-        return QuadraticMap(quad, x0.shape), quad, prox
-    if A is None or isinstance(A, IdentityMap):        # A = None: the identity on matrices; B travels with the loss
-        prox = NoProx() if (g is None and proxg is None) else _tag_of(proxg, ProxTag)
-        return (IdentityMap(x0.shape) if A is None else A), _tag_of(f, (LeastSquares, LogisticLoss)), prox
+def _build_matrix(A, At, loss, x0):
+    """The device map of a matrix, a sparse matrix or a map: built where the caller passed the raw matrix, and held to the shapes of x0 and b."""
     if isinstance(A, np.ndarray):
         if A.ndim != 2:
             raise AssertionError("matrix operator must be 2-D")            # linalg.py:40
@@ -381,13 +334,57 @@ def _recognise(A, At, f, gradf, g, proxg, x0):
         if At is not None and hasattr(At, "shape") and tuple(At.shape) != tuple(A.shape)[::-1]:
             raise AssertionError("At must have the transposed shape of A")
         A = SparseMatrixMap(A)
-    loss_f = _tag_of(f, (LeastSquares, LogisticLoss, SoftmaxLoss))
-    prox = NoProx() if (g is None and proxg is None) else _tag_of(proxg, ProxTag)      # :88-90
     if tuple(x0.shape) != A.Vshape:
         raise AssertionError(f"x0 has shape {x0.shape}, operator expects {A.Vshape}")   # linalg.py:58
-    if loss_f.b.shape != A.Wshape:
-        raise AssertionError(f"b has shape {loss_f.b.shape}, operator produces {A.Wshape}")
-    return A, loss_f, prox
+    if loss.b.shape != A.Wshape:
+        raise AssertionError(f"b has shape {loss.b.shape}, operator produces {A.Wshape}")
+    return A
+
+
+# form -> (the class of its loss tag, why the form does not serve the operands, the map it runs on).  Q, c, S and B travel with the loss: A = None there.
+_FORMS = {
+    "factorization": (Factorization, _factorization_refusal, lambda A, At, loss, x0: BilinearMap(loss, x0.shape)),
+    "quadratic": (Quadratic, _quadratic_refusal, lambda A, At, loss, x0: QuadraticMap(loss, x0.shape)),
+    "softmax": (SoftmaxLoss, _softmax_refusal, _build_matrix),
+    "identity": (_ELEMENTWISE, _identity_refusal, lambda A, At, loss, x0: IdentityMap(x0.shape) if A is None else A),
+    "matrix": (_ELEMENTWISE, _matrix_refusal, _build_matrix),
+}
+
+
+def _form_of(A, At, f, gradf):
+    """The form the operands ask for: by the loss tag behind f or gradf, then -- an elementwise loss -- by the operator."""
+    for form in ("factorization", "quadratic", "softmax"):
+        if _tag_of(f, _FORMS[form][0]) is not None or _tag_of(gradf, _FORMS[form][0]) is not None:
+            return form
+    # A = None with the `.f` / `.gradf` of ONE elementwise loss tag, or an explicit IdentityMap: the identity operator (csrc/fh_nuclear.h)
+    if isinstance(A, IdentityMap) or (A is None and At is None and _one_loss(f, gradf, _ELEMENTWISE) is not None):
+        return "identity"
+    return "matrix"
+
+
+def _build(form, A, At, f, gradf, g, proxg, x0):
+    """(map, loss, prox, whether the map is this call's to close): the device objects the operands become in `form`."""
+    loss_class, _, make = _FORMS[form]
+    loss = _tag_of(f, loss_class)
+    prox = NoProx() if (g is None and proxg is None) else _tag_of(proxg, ProxTag)      # :88-90
+    owns = A is None or isinstance(A, np.ndarray) or is_sparse_matrix(A)
+    return make(A, At, loss, np.asarray(x0, dtype=np.float64)), loss, prox, owns
+
+
+def _front_end(A, At, f, gradf, g, proxg, x0):
+    """The one walk over the reference's seven operands: the reason they cannot run on the device (a sentence), or what `_build` makes of them."""
+    form = _form_of(A, At, f, gradf)
+    return _FORMS[form][1](A, At, f, gradf, g, proxg, x0) or _build(form, A, At, f, gradf, g, proxg, x0)
+
+
+def _unrecognised(A, At, f, gradf, g, proxg, x0=None):
+    """None when the seven operands can run on the device, else the reason they cannot (a sentence): the first half of `_front_end`."""
+    return _FORMS[_form_of(A, At, f, gradf)][1](A, At, f, gradf, g, proxg, x0)
+
+
+def _recognise(A, At, f, gradf, g, proxg, x0):
+    """Map the reference's seven operands onto device objects, the second half of `_front_end` (call only when `_unrecognised` returned None)."""
+    return _build(_form_of(A, At, f, gradf), A, At, f, gradf, g, proxg, x0)[:3]
 
 
 class FBSolver:
@@ -835,21 +832,19 @@ def fasta(A, *operands, backend="auto", **options):
         raise TypeError("fasta() takes (A, f, gradf, g, proxg, x0) or (A, At, f, gradf, g, proxg, x0)")
     if backend not in ("auto", "hip", "numpy"):
         raise ValueError('backend must be "auto", "hip" or "numpy"')
-    why_not = "backend='numpy' was requested" if backend == "numpy" else _unrecognised(A, At, f, gradf, g, proxg, x0)
-    if why_not is not None:
+    found = "backend='numpy' was requested" if backend == "numpy" else _front_end(A, At, f, gradf, g, proxg, x0)
+    if isinstance(found, str):                                          # the reason the operands stay on the host
         if backend == "hip":
-            raise TypeError("fasta(backend='hip'): " + why_not)
+            raise TypeError("fasta(backend='hip'): " + found)
         from .generic import HostFBS, host_map
         options.pop("fused", None)                                      # device-loop policies, meaningless on the host
         options.pop("device_iters", None)
         options.pop("driver", None)
         x0 = np.asarray(x0)
         return HostFBS(host_map(A, At, x0), f, gradf, g, proxg, x0, **options).setup().run()
-    x0 = np.asarray(x0, dtype=np.float64)
-    owns = A is None or isinstance(A, np.ndarray) or is_sparse_matrix(A)
-    A, loss, prox = _recognise(A, At, f, gradf, g, proxg, x0)
+    A, loss, prox, owns = found
     try:
-        return FBSolver(A, loss, prox, x0, **options).setup().run()
+        return FBSolver(A, loss, prox, np.asarray(x0, dtype=np.float64), **options).setup().run()
     finally:
         if owns:
             A.close()
